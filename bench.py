@@ -18,9 +18,12 @@ Workload  = north_star's quoted target: 10 M x 768 bf16 rows, B=64, k=20, total 
 process, N devices (`comorag_amd.multi_index.MultiDeviceIndex` — per-shard worker threads enqueue, every shard's merge kernel
 writes its candidates into mapped host memory, host-side final merge); under a launcher with N > 1 ranks, rank 0 runs that leg
 in a child process after the one-rank-per-GPU measurement and reports it as `single_process` in the same JSON line.
-After the timed loop the LAST pipelined batch is compared with a synchronous search of the same batch (must be
-bit-identical), and recall@k against the fp32 CPU ranking is computed from THOSE ids.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HIP-event time of the scan kernel on
+A plain run sets up, warms up, times exactly --steps steps once, writes the last step's top-k with --dump-outputs DIR, and prints
+the line.  Everything else is behind --full: the timed region repeated, HIP-event kernel timing, clock sampling, the extra
+configurations, the PMC passes, the CPU baseline and the single-process leg.  With --full, after the timed loop the LAST pipelined
+batch is compared with a synchronous search of the same batch (must be bit-identical), and recall@k against the fp32 CPU ranking
+is computed from THOSE ids.
+Prints ONE JSON line on rank 0 (contract in the task statement) with, under --full, `roofline` (HIP-event time of the scan kernel on
 its own stream, algorithmic bytes, shader clock / power sampled during the timed regions) and `cpu_baseline` (the oracle's
 restatement of the reference's CPU code on this box's host cores, bounded samples).  That final line is <= 4 KB
 (tools/bench_line.py: contract keys, `config` with the flat `x_*` secondary numbers, `roofline`, reduced `cpu_baseline`,
@@ -59,8 +62,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="the timed K-step region is run this many times back to back (same warm state, each one bracketed by "
-                                                            "barrier + synchronize); value / ms_per_step are the MEDIAN region, min / max beside them")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: repeated timed regions, HIP-event kernel timing, clock sampling, the check of the "
+                         "last batch against a synchronous search, the extra configurations, the PMC passes, the CPU baseline and the "
+                         "single-process leg.  Without it a run sets up, warms up, times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (top-k ids as float64, scores as float32) "
+                         "to DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed K-step region is run this many times back to back (same warm state, each one bracketed by "
+                                                               "barrier + synchronize); value / ms_per_step are the MEDIAN region, min / max beside them "
+                                                               "(default: 5 with --full, else 1)")
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--batch", type=int, default=64)
@@ -83,7 +94,19 @@ def parse():
     ap.add_argument("--no-single-process-leg", action="store_true", help="N > 1 under a launcher: skip the single-process leg rank 0 runs afterwards")
     ap.add_argument("--single-process-timeout", type=float, default=300.0)
     ap.add_argument("--extras-timeout", type=float, default=240.0, help="N > 1: seconds the batch-256 / per-rank section may take before the headline line is printed without it")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:       # a plain run measures the headline only
+        args.no_extra = args.no_cpu_baseline = args.no_pmc = args.no_single_process_leg = True
+    return args
+
+
+def dump_outputs(path, ids, scores):
+    """--dump-outputs: the [B, k] top-k of the last timed step as a caller receives it (ids exact in float64)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "topk_ids.npy"), np.asarray(ids).astype(np.float64))
+    np.save(os.path.join(path, "topk_scores.npy"), np.asarray(scores).astype(np.float32))
 
 
 RNG_BLOCK = 1_000_000        # SURVEY.md 8(d): "for N = 10 M generate in 1 M-row blocks with default_rng([1234, blk])"
@@ -489,6 +512,8 @@ def single_process_main(args):
         return row, qs, last
 
     head, qs, last = run(args.batch, args.steps, args.warmup, 4321)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0], last[1])
     out = {"metric": "top-k queries/sec", "value": head["value"], "unit": "queries/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "data_note": "corpus rows drawn by " + _generator_note(),
            "config": {"workload": f"brute-force top-{args.k} over {args.rows} x {args.dim} {args.dtype} rows, batch {args.batch} (north_star target config; corpus fixed, "
@@ -546,6 +571,8 @@ def single_process_leg(args):
            "--query-batches", str(args.query_batches)]
     if args.share_device:
         cmd.append("--share-device")
+    if args.full:
+        cmd.append("--full")
     if args.no_extra:
         cmd.append("--no-extra")
     if args.survey_rng:
@@ -666,15 +693,20 @@ def main():
                 host = np.empty((args.rows, args.dim), dtype=np.float32)
         except Exception:
             host = None
-    sh = build_shard(torch, args, args.rows, rank, world, device, host=host, timing=world > 1)
+    sh = build_shard(torch, args, args.rows, rank, world, device, host=host, timing=world > 1 and args.full)
     # >= 20 timed scan launches for `roofline`: every 4th launch by default, more often when steps x repeats is small
-    every = max(1, min(PROFILE_EVERY, (args.steps * max(1, args.repeats)) // 20))
-    sampler = ClockSampler(_pci_address(torch, device))
+    # (a plain run times no launch: 0 switches the HIP events off)
+    every = max(1, min(PROFILE_EVERY, (args.steps * max(1, args.repeats)) // 20)) if args.full else 0
+    sampler = ClockSampler(_pci_address(torch, device)) if args.full else None
     dt, prof, last, qi, dts = run_steps(torch, dist, sh, qs, args.k, args.steps, args.warmup, world, device, every=every, ctl=ctl, repeats=args.repeats, sampler=sampler)
-    clock = sampler.summary()
-    gpu_ids, gpu_sc, same = verify_last_batch(sh, last, qs[qi].cpu().numpy(), args.k)
-    if qi != 0:                 # recall is computed for batch 0 (the CPU ranking of one batch is the expensive part)
-        gpu_ids = sh.search(qh, args.k)[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["o_ids"].cpu().numpy(), last["o_sc"].cpu().numpy())
+    clock = sampler.summary() if sampler is not None else None
+    same = True
+    if args.full:
+        gpu_ids, gpu_sc, same = verify_last_batch(sh, last, qs[qi].cpu().numpy(), args.k)
+        if qi != 0:             # recall is computed for batch 0 (the CPU ranking of one batch is the expensive part)
+            gpu_ids = sh.search(qh, args.k)[0]
     head = summarise(args.batch, args.steps, dt, prof, len(sh), args.dim, dual=bool(sh.local.get_option("pipe_dual_scan_active")), dts=dts)
     generator = _generator_note()
     out = {
@@ -704,6 +736,10 @@ def main():
     }
     if not same:
         out["verified"]["error"] = "pipelined outputs differ from the synchronous search of the same batch"
+    if not args.full:           # no kernel timing, clock sampling or check ran: those figures come with --full
+        out["roofline"] = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
+                           "rows_per_gpu": len(sh), "note": "kernel-level figures: bench.py --full"}
+        out["verified"] = {}
 
     # BASELINE config 3 as written: the same (sharded) corpus, batch 256 — one corpus pass of the wide kernel per batch
     # (multi-rank: this section holds the FIRST executions of the library's own RCCL communicator on real hardware — it runs under a
@@ -765,7 +801,9 @@ def main():
                 out["config"]["x_corpus_embed_bf16_chunks_per_s_sum_over_ranks"] = float(sum(rates))
                 out["config"]["x_corpus_embed_bf16_chunks_per_s_min_rank"] = float(min(rates))
 
-    if world > 1:
+    if not args.full:
+        pass                    # a plain run ends with the headline
+    elif world > 1:
         import threading
         def _guarded():
             try:
@@ -810,7 +848,7 @@ def main():
             out["pmc_this_run"] = tr
         else:
             out["roofline"]["traffic_error"] = tr["error"][:110]
-    if out["roofline"]["traffic"] is None:
+    if args.full and out["roofline"]["traffic"] is None:
         for prof_file in ("r5_pmc_hbm_traffic.json", "r4_pmc_hbm_traffic.json", "r3_pmc_hbm_traffic.json"):
             prof_file = os.path.join(ROOT, "profiles", prof_file)
             if os.path.exists(prof_file):

@@ -22,7 +22,7 @@ sys.dont_write_bytecode = True
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from oracle.ref_loader import ref_modules  # noqa: E402
+from oracle.ref_loader import REFERENCE_ROOT, ref_modules  # noqa: E402
 from oracle import retrieval_np as orc  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
@@ -229,7 +229,7 @@ def main():
 
         # C1: cinderella corpus → store → dense retrieval top-5 (fake embedder)
         # same parsing as main_openai.py:13-19 (skip blank lines, docs = 'contents')
-        cdir = "/root/reference/dataset/cinderella/cinderella_1"
+        cdir = os.path.join(REFERENCE_ROOT, "dataset", "cinderella", "cinderella_1")
         corpus = [json.loads(l) for l in open(f"{cdir}/corpus.jsonl", encoding="utf-8") if l.strip()]
         qas = [json.loads(l) for l in open(f"{cdir}/qas.jsonl", encoding="utf-8") if l.strip()]
         docs = [d["contents"] for d in corpus]
@@ -245,7 +245,9 @@ def main():
                # the fake embedder's vectors of the six chunks / three questions, so the GPU tier (no reference tree,
                # hence no chunk texts) can rebuild the same index
                "doc_vecs": np.array(cs.get_embeddings(keys)).tolist(),
-               "question_vecs": [emb._vec(qa["question"]).tolist() for qa in qas]}
+               "question_vecs": [emb._vec(qa["question"]).tolist() for qa in qas],
+               # the chunk texts themselves, so that the CPU tier's store test needs no reference tree either
+               "docs": docs}
         for qa in qas:
             q = qa["question"]
             ids_, sc_ = obj.dense_passage_retrieval(q)

@@ -30,3 +30,15 @@ def test_share_device_needs_gloo():
     assert r.returncode != 0
     want = "add --backend gloo" if torch.cuda.device_count() >= 1 else "needs one visible MI355X"
     assert want in r.stderr, r.stderr[-800:]
+
+
+def test_plain_run_leaves_everything_but_the_headline_to_full(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.steps == 7 and a.repeats == 1 and a.dump_outputs is None
+    assert a.no_extra and a.no_cpu_baseline and a.no_pmc and a.no_single_process_leg
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.repeats == 5 and a.dump_outputs == "out"
+    assert not (a.no_extra or a.no_cpu_baseline or a.no_pmc or a.no_single_process_leg)

@@ -40,7 +40,7 @@ def test_bench_two_ranks_sharing_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--rows", "300000",
-                        "--steps", "8", "--warmup", "2"], capture_output=True, text=True, timeout=850, env=env)
+                        "--steps", "8", "--warmup", "2", "--full"], capture_output=True, text=True, timeout=850, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], _first_error_lines(r.stderr), r.stderr[-3000:])
     out, side = _line_and_side(r.stdout)                            # ONE line, from rank 0
     assert out["n_gpus"] == 2 and out["steps"] == 8 and out["value"] > 0
@@ -74,7 +74,7 @@ def test_bench_single_process_mode_four_logical_shards():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--single-process", "--gpus", "4", "--share-device", "--rows", "600000", "--steps", "12", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--single-process", "--gpus", "4", "--share-device", "--rows", "600000", "--steps", "12", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=270, env=env)
     if r.returncode < 0:
         # Round 6: ONE of this child's ~75 runs on the GPU pool died by SIGABRT inside PyTorch (an uncaught c10::Error; the test then kept only
@@ -107,7 +107,7 @@ def test_bench_eight_ranks_sharing_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--share-device", "--rows", "80000",
-           "--steps", "4", "--warmup", "1", "--repeats", "2"]
+           "--steps", "4", "--warmup", "1", "--repeats", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=700, env=env)
     if r.returncode != 0:        # eight cold interpreters importing torch at once can miss the rendezvous on a fresh box: once more, warm
         first = [l for l in r.stderr.splitlines() if "Gloo" not in l][-15:]

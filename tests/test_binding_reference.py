@@ -1,6 +1,6 @@
 """The binding glue (comorag_amd/hooks.py, embedding_store.py, retrieval.py) on the REAL reference classes — CPU tier.
 
-Needs the reference tree (this container; the GPU box has none, tests skip there — its twins with the HIP index are in
+All but the cinderella test need the reference tree and skip without it (their twins with the HIP index are in
 tests/test_dropin_gpu.py).  The device index is replaced by conftest.NumpyIndex through the hooks' `index_factory`
 seam, so what is tested here is exactly the glue: which names get rebound, on which objects, with which semantics.
     ComoRAG.py:92-124   five stores + embedding-model factory          (module aliasing)
@@ -17,12 +17,13 @@ import types
 import numpy as np
 import pytest
 
-from oracle.ref_loader import REFERENCE_ROOT, reference_available
+from oracle.ref_loader import reference_available
 
-pytestmark = pytest.mark.skipif(not reference_available(), reason="reference tree not present")
+needs_reference = pytest.mark.skipif(not reference_available(), reason="reference tree not present")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+@needs_reference
 def test_patch_reference_modules_binds_the_real_comorag_module():
     """alias the three replaced modules, THEN import the reference's ComoRAG.  Runs in a fresh
     interpreter (module aliasing is process-global)."""
@@ -78,6 +79,7 @@ def _bare_rag(ComoRAG, stores, emb):
     return rag
 
 
+@needs_reference
 def test_install_on_a_real_comorag_instance(tmp_path, fake_embedder, numpy_index_cls):
     from oracle.ref_loader import ref_modules
     m = ref_modules()
@@ -123,6 +125,7 @@ def test_install_on_a_real_comorag_instance(tmp_path, fake_embedder, numpy_index
         np.testing.assert_allclose(c_sc, d_sc, atol=2e-6)
 
 
+@needs_reference
 def test_install_memory_pool_on_a_real_pool(fake_embedder, numpy_index_cls):
     """BASELINE config 4's shape on the reference's own MemoryPool: three cycles of (add nodes, retrieve); the rebound
     method must select the nodes the reference method selects on an identical pool, appending only the new rows."""
@@ -171,8 +174,7 @@ def test_config1_cinderella_plumbing(tmp_path, golden_dir, fake_embedder, numpy_
     from comorag_amd import retrieval
     from comorag_amd.embedding_store import EmbeddingStore
     c = json.load(open(os.path.join(golden_dir, "cinderella.json")))
-    cdir = os.path.join(REFERENCE_ROOT, "dataset", "cinderella", "cinderella_1")
-    docs = [json.loads(l)["contents"] for l in open(os.path.join(cdir, "corpus.jsonl"), encoding="utf-8") if l.strip()]   # main_openai.py:13-19
+    docs = c["docs"]                                               # the corpus' `contents`, as main_openai.py:13-19 reads them
     st = EmbeddingStore(fake_embedder, str(tmp_path / "cinder"), 8, "cinder")
     st.insert_strings(docs)
     st.insert_strings(docs[:2])                                    # re-insert: nothing new
@@ -254,6 +256,7 @@ class _NumpyGraph:
         return self.ppr(r, damping)[self.rows]
 
 
+@needs_reference
 def test_device_ppr_hooks_on_a_real_comorag_instance(tmp_path, fake_embedder, numpy_index_cls):
     """run_ppr and graph_search_with_fact_entities rebound on a real ComoRAG instance (§8 f4's glue): same ranking and
     scores as the reference's own methods over a graph whose personalized_pagerank the oracle answers."""
@@ -306,6 +309,7 @@ def test_device_ppr_hooks_on_a_real_comorag_instance(tmp_path, fake_embedder, nu
         np.testing.assert_allclose(got[1], want[1], atol=1e-9)
 
 
+@needs_reference
 def test_embedding_cache_files_are_interchangeable_with_the_reference_wrapper(tmp_path):
     """a14 make_cache_embed (embedding_model/base.py:112-187): a cache file written by the reference's wrapper must hit
     in ours and vice versa (same sha256 key over {"instruction", "promps" [sic], "max_length"}, same fp32 blobs)."""
@@ -338,6 +342,7 @@ def test_embedding_cache_files_are_interchangeable_with_the_reference_wrapper(tm
     assert calls == [["delta"]]
 
 
+@needs_reference
 def test_the_real_tri_retrieve_loop_runs_on_the_hooks(tmp_path, golden_dir, fake_embedder, numpy_index_cls, monkeypatch):
     """ComoRAG.tri_retrieve (ComoRAG.py:456-554) — the reference's OWN method, unmodified — on an instance whose stores are this package's
     EmbeddingStore and whose numeric call sites are rebound by hooks.install (the device index replaced by conftest.NumpyIndex, the module's

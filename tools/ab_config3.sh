@@ -2,7 +2,7 @@
 # Same-box A/B of the pipelined streams in bench.py's own flow: headline (10 M rows, B = 64) and config 3 (B = 256) per setting.
 for opt in "" "--index-option pipe_cu_mask=0" "--index-option pipe_cu_mask=1" ; do
   echo "== $opt"
-  timeout 200 python bench.py --steps 20 --warmup 5 --only-config3 $opt 2>/dev/null | python -c "
+  timeout 200 python bench.py --steps 20 --warmup 5 --full --only-config3 $opt 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['extra']['config3_batch256']
 print('headline', round(d['value']), d['ms_per_step'], d['roofline']['kernel_ms'], '| c3', round(c['value']), c['ms_per_step'], c['kernel_ms'])"

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 ROUND=${ROUND:-r6}
 O=$R/gpurun_out/${ROUND}_profiles; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $O/kt -o w -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $O/bench_under_trace.json 2> $O/kt.err
+rocprofv3 --kernel-trace -d $O/kt -o w -- python $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-pmc > $O/bench_under_trace.json 2> $O/kt.err
 python $R/tools/rocpd_stats.py $O/kt/w_results.db > $O/${ROUND}_bench_kernel_stats.txt
 python $R/tools/rocpd_dump.py $O/kt/w_results.db $O/${ROUND}_raw_bench_kernel_trace.csv.gz
 for c in FETCH_SIZE WRITE_SIZE; do
