@@ -20,6 +20,7 @@ CMR_FLAG_KEEP_F32 = 1
 CMR_MAX_K = 128
 ABI_VERSION = 2        # include/comorag_hip.h: CMR_ABI_VERSION
 CMR_MAX_K_2PASS = 4096
+CMR_MAX_K_EXACT = 64      # cmr_index_search_exact
 DTYPES = {"f32": CMR_F32, "fp32": CMR_F32, "float32": CMR_F32, "bf16": CMR_BF16, "bfloat16": CMR_BF16,
           "f16": CMR_F16, "fp16": CMR_F16, "float16": CMR_F16}
 
@@ -65,6 +66,9 @@ SIGNATURES = {
     "cmr_index_sorted_scores": (_i32, [_p, _p, _i32, _p, _p, _p, _p]),
     "cmr_index_rescore": (_i32, [_p, _p, _i32, _p, _i32, _i32, _p, _p]),
     "cmr_index_get_rows": (_i32, [_p, _p, _i64, _p]),
+    "cmr_index_search_exact": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),
+    "cmr_index_search_exact_pipelined": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _P(_p)]),
+    "cmr_index_round_stats": (_i32, [_p, _P(_f32), _P(_f32)]),
     "cmr_merge_topk": (_i32, [_p, _p, _i32, _i32, _i32, _p, _p]),
     "cmr_merge_topk_dev": (_i32, [_i32, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
     "cmr_graph_create": (_i32, [_i32, _i64, _i64, _p, _p, _p, _P(_p)]),
@@ -93,6 +97,7 @@ SIGNATURES = {
     "cmr_mindex_sorted_scores": (_i32, [_p, _p, _i32, _p, _p, _p, _p]),
     "cmr_mindex_rescore": (_i32, [_p, _p, _i32, _p, _i32, _i32, _p, _p]),
     "cmr_mindex_get_rows": (_i32, [_p, _p, _i64, _p]),
+    "cmr_mindex_search_exact": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),
     "cmr_mindex_search_pipelined": (_i32, [_p, _p, _i32, _i32, _P(_p)]),
     "cmr_mindex_collect": (_i32, [_p, _p, _p, _p, _p, _p]),
     "cmr_mindex_profile": (_i32, [_p, _i32, _P(_i64), _P(_f64), _P(_f64), _P(_f64)]),

@@ -77,6 +77,13 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// Scratch of the exact search (cmr_index_search_exact): stage-1 candidate lists [nq][kc] (ids, 16-bit scan scores), the re-score's
+// keys [nq][kc], its per-query arrival counters (zeroed when allocated, re-armed by the kernel) and the outputs of the sync call.
+struct ExactScratch {
+    DevBuf ids, sc, part, arrive, oids, osc, oex;
+    void release() { ids.release(); sc.release(); part.release(); arrive.release(); oids.release(); osc.release(); oex.release(); }
+};
+
 // Scratch of one in-flight search.  One per stream (searches on a stream are serialised by it).
 struct Workspace {
     hipStream_t stream = nullptr;
@@ -89,6 +96,7 @@ struct Workspace {
     // synchronous search: queries in, (ids | scores | min | max | non-finite flag) out through ONE pinned host buffer and
     // one copy each way — five pageable D2H copies cost more than the search of a small corpus
     DevBuf d_pack;
+    ExactScratch x;              // cmr_index_search_exact
     int* flag_ptr = nullptr;     // the non-finite-query flag the kernels set: flag.p, or the head of d_pack for the host API
     // Synchronous host API with mapped results: the word (device view of the pinned buffer, bytes 4..7) that the search's LAST kernel sets
     // once its results are written — 1: final, 2: the finishing stage overflowed and the merge recorded in `lazy` is still due.  Offered by
@@ -121,6 +129,7 @@ struct Workspace {
         fin_ctl.release(); fin_pmax.release(); fin_tau.release(); fin_dense.release(); fin_mm.release();
         d_q.release(); d_ids.release(); d_scores.release(); d_min.release(); d_max.release(); d_cand.release(); d_out.release();
         d_pack.release();
+        x.release();
         if (h_pin) (void)hipHostFree(h_pin);
         h_pin = nullptr; h_pin_dev = nullptr; h_pin_cap = 0;
         if (own_stream && stream) (void)hipStreamDestroy(stream);
@@ -219,6 +228,12 @@ struct cmr_index {
     int reserve_cus = -1;    // pipe_reserve_cus: CUs the pipelined main scan leaves free (-1 = by corpus size, see enqueue_pass)
     std::mutex pipe_mu;
     Pipe pipe;
+    // exact search (cmr_index_search_exact): the certificate's index-wide maxima (M_x, M_dx) on the device, updated by every
+    // accepted append; stage-1 candidates per query (exact_cand, in (k, CMR_MAX_K]); per-slot scratch of the pipelined call
+    float* d_stats = nullptr;
+    int exact_cand = CMR_MAX_K;
+    ExactScratch x_slot[CMR_PIPE_SLOTS];
+    unsigned x_next = 0;
     size_t panel_bytes() const { return (size_t)CMR_PANEL_ROWS * dpad * elem_size(dtype); }
 };
 
@@ -257,6 +272,7 @@ int set_option(cmr_index* idx, const char* name, long long v) {
     else if (n == "stream_nt") idx->stream_nt = (int)v;
     else if (n == "pipe_dual_scan") idx->dual_scan = (int)v;
     else if (n == "pipe_cu_mask") idx->cu_mask = (int)v;
+    else if (n == "exact_cand") { if (v < 2 || v > CMR_MAX_K) return fail(CMR_ERR_INVALID, "exact_cand must be in [2, %d]", CMR_MAX_K); idx->exact_cand = (int)v; }
 #ifdef CMR_DEV_KNOBS
     else if (n == "wide_abl") idx->wide_abl = (int)v;      // ablation kernels: results are WRONG by design (development builds only)
 #endif
@@ -883,9 +899,8 @@ int ensure_pipe(cmr_index* idx) {
 // Pipelined search: three internal streams.  Pre-phases run on `sp` back to back, candidate merges
 // on `sq`; main scans are serialised on `sm` (two HBM-bound scans at once only slow each other down) and leave
 // `reserve_cus` CUs free, on which the next pass's sampling scans and the merges run concurrently.
-int search_pipelined_enqueue(cmr_index* idx, const float* q_dev, int nq, int k, int64_t* ids_dev, float* scores_dev, float* min_dev,
-                             float* max_dev, hipEvent_t wait_event, hipEvent_t* done_event, const float* min_score = nullptr) {
-    std::lock_guard<std::mutex> pl(idx->pipe_mu);
+int search_pipelined_enqueue_locked(cmr_index* idx, const float* q_dev, int nq, int k, int64_t* ids_dev, float* scores_dev, float* min_dev,
+                                    float* max_dev, hipEvent_t wait_event, hipEvent_t* done_event, const float* min_score) {
     Pipe& P = idx->pipe;
     { int rc_ = ensure_pipe(idx); if (rc_) return rc_; }
     P.nslots = std::min(CMR_PIPE_SLOTS, std::max(2, idx->pipe_slots));
@@ -947,6 +962,11 @@ int search_pipelined_enqueue(cmr_index* idx, const float* q_dev, int nq, int k, 
     }
     if (done_event) *done_event = last ? last->main_done : nullptr;
     return CMR_OK;
+}
+int search_pipelined_enqueue(cmr_index* idx, const float* q_dev, int nq, int k, int64_t* ids_dev, float* scores_dev, float* min_dev,
+                             float* max_dev, hipEvent_t wait_event, hipEvent_t* done_event, const float* min_score = nullptr) {
+    std::lock_guard<std::mutex> pl(idx->pipe_mu);
+    return search_pipelined_enqueue_locked(idx, q_dev, nq, k, ids_dev, scores_dev, min_dev, max_dev, wait_event, done_event, min_score);
 }
 
 int scores_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, float* out_dev, long long ld) {
@@ -1014,6 +1034,7 @@ int grow(cmr_index* idx, long long need_panels) {
 int append_from_device(cmr_index* idx, const float* rows_dev, long long n, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(idx->d_flag, 0, sizeof(int), s));
     HIP_TRY(cmr_launch_convert_rows(idx->dtype, rows_dev, n, idx->dim, idx->dpad, idx->n, idx->corpus, idx->shadow, idx->d_flag, s));
+    HIP_TRY(cmr_launch_round_stats(idx->dtype, idx->shadow ? idx->shadow + (size_t)idx->n * idx->dim : rows_dev, n, idx->dim, idx->d_flag, idx->d_stats, s));
     int h = 0;
     HIP_TRY(hipMemcpyAsync(&h, idx->d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1119,9 +1140,13 @@ int32_t cmr_index_create(int32_t device_id, int32_t dim, int32_t dtype, int64_t 
         return fail(CMR_ERR_UNSUPPORTED, "dim %d (padded %d) exceeds the LDS-resident query tile for dtype %d", dim, round_up(dim, 128), dtype);
     }
     if (hipMalloc((void**)&idx->d_flag, sizeof(int)) != hipSuccess) { delete idx; return fail(CMR_ERR_OOM, "hipMalloc flag"); }
+    if (hipMalloc((void**)&idx->d_stats, 2 * sizeof(float)) != hipSuccess || hipMemset(idx->d_stats, 0, 2 * sizeof(float)) != hipSuccess) {
+        if (idx->d_stats) (void)hipFree(idx->d_stats);
+        (void)hipFree(idx->d_flag); delete idx; return fail(CMR_ERR_OOM, "hipMalloc round stats");
+    }
     const long long hint_panels = std::max<long long>((capacity_hint + CMR_PANEL_ROWS - 1) / CMR_PANEL_ROWS, 8);
     rc = grow(idx, hint_panels);
-    if (rc) { (void)hipFree(idx->d_flag); delete idx; return rc; }
+    if (rc) { (void)hipFree(idx->d_flag); (void)hipFree(idx->d_stats); delete idx; return rc; }
     *out = idx;
     return CMR_OK;
 }
@@ -1155,6 +1180,8 @@ int32_t cmr_index_destroy(cmr_index_t* idx) {
         if (idx->corpus) (void)hipFree(idx->corpus);
         if (idx->shadow) (void)hipFree(idx->shadow);
         if (idx->d_flag) (void)hipFree(idx->d_flag);
+        if (idx->d_stats) (void)hipFree(idx->d_stats);
+        for (ExactScratch& x : idx->x_slot) x.release();
         if (idx->d_blk) (void)hipFree(idx->d_blk);
         for (void* p : idx->blk_retired) (void)hipFree(p);
     }
@@ -1208,6 +1235,8 @@ int32_t cmr_index_append(cmr_index_t* idx, const float* rows, int64_t n) {
         memset(h, 0, 8);
         memcpy(h + 256, rows, bytes);
         HIP_TRY(cmr_launch_convert_rows(idx->dtype, (const float*)(d + 256), n, idx->dim, idx->dpad, idx->n, idx->corpus, idx->shadow, (int*)d, nullptr));
+        HIP_TRY(cmr_launch_round_stats(idx->dtype, idx->shadow ? idx->shadow + (size_t)idx->n * idx->dim : (const float*)(d + 256), n, idx->dim, (int*)d,
+                                       idx->d_stats, nullptr));
         HIP_TRY(hipStreamSynchronize(nullptr));
         int flagged = 0;
         memcpy(&flagged, h, sizeof(int));
@@ -1218,15 +1247,20 @@ int32_t cmr_index_append(cmr_index_t* idx, const float* rows, int64_t n) {
     // stage in chunks of <= 256 MiB of fp32
     const long long chunk_rows = std::max<long long>(1, (256ll << 20) / ((long long)idx->dim * 4));
     const long long n0 = idx->n;
+    // an append of several chunks that fails on a later one leaves the maxima of the exact search as they were before it
+    float stats0[2] = {0.0f, 0.0f};
+    const bool chunks = n > chunk_rows;
+    if (chunks) HIP_TRY(hipMemcpy(stats0, idx->d_stats, sizeof(stats0), hipMemcpyDeviceToHost));
+    auto undo_stats = [&]() { if (chunks) (void)hipMemcpy(idx->d_stats, stats0, sizeof(stats0), hipMemcpyHostToDevice); };
     for (long long r0 = 0; r0 < n; r0 += chunk_rows) {
         const long long nr = std::min<long long>(chunk_rows, n - r0);
         const size_t bytes = (size_t)nr * idx->dim * 4;
         hipError_t e = idx->stage.ensure(bytes);
-        if (e != hipSuccess) { idx->n = n0; return fail(CMR_ERR_OOM, "append staging: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) { idx->n = n0; undo_stats(); return fail(CMR_ERR_OOM, "append staging: %s", hipGetErrorString(e)); }
         e = hipMemcpyAsync(idx->stage.p, rows + (size_t)r0 * idx->dim, bytes, hipMemcpyHostToDevice, nullptr);
-        if (e != hipSuccess) { idx->n = n0; return fail(CMR_ERR_HIP, "H2D rows: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) { idx->n = n0; undo_stats(); return fail(CMR_ERR_HIP, "H2D rows: %s", hipGetErrorString(e)); }
         rc = append_from_device(idx, (const float*)idx->stage.p, nr, nullptr);
-        if (rc) { idx->n = n0; return rc; }
+        if (rc) { idx->n = n0; undo_stats(); return rc; }
     }
     return CMR_OK;
 }
@@ -1366,6 +1400,7 @@ int32_t cmr_index_get_option(cmr_index_t* idx, const char* name, int64_t* value)
     else if (n == "pipe_dual_scan_wide_active") *value = idx->dual_wide_active;
     else if (n == "pipe_cu_mask_active") *value = idx->pipe.last_masked;
     else if (n == "pipe_scan_cus") *value = idx->pipe.last_masked ? idx->pipe.scan_cus : idx->n_cu;
+    else if (n == "exact_cand") *value = idx->exact_cand;
     else return fail(CMR_ERR_INVALID, "unknown readable option '%s'", name);
     return CMR_OK;
 }
@@ -1806,6 +1841,145 @@ int32_t cmr_index_rescore(cmr_index_t* idx, const float* q, int32_t nq, const in
     HIP_TRY(hipMemcpyAsync(out_ids, ws->d_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out_scores, ws->d_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return CMR_OK;
+}
+
+// ---- exact fp32 top-k of a 16-bit index (include/comorag_hip.h: cmr_index_search_exact)
+namespace {
+
+int exact_scratch(ExactScratch* X, int nq, int kc, int k, bool outs, hipStream_t s) {
+    HIP_TRY(X->ids.ensure((size_t)nq * kc * 8));
+    HIP_TRY(X->sc.ensure((size_t)nq * kc * 4));
+    HIP_TRY(X->part.ensure(cmr_exact_part_bytes(nq, kc)));
+    if ((size_t)nq * sizeof(int) > X->arrive.cap || !X->arrive.p) {      // arrival counters: zeroed once, re-armed by the kernel
+        HIP_TRY(X->arrive.ensure((size_t)nq * sizeof(int)));
+        HIP_TRY(hipMemsetAsync(X->arrive.p, 0, X->arrive.cap, s));
+    }
+    if (outs) {
+        HIP_TRY(X->oids.ensure((size_t)nq * k * 8));
+        HIP_TRY(X->osc.ensure((size_t)nq * k * 4));
+        HIP_TRY(X->oex.ensure((size_t)nq * 4));
+    }
+    return CMR_OK;
+}
+
+// re-score + certify the stage-1 lists in X (global ids, as every search returns them) on `s`; output ids translated like any search's
+int exact_certify_enqueue(cmr_index* idx, ExactScratch* X, const float* q_dev, int nq, int kc, int k, int64_t* ids_dev, float* scores_dev,
+                          int* exact_dev, hipStream_t s) {
+    const int nb = (int)idx->blk_local.size();
+    HIP_TRY(cmr_launch_exact_certify(idx->dtype, idx->shadow, idx->dim, idx->n, kernel_id_base(idx), nb > 1 ? idx->d_blk : nullptr, nb, q_dev, nq,
+                                     (const int64_t*)X->ids.p, (const float*)X->sc.p, kc, k, idx->d_stats, X->part.p, (int*)X->arrive.p,
+                                     ids_dev, scores_dev, exact_dev, s));
+    return remap_ids_enqueue(idx, ids_dev, (long long)nq * k, s);
+}
+
+int exact_check(const cmr_index* idx, int k) {
+    if (k <= 0 || k > 64) return fail(CMR_ERR_UNSUPPORTED, "exact search supports k in [1, 64], got %d", k);
+    if (idx->dtype == CMR_F32) return CMR_OK;
+    if (!(idx->flags & CMR_FLAG_KEEP_F32)) return fail(CMR_ERR_UNSUPPORTED, "exact search of a 16-bit index needs CMR_FLAG_KEEP_F32 (the fp32 shadow)");
+    if (idx->exact_cand <= k) return fail(CMR_ERR_UNSUPPORTED, "exact_cand %d must be > k %d", idx->exact_cand, k);
+    return CMR_OK;
+}
+
+}  // namespace
+
+int32_t cmr_index_search_exact(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores, int32_t* out_exact) {
+    if (!idx || !q || !out_ids || !out_scores || !out_exact) return fail(CMR_ERR_INVALID, "NULL argument");
+    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
+    { int rc_ = exact_check(idx, k); if (rc_) return rc_; }
+    if (idx->dtype == CMR_F32) {      // an fp32 index ranks with fp32 arithmetic already: the plain search is the exact one
+        const int rc = host_search(idx, q, nq, k, out_ids, out_scores, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        for (int i = 0; i < nq; ++i) out_exact[i] = 1;
+        return CMR_OK;
+    }
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    int rc = set_device(idx->device);
+    if (rc) return rc;
+    Workspace* ws = acquire_ws(idx, nullptr, false);
+    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
+    struct Rel { cmr_index* i; Workspace* w; ~Rel() { release_ws(i, w); } } rel{idx, ws};
+    hipStream_t s = ws->stream;
+    ExactScratch* X = &ws->x;
+    // one stage: top-kc of the 16-bit scan, re-score + certify, results to the host
+    auto stage = [&](const float* qh, int n_q, int kc, int64_t* oi, float* os, int32_t* oe) -> int {
+        HIP_TRY(ws->d_q.ensure((size_t)n_q * idx->dim * 4));
+        HIP_TRY(hipMemcpyAsync(ws->d_q.p, qh, (size_t)n_q * idx->dim * 4, hipMemcpyHostToDevice, s));
+        int rc_ = exact_scratch(X, n_q, kc, k, true, s);
+        if (!rc_) rc_ = arm_flag(ws, s);
+        if (!rc_) rc_ = search_enqueue(idx, ws, (const float*)ws->d_q.p, n_q, kc, (int64_t*)X->ids.p, (float*)X->sc.p, nullptr, nullptr);
+        if (!rc_) rc_ = exact_certify_enqueue(idx, X, (const float*)ws->d_q.p, n_q, kc, k, (int64_t*)X->oids.p, (float*)X->osc.p, (int*)X->oex.p, s);
+        if (rc_) { (void)hipStreamSynchronize(s); return rc_; }
+        HIP_TRY(hipMemcpyAsync(oi, X->oids.p, (size_t)n_q * k * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(os, X->osc.p, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(oe, X->oex.p, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
+        return check_query_flag(ws);     // (synchronises)
+    };
+    rc = stage(q, nq, idx->exact_cand, out_ids, out_scores, out_exact);
+    if (rc) return rc;
+    // stage 2: the queries stage 1 could not certify, again from the two-pass search's CMR_MAX_K_2PASS candidates
+    std::vector<int> u;
+    for (int i = 0; i < nq; ++i) if (!out_exact[i]) u.push_back(i);
+    if (u.empty() || idx->n <= idx->exact_cand) return CMR_OK;
+    const int nu = (int)u.size(), kc2 = (int)std::min<long long>(CMR_MAX_K_2PASS, idx->n), d = idx->dim;
+    std::vector<float> q2((size_t)nu * d);
+    std::vector<int64_t> i2((size_t)nu * k);
+    std::vector<float> s2((size_t)nu * k);
+    std::vector<int32_t> e2((size_t)nu);
+    for (int j = 0; j < nu; ++j) memcpy(&q2[(size_t)j * d], q + (size_t)u[j] * d, (size_t)d * 4);
+    rc = stage(q2.data(), nu, kc2, i2.data(), s2.data(), e2.data());
+    if (rc) return rc;
+    for (int j = 0; j < nu; ++j) {
+        memcpy(out_ids + (size_t)u[j] * k, &i2[(size_t)j * k], (size_t)k * 8);
+        memcpy(out_scores + (size_t)u[j] * k, &s2[(size_t)j * k], (size_t)k * 4);
+        out_exact[u[j]] = e2[j];
+    }
+    return CMR_OK;
+}
+
+int32_t cmr_index_search_exact_pipelined(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, int64_t* ids_dev, float* scores_dev,
+                                         int32_t* exact_dev, void* wait_event, void** done_event) {
+    if (!idx || !q_dev || !ids_dev || !scores_dev || !exact_dev) return fail(CMR_ERR_INVALID, "NULL argument");
+    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
+    { int rc_ = exact_check(idx, k); if (rc_) return rc_; }
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    int rc = set_device(idx->device);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> pl(idx->pipe_mu);
+    rc = ensure_pipe(idx);
+    if (rc) return rc;
+    hipStream_t const sq = idx->pipe.sq;
+    hipEvent_t done = nullptr;
+    if (idx->dtype == CMR_F32) {
+        rc = search_pipelined_enqueue_locked(idx, q_dev, nq, k, ids_dev, scores_dev, nullptr, nullptr, (hipEvent_t)wait_event, &done, nullptr);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)exact_dev, 1, (size_t)nq, sq));
+    } else {
+        // stage-1 candidates in per-slot scratch: their writers (the merges) and their reader (the re-score) are all on the post stream,
+        // which orders each slot's next use behind this one
+        const int kc = idx->exact_cand;
+        ExactScratch* X = &idx->x_slot[idx->x_next++ % CMR_PIPE_SLOTS];
+        rc = exact_scratch(X, nq, kc, k, false, sq);
+        if (rc) return rc;
+        rc = search_pipelined_enqueue_locked(idx, q_dev, nq, kc, (int64_t*)X->ids.p, (float*)X->sc.p, nullptr, nullptr, (hipEvent_t)wait_event, &done, nullptr);
+        if (rc) return rc;
+        rc = exact_certify_enqueue(idx, X, q_dev, nq, kc, k, ids_dev, scores_dev, exact_dev, sq);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipEventRecord(done, sq));      // (the last slot's main_done, re-recorded behind the re-score)
+    if (done_event) *done_event = (void*)done;
+    return CMR_OK;
+}
+
+int32_t cmr_index_round_stats(cmr_index_t* idx, float* max_row_norm, float* max_round_err) {
+    if (!idx || !max_row_norm || !max_round_err) return fail(CMR_ERR_INVALID, "NULL argument");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    int rc = set_device(idx->device);
+    if (rc) return rc;
+    float h[2] = {0.0f, 0.0f};
+    HIP_TRY(hipMemcpy(h, idx->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+    *max_row_norm = h[0];
+    *max_round_err = h[1];
     return CMR_OK;
 }
 

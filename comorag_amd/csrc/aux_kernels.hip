@@ -1248,3 +1248,221 @@ hipError_t cmr_launch_pool(const void* hidden, int hidden_dtype, const int64_t* 
     hipLaunchKernelGGL(pool_finalize_kernel, dim3(b), dim3(256), 0, s, partial, mask, l, d, splits, normalize, out);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------
+// Exact top-k of a 16-bit index: the certificate's two index-wide maxima and the re-score + certify stage
+// (cmr_index_search_exact).
+//
+// Rounding statistics of appended rows: M_x = max_r ||round(x_r)||, M_dx = max_r ||round(x_r) - x_r|| (the same RNE rounding
+// as the append's packing).  One wave per row, sums of squares in fp64 and rounded UP to fp32, one atomicMax on the float
+// bits per workgroup (non-negative floats order like their bits) — the result does not depend on the order of the adds.
+// `flag`: the append's non-finite flag (device or mapped host memory), set by the convert launch before this one on the
+// same stream: a rejected append leaves the maxima as they were.
+template <int DT>
+__global__ __launch_bounds__(256) void round_stats_kernel(const float* __restrict__ rows, long long n, int dim, const int* __restrict__ flag,
+                                                          unsigned* __restrict__ stats) {
+    __shared__ float part[2][4];
+    if (flag && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float mx = 0.0f, mdx = 0.0f;
+    for (long long r = (long long)blockIdx.x * 4 + wave; r < n; r += (long long)gridDim.x * 4) {
+        const float* x = rows + (size_t)r * dim;
+        double sx = 0.0, sd = 0.0;
+        for (int i = lane; i < dim; i += 64) {
+            const float f = x[i];
+            const float t = DT == CMR_DT_BF16 ? cmr_bf2f(cmr_f2bf(f)) : cmr_h2f(cmr_f2h(f));
+            sx += (double)t * t;
+            sd += ((double)t - f) * ((double)t - f);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { sx += __shfl_xor(sx, off); sd += __shfl_xor(sd, off); }
+        mx = fmaxf(mx, __double2float_ru(sqrt(sx)));
+        mdx = fmaxf(mdx, __double2float_ru(sqrt(sd)));
+    }
+    if (lane == 0) { part[0][wave] = mx; part[1][wave] = mdx; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) { mx = fmaxf(mx, part[0][w]); mdx = fmaxf(mdx, part[1][w]); }
+        atomicMax(&stats[0], __float_as_uint(mx));
+        atomicMax(&stats[1], __float_as_uint(mdx));
+    }
+}
+
+hipError_t cmr_launch_round_stats(int dtype, const float* rows, long long n, int dim, const int* flag, float* stats, hipStream_t s) {
+    if (n <= 0 || dtype == CMR_DT_F32) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<long long>((n + 3) / 4, 1024);
+    unsigned* st = reinterpret_cast<unsigned*>(stats);
+    if (dtype == CMR_DT_BF16) hipLaunchKernelGGL(round_stats_kernel<CMR_DT_BF16>, dim3(grid), dim3(256), 0, s, rows, n, dim, flag, st);
+    else if (dtype == CMR_DT_F16) hipLaunchKernelGGL(round_stats_kernel<CMR_DT_F16>, dim3(grid), dim3(256), 0, s, rows, n, dim, flag, st);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// The fp32 re-score ŝ(q, row): a fixed-order function of the query and the shadow row alone.  Lane j of a 16-lane group owns the
+// 4-float chunks j, j + 16, ... of the row (an fmaf chain in k order inside each chunk and across the lane's chunks), then a
+// butterfly over the 16 lanes.  VEC (dim % 4 == 0, 16-byte aligned rows and query): the same chunks as 16-byte loads — the
+// same arithmetic.  Two rows per group are walked together so that each lane has 2 x (dim / 64) loads in flight.
+template <bool VEC>
+__device__ __forceinline__ void exact_dot2(const float* __restrict__ x0, const float* __restrict__ x1, const float* __restrict__ q, int dim, int l16,
+                                           float& s0, float& s1) {
+    float a0 = 0.0f, a1 = 0.0f;
+    const int nch = (dim + 3) >> 2;
+    if (VEC) {
+        const float4* p0 = reinterpret_cast<const float4*>(x0);
+        const float4* p1 = reinterpret_cast<const float4*>(x1 ? x1 : x0);
+        const float4* pq = reinterpret_cast<const float4*>(q);
+#pragma unroll 4
+        for (int c = l16; c < nch; c += 16) {
+            const float4 u = p0[c], v = p1[c], w = pq[c];
+            a0 = fmaf(u.x, w.x, a0); a0 = fmaf(u.y, w.y, a0); a0 = fmaf(u.z, w.z, a0); a0 = fmaf(u.w, w.w, a0);
+            a1 = fmaf(v.x, w.x, a1); a1 = fmaf(v.y, w.y, a1); a1 = fmaf(v.z, w.z, a1); a1 = fmaf(v.w, w.w, a1);
+        }
+    } else {
+        const float* y1 = x1 ? x1 : x0;
+        for (int c = l16; c < nch; c += 16) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = 4 * c + e;
+                if (i < dim) { const float w = q[i]; a0 = fmaf(x0[i], w, a0); a1 = fmaf(y1[i], w, a1); }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) { a0 += __shfl_xor(a0, off); a1 += __shfl_xor(a1, off); }
+    s0 = a0; s1 = a1;
+}
+
+// global id of a stage-1 candidate -> shard-local row (-1: not a row of this index).  nb <= 1: local = gid - id_base; otherwise
+// through the block table [local0[nb] | global0[nb]] (both ascending, so the map is monotone: local order == global order).
+__device__ __forceinline__ long long exact_local_row(long long gid, long long nrows, long long id_base, const long long* __restrict__ tab, int nb) {
+    if (gid < 0) return -1;
+    long long r;
+    if (nb <= 1) r = gid - id_base;
+    else {
+        int lo = 0, hi = nb - 1;               // last block with global0 <= gid
+        if (tab[nb] > gid) return -1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (tab[nb + mid] <= gid) lo = mid; else hi = mid - 1;
+        }
+        const long long len = (lo + 1 < nb ? tab[lo + 1] : nrows) - tab[lo];
+        const long long off = gid - tab[nb + lo];
+        if (off >= len) return -1;
+        r = tab[lo] + off;
+    }
+    return (r >= 0 && r < nrows) ? r : -1;
+}
+
+#define EXACT_CPW 32          // candidates per workgroup (16 groups of 16 lanes x 2 rows)
+
+// Re-score + certify.  grid (G = ceil(kc / 32), nq): workgroup (g, q) re-scores candidates [32 g, 32 g + 32) of query q from the
+// fp32 shadow and writes their keys (score, local row) to part[q][kc]; the last of the query's G workgroups to arrive (release
+// fence, ticket from a self-re-arming counter, acquire fence) selects the k best keys in LDS and certifies the query:
+//   E_q = ||dq|| M_x + ||q|| M_dx + 2 gamma ||q~|| M_x (gamma = dim 2^-23, rounded up),  T = s~_k - 2 E_q,
+//   exact = (nrows <= kc) || (s~_kc < T)
+// where s~ are the stage-1 (16-bit scan) scores of the sorted candidate list.  Vector atomics and plain stores only.
+template <int DT, bool VEC>
+__global__ __launch_bounds__(256) void exact_certify_kernel(const float* __restrict__ shadow, int dim, long long nrows, long long id_base,
+                                                            const long long* __restrict__ tab, int nb, const float* __restrict__ q,
+                                                            const int64_t* __restrict__ cand_ids, const float* __restrict__ cand_sc, int kc, int k,
+                                                            const float* __restrict__ stats, u64* __restrict__ part, int* __restrict__ arrive,
+                                                            int64_t* __restrict__ out_ids, float* __restrict__ out_scores, int* __restrict__ out_exact) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    __shared__ u64 res[64];
+    __shared__ u64 wbest[4];
+    __shared__ double red[3][4];
+    __shared__ int ticket;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = tid >> 4, l16 = tid & 15;
+    const int qi = blockIdx.y, G = gridDim.x;
+    const float* qv = q + (size_t)qi * dim;
+    {
+        const int c0 = blockIdx.x * EXACT_CPW + grp, c1 = c0 + 16;
+        const long long r0 = c0 < kc ? exact_local_row(cand_ids[(size_t)qi * kc + c0], nrows, id_base, tab, nb) : -1;
+        const long long r1 = c1 < kc ? exact_local_row(cand_ids[(size_t)qi * kc + c1], nrows, id_base, tab, nb) : -1;
+        if (r0 >= 0 || r1 >= 0) {             // (uniform over the 16 lanes of the group)
+            const float* x0 = shadow + (size_t)(r0 >= 0 ? r0 : r1) * dim;
+            const float* x1 = r1 >= 0 && r0 >= 0 ? shadow + (size_t)r1 * dim : nullptr;
+            float s0, s1;
+            exact_dot2<VEC>(x0, x1, qv, dim, l16, s0, s1);
+            if (l16 == 0) {
+                if (c0 < kc) part[(size_t)qi * kc + c0] = r0 < 0 ? 0ull : cmr_make_key(s0, (unsigned)r0);
+                if (c1 < kc) part[(size_t)qi * kc + c1] = r1 < 0 ? 0ull : cmr_make_key(r0 >= 0 ? s1 : s0, (unsigned)r1);
+            }
+        } else if (l16 == 0) {
+            if (c0 < kc) part[(size_t)qi * kc + c0] = 0ull;
+            if (c1 < kc) part[(size_t)qi * kc + c1] = 0ull;
+        }
+    }
+    if (G > 1) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // my keys are in L2 before my ticket is
+        __syncthreads();
+        if (tid == 0) ticket = atomicAdd(&arrive[qi], 1);
+        __syncthreads();
+        if (ticket != G - 1) return;
+        if (tid == 0) arrive[qi] = 0;                               // everybody has arrived: re-armed for the next launch
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // the other workgroups' keys, not stale L1 lines
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    // selection: the k best keys of the kc re-scored candidates (unique rows: the stage-1 list holds each row once)
+    u64* pool = reinterpret_cast<u64*>(sm);
+    for (int c = tid; c < kc; c += 256) pool[c] = part[(size_t)qi * kc + c];
+    // the query's norms for E_q (fp64 sums, the packing's RNE rounding)
+    double sq = 0.0, st = 0.0, sd = 0.0;
+    for (int i = tid; i < dim; i += 256) {
+        const float f = qv[i];
+        const float t = DT == CMR_DT_BF16 ? cmr_bf2f(cmr_f2bf(f)) : cmr_h2f(cmr_f2h(f));
+        sq += (double)f * f; st += (double)t * t; sd += ((double)t - f) * ((double)t - f);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { sq += __shfl_xor(sq, off); st += __shfl_xor(st, off); sd += __shfl_xor(sd, off); }
+    if (lane == 0) { red[0][wave] = sq; red[1][wave] = st; red[2][wave] = sd; }
+    __syncthreads();
+    cmr_block_select(pool, kc, k, res, wbest);
+    for (int i = tid; i < k; i += 256) {
+        const u64 key = res[i];
+        out_ids[(size_t)qi * k + i] = key ? (int64_t)cmr_key_row(key) + id_base : -1;
+        out_scores[(size_t)qi * k + i] = key ? cmr_key_score(key) : -__builtin_inff();
+    }
+    if (tid == 0) {
+        double nq2 = 0.0, nt2 = 0.0, nd2 = 0.0;
+        for (int w = 0; w < 4; ++w) { nq2 += red[0][w]; nt2 += red[1][w]; nd2 += red[2][w]; }
+        const double mx = stats[0], mdx = stats[1], gamma = (double)dim * 0x1p-23;
+        const double e = sqrt(nd2) * mx + sqrt(nq2) * mdx + 2.0 * gamma * sqrt(nt2) * mx;
+        const float E = (float)e * (1.0f + 1e-5f) + 1e-7f;
+        int ok = nrows <= (long long)kc;
+        if (!ok) {
+            const float sk = cand_sc[(size_t)qi * kc + k - 1], slast = cand_sc[(size_t)qi * kc + kc - 1];
+            ok = cand_ids[(size_t)qi * kc + kc - 1] >= 0 && (double)slast < (double)sk - 2.0 * (double)E;
+        }
+        out_exact[qi] = ok;
+    }
+}
+
+size_t cmr_exact_part_bytes(int nq, int kc) { return (size_t)nq * kc * sizeof(u64); }
+
+hipError_t cmr_launch_exact_certify(int dtype, const float* shadow, int dim, long long nrows, long long id_base, const long long* tab, int nb,
+                                    const float* q, int nq, const int64_t* cand_ids, const float* cand_sc, int kc, int k, const float* stats,
+                                    void* part, int* arrive, int64_t* out_ids, float* out_scores, int* out_exact, hipStream_t s) {
+    if (nq <= 0) return hipSuccess;
+    if (k > 64 || kc > 4096 || kc < k) return hipErrorInvalidValue;
+    const bool vec = (dim & 3) == 0 && (reinterpret_cast<uintptr_t>(q) & 15) == 0 && (reinterpret_cast<uintptr_t>(shadow) & 15) == 0;
+    dim3 grid((unsigned)((kc + EXACT_CPW - 1) / EXACT_CPW), (unsigned)nq), block(256);
+    const size_t lds = (size_t)kc * sizeof(u64);
+    u64* pt = reinterpret_cast<u64*>(part);
+#define EC(DT, V)                                                                                                                  \
+    {                                                                                                                              \
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(exact_certify_kernel<DT, V>),                             \
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);                                 \
+        if (e != hipSuccess) return e;                                                                                             \
+        hipLaunchKernelGGL((exact_certify_kernel<DT, V>), grid, block, lds, s, shadow, dim, nrows, id_base, tab, nb, q, cand_ids,  \
+                           cand_sc, kc, k, stats, pt, arrive, out_ids, out_scores, out_exact);                                     \
+    }
+    if (dtype == CMR_DT_BF16) { if (vec) EC(CMR_DT_BF16, true) else EC(CMR_DT_BF16, false) }
+    else if (dtype == CMR_DT_F16) { if (vec) EC(CMR_DT_F16, true) else EC(CMR_DT_F16, false) }
+    else return hipErrorInvalidValue;
+#undef EC
+    return hipGetLastError();
+}

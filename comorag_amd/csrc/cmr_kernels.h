@@ -169,3 +169,14 @@ hipError_t cmr_launch_add_layernorm_pool(const void* y, const void* bias, const 
 hipError_t cmr_launch_embed_layernorm_ragged(const int* ids32, const int* off, const void* word, const void* pos, const void* type, const void* gamma,
                                              const void* beta, float eps, long long rows, int L, int d, int vocab, int n_pos, int pos_off, int dtype,
                                              void* out, hipStream_t s);
+// exact top-k of a 16-bit index (cmr_index_search_exact): rows fp32 [n, dim] (device) -> atomicMax of (max ||round(x)||, max ||round(x) - x||)
+// into stats[2] (fp32, device), skipped when *flag (the append's non-finite flag, may be NULL) is set; no-op for fp32 indexes
+hipError_t cmr_launch_round_stats(int dtype, const float* rows, long long n, int dim, const int* flag, float* stats, hipStream_t s);
+// re-score the sorted stage-1 lists cand_ids / cand_sc [nq, kc] (global ids, -1 padded; 16-bit scan scores) from the fp32 shadow,
+// select the fp32 top-k (k <= 64, kc <= 4096) and certify each query (out_exact[nq] = 0 / 1) against stats = (M_x, M_dx).
+// part: cmr_exact_part_bytes(nq, kc) of scratch; arrive: nq zeroed ints (re-armed by the kernel); output ids carry id_base
+// (shards with a block table: id_base 0, ids are local rows until remapped)
+size_t cmr_exact_part_bytes(int nq, int kc);
+hipError_t cmr_launch_exact_certify(int dtype, const float* shadow, int dim, long long nrows, long long id_base, const long long* tab, int nb,
+                                    const float* q, int nq, const int64_t* cand_ids, const float* cand_sc, int kc, int k, const float* stats,
+                                    void* part, int* arrive, int64_t* out_ids, float* out_scores, int* out_exact, hipStream_t s);

@@ -642,6 +642,38 @@ int32_t cmr_mindex_rescore(cmr_mindex_t* m, const float* q, int32_t nq, const in
     return CMR_OK;
 }
 
+// each shard certifies its own top-k (its rows outside the list cannot enter it); the global top-k is in the union of the shards'
+// lists, so the merge of certified lists is the exact top-k of the whole index
+int32_t cmr_mindex_search_exact(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores, int32_t* out_exact) {
+    if (!m || !q || !out_ids || !out_scores || !out_exact) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (nq <= 0) return cmr_fail(CMR_ERR_INVALID, "nq must be > 0");
+    if (k <= 0 || k > 64) return cmr_fail(CMR_ERR_UNSUPPORTED, "exact search supports k in [1, 64], got %d", k);
+    std::shared_lock<std::shared_mutex> lk(m->mu);
+    const std::vector<int> act = active_shards(m);
+    const int A = (int)act.size();
+    const size_t nk = (size_t)nq * k;
+    if (A == 0) {
+        for (size_t i = 0; i < nk; ++i) { out_ids[i] = -1; out_scores[i] = -INFINITY; }
+        for (int i = 0; i < nq; ++i) out_exact[i] = 1;
+        return CMR_OK;
+    }
+    if (A == 1) return cmr_index_search_exact(m->shard[act[0]], q, nq, k, out_ids, out_scores, out_exact);
+    std::vector<int64_t> ids((size_t)A * nk);
+    std::vector<float> sc((size_t)A * nk);
+    std::vector<int32_t> ex((size_t)A * nq);
+    int rc = for_active(m, act, A >= m->parallel_min_shards, [&](int a, int s) {
+        return cmr_index_search_exact(m->shard[s], q, nq, k, ids.data() + (size_t)a * nk, sc.data() + (size_t)a * nk, ex.data() + (size_t)a * nq);
+    });
+    if (rc) return rc;
+    merge_sorted_lists(ids.data(), sc.data(), A, nq, k, out_ids, out_scores);
+    for (int i = 0; i < nq; ++i) {
+        int all = 1;
+        for (int a = 0; a < A; ++a) all &= ex[(size_t)a * nq + i] != 0;
+        out_exact[i] = all;
+    }
+    return CMR_OK;
+}
+
 int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, float* out) {
     if (!m || (n > 0 && (!ids || !out))) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (n <= 0) return CMR_OK;

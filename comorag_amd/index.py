@@ -284,6 +284,44 @@ class DenseIndex:
         L.check(L.lib().cmr_index_rescore(self._h, _ptr(q), nq, _ptr(cand), nc, k, _ptr(ids), _ptr(sc)))
         return ids, sc
 
+    # -- exact fp32 top-k (a 16-bit index created with keep_f32=True; an f32 index is exact already)
+    def search_exact(self, q, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The ids / scores of the reference's fp32 np.dot + argsort (ComoRAG.py:958-966) from a bf16 / f16 index:
+        (ids int64 [nq,k'], fp32 scores [nq,k'], exact bool [nq]) with k' = min(k, len(self)), k <= 64.  exact[i] is True only
+        when the certificate proves the list is the fp32 top-k (cmr_index_search_exact)."""
+        q = _f32c(q)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"q must be [nq,{self.dim}], got {q.shape}")
+        nq = q.shape[0]
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        ex = np.empty(nq, dtype=np.int32)
+        L.check(L.lib().cmr_index_search_exact(self._h, _ptr(q), nq, k, _ptr(ids), _ptr(sc), _ptr(ex)))
+        kk = min(k, len(self))
+        return ids[:, :kk], sc[:, :kk], ex.astype(bool)
+
+    def search_exact_pipelined(self, q_t, k: int, out_ids, out_scores, out_exact, wait_event=None):
+        """`search_exact` stage 1 in throughput mode (cmr_index_search_exact_pipelined): torch CUDA tensors out_ids int64 [nq,k],
+        out_scores fp32 [nq,k], out_exact int32 [nq]; returns the done-event handle (`wait` / `sync`).  Queries with
+        out_exact == 0 may be asked again through `search_exact`."""
+        import torch
+        assert q_t.is_cuda and q_t.dtype == torch.float32 and q_t.is_contiguous() and q_t.shape[1] == self.dim
+        assert out_exact.dtype == torch.int32 and out_exact.is_contiguous()
+        done = C.c_void_p()
+        we = C.c_void_p(wait_event.cuda_event) if wait_event is not None else None
+        L.check(L.lib().cmr_index_search_exact_pipelined(
+            self._h, C.c_void_p(q_t.data_ptr()), q_t.shape[0], k, C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
+            C.c_void_p(out_exact.data_ptr()), we, C.byref(done)))
+        return done
+
+    def round_stats(self) -> Tuple[float, float]:
+        """(max ||round(x)||, max ||round(x) - x||) over the appended rows: the maxima the exact search's certificate uses."""
+        a, b = C.c_float(0), C.c_float(0)
+        L.check(L.lib().cmr_index_round_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def get_rows(self, ids) -> np.ndarray:
         ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
         out = np.empty((len(ids), self.dim), dtype=np.float32)

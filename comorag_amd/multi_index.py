@@ -140,6 +140,22 @@ class MultiDeviceIndex:
         kk = min(k, len(self))
         return ids[:, :kk], sc[:, :kk], mn, mx
 
+    def search_exact(self, q, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """DenseIndex.search_exact over every shard (cmr_mindex_search_exact): each shard certifies its top-k, the host merges;
+        exact[i] = AND over the shards."""
+        q = _f32c(q)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"q must be [nq,{self.dim}], got {q.shape}")
+        nq = q.shape[0]
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        ex = np.empty(nq, dtype=np.int32)
+        L.check(L.lib().cmr_mindex_search_exact(self._h, _ptr(q), nq, k, _ptr(ids), _ptr(sc), _ptr(ex)))
+        kk = min(k, len(self))
+        return ids[:, :kk], sc[:, :kk], ex.astype(bool)
+
     def search_min_score(self, q, k: int, min_score: float) -> Tuple[np.ndarray, np.ndarray]:
         q = _f32c(q)
         if q.ndim == 1:

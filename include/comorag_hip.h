@@ -223,6 +223,27 @@ int32_t cmr_index_sorted_scores(cmr_index_t* idx, const float* q_f32, int32_t nq
 int32_t cmr_index_rescore(cmr_index_t* idx, const float* q_f32, int32_t nq, const int64_t* cand,
                           int32_t n_cand, int32_t k, int64_t* out_ids, float* out_scores);
 
+/* Exact fp32 top-k from a 16-bit index (CMR_FLAG_KEEP_F32): the ids and scores of the reference's fp32 np.dot + argsort
+ * (ComoRAG.py:958-966), with a per-query certificate.  Stage 1 takes the scan's top-kc (option exact_cand, default
+ * CMR_MAX_K, > k) and re-scores them in fp32 from the shadow (a fixed-order fmaf chain: the same row gets the same score from every
+ * call and shard layout).  Certificate: |scan - fp32| <= E_q = ||dq|| M_x + ||q|| M_dx + 2 dim 2^-23 ||q~|| M_x for every row, so
+ * exact = 1 when the list holds every row or its last scan score is < (k-th scan score) - 2 E_q: then no row outside it can enter.
+ *   k <= 64; out_ids / out_scores [nq, k] (score descending, then id ascending; -1 / -inf padded), out_exact [nq] int32 0 / 1.
+ *   Synchronous call: queries stage 1 leaves uncertified run again on CMR_MAX_K_2PASS candidates of the two-pass search; a query
+ *   still uncertified comes back with exact = 0 and the fp32 top-k of those candidates.  An fp32 index runs the plain search
+ *   (exact by construction, every flag 1); a 16-bit index without the shadow: CMR_ERR_UNSUPPORTED.                            */
+int32_t cmr_index_search_exact(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores,
+                               int32_t* out_exact);
+/* The exact search in throughput mode (ComoRAG.py:958-966): stage 1 only, on the pipeline of cmr_index_search_pipelined; the
+ * re-score + certificate (as above: exact = 1 when nothing outside the kc candidates can beat the k-th by more than 2 E_q) runs
+ * on the post stream (stream 2) and *done_event is recorded behind it.  Device buffers; exact_dev [nq] int32.  Queries with
+ * exact = 0 may be asked again through cmr_index_search_exact.                                                                 */
+int32_t cmr_index_search_exact_pipelined(cmr_index_t* idx, const float* q_f32_dev, int32_t nq, int32_t k, int64_t* ids_dev,
+                                         float* scores_dev, int32_t* exact_dev, void* wait_event, void** done_event);
+/* The certificate's index-wide maxima in use (ComoRAG.py:958-966 is what they make exact): M_x = max ||round(x)|| and
+ * M_dx = max ||round(x) - x|| over every appended row, rounded up; 0 for an fp32 index (E_q = ||dq|| M_x + ||q|| M_dx + ...).   */
+int32_t cmr_index_round_stats(cmr_index_t* idx, float* max_row_norm, float* max_round_err);
+
 /* Gather rows back to the host as fp32 (dequantised), out [n, dim]; ids as returned by search (with the id base). */
 int32_t cmr_index_get_rows(cmr_index_t* idx, const int64_t* ids, int64_t n, float* out);
 
@@ -340,6 +361,11 @@ int32_t cmr_mindex_sorted_scores(cmr_mindex_t* m, const float* q_f32, int32_t nq
 int32_t cmr_mindex_rescore(cmr_mindex_t* m, const float* q_f32, int32_t nq, const int64_t* cand, int32_t n_cand, int32_t k,
                            int64_t* out_ids, float* out_scores);
 int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, float* out);
+/* Exact fp32 top-k over every shard (ComoRAG.py:958-966): each shard certifies its local top-k (cmr_index_search_exact: exact when
+ * no row outside its candidates can beat its k-th by more than 2 E_q), the host merges the fp32 lists with the exported tie rule,
+ * out_exact = AND over the shards.                                                                                             */
+int32_t cmr_mindex_search_exact(cmr_mindex_t* m, const float* q_f32, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores,
+                                int32_t* out_exact);
 int32_t cmr_mindex_search_pipelined(cmr_mindex_t* m, const float* const* q_dev /*[n_shards]*/, int32_t nq, int32_t k, void** ticket);
 int32_t cmr_mindex_collect(cmr_mindex_t* m, void* ticket, int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
 /* host-side cost of the throughput mode since the last reset: collected batches, mean microseconds a shard's enqueue job took
