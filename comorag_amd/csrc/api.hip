@@ -1045,11 +1045,13 @@ int append_from_device(cmr_index* idx, const float* rows_dev, long long n, hipSt
 
 }  // namespace
 
-// ---- for ppr.hip: one host query -> N raw scores in the workspace's device buffer, index lock + workspace kept until release
+// ---- for ppr.hip: host queries -> N raw scores each in the workspace's device buffer, index lock + workspace kept until release
 namespace { thread_local Workspace* tl_scores_ws = nullptr; }
 
-int cmr_index_scores_to_device(cmr_index_t* idx, const float* q_host, float** scores_dev, long long* n, void** stream) {
-    if (!idx || !q_host || !scores_dev || !n || !stream) return fail(CMR_ERR_INVALID, "NULL argument");
+// nb host queries [nb, dim] -> [nb, n] scores.  Row b must hold the bits a ONE-query scan of query b gives (the batched PPR promises
+// what the single call returns).
+int cmr_index_scores_to_device_batch(cmr_index_t* idx, const float* q_host, int nb, float** scores_dev, long long* n, void** stream) {
+    if (!idx || !q_host || !scores_dev || !n || !stream || nb < 1) return fail(CMR_ERR_INVALID, "NULL argument");
     if (tl_scores_ws) return fail(CMR_ERR_INVALID, "nested cmr_index_scores_to_device on one thread");
     idx->mu.lock_shared();
     int rc = set_device(idx->device);
@@ -1058,14 +1060,22 @@ int cmr_index_scores_to_device(cmr_index_t* idx, const float* q_host, float** sc
     if (!rc) {
         hipStream_t s = ws->stream;
         auto body = [&]() -> int {
-            const size_t q_bytes = (size_t)idx->dim * 4;
+            const size_t q_bytes = (size_t)nb * idx->dim * 4;
             HIP_TRY(ws->d_q.ensure(q_bytes));
-            HIP_TRY(ws->d_out.ensure(std::max<size_t>((size_t)idx->n * 4, 8)));
+            HIP_TRY(ws->d_out.ensure(std::max<size_t>((size_t)nb * idx->n * 4, 8)));
             HIP_TRY(ws->ensure_pin(q_bytes));
             memcpy(ws->h_pin, q_host, q_bytes);
             HIP_TRY(hipMemcpyAsync(ws->d_q.p, ws->h_pin, q_bytes, hipMemcpyHostToDevice, s));
             if (idx->n == 0) return CMR_OK;
-            return scores_enqueue(idx, ws, (const float*)ws->d_q.p, 1, (float*)ws->d_out.p, idx->n);
+            // up to 32 queries share ONE geometry (make_geom: nqt = 1, the same kernel variant and grid as a one-query scan) and a query
+            // is one MFMA column whose products and sums never meet another column's: one nq = nb scan gives every row its one-query bits
+            // (checked on the device at 5 K x 128, 5 K x 768 and 200 K x 768, f32 and bf16).  Above 32 the tile changes: one by one, no sync.
+            if (nb <= 32) return scores_enqueue(idx, ws, (const float*)ws->d_q.p, nb, (float*)ws->d_out.p, idx->n);
+            for (int b = 0; b < nb; ++b) {
+                int rc_ = scores_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)b * idx->dim, 1, (float*)ws->d_out.p + (size_t)b * idx->n, idx->n);
+                if (rc_) return rc_;
+            }
+            return CMR_OK;
         };
         rc = body();
         if (rc) (void)hipStreamSynchronize(s);
@@ -1078,6 +1088,15 @@ int cmr_index_scores_to_device(cmr_index_t* idx, const float* q_host, float** sc
     tl_scores_ws = ws;
     *scores_dev = (float*)ws->d_out.p; *n = idx->n; *stream = (void*)ws->stream;
     return CMR_OK;
+}
+
+int cmr_index_scores_to_device(cmr_index_t* idx, const float* q_host, float** scores_dev, long long* n, void** stream) {
+    return cmr_index_scores_to_device_batch(idx, q_host, 1, scores_dev, n, stream);
+}
+
+long long cmr_index_row_count(cmr_index_t* idx) {      // for ppr.hip's argument checks (no device call)
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    return idx->n;
 }
 
 int cmr_index_scores_release(cmr_index_t* idx) {

@@ -11,6 +11,7 @@ scope), exactly the numeric call sites of SURVEY.md §8a:
     MemoryPool.retrieve_similar_nodes  utils/memory_utils.py:188-235 (instance-level, optional)
     run_ppr                     ComoRAG.py:1086-1105         → power iteration on a CSR copy of the graph in HBM (no igraph call)
     graph_search_with_fact_entities  :992-1053               → its passage loop + run_ppr fused on the device (cmr_index_ppr)
+    graph_search_with_fact_entities_batch  (new method)      → the same for a list of calls, ONE batched PageRank (cmr_index_ppr_batch)
 Everything else (LLM calls, graph construction, clustering) keeps running the reference's code.
 """
 from __future__ import annotations
@@ -65,7 +66,8 @@ def install(rag, index_dtype: Optional[str] = None, device: int = 0, patch_modul
     CPU-tier binding tests pass a numpy stand-in there to exercise this glue on the real reference classes without a GPU.
     `graph_factory(igraph_like, device) -> graph` likewise (default `comorag_amd.ppr.DeviceGraph.from_igraph`); it must offer
     `set_passage_vertices(idxs)` and `ppr(reset, damping)`; the fused path additionally goes through
-    `comorag_amd.ppr.ppr_passage_scores` unless the graph object brings its own `passage_scores(index, q, phrase_w, pnw, damping)`."""
+    `comorag_amd.ppr.ppr_passage_scores` unless the graph object brings its own `passage_scores(index, q, phrase_w, pnw, damping)`.
+    `graph_search_with_fact_entities_batch` uses the graph's `ppr_batch(resets, damping, tol, max_iter)` where it has one and loops otherwise."""
     cfg = getattr(rag, "global_config", None)
     dtype = index_dtype or getattr(cfg, "index_dtype", None) or "f32"
     n_sh = num_shards if num_shards is not None else getattr(cfg, "num_shards", None)
@@ -154,6 +156,23 @@ def install(rag, index_dtype: Optional[str] = None, device: int = 0, patch_modul
         g, index = self._hip["graph"], self._hip["passage"]
         if g is None or index is None:
             return orig_graph_search(query, link_top_k, query_fact_scores, top_k_facts, top_k_fact_indices, passage_node_weight)
+        q, phrase_weights, used_phrases_with_scores = _graph_search_host(self, g, index, query, link_top_k, query_fact_scores, top_k_facts,
+                                                                         top_k_fact_indices, passage_node_weight)
+        if hasattr(g, "passage_scores"):
+            doc_scores = g.passage_scores(index, q, phrase_weights, passage_node_weight, 0.5)
+        else:
+            from . import ppr
+            doc_scores = ppr.ppr_passage_scores(index, g, q, phrase_weights, passage_node_weight, 0.5)
+        return _ranked(self, doc_scores, used_phrases_with_scores)
+
+    def _ranked(self, doc_scores, used_phrases_with_scores):
+        sorted_doc_ids = np.argsort(doc_scores)[::-1]
+        sorted_doc_scores = doc_scores[sorted_doc_ids.tolist()]
+        assert len(sorted_doc_ids) == len(self.passage_node_idxs)
+        return sorted_doc_ids, sorted_doc_scores, used_phrases_with_scores
+
+    def _graph_search_host(self, g, index, query, link_top_k, query_fact_scores, top_k_facts, top_k_fact_indices, passage_node_weight):
+        """The host part of graph_search_with_fact_entities: (query vector, phrase weights [n_vertices], used phrases)."""
         from importlib import import_module
         mdhash = import_module(type(self).__module__).compute_mdhash_id
         phrase_weights = np.zeros(len(self.node_name_to_vertex_idx) if not hasattr(g, "n_vertices") else g.n_vertices)
@@ -179,21 +198,40 @@ def install(rag, index_dtype: Optional[str] = None, device: int = 0, patch_modul
         # positive passage_node_weight (the best passage normalises to 1.0), so the test needs no score from the device
         assert phrase_weights.sum() > 0 or (len(index) > 0 and passage_node_weight > 0), \
             f'No phrases found in the graph for the given facts: {top_k_facts}'
-        if hasattr(g, "passage_scores"):
-            doc_scores = g.passage_scores(index, q, phrase_weights, passage_node_weight, 0.5)
-        else:
-            from . import ppr
-            doc_scores = ppr.ppr_passage_scores(index, g, q, phrase_weights, passage_node_weight, 0.5)
-        sorted_doc_ids = np.argsort(doc_scores)[::-1]
-        sorted_doc_scores = doc_scores[sorted_doc_ids.tolist()]
-        assert len(sorted_doc_ids) == len(self.passage_node_idxs)
-        return sorted_doc_ids, sorted_doc_scores, used_phrases_with_scores
+        return q, phrase_weights, used_phrases_with_scores
+
+    def graph_search_with_fact_entities_batch(self, calls):
+        """`calls`: a list of graph_search_with_fact_entities' argument tuples (query, link_top_k, query_fact_scores, top_k_facts,
+        top_k_fact_indices[, passage_node_weight]) — what ComoRAG.try_answer's threads (ComoRAG.py:432-453) each pass.  Returns the list
+        of what the single method returns for each, bit for bit: the host part runs per call, the device part is ONE batched
+        scan + PageRank per distinct passage_node_weight (comorag_amd.ppr.ppr_passage_scores_batch).  A graph object that brings its own
+        `passage_scores` and nothing batched is served call by call."""
+        g, index = self._hip["graph"], self._hip["passage"]
+        calls = [tuple(c) for c in calls]
+        if g is None or index is None or (hasattr(g, "passage_scores") and not hasattr(g, "passage_scores_batch")):
+            return [self.graph_search_with_fact_entities(*c) for c in calls]
+        pnws = [float(c[5]) if len(c) > 5 else 0.05 for c in calls]
+        host = [_graph_search_host(self, g, index, *c[:5], pnw) for c, pnw in zip(calls, pnws)]
+        out = [None] * len(calls)
+        for pnw in sorted(set(pnws)):
+            sel = [i for i, p in enumerate(pnws) if p == pnw]
+            Q = np.stack([np.asarray(host[i][0], dtype=np.float32).reshape(-1) for i in sel])
+            pw = [host[i][1] for i in sel]
+            if hasattr(g, "passage_scores_batch"):
+                scores = g.passage_scores_batch(index, Q, pw, pnw, 0.5)
+            else:
+                from . import ppr
+                scores = ppr.ppr_passage_scores_batch(index, g, Q, pw, pnw, 0.5)
+            for i, doc_scores in zip(sel, scores):
+                out[i] = _ranked(self, np.asarray(doc_scores), host[i][2])
+        return out
 
     fns = [prepare_retrieval_objects, get_query_embeddings, get_fact_scores, dense_passage_retrieval]
     if ppr_on_device and orig_run_ppr is not None:
         fns.append(run_ppr)
     if ppr_on_device and orig_graph_search is not None:
         fns.append(graph_search_with_fact_entities)
+        fns.append(graph_search_with_fact_entities_batch)
     for fn in fns:
         setattr(rag, fn.__name__, types.MethodType(fn, rag))
 

@@ -62,6 +62,21 @@ class DeviceGraph:
         self.last_iters = it.value
         return out
 
+    def ppr_batch(self, resets, damping: float = 0.5, tol: float = 1e-12, max_iter: int = 200) -> np.ndarray:
+        """`ppr` for B reset vectors [B, n_vertices] at once -> [B, n_vertices]; row b is `ppr(resets[b])` bit for bit.  The device runs
+        up to CMR_PPR_MAX_BATCH queries per power iteration (the graph is read once per step for all of them); larger B goes in chunks."""
+        r = np.ascontiguousarray(resets, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != self.n_vertices:
+            raise ValueError(f"resets must be [B, {self.n_vertices}]")
+        out = np.empty(r.shape, dtype=np.float64)
+        it = C.c_int32(0)
+        for b0 in range(0, r.shape[0], L.CMR_PPR_MAX_BATCH):
+            nb = min(L.CMR_PPR_MAX_BATCH, r.shape[0] - b0)
+            L.check(L.lib().cmr_graph_ppr_batch(self._h, r[b0:b0 + nb].ctypes.data_as(C.c_void_p), nb, float(damping), float(tol), int(max_iter),
+                                                out[b0:b0 + nb].ctypes.data_as(C.c_void_p), C.byref(it)))
+            self.last_iters = it.value
+        return out
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             L.lib().cmr_graph_destroy(self._h)
@@ -128,3 +143,76 @@ def ppr_passage_ranking(index, graph: DeviceGraph, query_embedding, phrase_weigh
     doc_scores = ppr_passage_scores(index, graph, query_embedding, phrase_weights, passage_node_weight, damping)
     sorted_doc_ids = np.argsort(doc_scores)[::-1]
     return sorted_doc_ids, doc_scores[sorted_doc_ids.tolist()]
+
+
+def _seed_arrays(phrase_weights) -> Tuple[np.ndarray, np.ndarray]:
+    """(vertices int32, weights float64) of one query's phrase weights, as `ppr_passage_scores` ships them."""
+    if phrase_weights is None:
+        return np.empty(0, np.int32), np.empty(0, np.float64)
+    if isinstance(phrase_weights, tuple):
+        return np.ascontiguousarray(phrase_weights[0], np.int32), np.ascontiguousarray(phrase_weights[1], np.float64)
+    pw = np.asarray(phrase_weights, dtype=np.float64)
+    sv = np.flatnonzero(pw != 0).astype(np.int32)
+    return sv, np.ascontiguousarray(pw[sv])
+
+
+def ppr_passage_scores_batch(index, graph, query_embeddings, phrase_weights: Optional[Sequence] = None, passage_node_weight: float = 0.05,
+                             damping: float = 0.5, tol: float = 1e-12, max_iter: int = 200) -> np.ndarray:
+    """`ppr_passage_scores` for B queries [B, d] -> [B, n_rows]; row b is the single call's result for (Q[b], phrase_weights[b]) bit for
+    bit.  `phrase_weights`: None, or one entry per query (dense array | (vertices, weights) | None).  The B power iterations run as one
+    (ComoRAG.try_answer issues up to 16 graph searches at once, ComoRAG.py:432-453); B above CMR_PPR_MAX_BATCH goes in chunks."""
+    Q = np.ascontiguousarray(np.asarray(query_embeddings, dtype=np.float32))
+    if Q.ndim != 2:
+        raise ValueError("query_embeddings must be [B, d]")
+    B = Q.shape[0]
+    pws = [None] * B if phrase_weights is None else list(phrase_weights)
+    if len(pws) != B:
+        raise ValueError(f"{len(pws)} phrase-weight entries for {B} queries")
+    if hasattr(index, "n_shards") or not hasattr(index, "_h"):
+        # row-sharded index: the host branch of ppr_passage_scores, the scores of all B queries in one call, the reference's
+        # lines per row, ONE batched PageRank
+        from .utils.misc_utils import min_max_normalize
+        S = index.scores(Q) if B else np.empty((0, 0), np.float32)
+        resets = np.zeros((B, graph.n_vertices), dtype=np.float64)
+        for b in range(B):
+            norm = min_max_normalize(S[b])
+            reset = resets[b]
+            if pws[b] is not None:
+                if isinstance(pws[b], tuple):
+                    np.add.at(reset, np.asarray(pws[b][0], np.int64), np.asarray(pws[b][1], np.float64))
+                else:
+                    reset += np.asarray(pws[b], dtype=np.float64)
+            reset[graph.passage_vertices] += norm.astype(np.float64) * float(passage_node_weight)
+        if B == 0:
+            return np.empty((0, len(graph.passage_vertices)), dtype=np.float64)
+        return np.ascontiguousarray(_graph_ppr_batch(graph, resets, damping, tol, max_iter)[:, graph.passage_vertices])
+    out = np.empty((B, graph.n_rows), dtype=np.float64)
+    it = C.c_int32(0)
+    for b0 in range(0, B, L.CMR_PPR_MAX_BATCH):
+        nb = min(L.CMR_PPR_MAX_BATCH, B - b0)
+        seeds = [_seed_arrays(pw) for pw in pws[b0:b0 + nb]]
+        off = np.zeros(nb + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(v) for v, _ in seeds])
+        sv = np.ascontiguousarray(np.concatenate([v for v, _ in seeds]), dtype=np.int32)
+        sw = np.ascontiguousarray(np.concatenate([w for _, w in seeds]), dtype=np.float64)
+        L.check(L.lib().cmr_index_ppr_batch(index._h, graph._h, Q[b0:b0 + nb].ctypes.data_as(C.c_void_p), nb, off.ctypes.data_as(C.c_void_p),
+                                            sv.ctypes.data_as(C.c_void_p), sw.ctypes.data_as(C.c_void_p), float(passage_node_weight), float(damping),
+                                            float(tol), int(max_iter), out[b0:b0 + nb].ctypes.data_as(C.c_void_p), C.byref(it)))
+    return out
+
+
+def _graph_ppr_batch(graph, resets: np.ndarray, damping: float, tol: float, max_iter: int) -> np.ndarray:
+    """graph.ppr_batch, or — a custom graph object without it — its `ppr` row by row."""
+    if hasattr(graph, "ppr_batch"):
+        return np.asarray(graph.ppr_batch(resets, damping=damping, tol=tol, max_iter=max_iter))
+    return np.stack([np.asarray(graph.ppr(r, damping=damping, tol=tol, max_iter=max_iter)) for r in resets])
+
+
+def ppr_passage_ranking_batch(index, graph, query_embeddings, phrase_weights: Optional[Sequence] = None, passage_node_weight: float = 0.05,
+                              damping: float = 0.5) -> list:
+    """[(sorted_doc_ids, sorted_doc_scores)] per query, each exactly as ComoRAG.run_ppr returns them (ComoRAG.py:1101-1105)."""
+    out = []
+    for doc_scores in ppr_passage_scores_batch(index, graph, query_embeddings, phrase_weights, passage_node_weight, damping):
+        sorted_doc_ids = np.argsort(doc_scores)[::-1]
+        out.append((sorted_doc_ids, doc_scores[sorted_doc_ids.tolist()]))
+    return out

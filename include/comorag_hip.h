@@ -282,6 +282,22 @@ int32_t cmr_graph_ppr(cmr_graph_t* g, const double* reset, double damping, doubl
 int32_t cmr_index_ppr(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, const int32_t* seed_vertices,
                       const double* seed_weights, int32_t n_seeds, double passage_node_weight, double damping, double tol,
                       int32_t max_iter, double* out_doc_scores, int32_t* iters);
+/* The same for nb <= CMR_PPR_MAX_BATCH queries per power iteration (ComoRAG.try_answer, ComoRAG.py:432-453, runs up to 16
+ * graph searches at once, each ending in run_ppr :1086-1105): the graph is read once per step for all of them.  More than
+ * CMR_PPR_MAX_BATCH: CMR_ERR_UNSUPPORTED (split the batch; comorag_amd/ppr.py does).  Arguments are checked before any
+ * device call (CMR_ERR_INVALID).  One NaN / Inf query fails the whole batch (CMR_ERR_NONFINITE).
+ *   cmr_graph_ppr_batch   run_ppr for nb reset vectors (:1086-1105 from each thread of :432-453): reset / out_scores
+ *                         [nb, n_vertices] row-major, the caller's vertex order; row b equals cmr_graph_ppr(reset[b]) bit for bit.
+ *   cmr_index_ppr_batch   cmr_index_ppr for nb queries (:1034-1044 + :1086-1105 each): q_f32 [nb, dim]; seeds in CSR form:
+ *                         seed_offsets [nb + 1], seed_vertices / seed_weights [seed_offsets[nb]] (duplicates within one query
+ *                         are summed in input order, as in cmr_index_ppr); out_doc_scores [nb, n_rows].  Row b equals
+ *                         cmr_index_ppr(q[b], seeds of b) bit for bit.                                                       */
+#define CMR_PPR_MAX_BATCH 16
+int32_t cmr_graph_ppr_batch(cmr_graph_t* g, const double* reset, int32_t nb, double damping, double tol, int32_t max_iter,
+                            double* out_scores, int32_t* iters);
+int32_t cmr_index_ppr_batch(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, int32_t nb, const int32_t* seed_offsets,
+                            const int32_t* seed_vertices, const double* seed_weights, double passage_node_weight,
+                            double damping, double tol, int32_t max_iter, double* out_doc_scores, int32_t* iters);
 
 /* ---- row-shard exchange ------------------------------------------------------------------
  * One process per GPU, each with a row shard (cmr_index_set_id_base makes its searches return global ids).  Per query
