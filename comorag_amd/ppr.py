@@ -100,35 +100,48 @@ def run_ppr(graph: DeviceGraph, reset_prob, passage_node_idxs, damping: Optional
     return sorted_doc_ids, sorted_doc_scores
 
 
+def _seed_arrays(phrase_weights) -> Tuple[np.ndarray, np.ndarray]:
+    """(vertices int32, weights float64) of one query's phrase weights, as the fused calls ship them."""
+    if phrase_weights is None:
+        return np.empty(0, np.int32), np.empty(0, np.float64)
+    if isinstance(phrase_weights, tuple):
+        return np.ascontiguousarray(phrase_weights[0], np.int32), np.ascontiguousarray(phrase_weights[1], np.float64)
+    pw = np.asarray(phrase_weights, dtype=np.float64)
+    sv = np.flatnonzero(pw != 0).astype(np.int32)
+    return sv, np.ascontiguousarray(pw[sv])
+
+
+def _host_branch(index) -> bool:
+    """A row-sharded index (MultiDeviceIndex) or any index without a device handle: its shards live on several devices, the graph on
+    one — the N scores come to the host once (4 N bytes), the reset vector is built there, PageRank runs on the device."""
+    return hasattr(index, "n_shards") or not hasattr(index, "_h")
+
+
+def _host_reset(graph, scores, phrase_weights, passage_node_weight: float) -> np.ndarray:
+    """One query's reset vector by the reference's own lines (ComoRAG.py:1034-1045): min-max, score x passage_node_weight into the
+    passages' vertices, product in float64 as numpy 1.26 forms it."""
+    from .utils.misc_utils import min_max_normalize
+    norm = min_max_normalize(scores)
+    reset = np.zeros(graph.n_vertices, dtype=np.float64)
+    if phrase_weights is not None:
+        if isinstance(phrase_weights, tuple):
+            np.add.at(reset, np.asarray(phrase_weights[0], np.int64), np.asarray(phrase_weights[1], np.float64))
+        else:
+            reset += np.asarray(phrase_weights, dtype=np.float64)
+    reset[graph.passage_vertices] += norm.astype(np.float64) * float(passage_node_weight)
+    return reset
+
+
 def ppr_passage_scores(index, graph: DeviceGraph, query_embedding, phrase_weights=None, passage_node_weight: float = 0.05,
                        damping: float = 0.5, tol: float = 1e-12, max_iter: int = 200) -> np.ndarray:
     """The fused path for one query: doc_scores[i] = pagerank[vertex of passage row i], with the DPR scores scattered into
     the reset vector on the device.  `phrase_weights`: dense [n_vertices] array (only its non-zero entries are shipped)
     or a (vertices, weights) pair.  `graph.set_passage_vertices(...)` must map every row of `index`."""
     q = np.ascontiguousarray(np.asarray(query_embedding, dtype=np.float32).reshape(-1))
-    if hasattr(index, "n_shards") or not hasattr(index, "_h"):
-        # a row-sharded index (MultiDeviceIndex): its shards live on several devices, the graph on one — the N scores come to
-        # the host once (4 N bytes), the reference's own lines build the reset vector (ComoRAG.py:1034-1045: min-max, score x
-        # passage_node_weight into the passages' vertices, product in float64 as numpy 1.26 forms it), PageRank runs on the device
-        from .utils.misc_utils import min_max_normalize
-        s = index.scores(q[None, :])[0]
-        norm = min_max_normalize(s)
-        reset = np.zeros(graph.n_vertices, dtype=np.float64)
-        if phrase_weights is not None:
-            if isinstance(phrase_weights, tuple):
-                np.add.at(reset, np.asarray(phrase_weights[0], np.int64), np.asarray(phrase_weights[1], np.float64))
-            else:
-                reset += np.asarray(phrase_weights, dtype=np.float64)
-        reset[graph.passage_vertices] += norm.astype(np.float64) * float(passage_node_weight)
+    if _host_branch(index):
+        reset = _host_reset(graph, index.scores(q[None, :])[0], phrase_weights, passage_node_weight)
         return graph.ppr(reset, damping=damping, tol=tol, max_iter=max_iter)[graph.passage_vertices]
-    if phrase_weights is None:
-        sv, sw = np.empty(0, np.int32), np.empty(0, np.float64)
-    elif isinstance(phrase_weights, tuple):
-        sv, sw = np.ascontiguousarray(phrase_weights[0], np.int32), np.ascontiguousarray(phrase_weights[1], np.float64)
-    else:
-        pw = np.asarray(phrase_weights, dtype=np.float64)
-        sv = np.flatnonzero(pw != 0).astype(np.int32)
-        sw = np.ascontiguousarray(pw[sv])
+    sv, sw = _seed_arrays(phrase_weights)
     out = np.empty(graph.n_rows, dtype=np.float64)
     it = C.c_int32(0)
     L.check(L.lib().cmr_index_ppr(index._h, graph._h, q.ctypes.data_as(C.c_void_p), sv.ctypes.data_as(C.c_void_p), sw.ctypes.data_as(C.c_void_p),
@@ -145,17 +158,6 @@ def ppr_passage_ranking(index, graph: DeviceGraph, query_embedding, phrase_weigh
     return sorted_doc_ids, doc_scores[sorted_doc_ids.tolist()]
 
 
-def _seed_arrays(phrase_weights) -> Tuple[np.ndarray, np.ndarray]:
-    """(vertices int32, weights float64) of one query's phrase weights, as `ppr_passage_scores` ships them."""
-    if phrase_weights is None:
-        return np.empty(0, np.int32), np.empty(0, np.float64)
-    if isinstance(phrase_weights, tuple):
-        return np.ascontiguousarray(phrase_weights[0], np.int32), np.ascontiguousarray(phrase_weights[1], np.float64)
-    pw = np.asarray(phrase_weights, dtype=np.float64)
-    sv = np.flatnonzero(pw != 0).astype(np.int32)
-    return sv, np.ascontiguousarray(pw[sv])
-
-
 def ppr_passage_scores_batch(index, graph, query_embeddings, phrase_weights: Optional[Sequence] = None, passage_node_weight: float = 0.05,
                              damping: float = 0.5, tol: float = 1e-12, max_iter: int = 200) -> np.ndarray:
     """`ppr_passage_scores` for B queries [B, d] -> [B, n_rows]; row b is the single call's result for (Q[b], phrase_weights[b]) bit for
@@ -168,21 +170,12 @@ def ppr_passage_scores_batch(index, graph, query_embeddings, phrase_weights: Opt
     pws = [None] * B if phrase_weights is None else list(phrase_weights)
     if len(pws) != B:
         raise ValueError(f"{len(pws)} phrase-weight entries for {B} queries")
-    if hasattr(index, "n_shards") or not hasattr(index, "_h"):
-        # row-sharded index: the host branch of ppr_passage_scores, the scores of all B queries in one call, the reference's
-        # lines per row, ONE batched PageRank
-        from .utils.misc_utils import min_max_normalize
+    if _host_branch(index):
+        # the scores of all B queries in one call, the reset vector per row, ONE batched PageRank
         S = index.scores(Q) if B else np.empty((0, 0), np.float32)
         resets = np.zeros((B, graph.n_vertices), dtype=np.float64)
         for b in range(B):
-            norm = min_max_normalize(S[b])
-            reset = resets[b]
-            if pws[b] is not None:
-                if isinstance(pws[b], tuple):
-                    np.add.at(reset, np.asarray(pws[b][0], np.int64), np.asarray(pws[b][1], np.float64))
-                else:
-                    reset += np.asarray(pws[b], dtype=np.float64)
-            reset[graph.passage_vertices] += norm.astype(np.float64) * float(passage_node_weight)
+            resets[b] = _host_reset(graph, S[b], pws[b], passage_node_weight)
         if B == 0:
             return np.empty((0, len(graph.passage_vertices)), dtype=np.float64)
         return np.ascontiguousarray(_graph_ppr_batch(graph, resets, damping, tol, max_iter)[:, graph.passage_vertices])
