@@ -8,7 +8,10 @@ Steps
     a variant whose ring registers are touched by compiler-generated code (after their first
     asm load) is marked unsafe
     and the library falls back to the compiler-counted ring for it → ring_audit.cpp
- 3. hipcc -c aux_kernels.hip api.hip ring_audit.cpp ; link → comorag_amd/lib/libcomorag_hip.so
+ 3. hipcc -c every other file of SOURCES (aux_kernels.hip, api.hip, comm.hip, ppr.hip, encoder_kernels.hip, multi.hip) and
+    ring_audit.cpp ; link → comorag_amd/lib/libcomorag_hip.so
+SOURCES and HEADERS also feed the build stamp: a file the library is built from and that is missing there would let a stale
+library pass for fresh.
 The .so is git-ignored but travels to the GPU box with the gpurun snapshot.
 """
 from __future__ import annotations
@@ -37,7 +40,7 @@ if os.environ.get("CMR_BUILD_LIB"):          # experiment builds go to their own
 # unrolled size exceeds LLVM's default limit for "#pragma unroll" (16 K) and hipcc silently keeps the loops.
 SCAN_FLAGS = ["-mllvm", "-pragma-unroll-threshold=1048576"]
 SOURCES = ["scan_kernels.hip", "aux_kernels.hip", "api.hip", "comm.hip", "ppr.hip", "encoder_kernels.hip", "multi.hip"]
-HEADERS = ["cmr_device.h", "cmr_kernels.h", "cmr_internal.h", "cmr_select.h", os.path.join("..", "..", "include", "comorag_hip.h")]
+HEADERS = ["cmr_device.h", "cmr_kernels.h", "cmr_internal.h", "cmr_select.h", "index_state.h", "search_plan.h", os.path.join("..", "..", "include", "comorag_hip.h")]
 
 _KERNEL_RE = re.compile(r"^_Z11scan_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEv5ScanP:")
 
@@ -379,7 +382,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
                     "        }\n"
                     "    return any;\n"
                     "}\n")
-        for src in ("aux_kernels.hip", "api.hip", "comm.hip", "ppr.hip", "encoder_kernels.hip", "multi.hip"):
+        for src in SOURCES[1:]:       # (scan_kernels.hip was compiled above, with its own flags)
             o = os.path.join(tmp, src.replace(".hip", ".o"))
             _run([HIPCC, *FLAGS, "-c", os.path.join(CSRC, src), "-o", o], cwd=tmp)
             objs.append(o)

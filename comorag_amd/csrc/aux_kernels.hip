@@ -2,8 +2,11 @@
 // merges, exact re-score, row gather and the encoder tail (masked mean-pool + L2 normalise).
 // All are launch-latency or HBM bound; none uses MFMA.
 #include <algorithm>
+#include <map>
+#include <mutex>
 
 #include "cmr_device.h"
+#include "cmr_internal.h"
 #include "cmr_kernels.h"
 #include "cmr_select.h"
 
@@ -1466,3 +1469,33 @@ hipError_t cmr_launch_exact_certify(int dtype, const float* shadow, int dim, lon
 #undef EC
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------ C-ABI (include/comorag_hip.h)
+extern "C" {
+
+int32_t cmr_pool_l2norm(int32_t device_id, const void* hidden_dev, int32_t hidden_dtype, const int64_t* mask_dev, int32_t b,
+                        int32_t l, int32_t d, int32_t normalize, float* out_dev, void* stream) {
+    if (!hidden_dev || !mask_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (b <= 0 || l <= 0 || d <= 0) return cmr_fail(CMR_ERR_INVALID, "b, l, d must be > 0");
+    if (hidden_dtype != CMR_F32 && hidden_dtype != CMR_BF16 && hidden_dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "unknown dtype");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    const int splits = cmr_pool_splits(b, l, d);
+    // partials live in a per-device, per-stream scratch that grows on demand
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, DevBuf> scratch;
+    float* partial = nullptr;
+    {
+        std::lock_guard<std::mutex> g(mu);
+        DevBuf& bf = scratch[{device_id, (hipStream_t)stream}];
+        if (bf.cap < (size_t)b * splits * d * 4) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        HIP_TRY(bf.ensure((size_t)b * splits * d * 4));
+        partial = (float*)bf.p;
+    }
+    HIP_TRY(cmr_launch_pool(hidden_dev, hidden_dtype, mask_dev, b, l, d, normalize, partial, out_dev, splits, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+}  // extern "C"

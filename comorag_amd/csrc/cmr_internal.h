@@ -1,11 +1,47 @@
-// Library-internal entry points shared by api.hip, comm.hip and multi.hip.  NOT part of the C-ABI (include/comorag_hip.h).
+// Library-internal entry points and helpers shared by the host sources (api.hip, comm.hip, multi.hip, ppr.hip and the entry points
+// at the end of aux_kernels.hip / encoder_kernels.hip).  NOT part of the C-ABI (include/comorag_hip.h).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 #include "../../include/comorag_hip.h"
 
 // sets the calling thread's error message (cmr_last_error) and returns `code`
 int cmr_fail(int code, const char* fmt, ...);
+
+// the one HIP error check of the library: returns from the calling function with the error text set
+#define HIP_TRY(expr)                                                                             \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) {                                                                   \
+            const int code_ = (e_ == hipErrorOutOfMemory) ? CMR_ERR_OOM                           \
+                              : (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? CMR_ERR_NO_DEVICE \
+                                                                                        : CMR_ERR_HIP; \
+            return cmr_fail(code_, "%s failed: %s", #expr, hipGetErrorString(e_));                \
+        }                                                                                         \
+    } while (0)
+
+// device of the calling thread / is `device_id` a gfx950 this library can run on (api.hip; validated devices are remembered)
+__attribute__((visibility("hidden"))) int cmr_set_device(int device);
+__attribute__((visibility("hidden"))) int cmr_check_device(int device_id);
+
+// a device buffer that only grows
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t need) {
+        if (need <= cap) return hipSuccess;
+        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
+        size_t want = std::max(need, cap * 2);
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) return e;
+        cap = want;
+        return hipSuccess;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
 
 // cmr_index_search in two halves: `begin` enqueues the whole search on a workspace stream of the index and returns at once,
 // `finish` waits for it, reports a non-finite query and copies ids / scores / min / max out (any of them may be NULL).  Every
@@ -19,3 +55,10 @@ void cmr_index_search_abandon(CmrPending* p);
 
 // shrink an index to its first n_rows rows (roll-back of a multi-shard append that failed on a later shard)
 int cmr_index_truncate(cmr_index_t* idx, long long n_rows);
+
+// for ppr.hip: scores of nb host queries [nb, dim] into a device buffer [nb, n] of the index's workspace, row b holding the bits a
+// one-query scan of q_host[b] gives (shared index lock held, workspace reserved for the calling thread) until
+// cmr_index_scores_release, which also reports a non-finite query
+int cmr_index_scores_to_device_batch(cmr_index_t* idx, const float* q_host, int nb, float** scores_dev, long long* n, void** stream);
+int cmr_index_scores_release(cmr_index_t* idx);
+long long cmr_index_row_count(cmr_index_t* idx);      // (no device call)

@@ -15,9 +15,8 @@
 
 #include "../../include/comorag_hip.h"
 #include "cmr_device.h"
+#include "cmr_internal.h"
 #include "cmr_kernels.h"
-
-int cmr_fail(int code, const char* fmt, ...);   // api.hip
 
 namespace {
 
@@ -107,19 +106,13 @@ static hipError_t launch_merge_keys(const u64* keys, int S, int nq, int k, int64
     return hipGetLastError();
 }
 
-#define COMM_HIP_TRY(expr)                                                                                             \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) return cmr_fail(e_ == hipErrorOutOfMemory ? CMR_ERR_OOM : CMR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------ C-ABI
 extern "C" {
 
 int32_t cmr_pack_candidates_dev(const int64_t* ids_dev, const float* scores_dev, int64_t n, uint64_t* keys_dev, void* stream) {
     if (!ids_dev || !scores_dev || !keys_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (n < 0) return cmr_fail(CMR_ERR_INVALID, "n < 0");
-    COMM_HIP_TRY(launch_pack(ids_dev, scores_dev, n, (u64*)keys_dev, (hipStream_t)stream));
+    HIP_TRY(launch_pack(ids_dev, scores_dev, n, (u64*)keys_dev, (hipStream_t)stream));
     return CMR_OK;
 }
 
@@ -128,7 +121,7 @@ int32_t cmr_merge_keys_dev(const uint64_t* keys_dev, int32_t n_shards, int32_t n
     if (!keys_dev || !out_ids_dev || !out_scores_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (n_shards <= 0 || nq <= 0 || k <= 0) return cmr_fail(CMR_ERR_INVALID, "n_shards, nq, k must be > 0");
     if ((long long)n_shards * k > 4096) return cmr_fail(CMR_ERR_UNSUPPORTED, "n_shards * k = %lld > 4096", (long long)n_shards * k);
-    COMM_HIP_TRY(launch_merge_keys((const u64*)keys_dev, n_shards, nq, k, out_ids_dev, out_scores_dev, (hipStream_t)stream));
+    HIP_TRY(launch_merge_keys((const u64*)keys_dev, n_shards, nq, k, out_ids_dev, out_scores_dev, (hipStream_t)stream));
     return CMR_OK;
 }
 
@@ -150,7 +143,7 @@ int32_t cmr_comm_create(int32_t world, int32_t rank, const uint8_t* id128, int32
     if (world <= 0 || rank < 0 || rank >= world) return cmr_fail(CMR_ERR_INVALID, "rank %d outside [0, %d)", rank, world);
     Rccl* r = rccl();
     if (!r) return cmr_fail(CMR_ERR_UNSUPPORTED, "RCCL (librccl.so) could not be loaded");
-    COMM_HIP_TRY(hipSetDevice(device_id));
+    HIP_TRY(hipSetDevice(device_id));
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
     cmr_comm* c = new cmr_comm();
@@ -193,22 +186,22 @@ int32_t cmr_comm_allgather_merge(cmr_comm_t* c, const int64_t* ids_dev, const fl
     if ((long long)c->world * k > 4096) return cmr_fail(CMR_ERR_UNSUPPORTED, "world * k = %lld > 4096", (long long)c->world * k);
     Rccl* r = rccl();
     if (!r) return cmr_fail(CMR_ERR_UNSUPPORTED, "RCCL (librccl.so) could not be loaded");
-    COMM_HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)nq * k;
     if (n > c->cap) {     // grow (rare; the previous exchange on another stream may still read the old buffers)
-        COMM_HIP_TRY(hipDeviceSynchronize());
-        if (c->send) COMM_HIP_TRY(hipFree(c->send));
-        if (c->recv) COMM_HIP_TRY(hipFree(c->recv));
+        HIP_TRY(hipDeviceSynchronize());
+        if (c->send) HIP_TRY(hipFree(c->send));
+        if (c->recv) HIP_TRY(hipFree(c->recv));
         c->send = c->recv = nullptr; c->cap = 0;
-        COMM_HIP_TRY(hipMalloc((void**)&c->send, n * 8));
-        COMM_HIP_TRY(hipMalloc((void**)&c->recv, n * 8 * c->world));
+        HIP_TRY(hipMalloc((void**)&c->send, n * 8));
+        HIP_TRY(hipMalloc((void**)&c->recv, n * 8 * c->world));
         c->cap = n;
     }
-    COMM_HIP_TRY(launch_pack(ids_dev, scores_dev, (long long)n, c->send, s));
+    HIP_TRY(launch_pack(ids_dev, scores_dev, (long long)n, c->send, s));
     ncclResult_t rc = r->AllGather(c->send, c->recv, n, ncclUint64, c->nccl, s);          // ONE collective: nq*k*8 bytes per rank
     if (rc != ncclSuccess) return cmr_fail(CMR_ERR_HIP, "ncclAllGather: %s", r->GetErrorString ? r->GetErrorString(rc) : "error");
-    COMM_HIP_TRY(launch_merge_keys(c->recv, c->world, nq, k, out_ids_dev, out_scores_dev, s));
+    HIP_TRY(launch_merge_keys(c->recv, c->world, nq, k, out_ids_dev, out_scores_dev, s));
     return CMR_OK;
 }
 

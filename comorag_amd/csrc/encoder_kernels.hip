@@ -21,6 +21,7 @@
 // are in flight while chunk c is multiplied, one barrier per chunk.  35 KiB of LDS per workgroup: several workgroups share a
 // CU, so one's exponentials overlap another's MFMAs (the 64-wide head makes the softmax, not the matrix pipe, the longer leg).
 #include "cmr_device.h"
+#include "cmr_internal.h"
 #include "cmr_kernels.h"
 
 typedef __attribute__((ext_vector_type(2))) __bf16 enc_bf16x2;
@@ -870,3 +871,93 @@ hipError_t cmr_launch_add_layernorm(const void* y, const void* bias, const void*
     if (dtype == CMR_DT_BF16) return launch_add_ln<CMR_DT_BF16>(y, bias, res, gamma, beta, eps, rows, d, out, s);
     return launch_add_ln<CMR_DT_F16>(y, bias, res, gamma, beta, eps, rows, d, out, s);
 }
+
+// ------------------------------------------------------------------------------------------ C-ABI (include/comorag_hip.h)
+// argument checks of the encoder entry points; each ends in one launcher call above
+extern "C" {
+
+int32_t cmr_encoder_attention(int32_t device_id, const void* qkv_dev, int32_t dtype, const int32_t* lens_dev, int32_t b, int32_t l,
+                              int32_t n_heads, int32_t head_dim, void* out_dev, void* stream) {
+    if (!qkv_dev || !lens_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (b <= 0 || l <= 0 || n_heads <= 0) return cmr_fail(CMR_ERR_INVALID, "b, l, n_heads must be > 0");
+    if (head_dim != 64) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: head_dim must be 64 (BERT-base / BERT-large heads)");
+    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: dtype must be bf16 or f16");
+    if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & 15) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: buffers must be 16-byte aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_attention(qkv_dev, dtype, lens_dev, b, l, n_heads, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_add_layernorm(int32_t device_id, const void* y_dev, const void* bias_dev, const void* residual_dev, const void* gamma_dev,
+                                  const void* beta_dev, float eps, int64_t rows, int32_t d, int32_t dtype, void* out_dev, void* stream) {
+    if (!y_dev || !gamma_dev || !beta_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (rows <= 0 || d <= 0 || d % 4 || d > 2048) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm: rows > 0, d a multiple of 4, d <= 2048");
+    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm: dtype must be bf16 or f16");
+    if (((uintptr_t)y_dev | (uintptr_t)bias_dev | (uintptr_t)residual_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & 7)
+        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm: buffers must be 8-byte aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_add_layernorm(y_dev, bias_dev, residual_dev, gamma_dev, beta_dev, eps, rows, d, dtype, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_add_layernorm_pool(int32_t device_id, const void* y_dev, const void* bias_dev, const void* residual_dev, const void* gamma_dev,
+                                       const void* beta_dev, float eps, int32_t b, int32_t l, int32_t d, int32_t dtype, const int32_t* lens_dev,
+                                       int32_t normalize, float* partial_dev, float* out_dev, void* stream) {
+    if (!y_dev || !gamma_dev || !beta_dev || !lens_dev || !partial_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (b <= 0 || l <= 0 || d <= 0) return cmr_fail(CMR_ERR_INVALID, "b, l, d must be > 0");
+    if (l % 16 || d % 8 || d > 2048) return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_pool: l must be a multiple of 16, d a multiple of 8 and <= 2048");
+    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm_pool: dtype must be bf16 or f16");
+    if (((uintptr_t)y_dev | (uintptr_t)bias_dev | (uintptr_t)residual_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)partial_dev | (uintptr_t)out_dev) & 15)
+        return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_pool: buffers must be 16-byte aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_add_layernorm_pool(y_dev, bias_dev, residual_dev, gamma_dev, beta_dev, eps, b, l, d, dtype, (const int*)lens_dev, normalize, partial_dev,
+                                          out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_embed_layernorm(int32_t device_id, const int64_t* ids_dev, const int64_t* token_type_dev, const void* word_dev, const void* pos_dev,
+                                    const void* type_dev, const void* gamma_dev, const void* beta_dev, float eps, int64_t rows, int32_t l, int32_t d,
+                                    int32_t vocab, int32_t n_positions, int32_t n_types, int32_t position_offset, int32_t dtype, void* out_dev, void* stream) {
+    if (!ids_dev || !word_dev || !pos_dev || !type_dev || !gamma_dev || !beta_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (rows <= 0 || l <= 0 || d <= 0 || d % 4 || d > 2048) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: rows, l > 0, d a multiple of 4, d <= 2048");
+    if (vocab <= 0 || n_positions <= 0 || n_types <= 0 || position_offset < 0) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: empty embedding table / negative position offset");
+    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: dtype must be bf16 or f16");
+    if (((uintptr_t)word_dev | (uintptr_t)pos_dev | (uintptr_t)type_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & 7)
+        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: buffers must be 8-byte aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_embed_layernorm((const long long*)ids_dev, (const long long*)token_type_dev, word_dev, pos_dev, type_dev, gamma_dev, beta_dev, eps,
+                                       rows, l, d, vocab, n_positions, n_types, position_offset, dtype, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_embed_layernorm_ragged(int32_t device_id, const int32_t* ids32_dev, const int32_t* offsets_dev, const void* word_dev, const void* pos_dev,
+                                           const void* type_dev, const void* gamma_dev, const void* beta_dev, float eps, int32_t b, int32_t l, int32_t d,
+                                           int32_t vocab, int32_t n_positions, int32_t position_offset, int32_t dtype, void* out_dev, void* stream) {
+    if (!ids32_dev || !offsets_dev || !word_dev || !pos_dev || !type_dev || !gamma_dev || !beta_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (b <= 0 || l <= 0 || d <= 0 || d % 4 || d > 2048) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: b, l > 0, d a multiple of 4, d <= 2048");
+    if (vocab <= 0 || n_positions <= 0 || position_offset < 0) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: empty embedding table / negative position offset");
+    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: dtype must be bf16 or f16");
+    if (((uintptr_t)word_dev | (uintptr_t)pos_dev | (uintptr_t)type_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & 7)
+        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: buffers must be 8-byte aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_embed_layernorm_ragged((const int*)ids32_dev, (const int*)offsets_dev, word_dev, pos_dev, type_dev, gamma_dev, beta_dev, eps, (long long)b * l, l,
+                                              d, vocab, n_positions, position_offset, dtype, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+}  // extern "C"

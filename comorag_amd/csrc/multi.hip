@@ -35,12 +35,6 @@
 
 namespace {
 
-#define M_HIP_TRY(expr)                                                                                                \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) return cmr_fail(e_ == hipErrorOutOfMemory ? CMR_ERR_OOM : CMR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 struct Latch {
     std::mutex mu;
     std::condition_variable cv;
@@ -470,11 +464,11 @@ int32_t cmr_mindex_append_dev(cmr_mindex_t* m, const float* rows_dev, int64_t n,
         if (m->device[s] == src_device && !m->force_peer_staging) return cmr_index_append_dev(m->shard[s], src, cnt, stream);
         // the chunk's shard lives on another GPU: device-to-device copy into a staging buffer there (hipMemcpyPeer goes over
         // xGMI where the devices are peers and through the host where they are not), then a local append
-        if (!synced) { M_HIP_TRY(hipSetDevice(src_device)); M_HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); synced = true; }
-        M_HIP_TRY(hipSetDevice(m->device[s]));
+        if (!synced) { HIP_TRY(hipSetDevice(src_device)); HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); synced = true; }
+        HIP_TRY(hipSetDevice(m->device[s]));
         void* stage = nullptr;
         const size_t bytes = (size_t)cnt * m->dim * 4;
-        M_HIP_TRY(hipMalloc(&stage, bytes));
+        HIP_TRY(hipMalloc(&stage, bytes));
         hipError_t e = hipMemcpyPeer(stage, m->device[s], src, src_device, bytes);
         int rc = e == hipSuccess ? cmr_index_append_dev(m->shard[s], (const float*)stage, cnt, nullptr)
                                  : cmr_fail(CMR_ERR_HIP, "hipMemcpyPeer %d -> %d: %s", src_device, m->device[s], hipGetErrorString(e));
@@ -713,9 +707,9 @@ int32_t cmr_mindex_search_pipelined(cmr_mindex_t* m, const float* const* q_dev, 
     const size_t nk = (size_t)nq * k;
     const size_t need = (size_t)std::max(A, 1) * (nk * 12 + (size_t)nq * 8);
     if (need > t.cap) {
-        if (t.h) { M_HIP_TRY(hipHostFree(t.h)); t.h = nullptr; t.cap = 0; }
+        if (t.h) { HIP_TRY(hipHostFree(t.h)); t.h = nullptr; t.cap = 0; }
         // portable + mapped: every device of the process may write it (unified addressing: host pointer == device pointer)
-        M_HIP_TRY(hipHostMalloc(&t.h, need, hipHostMallocPortable | hipHostMallocMapped));
+        HIP_TRY(hipHostMalloc(&t.h, need, hipHostMallocPortable | hipHostMallocMapped));
         t.cap = need;
     }
     // everything that can fail comes BEFORE the slot is claimed: on an error the caller's *ticket stays as it was and no ring position is used up

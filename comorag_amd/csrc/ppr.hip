@@ -32,15 +32,8 @@
 #include <vector>
 
 #include "../../include/comorag_hip.h"
+#include "cmr_internal.h"
 #include "cmr_kernels.h"
-
-int cmr_fail(int code, const char* fmt, ...);                                                                     // api.hip
-// api.hip: scores of nb host queries [nb, dim] into a device buffer [nb, n] of the index's workspace, row b holding the bits a
-// one-query scan of q_host[b] gives (shared index lock held, workspace reserved for the calling thread) until
-// cmr_index_scores_release, which also reports a non-finite query
-int cmr_index_scores_to_device_batch(cmr_index_t* idx, const float* q_host, int nb, float** scores_dev, long long* n, void** stream);
-int cmr_index_scores_release(cmr_index_t* idx);
-long long cmr_index_row_count(cmr_index_t* idx);
 
 #define PPR_T 256
 #define PPR_RED_BLOCKS 256
@@ -101,12 +94,6 @@ struct cmr_graph {
     std::atomic<bool> use_graph{true}; // power iteration replayed as a captured hipGraph (cleared if capture ever fails)
     std::condition_variable idle;
 };
-
-#define PPR_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) return cmr_fail(e_ == hipErrorOutOfMemory ? CMR_ERR_OOM : CMR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------ kernels
 // Row b of a batch equals the single call bit for bit: for every (row, query) both families of kernels execute the same
@@ -630,12 +617,12 @@ static int ppr_iterate(cmr_graph* g, PprScratch* sc, double damping, double tol,
         if (!sc->iter_exec) g->use_graph = false;
     }
     if (g->use_graph && sc->iter_exec) {
-        PPR_TRY(hipGraphLaunch(sc->iter_exec, s));
+        HIP_TRY(hipGraphLaunch(sc->iter_exec, s));
         *result = sc->iter_result;
         return CMR_OK;
     }
     ppr_iterate_launches(g, sc, damping, iters, s, result);
-    PPR_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return CMR_OK;
 }
 
@@ -663,11 +650,11 @@ static void launch_scatter(cmr_graph* g, PprScratch* sc, const float* scores, lo
 static int ensure_seeds(PprScratch* sc, long long n) {
     if (n <= sc->seed_cap) return CMR_OK;
     for (void* p : {(void*)sc->seed_v, (void*)sc->seed_q, (void*)sc->seed_w})
-        if (p) PPR_TRY(hipFree(p));
+        if (p) HIP_TRY(hipFree(p));
     sc->seed_v = nullptr; sc->seed_q = nullptr; sc->seed_w = nullptr; sc->seed_cap = 0;
-    PPR_TRY(hipMalloc((void**)&sc->seed_v, (size_t)n * 4));
-    PPR_TRY(hipMalloc((void**)&sc->seed_q, (size_t)n * 4));
-    PPR_TRY(hipMalloc((void**)&sc->seed_w, (size_t)n * 8));
+    HIP_TRY(hipMalloc((void**)&sc->seed_v, (size_t)n * 4));
+    HIP_TRY(hipMalloc((void**)&sc->seed_q, (size_t)n * 4));
+    HIP_TRY(hipMalloc((void**)&sc->seed_w, (size_t)n * 8));
     sc->seed_cap = n;
     return CMR_OK;
 }
@@ -694,26 +681,26 @@ static int ppr_graph_run(cmr_graph* g, const double* reset, int nb, double dampi
     if (!g || !reset || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (nb < 1) return cmr_fail(CMR_ERR_INVALID, "nb must be >= 1 (got %d)", nb);
     if (nb > CMR_PPR_MAX_BATCH) return cmr_fail(CMR_ERR_UNSUPPORTED, "nb = %d exceeds CMR_PPR_MAX_BATCH (%d): split the batch", nb, CMR_PPR_MAX_BATCH);
-    PPR_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipSetDevice(g->device));
     PprScratch* sc = nullptr;
     int rc = scratch_acquire(g, ppr_width(nb), 0, &sc);
     if (rc) return rc;
     ScratchGuard guard{g, sc};
-    if (!sc->own) PPR_TRY(hipStreamCreateWithFlags(&sc->own, hipStreamNonBlocking));
+    if (!sc->own) HIP_TRY(hipStreamCreateWithFlags(&sc->own, hipStreamNonBlocking));
     hipStream_t s = sc->own;                                // concurrent callers do not queue behind each other on the null stream
     const long long nv = g->nv;
     auto body = [&]() -> int {
         // the caller's vertex order on both sides of the ABI, the internal (degree-class) order between them: the caller's [nb][nv]
         // rows are staged in y (nv * bw >= nv * nb doubles) and transposed into the internal [nv][bw] order
-        PPR_TRY(hipMemcpyAsync(sc->y, reset, (size_t)nb * nv * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(sc->y, reset, (size_t)nb * nv * 8, hipMemcpyHostToDevice, s));
         launch_permute_in(g, sc, sc->y, nb, s);
         double* res = nullptr;
         int rc_ = ppr_iterate(g, sc, damping, tol, max_iter, s, iters, &res);
         if (rc_) return rc_;
         double* tmp = res == sc->x ? sc->y : sc->x;
         launch_gather(sc, res, g->perm, nv, nb, tmp, s);
-        PPR_TRY(hipGetLastError());
-        PPR_TRY(hipMemcpyAsync(out_scores, tmp, (size_t)nb * nv * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out_scores, tmp, (size_t)nb * nv * 8, hipMemcpyDeviceToHost, s));
         return CMR_OK;
     };
     rc = body();
@@ -768,19 +755,19 @@ static int ppr_index_run(cmr_index_t* idx, cmr_graph* g, const float* q_f32, int
         int rc_ = ensure_seeds(sc, std::max<long long>(ns, 1));
         if (rc_) return rc_;
         if (ns) {
-            PPR_TRY(hipMemcpyAsync(sc->seed_v, sv.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-            if (bw > 1) PPR_TRY(hipMemcpyAsync(sc->seed_q, sq.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
-            PPR_TRY(hipMemcpyAsync(sc->seed_w, sw.data(), (size_t)ns * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(sc->seed_v, sv.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+            if (bw > 1) HIP_TRY(hipMemcpyAsync(sc->seed_q, sq.data(), (size_t)ns * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(sc->seed_w, sw.data(), (size_t)ns * 8, hipMemcpyHostToDevice, s));
         }
-        PPR_TRY(hipMemsetAsync(sc->reset, 0, (size_t)g->nv * bw * 8, s));
+        HIP_TRY(hipMemsetAsync(sc->reset, 0, (size_t)g->nv * bw * 8, s));
         if (n) launch_scatter(g, sc, scores, n, nb, passage_node_weight, s);
         if (ns) hipLaunchKernelGGL(ppr_seed_batch_kernel, dim3(blocks_for(ns)), dim3(PPR_T), 0, s, sc->seed_v, bw > 1 ? sc->seed_q : nullptr, sc->seed_w, ns, bw, sc->reset);
         double* res = nullptr;
         rc_ = ppr_iterate(g, sc, damping, tol, max_iter, s, iters, &res);
         if (rc_) return rc_;
         if (n) launch_gather(sc, res, g->vertex_of_row, n, nb, sc->out, s);
-        PPR_TRY(hipGetLastError());
-        PPR_TRY(hipMemcpyAsync(out_doc_scores, sc->out, (size_t)nb * n * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out_doc_scores, sc->out, (size_t)nb * n * 8, hipMemcpyDeviceToHost, s));
         return CMR_OK;
     };
     rc = body();
@@ -801,7 +788,7 @@ int32_t cmr_graph_create(int32_t device_id, int64_t n_vertices, int64_t n_edges,
     if (!out) return cmr_fail(CMR_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (n_vertices <= 0 || n_vertices >= (1ll << 31) || n_edges < 0 || (n_edges > 0 && (!src || !dst))) return cmr_fail(CMR_ERR_INVALID, "bad graph arguments");
-    PPR_TRY(hipSetDevice(device_id));
+    HIP_TRY(hipSetDevice(device_id));
     // symmetric CSR on the host: every undirected edge (u, v) contributes v to u's row and u to v's row (a self-loop once,
     // with its weight counted once in the strength), rows in ascending neighbour order so the sums have one fixed order
     std::vector<double> strength((size_t)n_vertices, 0.0);
@@ -901,16 +888,16 @@ int32_t cmr_graph_set_passage_vertices(cmr_graph_t* g, const int32_t* vertex_of_
     if (!g || (n_rows > 0 && !vertex_of_row) || n_rows < 0) return cmr_fail(CMR_ERR_INVALID, "bad argument");
     for (int64_t i = 0; i < n_rows; ++i)
         if (vertex_of_row[i] < 0 || vertex_of_row[i] >= g->nv) return cmr_fail(CMR_ERR_INVALID, "row %lld maps to vertex %d outside the graph", (long long)i, vertex_of_row[i]);
-    PPR_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipSetDevice(g->device));
     std::unique_lock<std::mutex> lk(g->mu);
     g->idle.wait(lk, [&] { return g->users == 0; });       // no query may be reading the old map
-    if (g->vertex_of_row) PPR_TRY(hipFree(g->vertex_of_row));
+    if (g->vertex_of_row) HIP_TRY(hipFree(g->vertex_of_row));
     g->vertex_of_row = nullptr; g->n_rows = 0;
-    PPR_TRY(hipMalloc((void**)&g->vertex_of_row, std::max<size_t>((size_t)n_rows * 4, 8)));
+    HIP_TRY(hipMalloc((void**)&g->vertex_of_row, std::max<size_t>((size_t)n_rows * 4, 8)));
     if (n_rows) {
         std::vector<int> internal((size_t)n_rows);
         for (int64_t i = 0; i < n_rows; ++i) internal[i] = g->perm_h[vertex_of_row[i]];
-        PPR_TRY(hipMemcpy(g->vertex_of_row, internal.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g->vertex_of_row, internal.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice));
     }
     g->n_rows = n_rows;
     return CMR_OK;

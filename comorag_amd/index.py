@@ -10,6 +10,7 @@ the *_dev methods.
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import numpy as np
@@ -27,9 +28,162 @@ def _ptr(a: np.ndarray) -> int:
     return a.__array_interface__["data"][0]
 
 
-class DenseIndex:
+# the calls whose host-array marshalling `DenseIndex` (cmr_index_*) and `MultiDeviceIndex` (cmr_mindex_*) share
+_HOST_CALLS = ("destroy", "size", "info", "append", "search", "search_exact", "search_min_score", "scores", "sorted_scores",
+               "rescore", "get_rows")
+_bound = {}
+
+
+def _host_calls(prefix: str) -> SimpleNamespace:
+    """The library's `prefix` + name functions, resolved once per prefix: a call then costs two attribute reads."""
+    c = _bound.get(prefix)
+    if c is None:
+        lib = L.lib()
+        c = _bound[prefix] = SimpleNamespace(**{n: getattr(lib, prefix + n) for n in _HOST_CALLS})
+    return c
+
+
+class HostArrayIndex:
+    """numpy in, numpy out: the call surface `DenseIndex` and `MultiDeviceIndex` have in common.  A subclass names the prefix of
+    its C functions (`_PREFIX`), sets `self._c = _host_calls(self._PREFIX)` before it creates `self._h`, and has `dim`."""
+    _PREFIX = ""
+
+    # -- lifetime
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            if not getattr(self, "_borrowed", False):
+                self._c.destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        n = C.c_int64(0)
+        L.check(self._c.size(self._h, C.byref(n)))
+        return n.value
+
+    @property
+    def device_bytes(self) -> int:
+        b = C.c_int64(0)
+        L.check(self._c.info(self._h, None, None, None, C.byref(b)))
+        return b.value
+
+    def _queries(self, q) -> np.ndarray:
+        q = _f32c(q)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"q must be [nq,{self.dim}], got {q.shape}")
+        return q
+
+    # -- append
+    def append(self, rows) -> None:
+        rows = _f32c(rows)
+        if rows.ndim == 1:
+            rows = rows[None, :]
+        if rows.shape[0] == 0:
+            return
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n,{self.dim}], got {rows.shape}")
+        L.check(self._c.append(self._h, _ptr(rows), rows.shape[0]))
+
+    # -- search
+    def search(self, q, k: int, with_minmax: bool = True
+               ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """q [nq,dim] → (ids int64 [nq,k'], raw scores fp32 [nq,k'], min [nq], max [nq]) with
+        k' = min(k, len(self)); order: score desc, row asc."""
+        q = self._queries(q)
+        nq = q.shape[0]
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        mn = np.empty(nq, dtype=np.float32) if with_minmax else None
+        mx = np.empty(nq, dtype=np.float32) if with_minmax else None
+        L.check(self._c.search(self._h, _ptr(q), nq, k, _ptr(ids), _ptr(sc),
+                               _ptr(mn) if with_minmax else None, _ptr(mx) if with_minmax else None))
+        kk = min(k, len(self))
+        return ids[:, :kk], sc[:, :kk], mn, mx
+
+    def search_min_score(self, q, k: int, min_score: float) -> Tuple[np.ndarray, np.ndarray]:
+        """The k best rows among those with raw score >= min_score: (ids [nq,k], scores [nq,k]), -1 / -inf padded."""
+        q = self._queries(q)
+        nq = q.shape[0]
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        L.check(self._c.search_min_score(self._h, _ptr(q), nq, k, float(min_score), _ptr(ids), _ptr(sc)))
+        return ids, sc
+
+    # -- exact fp32 top-k (a 16-bit index created with keep_f32=True; an f32 index is exact already)
+    def search_exact(self, q, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The ids / scores of the reference's fp32 np.dot + argsort (ComoRAG.py:958-966) from a bf16 / f16 index:
+        (ids int64 [nq,k'], fp32 scores [nq,k'], exact bool [nq]) with k' = min(k, len(self)), k <= 64.  exact[i] is True only
+        when the certificate proves the list is the fp32 top-k (cmr_index_search_exact; over the shards of a
+        `MultiDeviceIndex` each shard certifies its top-k, the host merges, exact[i] = AND over the shards)."""
+        q = self._queries(q)
+        nq = q.shape[0]
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        ex = np.empty(nq, dtype=np.int32)
+        L.check(self._c.search_exact(self._h, _ptr(q), nq, k, _ptr(ids), _ptr(sc), _ptr(ex)))
+        kk = min(k, len(self))
+        return ids[:, :kk], sc[:, :kk], ex.astype(bool)
+
+    def scores(self, q) -> np.ndarray:
+        """All raw scores [nq, N] (fp32)."""
+        q = _f32c(q)
+        if q.ndim == 1:
+            q = q[None, :]
+        n = len(self)
+        out = np.empty((q.shape[0], n), dtype=np.float32)
+        if n:
+            L.check(self._c.scores(self._h, _ptr(q), q.shape[0], _ptr(out), n))
+        return out
+
+    def sorted_scores(self, q):
+        """Complete ranking: (ids int64 [nq,N], raw scores fp32 [nq,N] descending, min [nq], max [nq])."""
+        q = _f32c(q)
+        if q.ndim == 1:
+            q = q[None, :]
+        n, nq = len(self), q.shape[0]
+        ids = np.empty((nq, n), dtype=np.int64)
+        sc = np.empty((nq, n), dtype=np.float32)
+        mn = np.empty(nq, dtype=np.float32)
+        mx = np.empty(nq, dtype=np.float32)
+        if n:
+            L.check(self._c.sorted_scores(self._h, _ptr(q), nq, _ptr(ids), _ptr(sc), _ptr(mn), _ptr(mx)))
+        return ids, sc, mn, mx
+
+    def rescore(self, q, cand, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        q = _f32c(q)
+        if q.ndim == 1:
+            q = q[None, :]
+        cand = np.ascontiguousarray(cand, dtype=np.int64)
+        if cand.ndim == 1:
+            cand = cand[None, :]
+        nq, nc = cand.shape
+        k = min(k, nc)
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        L.check(self._c.rescore(self._h, _ptr(q), nq, _ptr(cand), nc, k, _ptr(ids), _ptr(sc)))
+        return ids, sc
+
+    def get_rows(self, ids) -> np.ndarray:
+        ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
+        out = np.empty((len(ids), self.dim), dtype=np.float32)
+        if len(ids):
+            L.check(self._c.get_rows(self._h, _ptr(ids), len(ids), _ptr(out)))
+        return out
+
+
+class DenseIndex(HostArrayIndex):
+    _PREFIX = "cmr_index_"
+
     def __init__(self, dim: int, dtype: str = "bf16", device: int = 0, capacity_hint: int = 0,
                  keep_f32: bool = False, options: Optional[dict] = None):
+        self._c = _host_calls(self._PREFIX)
         self._h = C.c_void_p()
         self.dim = int(dim)
         self.dtype = dtype
@@ -44,6 +198,7 @@ class DenseIndex:
     def _borrow(cls, handle, dim: int, dtype: str, device: int, owner=None) -> "DenseIndex":
         """A view of a cmr_index_t somebody else owns (a shard of a MultiDeviceIndex): never destroyed from here."""
         self = cls.__new__(cls)
+        self._c = _host_calls(cls._PREFIX)
         self._h, self.dim, self.dtype, self.device, self.keep_f32 = handle, int(dim), dtype, int(device), False
         self._borrowed, self._owner = True, owner
         return self
@@ -58,41 +213,6 @@ class DenseIndex:
         L.check(L.lib().cmr_index_get_option(self._h, name.encode(), C.byref(v)))
         return v.value
 
-    # -- lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            if not getattr(self, "_borrowed", False):
-                L.lib().cmr_index_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self) -> int:
-        n = C.c_int64(0)
-        L.check(L.lib().cmr_index_size(self._h, C.byref(n)))
-        return n.value
-
-    @property
-    def device_bytes(self) -> int:
-        b = C.c_int64(0)
-        L.check(L.lib().cmr_index_info(self._h, None, None, None, C.byref(b)))
-        return b.value
-
-    # -- append
-    def append(self, rows) -> None:
-        rows = _f32c(rows)
-        if rows.ndim == 1:
-            rows = rows[None, :]
-        if rows.shape[0] == 0:
-            return
-        if rows.ndim != 2 or rows.shape[1] != self.dim:
-            raise ValueError(f"rows must be [n,{self.dim}], got {rows.shape}")
-        L.check(L.lib().cmr_index_append(self._h, _ptr(rows), rows.shape[0]))
-
     def append_dev(self, rows_t, stream: Optional[int] = None) -> None:
         """rows_t: torch float32 CUDA tensor [n, dim], contiguous, on this index's device."""
         import torch
@@ -105,37 +225,6 @@ class DenseIndex:
         if stream is None:
             stream = torch.cuda.current_stream(rows_t.device).cuda_stream
         L.check(L.lib().cmr_index_append_dev(self._h, C.c_void_p(rows_t.data_ptr()), rows_t.shape[0], C.c_void_p(stream)))
-
-    # -- search
-    def search(self, q, k: int, with_minmax: bool = True
-               ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
-        """q [nq,dim] → (ids int64 [nq,k'], raw scores fp32 [nq,k'], min [nq], max [nq]) with
-        k' = min(k, len(self)); order: score desc, row asc."""
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"q must be [nq,{self.dim}], got {q.shape}")
-        nq = q.shape[0]
-        ids = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        mn = np.empty(nq, dtype=np.float32) if with_minmax else None
-        mx = np.empty(nq, dtype=np.float32) if with_minmax else None
-        L.check(L.lib().cmr_index_search(self._h, _ptr(q), nq, k, _ptr(ids), _ptr(sc),
-                                         _ptr(mn) if with_minmax else None, _ptr(mx) if with_minmax else None))
-        kk = min(k, len(self))
-        return ids[:, :kk], sc[:, :kk], mn, mx
-
-    def search_min_score(self, q, k: int, min_score: float) -> Tuple[np.ndarray, np.ndarray]:
-        """The k best rows among those with raw score >= min_score: (ids [nq,k], scores [nq,k]), -1 / -inf padded."""
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        nq = q.shape[0]
-        ids = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        L.check(L.lib().cmr_index_search_min_score(self._h, _ptr(q), nq, k, float(min_score), _ptr(ids), _ptr(sc)))
-        return ids, sc
 
     def search_min_score_dev(self, q_t, k: int, min_score: float, out_ids=None, out_scores=None, stream: Optional[int] = None):
         """`search_min_score` on torch CUDA tensors, enqueued on torch's current stream without synchronising."""
@@ -233,17 +322,6 @@ class DenseIndex:
     def sync(done_handle) -> None:
         L.check(L.lib().cmr_event_synchronize(done_handle))
 
-    def scores(self, q) -> np.ndarray:
-        """All raw scores [nq, N] (fp32)."""
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        n = len(self)
-        out = np.empty((q.shape[0], n), dtype=np.float32)
-        if n:
-            L.check(L.lib().cmr_index_scores(self._h, _ptr(q), q.shape[0], _ptr(out), n))
-        return out
-
     def scores_dev(self, q_t, out=None, stream: Optional[int] = None):
         import torch
         assert q_t.is_cuda and q_t.dtype == torch.float32 and q_t.is_contiguous()
@@ -255,52 +333,6 @@ class DenseIndex:
         L.check(L.lib().cmr_index_scores_dev(self._h, C.c_void_p(q_t.data_ptr()), q_t.shape[0],
                                              C.c_void_p(out.data_ptr()), out.stride(0), C.c_void_p(stream)))
         return out
-
-    def sorted_scores(self, q):
-        """Complete ranking: (ids int64 [nq,N], raw scores fp32 [nq,N] descending, min [nq], max [nq])."""
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        n, nq = len(self), q.shape[0]
-        ids = np.empty((nq, n), dtype=np.int64)
-        sc = np.empty((nq, n), dtype=np.float32)
-        mn = np.empty(nq, dtype=np.float32)
-        mx = np.empty(nq, dtype=np.float32)
-        if n:
-            L.check(L.lib().cmr_index_sorted_scores(self._h, _ptr(q), nq, _ptr(ids), _ptr(sc), _ptr(mn), _ptr(mx)))
-        return ids, sc, mn, mx
-
-    def rescore(self, q, cand, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        cand = np.ascontiguousarray(cand, dtype=np.int64)
-        if cand.ndim == 1:
-            cand = cand[None, :]
-        nq, nc = cand.shape
-        k = min(k, nc)
-        ids = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        L.check(L.lib().cmr_index_rescore(self._h, _ptr(q), nq, _ptr(cand), nc, k, _ptr(ids), _ptr(sc)))
-        return ids, sc
-
-    # -- exact fp32 top-k (a 16-bit index created with keep_f32=True; an f32 index is exact already)
-    def search_exact(self, q, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """The ids / scores of the reference's fp32 np.dot + argsort (ComoRAG.py:958-966) from a bf16 / f16 index:
-        (ids int64 [nq,k'], fp32 scores [nq,k'], exact bool [nq]) with k' = min(k, len(self)), k <= 64.  exact[i] is True only
-        when the certificate proves the list is the fp32 top-k (cmr_index_search_exact)."""
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"q must be [nq,{self.dim}], got {q.shape}")
-        nq = q.shape[0]
-        ids = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        ex = np.empty(nq, dtype=np.int32)
-        L.check(L.lib().cmr_index_search_exact(self._h, _ptr(q), nq, k, _ptr(ids), _ptr(sc), _ptr(ex)))
-        kk = min(k, len(self))
-        return ids[:, :kk], sc[:, :kk], ex.astype(bool)
 
     def search_exact_pipelined(self, q_t, k: int, out_ids, out_scores, out_exact, wait_event=None):
         """`search_exact` stage 1 in throughput mode (cmr_index_search_exact_pipelined): torch CUDA tensors out_ids int64 [nq,k],
@@ -321,13 +353,6 @@ class DenseIndex:
         a, b = C.c_float(0), C.c_float(0)
         L.check(L.lib().cmr_index_round_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
-
-    def get_rows(self, ids) -> np.ndarray:
-        ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
-        out = np.empty((len(ids), self.dim), dtype=np.float32)
-        if len(ids):
-            L.check(L.lib().cmr_index_get_rows(self._h, _ptr(ids), len(ids), _ptr(out)))
-        return out
 
     # -- measurement
     def profile(self, on) -> None:

@@ -15,12 +15,12 @@ Devices: `devices=[0, 1, ...]` names the GPU of every shard; a device may be nam
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence
 
 import numpy as np
 
 from . import _lib as L
-from .index import DenseIndex, _f32c, _ptr
+from .index import DenseIndex, HostArrayIndex, _host_calls, _ptr
 
 
 MULTI_ONLY_OPTIONS = ("append_block_rows", "parallel_min_shards", "force_peer_staging")
@@ -42,9 +42,14 @@ def resolve_devices(num_shards: Optional[int] = None, devices: Optional[Sequence
     return [(int(device) + i) % n for i in range(s)]
 
 
-class MultiDeviceIndex:
+class MultiDeviceIndex(HostArrayIndex):
+    """Host arrays in / out (append, search, search_exact, search_min_score, scores, sorted_scores, rescore, get_rows, len): the
+    methods of `HostArrayIndex`, on cmr_mindex_*."""
+    _PREFIX = "cmr_mindex_"
+
     def __init__(self, dim: int, dtype: str = "bf16", devices: Optional[Sequence[int]] = None, num_shards: Optional[int] = None,
                  device: int = 0, capacity_hint: int = 0, keep_f32: bool = False, options: Optional[dict] = None):
+        self._c = _host_calls(self._PREFIX)
         self._h = C.c_void_p()
         self.dim, self.dtype, self.keep_f32 = int(dim), dtype, bool(keep_f32)
         self.devices = resolve_devices(num_shards, devices, device)
@@ -57,23 +62,7 @@ class MultiDeviceIndex:
         for name, value in (options or {}).items():
             self.set_option(name, value)
 
-    # -- lifetime / facts
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h:
-            L.lib().cmr_mindex_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self) -> int:
-        n = C.c_int64(0)
-        L.check(L.lib().cmr_mindex_size(self._h, C.byref(n)))
-        return n.value
-
+    # -- facts
     def set_option(self, name: str, value: int) -> None:
         """"append_block_rows" / "parallel_min_shards" / "force_peer_staging", or any route selector of `DenseIndex.set_option` (goes to
         every shard, with no search in flight)."""
@@ -84,29 +73,12 @@ class MultiDeviceIndex:
         L.check(L.lib().cmr_mindex_info(self._h, None, None, rows, None))
         return list(rows)
 
-    @property
-    def device_bytes(self) -> int:
-        b = C.c_int64(0)
-        L.check(L.lib().cmr_mindex_info(self._h, None, None, None, C.byref(b)))
-        return b.value
-
     def shard(self, s: int) -> DenseIndex:
         """Borrowed `DenseIndex` view of shard s (profiling, reading options).  Never append to it; while other threads search, set
         route selectors through `MultiDeviceIndex.set_option` (exclusive over the whole handle), not on this view."""
         h = C.c_void_p()
         L.check(L.lib().cmr_mindex_shard(self._h, int(s), C.byref(h)))
         return DenseIndex._borrow(h, self.dim, self.dtype, self.devices[s], owner=self)
-
-    # -- append
-    def append(self, rows) -> None:
-        rows = _f32c(rows)
-        if rows.ndim == 1:
-            rows = rows[None, :]
-        if rows.shape[0] == 0:
-            return
-        if rows.ndim != 2 or rows.shape[1] != self.dim:
-            raise ValueError(f"rows must be [n,{self.dim}], got {rows.shape}")
-        L.check(L.lib().cmr_mindex_append(self._h, _ptr(rows), rows.shape[0]))
 
     def append_dev(self, rows_t, stream: Optional[int] = None) -> None:
         """torch float32 CUDA tensor [n, dim] on ANY device (an encoder's output): chunks whose shard lives on that device
@@ -122,93 +94,6 @@ class MultiDeviceIndex:
         if stream is None:
             stream = torch.cuda.current_stream(rows_t.device).cuda_stream
         L.check(L.lib().cmr_mindex_append_dev(self._h, C.c_void_p(rows_t.data_ptr()), rows_t.shape[0], rows_t.device.index, C.c_void_p(stream)))
-
-    # -- search (host arrays in / out, as DenseIndex)
-    def search(self, q, k: int, with_minmax: bool = True):
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"q must be [nq,{self.dim}], got {q.shape}")
-        nq = q.shape[0]
-        ids = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        mn = np.empty(nq, dtype=np.float32) if with_minmax else None
-        mx = np.empty(nq, dtype=np.float32) if with_minmax else None
-        L.check(L.lib().cmr_mindex_search(self._h, _ptr(q), nq, k, _ptr(ids), _ptr(sc),
-                                          _ptr(mn) if with_minmax else None, _ptr(mx) if with_minmax else None))
-        kk = min(k, len(self))
-        return ids[:, :kk], sc[:, :kk], mn, mx
-
-    def search_exact(self, q, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """DenseIndex.search_exact over every shard (cmr_mindex_search_exact): each shard certifies its top-k, the host merges;
-        exact[i] = AND over the shards."""
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"q must be [nq,{self.dim}], got {q.shape}")
-        nq = q.shape[0]
-        ids = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        ex = np.empty(nq, dtype=np.int32)
-        L.check(L.lib().cmr_mindex_search_exact(self._h, _ptr(q), nq, k, _ptr(ids), _ptr(sc), _ptr(ex)))
-        kk = min(k, len(self))
-        return ids[:, :kk], sc[:, :kk], ex.astype(bool)
-
-    def search_min_score(self, q, k: int, min_score: float) -> Tuple[np.ndarray, np.ndarray]:
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        nq = q.shape[0]
-        ids = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        L.check(L.lib().cmr_mindex_search_min_score(self._h, _ptr(q), nq, k, float(min_score), _ptr(ids), _ptr(sc)))
-        return ids, sc
-
-    def scores(self, q) -> np.ndarray:
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        n = len(self)
-        out = np.empty((q.shape[0], n), dtype=np.float32)
-        if n:
-            L.check(L.lib().cmr_mindex_scores(self._h, _ptr(q), q.shape[0], _ptr(out), n))
-        return out
-
-    def sorted_scores(self, q):
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        n, nq = len(self), q.shape[0]
-        ids = np.empty((nq, n), dtype=np.int64)
-        sc = np.empty((nq, n), dtype=np.float32)
-        mn = np.empty(nq, dtype=np.float32)
-        mx = np.empty(nq, dtype=np.float32)
-        if n:
-            L.check(L.lib().cmr_mindex_sorted_scores(self._h, _ptr(q), nq, _ptr(ids), _ptr(sc), _ptr(mn), _ptr(mx)))
-        return ids, sc, mn, mx
-
-    def rescore(self, q, cand, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        q = _f32c(q)
-        if q.ndim == 1:
-            q = q[None, :]
-        cand = np.ascontiguousarray(cand, dtype=np.int64)
-        if cand.ndim == 1:
-            cand = cand[None, :]
-        nq, nc = cand.shape
-        k = min(k, nc)
-        ids = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        L.check(L.lib().cmr_mindex_rescore(self._h, _ptr(q), nq, _ptr(cand), nc, k, _ptr(ids), _ptr(sc)))
-        return ids, sc
-
-    def get_rows(self, ids) -> np.ndarray:
-        ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
-        out = np.empty((len(ids), self.dim), dtype=np.float32)
-        if len(ids):
-            L.check(L.lib().cmr_mindex_get_rows(self._h, _ptr(ids), len(ids), _ptr(out)))
-        return out
 
     # -- throughput mode
     def place_queries(self, q) -> list:

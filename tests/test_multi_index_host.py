@@ -87,6 +87,20 @@ def test_resolve_devices_and_config_fields():
     assert shard_config(None) == {"num_shards": None, "devices": None, "options": None}
 
 
+def test_queries_of_the_wrong_width_are_refused_before_the_library_reads_them():
+    """search / search_exact / search_min_score share one check (HostArrayIndex._queries): a [nq, d != dim] batch raises instead
+    of letting the library read nq * dim floats from a smaller array.  No handle is needed: the check precedes every C call."""
+    from comorag_amd.index import DenseIndex
+    from comorag_amd.multi_index import MultiDeviceIndex
+    bad = np.zeros((2, 7), dtype=np.float32)
+    for cls in (DenseIndex, MultiDeviceIndex):
+        idx = cls.__new__(cls)
+        idx.dim = 8
+        for call in (lambda: idx.search(bad, 3), lambda: idx.search_exact(bad, 3), lambda: idx.search_min_score(bad, 3, 0.5)):
+            with pytest.raises(ValueError, match="q must be"):
+                call()
+
+
 class ShardedNumpyIndex:
     """numpy stand-in with MultiDeviceIndex's surface: conftest.NumpyIndex shards, rows routed by the LIBRARY's
     cmr_mindex_plan_append, global ids dense in append order, host merge.  TEST INFRASTRUCTURE (CPU tier only)."""
