@@ -14,6 +14,7 @@
 #include <atomic>
 #include <climits>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -51,12 +52,12 @@ namespace {
 // Route selectors of an index (cmr_index_set_option).  Every one of them picks between implementations that return the
 // SAME results; they exist so that tests can hold the routes against each other and tools can A/B a kernel decision.
 // One row per name: where a value is stored and what happens to it on the way — taken as it is (any), clamped to [a, b]
-// (clamp), or refused with `reject` unless it is one of a / b / c (oneof) or inside [a, b] (range) — and, for the names
+// (clamp), or refused with `reject` unless it is one of a / b / c (oneof), inside [a, b] (range) or 0 or inside [a, b] (zero_or) — and, for the names
 // cmr_index_get_option answers, how it is read.  The measurements behind the defaults are on the fields (index_state.h).
 struct Option {
     const char* name;
     void (*store)(cmr_index*, long long);      // nullptr: read-only
-    enum Kind { any, clamp, oneof, range } kind;
+    enum Kind { any, clamp, oneof, range, zero_or } kind;
     long long a, b, c;
     const char* reject;
     long long (*read)(const cmr_index*);       // nullptr: not readable
@@ -96,6 +97,10 @@ const Option kOptions[] = {
     {"pipe_dual_scan", OPT_FIELD(dual_scan), Option::any, 0, 0, 0, nullptr, nullptr},
     {"pipe_cu_mask", OPT_FIELD(cu_mask), Option::any, 0, 0, 0, nullptr, nullptr},
     {"exact_cand", OPT_FIELD(exact_cand), Option::range, 2, CMR_MAX_K, 0, "exact_cand must be in [2, " CMR_STR(CMR_MAX_K) "]", OPT_READ(i->exact_cand)},
+    {"combine", [](cmr_index* i, long long v) { i->combine.store((int)v, std::memory_order_relaxed); }, Option::zero_or, 2, cmr_combine::kMaxWidth, 0,
+     "combine must be 0 (off) or in [2, " CMR_STR(CMR_PPR_MAX_BATCH) "]", OPT_READ(i->combine.load(std::memory_order_relaxed))},
+    {"combine_wait_us", [](cmr_index* i, long long v) { i->combine_wait_us.store(v, std::memory_order_relaxed); }, Option::clamp, 0, 10000000, 0, nullptr,
+     OPT_READ(i->combine_wait_us.load(std::memory_order_relaxed))},
 #ifdef CMR_DEV_KNOBS
     {"wide_abl", OPT_FIELD(wide_abl), Option::any, 0, 0, 0, nullptr, nullptr},      // ablation kernels: results are WRONG by design (development builds only)
 #endif
@@ -103,6 +108,9 @@ const Option kOptions[] = {
     {"pipe_dual_scan_wide_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_wide_active)},
     {"pipe_cu_mask_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->pipe.last_masked)},
     {"pipe_scan_cus", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->pipe.last_masked ? i->pipe.scan_cus : i->n_cu)},
+    {"combine_batches", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->combiner.batches())},
+    {"combine_queries", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->combiner.queries())},
+    {"combine_max_width", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->combiner.max_width())},
 };
 #undef OPT_FIELD
 #undef OPT_READ
@@ -115,7 +123,7 @@ const Option* find_option(const char* name) {
 int set_option(cmr_index* idx, const char* name, long long v) {
     const Option* o = find_option(name ? name : "");
     if (!o || !o->store) return fail(CMR_ERR_INVALID, "unknown option '%s'", name ? name : "");
-    const bool refused = o->kind == Option::oneof ? (v != o->a && v != o->b && v != o->c) : o->kind == Option::range ? (v < o->a || v > o->b) : false;
+    const bool refused = o->kind == Option::oneof ? (v != o->a && v != o->b && v != o->c) : o->kind == Option::range ? (v < o->a || v > o->b) : o->kind == Option::zero_or ? (v != 0 && (v < o->a || v > o->b)) : false;
     if (refused) return fail(CMR_ERR_INVALID, "%s", o->reject);
     if (o->kind == Option::clamp) v = std::max(o->a, std::min(v, o->b));
     o->store(idx, v);
@@ -675,6 +683,16 @@ long long cmr_index_row_count(cmr_index_t* idx) {      // for ppr.hip's argument
     return idx->n;
 }
 
+// ---- for ppr.hip: the index's combiner (combine.h) — its width (0: off; *dim for the host check of the query), one submission
+int cmr_index_combine_width(cmr_index_t* idx, int* dim) {
+    if (!idx) return 0;
+    *dim = idx->dim;
+    return idx->combine.load(std::memory_order_relaxed);
+}
+void cmr_index_combine_submit(cmr_index_t* idx, const cmr_combine::Key& key, cmr_combine::Request* req, int width, cmr_combine::RunFn run, void* ctx) {
+    idx->combiner.submit(key, req, width, idx->combine_wait_us.load(std::memory_order_relaxed), run, ctx);
+}
+
 int cmr_index_scores_release(cmr_index_t* idx) {
     Workspace* ws = tl_scores_ws;
     if (!idx || !ws) return CMR_OK;
@@ -1205,9 +1223,60 @@ static int32_t host_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t
     return cmr_index_search_finish(p, out_ids, out_scores, out_min, out_max);
 }
 
+// ---- combined synchronous calls (combine.h): what the leader of a batch runs.  A batch of one is the caller's own call,
+// unchanged; a wider one is ONE call of the same entry point on the concatenated queries, whose rows hold the bits of the single calls
+// (DESIGN 4.9b), scattered to the participants.
+struct CombinedSearch { const float* q; int nq, k; int64_t* ids; float* scores; float* mn; float* mx; };
+struct CombinedScores { const float* q; int nq; float* out; long long ld; };
+
+// code and (on failure) this thread's message into the request; the participant publishes them in its own thread
+static void combine_answer(cmr_combine::Request* r, int rc) {
+    r->rc = rc;
+    if (rc) r->err = g_err;
+}
+static int combine_result(const cmr_combine::Request& r) {
+    if (r.rc) g_err = r.err;
+    return r.rc;
+}
+
+static void combined_search_run(void* ctx, cmr_combine::Request** reqs, int n) {
+    cmr_index* const idx = (cmr_index*)ctx;
+    const CombinedSearch* a0 = (const CombinedSearch*)reqs[0]->args;
+    if (n == 1) { combine_answer(reqs[0], host_search(idx, a0->q, a0->nq, a0->k, a0->ids, a0->scores, a0->mn, a0->mx, nullptr)); return; }
+    int NQ = 0;
+    for (int i = 0; i < n; ++i) NQ += reqs[i]->nq;
+    const int k = a0->k;
+    const size_t dim = (size_t)idx->dim;
+    std::vector<float> q((size_t)NQ * dim), sc((size_t)NQ * k), mm((size_t)NQ * 2);
+    std::vector<int64_t> ids((size_t)NQ * k);
+    for (int i = 0, at = 0; i < n; at += reqs[i++]->nq) memcpy(q.data() + (size_t)at * dim, ((const CombinedSearch*)reqs[i]->args)->q, (size_t)reqs[i]->nq * dim * 4);
+    const int rc = host_search(idx, q.data(), NQ, k, ids.data(), sc.data(), mm.data(), mm.data() + NQ, nullptr);
+    for (int i = 0, at = 0; i < n; at += reqs[i++]->nq) {
+        const CombinedSearch* a = (const CombinedSearch*)reqs[i]->args;
+        combine_answer(reqs[i], rc);
+        if (rc) continue;
+        const size_t nk = (size_t)a->nq * k;
+        memcpy(a->ids, ids.data() + (size_t)at * k, nk * 8);
+        memcpy(a->scores, sc.data() + (size_t)at * k, nk * 4);
+        if (a->mn) memcpy(a->mn, mm.data() + at, (size_t)a->nq * 4);
+        if (a->mx) memcpy(a->mx, mm.data() + NQ + at, (size_t)a->nq * 4);
+    }
+}
+
 int32_t cmr_index_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores,
                          float* out_min, float* out_max) {
-    return host_search(idx, q, nq, k, out_ids, out_scores, out_min, out_max, nullptr);
+    const int W = idx ? idx->combine.load(std::memory_order_relaxed) : 0;
+    // joins a batch: fewer queries than the batch holds, the fused search (k <= CMR_MAX_K), and finite queries — the batch kernels carry one
+    // non-finite flag per launch, so such a query takes the single call and gets its CMR_ERR_NONFINITE there, as every refused argument gets its error
+    if (!W || !q || !out_ids || !out_scores || nq <= 0 || nq >= W || k <= 0 || k > CMR_MAX_K || !cmr_combine::all_finite(q, (size_t)nq * idx->dim))
+        return host_search(idx, q, nq, k, out_ids, out_scores, out_min, out_max, nullptr);
+    CombinedSearch a{q, nq, k, out_ids, out_scores, out_min, out_max};
+    cmr_combine::Request r;
+    r.args = &a; r.nq = nq;
+    cmr_combine::Key key;
+    key.w[0] = 1; key.w[1] = (uint64_t)k;
+    idx->combiner.submit(key, &r, W, idx->combine_wait_us.load(std::memory_order_relaxed), combined_search_run, idx);
+    return combine_result(r);
 }
 
 int32_t cmr_index_search_min_score(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, float min_score, int64_t* out_ids,
@@ -1230,13 +1299,9 @@ int32_t cmr_index_scores_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, f
     return scores_enqueue(idx, ws, q_dev, nq, out_dev, ld);
 }
 
-int32_t cmr_index_scores(cmr_index_t* idx, const float* q, int32_t nq, float* out, int64_t ld) {
-    if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
-    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
-    SyncCall call(idx);
-    if (ld == 0) ld = idx->n;
-    if (ld < idx->n) return fail(CMR_ERR_INVALID, "ld %lld < rows %lld", (long long)ld, idx->n);
-    if (idx->n == 0) return CMR_OK;
+// cmr_index_scores behind its argument checks: `call` holds the index's shared lock, ld >= idx->n > 0
+static int scores_sync(SyncCall& call, const float* q, int32_t nq, float* out, int64_t ld) {
+    cmr_index* const idx = call.idx;
     int rc = call.open();
     if (rc) return rc;
     Workspace* const ws = call.ws;
@@ -1284,6 +1349,59 @@ int32_t cmr_index_scores(cmr_index_t* idx, const float* q, int32_t nq, float* ou
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld * 4, ws->d_out.p, (size_t)idx->n * 4, (size_t)idx->n * 4, (size_t)nq,
                              hipMemcpyDeviceToHost, s));
     return check_query_flag(ws);
+}
+
+// one lock for the batch; every caller's ld is judged under it and a caller that fails is answered alone
+static void combined_scores_run(void* ctx, cmr_combine::Request** reqs, int n) {
+    cmr_index* const idx = (cmr_index*)ctx;
+    SyncCall call(idx);
+    const long long rows = idx->n;
+    cmr_combine::Request* live[cmr_combine::kMaxWidth];
+    int nl = 0, NQ = 0;
+    for (int i = 0; i < n; ++i) {
+        CombinedScores* a = (CombinedScores*)reqs[i]->args;
+        if (a->ld == 0) a->ld = rows;
+        if (a->ld < rows) { combine_answer(reqs[i], fail(CMR_ERR_INVALID, "ld %lld < rows %lld", a->ld, rows)); continue; }
+        if (rows == 0) { combine_answer(reqs[i], CMR_OK); continue; }
+        live[nl++] = reqs[i];
+        NQ += reqs[i]->nq;
+    }
+    if (nl == 0) return;
+    if (nl == 1) {
+        const CombinedScores* a = (const CombinedScores*)live[0]->args;
+        combine_answer(live[0], scores_sync(call, a->q, a->nq, a->out, a->ld));
+        return;
+    }
+    const size_t dim = (size_t)idx->dim;
+    std::unique_ptr<float[]> q(new float[(size_t)NQ * dim]), out(new float[(size_t)NQ * rows]);
+    for (int i = 0, at = 0; i < nl; at += live[i++]->nq) memcpy(q.get() + (size_t)at * dim, ((const CombinedScores*)live[i]->args)->q, (size_t)live[i]->nq * dim * 4);
+    const int rc = scores_sync(call, q.get(), NQ, out.get(), rows);
+    for (int i = 0, at = 0; i < nl; at += live[i++]->nq) {
+        const CombinedScores* a = (const CombinedScores*)live[i]->args;
+        combine_answer(live[i], rc);
+        if (rc) continue;
+        for (int qi = 0; qi < a->nq; ++qi) memcpy(a->out + (size_t)qi * a->ld, out.get() + (size_t)(at + qi) * rows, (size_t)rows * 4);
+    }
+}
+
+int32_t cmr_index_scores(cmr_index_t* idx, const float* q, int32_t nq, float* out, int64_t ld) {
+    if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
+    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
+    const int W = idx->combine.load(std::memory_order_relaxed);
+    if (W && nq < W && cmr_combine::all_finite(q, (size_t)nq * idx->dim)) {      // (a non-finite query: the single call below, and its error)
+        CombinedScores a{q, nq, out, ld};
+        cmr_combine::Request r;
+        r.args = &a; r.nq = nq;
+        cmr_combine::Key key;
+        key.w[0] = 2;
+        idx->combiner.submit(key, &r, W, idx->combine_wait_us.load(std::memory_order_relaxed), combined_scores_run, idx);
+        return combine_result(r);
+    }
+    SyncCall call(idx);
+    if (ld == 0) ld = idx->n;
+    if (ld < idx->n) return fail(CMR_ERR_INVALID, "ld %lld < rows %lld", (long long)ld, idx->n);
+    if (idx->n == 0) return CMR_OK;
+    return scores_sync(call, q, nq, out, ld);
 }
 
 int32_t cmr_index_sorted_scores(cmr_index_t* idx, const float* q, int32_t nq, int64_t* out_ids, float* out_scores, float* out_min,

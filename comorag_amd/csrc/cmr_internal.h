@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "../../include/comorag_hip.h"
+#include "combine.h"
 
 // sets the calling thread's error message (cmr_last_error) and returns `code`
 int cmr_fail(int code, const char* fmt, ...);
@@ -62,3 +63,8 @@ int cmr_index_truncate(cmr_index_t* idx, long long n_rows);
 int cmr_index_scores_to_device_batch(cmr_index_t* idx, const float* q_host, int nb, float** scores_dev, long long* n, void** stream);
 int cmr_index_scores_release(cmr_index_t* idx);
 long long cmr_index_row_count(cmr_index_t* idx);      // (no device call)
+
+// for ppr.hip: the combiner of an index (combine.h) — its width (0: off; *dim: floats of one query) and one submission
+// with the index's gather window
+int cmr_index_combine_width(cmr_index_t* idx, int* dim);
+void cmr_index_combine_submit(cmr_index_t* idx, const cmr_combine::Key& key, cmr_combine::Request* req, int width, cmr_combine::RunFn run, void* ctx);

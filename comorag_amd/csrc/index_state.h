@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -14,6 +15,7 @@
 #include "../../include/comorag_hip.h"
 #include "cmr_kernels.h"
 #include "cmr_internal.h"
+#include "combine.h"
 
 #define CMR_DT_F32 0
 #define CMR_PANEL_ROWS 32
@@ -170,6 +172,11 @@ struct cmr_index {
                              // 2 M rows — 520 / 523 / 525 / 538 / 589 against 563 / 560 / 577 / 588 / 615
     int dual_wide_active = 0;   // read-only ("pipe_dual_scan_wide_active"): the same for the last wide pass
     int dual_active = 0;     // read-only ("pipe_dual_scan_active"): did the last pipelined <= 64-query pass alternate between the two scan streams
+    // combine (0 = off, 2..16): concurrent cmr_index_search / cmr_index_scores / cmr_index_ppr calls of up to this many queries in all share
+    // ONE batched call (combine.h); combine_wait_us: the leader's gather window.  Read by the entry points before any lock.
+    std::atomic<int> combine{0};
+    std::atomic<long long> combine_wait_us{0};
+    cmr_combine::Combiner combiner;
     long long id_base = 0;   // added to every returned row id (global ids of a row shard)
     // A row shard that took incremental appends holds several runs of consecutive global ids (cmr_index_set_id_blocks): the
     // kernels then run with base 0 and a remap launch translates their ids; candidate / row ids coming IN are translated

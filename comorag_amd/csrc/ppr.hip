@@ -912,9 +912,68 @@ int32_t cmr_graph_ppr_batch(cmr_graph_t* g, const double* reset, int32_t nb, dou
     return ppr_graph_run(g, reset, nb, damping, tol, max_iter, out_scores, iters);
 }
 
+// ---- combined cmr_index_ppr calls (combine.h): concurrent single calls on one index, one graph and one parameter set run as
+// ONE cmr_index_ppr_batch, whose rows hold the bits of the single calls
+struct CombinedPpr {
+    cmr_index_t* idx; cmr_graph* g; const float* q; const int32_t* sv; const double* sw; int n_seeds;
+    double pnw, damping, tol; int max_iter; double* out; int32_t* iters;
+};
+
+static void combined_ppr_run(void* ctx, cmr_combine::Request** reqs, int n) {
+    const int dim = (int)(intptr_t)ctx;
+    const CombinedPpr* a0 = (const CombinedPpr*)reqs[0]->args;
+    auto answer = [](cmr_combine::Request* r, int rc) { r->rc = rc; if (rc) r->err = cmr_last_error(); };
+    if (n == 1) {       // the caller's own call, its own arguments
+        const int32_t seed_offsets[2] = {0, a0->n_seeds};
+        answer(reqs[0], ppr_index_run(a0->idx, a0->g, a0->q, 1, seed_offsets, a0->sv, a0->sw, a0->pnw, a0->damping, a0->tol, a0->max_iter, a0->out, a0->iters));
+        return;
+    }
+    // the participants' seeds in the batch call's CSR form; the row count the results are scattered by is the one the call agreed
+    // with (ppr_index_run fails when index and passage-vertex map disagree — for everybody: they share both)
+    const long long rows = a0->g->n_rows;
+    std::vector<float> q((size_t)n * dim);
+    std::vector<int32_t> off((size_t)n + 1, 0), sv;
+    std::vector<double> sw, out((size_t)n * std::max<long long>(rows, 1));
+    for (int i = 0; i < n; ++i) {
+        const CombinedPpr* a = (const CombinedPpr*)reqs[i]->args;
+        memcpy(q.data() + (size_t)i * dim, a->q, (size_t)dim * 4);
+        sv.insert(sv.end(), a->sv, a->sv + a->n_seeds);
+        sw.insert(sw.end(), a->sw, a->sw + a->n_seeds);
+        off[i + 1] = (int32_t)sv.size();
+    }
+    int32_t it = 0;
+    int rc = ppr_index_run(a0->idx, a0->g, q.data(), n, off.data(), sv.data(), sw.data(), a0->pnw, a0->damping, a0->tol, a0->max_iter, out.data(), &it);
+    if (!rc && a0->g->n_rows != rows) rc = cmr_fail(CMR_ERR_INVALID, "the passage-vertex map changed during the call");
+    for (int i = 0; i < n; ++i) {
+        const CombinedPpr* a = (const CombinedPpr*)reqs[i]->args;
+        answer(reqs[i], rc);
+        if (rc) continue;
+        memcpy(a->out, out.data() + (size_t)i * rows, (size_t)rows * 8);
+        if (a->iters) *a->iters = it;
+    }
+}
+
 int32_t cmr_index_ppr(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, const int32_t* seed_vertices, const double* seed_weights, int32_t n_seeds,
                       double passage_node_weight, double damping, double tol, int32_t max_iter, double* out_doc_scores, int32_t* iters) {
     if (n_seeds < 0) return cmr_fail(CMR_ERR_INVALID, "bad argument");
+    int dim = 0;
+    const int W = cmr_index_combine_width(idx, &dim);
+    if (W) {
+        // what needs no lock is judged here; a call that would be refused, or whose query is not finite (the batch kernels carry one flag per
+        // launch), takes the single call below and gets its error there
+        bool joins = g && q_f32 && out_doc_scores && (n_seeds == 0 || (seed_vertices && seed_weights)) && cmr_combine::all_finite(q_f32, (size_t)dim);
+        for (int i = 0; joins && i < n_seeds; ++i) joins = seed_vertices[i] >= 0 && seed_vertices[i] < g->nv;
+        if (joins) {
+            CombinedPpr a{idx, g, q_f32, seed_vertices, seed_weights, n_seeds, passage_node_weight, damping, tol, max_iter, out_doc_scores, iters};
+            cmr_combine::Request r;
+            r.args = &a;
+            cmr_combine::Key key;
+            key.w[0] = 3; key.w[1] = (uint64_t)(uintptr_t)g; key.w[2] = cmr_combine::Key::bits(passage_node_weight); key.w[3] = cmr_combine::Key::bits(damping);
+            key.w[4] = cmr_combine::Key::bits(tol); key.w[5] = (uint64_t)(int64_t)max_iter;
+            cmr_index_combine_submit(idx, key, &r, W, combined_ppr_run, (void*)(intptr_t)dim);
+            return r.rc ? cmr_fail(r.rc, "%s", r.err.c_str()) : CMR_OK;
+        }
+    }
     const int32_t seed_offsets[2] = {0, n_seeds};
     return ppr_index_run(idx, g, q_f32, 1, seed_offsets, seed_vertices, seed_weights, passage_node_weight, damping, tol, max_iter, out_doc_scores, iters);
 }

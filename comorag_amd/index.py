@@ -208,10 +208,16 @@ class DenseIndex(HostArrayIndex):
         L.check(L.lib().cmr_index_set_option(self._h, name.encode(), int(value)))
 
     def get_option(self, name: str) -> int:
-        """Read-only pipeline facts (cmr_index_get_option): "pipe_dual_scan_active", "pipe_cu_mask_active", "pipe_scan_cus"."""
+        """Readable options (cmr_index_get_option): "pipe_dual_scan_active", "pipe_cu_mask_active", "pipe_scan_cus", "exact_cand", "combine",
+        "combine_wait_us" and the combiner's counters (`combine_stats`)."""
         v = C.c_int64(0)
         L.check(L.lib().cmr_index_get_option(self._h, name.encode(), C.byref(v)))
         return v.value
+
+    def combine_stats(self) -> dict:
+        """Counters of the combiner (option "combine" = 2..16: concurrent single search / scores / PPR calls of this index's callers share
+        one batched call): device calls made for combined work, queries served by them, the widest batch so far."""
+        return {name: self.get_option("combine_" + name) for name in ("batches", "queries", "max_width")}
 
     def append_dev(self, rows_t, stream: Optional[int] = None) -> None:
         """rows_t: torch float32 CUDA tensor [n, dim], contiguous, on this index's device."""

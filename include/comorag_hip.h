@@ -181,6 +181,17 @@ int32_t cmr_index_set_id_blocks(cmr_index_t* idx, int32_t n_blocks, const int64_
  * dim and every fp32 index run a batch of B > 64 queries on the query-split grid of the narrow kernel (up to four query tiles
  * per corpus pass) — same results.                                                                                           */
 int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
+/* Combining concurrent callers (comorag_amd/csrc/combine.h).  "combine" = 0 (default: off) or W in [2, 16]: single
+ * calls that several threads issue on this index at the same time share ONE batched call of up to W queries and each caller gets the bits of
+ * its own call —
+ *   cmr_index_search  (same k, k <= CMR_MAX_K, nq < W),  cmr_index_scores  (nq < W),
+ *   cmr_index_ppr     (same graph, passage_node_weight, damping, tol, max_iter; runs as cmr_index_ppr_batch).
+ * "combine_wait_us" (default 0): the gather window — the first caller waits until W queries have joined or the window has passed; at 0
+ * batches form only from calls that arrive while an earlier batch is on the device, and a caller alone runs its unchanged single call.
+ * A call with a NaN / Inf query, or with arguments the call refuses, never joins a batch: it gets its own error.
+ * Read-only: "combine_batches" (device calls made for combined work), "combine_queries" (queries they served), "combine_max_width".
+ * NOT combined: cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
+ * cmr_mindex_* (the option has no effect on searches issued through a multi-device handle) and the encoder.                       */
 /* What the pipeline actually does (read-only): "pipe_dual_scan_active" / "pipe_dual_scan_wide_active" (the last pipelined <= 64-query / wide pass alternated between
  * the two scan streams: by default only scans shorter than ~1 ms do — launches that overlap have no per-launch duration, so a
  * caller that times kernels must know), "pipe_cu_mask_active", "pipe_scan_cus".                                            */
