@@ -104,6 +104,7 @@ const Option kOptions[] = {
 #ifdef CMR_DEV_KNOBS
     {"wide_abl", OPT_FIELD(wide_abl), Option::any, 0, 0, 0, nullptr, nullptr},      // ablation kernels: results are WRONG by design (development builds only)
 #endif
+    {"last_route", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->last_route.load(std::memory_order_relaxed))},
     {"pipe_dual_scan_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_active)},
     {"pipe_dual_scan_wide_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_wide_active)},
     {"pipe_cu_mask_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->pipe.last_masked)},
@@ -244,6 +245,7 @@ int search_large_k_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, in
         const int nb = std::min(blockq, nq - q0);
         int rc = scores_enqueue(idx, ws, q_dev + (size_t)q0 * idx->dim, nb, (float*)ws->d_out.p, ld);
         if (rc) return rc;
+        idx->last_route.store(route_code(CMR_ROUTE_LARGE_K), std::memory_order_relaxed);
         HIP_TRY(cmr_launch_topk_rows((const float*)ws->d_out.p, ld, (int)n, nb, k, kernel_id_base(idx), ids_dev + (size_t)q0 * k,
                                      scores_dev + (size_t)q0 * k, min_dev ? min_dev + q0 : nullptr,
                                      max_dev ? max_dev + q0 : nullptr, s));
@@ -380,6 +382,8 @@ int plan_and_enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, 
     PassPlan plan;
     int rc = plan_pass(idx, st.request(ps.nqp, k, ps.route, min_score != nullptr, reserve_cus), &plan);
     if (rc) return rc;
+    if (ps.q0 == 0)      // (a batch of several passes: its first, and the bit that says more follow)
+        idx->last_route.store(route_code(plan, min_score != nullptr) | (ps.nqp < ps.nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
     return enqueue_pass(idx, ws, st, plan, q_dev + (size_t)ps.q0 * idx->dim, min_score, ids_dev + (size_t)ps.q0 * k, scores_dev + (size_t)ps.q0 * k,
                         min_dev ? min_dev + ps.q0 : nullptr, max_dev ? max_dev + ps.q0 : nullptr);
 }
@@ -390,8 +394,9 @@ int search_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, in
         if (min_score) return fail(CMR_ERR_UNSUPPORTED, "threshold search supports k <= %d", CMR_MAX_K);
         return search_large_k_enqueue(idx, ws, q_dev, nq, k, ids_dev, scores_dev, min_dev, max_dev);
     }
-    if (small_path_kind(idx, nq, k, min_score != nullptr)) {   // small corpus, few queries: ONE launch does packing, scan, selection and min/max
+    if (const int kind = small_path_kind(idx, nq, k, min_score != nullptr)) {   // small corpus, few queries: ONE launch does packing, scan, selection and min/max
         const long long npanels = idx->npanels();
+        idx->last_route.store(route_code(kind == 1 ? CMR_ROUTE_TINY : CMR_ROUTE_SMALL), std::memory_order_relaxed);
         { int rc_ = arm_flag(ws, ws->stream); if (rc_) return rc_; }
         HIP_TRY(ws->d_out.ensure(cmr_tiny_scratch_bytes(nq, (int)npanels, k, idx->tiny_multi, idx->small_max_panels)));
         if (!ws->arrive.p) {          // arrival counter of the multi-workgroup search: zeroed once, re-armed by the kernel
@@ -581,7 +586,7 @@ int check_query_flag(Workspace* ws) {
     HIP_TRY(hipStreamSynchronize(ws->stream));
     if (h) {
         HIP_TRY(hipMemsetAsync(ws->flag_ptr, 0, sizeof(int), ws->stream));
-        return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf");
+        return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf or a value that rounds to Inf in the index dtype");
     }
     return CMR_OK;
 }
@@ -622,7 +627,7 @@ int append_from_device(cmr_index* idx, const float* rows_dev, long long n, hipSt
     int h = 0;
     HIP_TRY(hipMemcpyAsync(&h, idx->d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (h) return fail(CMR_ERR_NONFINITE, "appended rows contain NaN/Inf (index unchanged)");
+    if (h) return fail(CMR_ERR_NONFINITE, "appended rows contain NaN/Inf or a value that rounds to Inf in the index dtype (index unchanged)");
     idx->n += n;
     return CMR_OK;
 }
@@ -683,10 +688,11 @@ long long cmr_index_row_count(cmr_index_t* idx) {      // for ppr.hip's argument
     return idx->n;
 }
 
-// ---- for ppr.hip: the index's combiner (combine.h) — its width (0: off; *dim for the host check of the query), one submission
-int cmr_index_combine_width(cmr_index_t* idx, int* dim) {
+// ---- for ppr.hip: the index's combiner (combine.h) — its width (0: off; *dim and *dtype for the host check of the query), one submission
+int cmr_index_combine_width(cmr_index_t* idx, int* dim, int* dtype) {
     if (!idx) return 0;
     *dim = idx->dim;
+    *dtype = idx->dtype;
     return idx->combine.load(std::memory_order_relaxed);
 }
 void cmr_index_combine_submit(cmr_index_t* idx, const cmr_combine::Key& key, cmr_combine::Request* req, int width, cmr_combine::RunFn run, void* ctx) {
@@ -846,7 +852,7 @@ int32_t cmr_index_append(cmr_index_t* idx, const float* rows, int64_t n) {
         HIP_TRY(hipStreamSynchronize(nullptr));
         int flagged = 0;
         memcpy(&flagged, h, sizeof(int));
-        if (flagged) return fail(CMR_ERR_NONFINITE, "appended rows contain NaN/Inf (index unchanged)");
+        if (flagged) return fail(CMR_ERR_NONFINITE, "appended rows contain NaN/Inf or a value that rounds to Inf in the index dtype (index unchanged)");
         idx->n += n;
         return CMR_OK;
     }
@@ -1182,7 +1188,7 @@ int cmr_index_search_finish(CmrPending* P, int64_t* out_ids, float* out_scores, 
     memcpy(&flagged, hp, sizeof(int));
     if (flagged) {
         if (!P->mapped) HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, sizeof(int), ws->stream));
-        return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf");
+        return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf or a value that rounds to Inf in the index dtype");
     }
     const size_t nk = (size_t)P->nq * P->k;
     if (out_ids) memcpy(out_ids, hp + P->o_ids, nk * 8);
@@ -1268,7 +1274,7 @@ int32_t cmr_index_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t k
     const int W = idx ? idx->combine.load(std::memory_order_relaxed) : 0;
     // joins a batch: fewer queries than the batch holds, the fused search (k <= CMR_MAX_K), and finite queries — the batch kernels carry one
     // non-finite flag per launch, so such a query takes the single call and gets its CMR_ERR_NONFINITE there, as every refused argument gets its error
-    if (!W || !q || !out_ids || !out_scores || nq <= 0 || nq >= W || k <= 0 || k > CMR_MAX_K || !cmr_combine::all_finite(q, (size_t)nq * idx->dim))
+    if (!W || !q || !out_ids || !out_scores || nq <= 0 || nq >= W || k <= 0 || k > CMR_MAX_K || !cmr_combine::all_finite(q, (size_t)nq * idx->dim, idx->dtype))
         return host_search(idx, q, nq, k, out_ids, out_scores, out_min, out_max, nullptr);
     CombinedSearch a{q, nq, k, out_ids, out_scores, out_min, out_max};
     cmr_combine::Request r;
@@ -1326,6 +1332,7 @@ static int scores_sync(SyncCall& call, const float* q, int32_t nq, float* out, i
                 q_in = (const float*)ws->d_q.p;
             }
             HIP_TRY(ws->d_out.ensure((size_t)nq * npanels * CMR_PANEL_ROWS * 4));
+            idx->last_route.store(route_code(CMR_ROUTE_SCORES_SINGLE), std::memory_order_relaxed);
             if (idx->sync_poll && !ws->arrive.p) {          // arrival counter: zeroed once, re-armed by the kernel
                 HIP_TRY(ws->arrive.ensure(sizeof(int)));
                 HIP_TRY(hipMemsetAsync(ws->arrive.p, 0, sizeof(int), s));
@@ -1336,7 +1343,7 @@ static int scores_sync(SyncCall& call, const float* q, int32_t nq, float* out, i
             else HIP_TRY(hipStreamSynchronize(s));
             int flagged = 0;
             memcpy(&flagged, h, sizeof(int));
-            if (flagged) return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf");
+            if (flagged) return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf or a value that rounds to Inf in the index dtype");
             for (int qi = 0; qi < nq; ++qi) memcpy(out + (size_t)qi * ld, h + o_sc + (size_t)qi * idx->n * 4, (size_t)idx->n * 4);
             return CMR_OK;
         }
@@ -1346,6 +1353,7 @@ static int scores_sync(SyncCall& call, const float* q, int32_t nq, float* out, i
     HIP_TRY(hipMemcpyAsync(ws->d_q.p, q, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, s));
     rc = scores_enqueue(idx, ws, (const float*)ws->d_q.p, nq, (float*)ws->d_out.p, idx->n);
     if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    idx->last_route.store(route_code(CMR_ROUTE_SCORES), std::memory_order_relaxed);
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld * 4, ws->d_out.p, (size_t)idx->n * 4, (size_t)idx->n * 4, (size_t)nq,
                              hipMemcpyDeviceToHost, s));
     return check_query_flag(ws);
@@ -1388,7 +1396,7 @@ int32_t cmr_index_scores(cmr_index_t* idx, const float* q, int32_t nq, float* ou
     if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
     const int W = idx->combine.load(std::memory_order_relaxed);
-    if (W && nq < W && cmr_combine::all_finite(q, (size_t)nq * idx->dim)) {      // (a non-finite query: the single call below, and its error)
+    if (W && nq < W && cmr_combine::all_finite(q, (size_t)nq * idx->dim, idx->dtype)) {      // (a non-finite query: the single call below, and its error)
         CombinedScores a{q, nq, out, ld};
         cmr_combine::Request r;
         r.args = &a; r.nq = nq;
@@ -1419,6 +1427,7 @@ int32_t cmr_index_sorted_scores(cmr_index_t* idx, const float* q, int32_t nq, in
     HIP_TRY(ws->d_out.ensure((size_t)n * 4));
     HIP_TRY(ws->d_cand.ensure(cmr_sort_workspace_bytes(n)));
     HIP_TRY(hipMemcpyAsync(ws->d_q.p, q, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, s));
+    idx->last_route.store(route_code(CMR_ROUTE_SORTED), std::memory_order_relaxed);
     // Several queries: scan + sort of query i + 1 run while the 12 N bytes of query i cross the link on a second stream
     // (two result sets, two event pairs; one query: no second stream, no events).  Nothing synchronises per query.
     const int nset = nq > 1 ? 2 : 1;

@@ -41,6 +41,8 @@ __device__ __forceinline__ uint4 cmr_pack_slot(const float* row, int dim, int ks
                 bad |= !cmr_finite(f);
                 unsigned short h;
                 if (DT == CMR_DT_BF16) h = Pack<CMR_DT_BF16>::cvt(f); else h = Pack<CMR_DT_F16>::cvt(f);
+                // a finite fp32 value may round to an infinity of the index dtype (70000 in f16, 3.4e38 in bf16): exponent field all ones
+                bad |= DT == CMR_DT_BF16 ? (h & 0x7F80u) == 0x7F80u : (h & 0x7C00u) == 0x7C00u;
                 w[e >> 1] |= (unsigned)h << (16 * (e & 1));
             }
         }

@@ -66,5 +66,5 @@ long long cmr_index_row_count(cmr_index_t* idx);      // (no device call)
 
 // for ppr.hip: the combiner of an index (combine.h) — its width (0: off; *dim: floats of one query) and one submission
 // with the index's gather window
-int cmr_index_combine_width(cmr_index_t* idx, int* dim);
+int cmr_index_combine_width(cmr_index_t* idx, int* dim, int* dtype);
 void cmr_index_combine_submit(cmr_index_t* idx, const cmr_combine::Key& key, cmr_combine::Request* req, int width, cmr_combine::RunFn run, void* ctx);

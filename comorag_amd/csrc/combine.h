@@ -139,12 +139,15 @@ private:
     long long batches_ = 0, queries_ = 0, max_width_ = 0;
 };
 
-// any NaN / Inf among n floats (a query that would set the batch kernels' one flag per launch stays out of a batch)
-inline bool all_finite(const float* v, size_t n) {
+// any NaN / Inf among n floats, as the packing kernels judge them for an index of `dtype` (0 fp32, 1 bf16, 2 f16: a finite fp32 value
+// that rounds to an infinity there counts) — a query that would set the batch kernels' one flag per launch stays out of a batch
+inline bool all_finite(const float* v, size_t n, int dtype = 0) {
     for (size_t i = 0; i < n; ++i) {
         uint32_t u;
         memcpy(&u, v + i, 4);
         if ((u & 0x7F800000u) == 0x7F800000u) return false;
+        if (dtype == 1 && (((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16) & 0x7F80u) == 0x7F80u) return false;      // bf16, round to nearest even
+        if (dtype == 2 && (u & 0x7FFFFFFFu) >= 0x477FF000u) return false;                                     // f16: |v| >= 65520 rounds to Inf
     }
     return true;
 }

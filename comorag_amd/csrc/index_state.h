@@ -171,6 +171,9 @@ struct cmr_index {
                              // 1 M rows — 1 / 2 / 4 / 8 / 16 queries 287 / 292 / 297 / 322 / 392 us against 300 / 313 / 333 / 336 / 372;
                              // 2 M rows — 520 / 523 / 525 / 538 / 589 against 563 / 560 / 577 / 588 / 615
     int dual_wide_active = 0;   // read-only ("pipe_dual_scan_wide_active"): the same for the last wide pass
+    // read-only ("last_route"): how the last search / scores call planned on this index was routed (CMR_ROUTE_* in include/comorag_hip.h;
+    // search_plan.h route_code).  Written by host code under the shared lock, so concurrent callers race benignly: relaxed atomic.
+    std::atomic<long long> last_route{0};
     int dual_active = 0;     // read-only ("pipe_dual_scan_active"): did the last pipelined <= 64-query pass alternate between the two scan streams
     // combine (0 = off, 2..16): concurrent cmr_index_search / cmr_index_scores / cmr_index_ppr calls of up to this many queries in all share
     // ONE batched call (combine.h); combine_wait_us: the leader's gather window.  Read by the entry points before any lock.

@@ -956,12 +956,12 @@ static void combined_ppr_run(void* ctx, cmr_combine::Request** reqs, int n) {
 int32_t cmr_index_ppr(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, const int32_t* seed_vertices, const double* seed_weights, int32_t n_seeds,
                       double passage_node_weight, double damping, double tol, int32_t max_iter, double* out_doc_scores, int32_t* iters) {
     if (n_seeds < 0) return cmr_fail(CMR_ERR_INVALID, "bad argument");
-    int dim = 0;
-    const int W = cmr_index_combine_width(idx, &dim);
+    int dim = 0, dtype = 0;
+    const int W = cmr_index_combine_width(idx, &dim, &dtype);
     if (W) {
         // what needs no lock is judged here; a call that would be refused, or whose query is not finite (the batch kernels carry one flag per
         // launch), takes the single call below and gets its error there
-        bool joins = g && q_f32 && out_doc_scores && (n_seeds == 0 || (seed_vertices && seed_weights)) && cmr_combine::all_finite(q_f32, (size_t)dim);
+        bool joins = g && q_f32 && out_doc_scores && (n_seeds == 0 || (seed_vertices && seed_weights)) && cmr_combine::all_finite(q_f32, (size_t)dim, dtype);
         for (int i = 0; joins && i < n_seeds; ++i) joins = seed_vertices[i] >= 0 && seed_vertices[i] < g->nv;
         if (joins) {
             CombinedPpr a{idx, g, q_f32, seed_vertices, seed_weights, n_seeds, passage_node_weight, damping, tol, max_iter, out_doc_scores, iters};

@@ -270,6 +270,17 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     return CMR_OK;
 }
 
+// "last_route" (include/comorag_hip.h): path | sampling levels << 4 | tau_in_scan << 6 | single 128-panel level << 7 | query tiles per workgroup << 8 |
+// threshold search << 10 (| CMR_ROUTE_MORE_PASSES where the batch is cut into several passes: plan_and_enqueue_pass)
+long long route_code(int path, int n_levels = 0, bool tau_in_scan = false, bool single_level = false, int nqt = 1, bool threshold = false) {
+    return (long long)path | ((long long)n_levels << 4) | ((long long)(tau_in_scan ? 1 : 0) << 6) | ((long long)(single_level ? 1 : 0) << 7) | ((long long)nqt << 8) |
+           ((long long)(threshold ? 1 : 0) << 10);
+}
+long long route_code(const PassPlan& p, bool threshold) {
+    const int path = p.wide ? CMR_ROUTE_WIDE : p.G > 1 ? CMR_ROUTE_QUERY_SPLIT : p.fin ? CMR_ROUTE_FIN : CMR_ROUTE_CHAIN;
+    return route_code(path, p.n_levels, p.tau_in_scan, p.single_level, p.g.nqt, threshold);
+}
+
 // ---- a batch splits into passes
 
 // Batches of more than one narrow pass: which kernel runs them, and how many queries it takes per corpus pass (0 = narrow passes).

@@ -208,7 +208,8 @@ class DenseIndex(HostArrayIndex):
         L.check(L.lib().cmr_index_set_option(self._h, name.encode(), int(value)))
 
     def get_option(self, name: str) -> int:
-        """Readable options (cmr_index_get_option): "pipe_dual_scan_active", "pipe_cu_mask_active", "pipe_scan_cus", "exact_cand", "combine",
+        """Readable options (cmr_index_get_option): "last_route" (which path served the last call: CMR_ROUTE_* and the bits beside it in
+        include/comorag_hip.h), "pipe_dual_scan_active", "pipe_cu_mask_active", "pipe_scan_cus", "exact_cand", "combine",
         "combine_wait_us" and the combiner's counters (`combine_stats`)."""
         v = C.c_int64(0)
         L.check(L.lib().cmr_index_get_option(self._h, name.encode(), C.byref(v)))

@@ -32,7 +32,11 @@
  * tests/test_dropin_gpu.py pins both sides of the threshold.)  Scores on the
  * wire are RAW inner products; ComoRAG's min-max normalisation (utils/misc_utils.py:141-150) is
  * applied by the Python layer from out_min/out_max so its formula stays textually the
- * reference's.  Inputs must be finite (checked: CMR_ERR_NONFINITE).
+ * reference's.  Inputs must be finite IN THE INDEX DTYPE (checked: CMR_ERR_NONFINITE): NaN / Inf, and for a bf16 / f16 index also a
+ * finite fp32 value that rounds to an infinity there (|v| >= 65520 in f16, |v| >= 2^127 (2 - 2^-8) ~ 3.39e38 in bf16), are refused in
+ * appended rows (the index is unchanged) and in queries alike; an fp32 index takes every finite value.
+ * f16 subnormals (|v| < 2^-14 after rounding) are stored and multiplied as they are: the gfx950 matrix instructions do not flush
+ * them (tests/test_value_domain_gpu.py pins it).
  *
  * Encoder stages (cmr_encoder_*): the library computes the model's own functions — softmax attention, fp32 LayerNorm statistics, masked
  * mean-pool + L2 normalisation; the FFN's GELU runs in PyTorch, by default in the model's exact (erf) form.  The Python layer can OPT IN (`embedding_gelu = "epilogue"`) to hipBLASLt's bias + GELU GEMM epilogue,
@@ -62,7 +66,7 @@ enum cmr_status {
     CMR_ERR_NO_DEVICE = -2,   /* no usable HIP device / wrong arch */
     CMR_ERR_HIP = -3,         /* a HIP runtime call failed (message has the call) */
     CMR_ERR_OOM = -4,
-    CMR_ERR_NONFINITE = -5,   /* NaN/Inf in rows or queries */
+    CMR_ERR_NONFINITE = -5,   /* NaN/Inf in rows or queries, or a value that rounds to Inf in the index dtype */
     CMR_ERR_UNSUPPORTED = -6  /* e.g. k above CMR_MAX_K */
 };
 
@@ -192,6 +196,26 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  * Read-only: "combine_batches" (device calls made for combined work), "combine_queries" (queries they served), "combine_max_width".
  * NOT combined: cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
  * cmr_mindex_* (the option has no effect on searches issued through a multi-device handle) and the encoder.                       */
+/* Which path served the last call (read-only): "last_route", written by the host when a search or all-scores call on this index is
+ * planned (for a batch of several corpus passes: its first pass); 0 before the first call.  Concurrent callers overwrite each other.
+ *   bits 0..3   the path, CMR_ROUTE_*
+ *   bits 4..5   sampling levels in front of the main scan (0, 1, 2)
+ *   bit  6      the one sampling level's thresholds are derived inside the main scan (sample_tau_in_scan)
+ *   bit  7      that level is the single 128-panel sample of a small batch (sample_single)
+ *   bits 8..9   query tiles of 32 per workgroup (1, 2)
+ *   bit  10     threshold search (cmr_index_search_min_score*)
+ *   bit  11     the batch took more than one corpus pass: the bits above describe its first, later passes may be routed otherwise   */
+#define CMR_ROUTE_MORE_PASSES (1 << 11)
+#define CMR_ROUTE_TINY 1          /* single launch, <= 1024 rows */
+#define CMR_ROUTE_SMALL 2         /* single launch, hierarchical selection */
+#define CMR_ROUTE_CHAIN 3         /* narrow kernel: pack / [sample] / scan / merge */
+#define CMR_ROUTE_FIN 4           /* narrow kernel with the finishing stage */
+#define CMR_ROUTE_WIDE 5          /* register-resident wide kernel */
+#define CMR_ROUTE_QUERY_SPLIT 6   /* query-split grid of the narrow kernel */
+#define CMR_ROUTE_LARGE_K 7       /* k > CMR_MAX_K: all scores, then per-row selection */
+#define CMR_ROUTE_SCORES_SINGLE 8 /* cmr_index_scores, single launch */
+#define CMR_ROUTE_SCORES 9        /* cmr_index_scores, general scan */
+#define CMR_ROUTE_SORTED 10       /* cmr_index_sorted_scores: general scan + radix sort */
 /* What the pipeline actually does (read-only): "pipe_dual_scan_active" / "pipe_dual_scan_wide_active" (the last pipelined <= 64-query / wide pass alternated between
  * the two scan streams: by default only scans shorter than ~1 ms do — launches that overlap have no per-launch duration, so a
  * caller that times kernels must know), "pipe_cu_mask_active", "pipe_scan_cus".                                            */
