@@ -217,17 +217,17 @@ def audit_ring(asm_text: str) -> dict:
     return result
 
 
-_WIDE_RE = re.compile(r"^_Z16scan_wide_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi0ELi(\d+)EEv5ScanP:")   # ABL = 0 only
+_WIDE_RE = re.compile(r"^_Z16scan_wide_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEv5ScanP:")
 
 
 def audit_wide(asm_text: str) -> dict:
     """The wide kernel keeps 384 registers of query fragments resident and issues its MFMAs as inline asm (hipcc pads
-    no hazards around them).  Per scan_wide_kernel<DT,KS,NT,CAP,NST,KLDS> require: no scratch traffic at all (a spill
+    no hazards around them).  Per scan_wide_kernel<DT,KS,NT,CAP,NSTG> require: no scratch traffic at all (a spill
     reload inside the panel loop would drain the hand-counted DMA ring), no v_accvgpr_write and no more v_accvgpr_read
     than the epilogue instances account for (anything more means fragments are being shuttled between the register
     files in front of the MFMAs), and no compiler VALU write of an MFMA A/B operand register
     in the three instructions before an asm MFMA (VALU write -> MFMA read needs wait states hipcc does not insert).
-    Returns {(dt,ks,nt,cap,waves): problem string or ''}."""
+    Returns {(dt,ks,nt,cap,nstg): problem string or ''}."""
     result = {}
     lines = asm_text.split("\n")
     i = 0
@@ -236,7 +236,7 @@ def audit_wide(asm_text: str) -> dict:
         if not m:
             i += 1
             continue
-        dt, ks, nt, cap, nst, klds, nw = (int(x) for x in m.groups())
+        dt, ks, nt, cap, nstg = (int(x) for x in m.groups())
         j = i + 1
         body = []
         while j < len(lines) and not lines[j].startswith(".Lfunc_end"):
@@ -257,7 +257,7 @@ def audit_wide(asm_text: str) -> dict:
         # loop).  Anything beyond that means query fragments are being shuttled between the register files in front of
         # the MFMAs.
         n_read = sum(c.startswith("v_accvgpr_read") for c in code)
-        lim_read = 64 * 3 if nt == 2 else (64 if nw == 8 else 48)      # 8-wave kernel: asm fold + cold partial fold + two pushes that re-read
+        lim_read = 64 * 3 if nt == 2 else 48
         if n_read > lim_read:
             problems.append(f"{n_read} v_accvgpr_read > {lim_read}")
         n_mfma = 0
@@ -272,7 +272,7 @@ def audit_wide(asm_text: str) -> dict:
                     problems.append(f"VALU write of an MFMA operand right before it: '{prev}' -> '{c}'")
         if n_mfma < ks * nt:
             problems.append(f"only {n_mfma} MFMAs found")
-        result[(dt, ks, nt, cap, nw)] = "; ".join(problems)
+        result[(dt, ks, nt, cap, nstg)] = "; ".join(problems)
     return result
 
 

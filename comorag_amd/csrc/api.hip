@@ -91,7 +91,6 @@ const Option kOptions[] = {
     {"sample_maxmul", OPT_FIELD(sample_maxmul), Option::clamp, 0, LLONG_MAX, 0, nullptr, nullptr},
     {"pipe_reserve_cus", OPT_FIELD(reserve_cus), Option::any, 0, 0, 0, nullptr, nullptr},
     {"pipe_slots", OPT_FIELD(pipe_slots), Option::any, 0, 0, 0, nullptr, nullptr},
-    {"wide_waves", OPT_FIELD(wide_waves), Option::oneof, 0, 4, 8, "wide_waves must be 0 (default), 4 or 8", nullptr},
     {"wide_mode", OPT_FIELD(wide_mode), Option::range, 0, 2, 0, "wide_mode must be 0 (default), 1 (register-resident kernel) or 2 (query-split grid)", nullptr},
     {"stream_nt", OPT_FIELD(stream_nt), Option::any, 0, 0, 0, nullptr, nullptr},
     {"pipe_dual_scan", OPT_FIELD(dual_scan), Option::any, 0, 0, 0, nullptr, nullptr},
@@ -101,9 +100,6 @@ const Option kOptions[] = {
      "combine must be 0 (off) or in [2, " CMR_STR(CMR_PPR_MAX_BATCH) "]", OPT_READ(i->combine.load(std::memory_order_relaxed))},
     {"combine_wait_us", [](cmr_index* i, long long v) { i->combine_wait_us.store(v, std::memory_order_relaxed); }, Option::clamp, 0, 10000000, 0, nullptr,
      OPT_READ(i->combine_wait_us.load(std::memory_order_relaxed))},
-#ifdef CMR_DEV_KNOBS
-    {"wide_abl", OPT_FIELD(wide_abl), Option::any, 0, 0, 0, nullptr, nullptr},      // ablation kernels: results are WRONG by design (development builds only)
-#endif
     {"last_route", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->last_route.load(std::memory_order_relaxed))},
     {"pipe_dual_scan_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_active)},
     {"pipe_dual_scan_wide_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_wide_active)},
@@ -130,19 +126,6 @@ int set_option(cmr_index* idx, const char* name, long long v) {
     o->store(idx, v);
     return CMR_OK;
 }
-
-#ifdef CMR_DEV_KNOBS
-// development builds (-DCMR_DEV_KNOBS, tools/): the same options from the environment, CMR_<OPTION NAME IN CAPITALS>
-void options_from_env(cmr_index* idx) {
-    for (const Option& o : kOptions) {
-        if (!o.store) continue;
-        std::string env = "CMR_";
-        for (const char* c = o.name; *c; ++c) env += (char)toupper(*c);
-        const char* v = getenv(env.c_str());
-        if (v && *v) (void)set_option(idx, o.name, atoll(v));
-    }
-}
-#endif
 
 // shard-local ids -> global ids, on the stream that produced them (no-op for a single block)
 int remap_ids_enqueue(cmr_index* idx, int64_t* ids_dev, long long n, hipStream_t s);
@@ -751,9 +734,6 @@ int32_t cmr_index_create(int32_t device_id, int32_t dim, int32_t dtype, int64_t 
     idx->flags = flags;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) idx->n_cu = prop.multiProcessorCount;
-#ifdef CMR_DEV_KNOBS
-    options_from_env(idx);
-#endif
     if (cmr_scan_max_nqt(dtype, idx->dpad) == 0) {
         delete idx;
         return fail(CMR_ERR_UNSUPPORTED, "dim %d (padded %d) exceeds the LDS-resident query tile for dtype %d", dim, round_up(dim, 128), dtype);

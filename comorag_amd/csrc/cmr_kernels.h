@@ -16,8 +16,6 @@ struct CmrScanGeom {
     int grid;       // workgroups
     int asm_ring;   // 1: hand-counted inline-asm load ring, 0: compiler-counted loads
     size_t lds;     // dynamic LDS bytes
-    int wide_waves; // wide kernel at 768-d: 0 = default, 4 = one wave per SIMD x 2 tiles, 8 = two waves per SIMD x 1 tile
-    int wide_abl;   // development builds only (-DCMR_DEV_KNOBS): ablation variant of the wide kernel
     int stream_default_policy;   // narrow top-k kernel: 1 = corpus loads with the default cache policy instead of non-temporal (query-split grid)
 };
 
@@ -83,8 +81,6 @@ struct CmrScanArgs {
 #define CMR_FIN_WGS 64        // workgroups finished
 #define CMR_FIN_STATE 96      // result state: 1 = the scan wrote the final results itself, 2 = a list overflowed (the merge launch decides)
 #define CMR_FIN_OVER 128      // some workgroup's staging area overflowed
-#define CMR_FIN_DBG 136
-#define CMR_FIN_DBG2 196      // development builds: per-wave sums (behind CMR_FIN_CLAIM's word, same line)
 #define CMR_FIN_PUB 160       // supplying workgroups whose maxima are written through
 #define CMR_FIN_CLAIM 192     // queries whose threshold somebody has taken on
 #define CMR_FIN_MAX_QUERIES 16
@@ -102,7 +98,7 @@ hipError_t cmr_launch_scan_fin(const CmrScanGeom& g, const CmrScanArgs& a, hipSt
 // in sampling mode (sample_waves > 0) the grid's workgroups split the sample_waves strided panels among them
 hipError_t cmr_launch_scan_wide(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);
 int cmr_wide_queries(int dtype, int dpad);      // queries per pass of the wide kernel (0 = unavailable)
-size_t cmr_wide_lds_bytes(int ks, int cap, int waves);
+size_t cmr_wide_lds_bytes(int ks, int cap);
 
 // queries fp32 [nq, dim] (device) -> fragment-ordered blocks of the index dtype, zero padded
 hipError_t cmr_launch_prep_queries(int dtype, const float* q, int nq, int dim, int dpad, int nqt,

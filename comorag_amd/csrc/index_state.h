@@ -148,13 +148,11 @@ struct cmr_index {
     int small_max_panels = 6144;   // small_max_panels: largest corpus (in 32-row panels) the single-launch path takes
     int no_small = 0;        // scan_no_small = 1: corpora of 1025 rows .. 64 K rows take the general path also for few queries
     int zero_copy = 1;       // zero_copy = 0: the synchronous host API copies queries / results instead of mapping them
-    int wide_waves = 0;      // wide_waves = 4 | 8: waves per workgroup of the wide kernel at 768-d (0 = the measured default)
     int dual_scan = -1;      // pipe_dual_scan: -1 (default: with the masks, for scans shorter than 1 ms) | 1 (always) | 0 (never): main scans alternate between two streams, so the next scan's workgroups take over the CUs this
                              // scan's workgroups leave (no idle gap between two scans); needs pipe_cu_mask, else the next scan would simply
                              // occupy the CUs left free for the pre-phase
     int cu_mask = -1;        // pipe_cu_mask = -1 (default on a 256-CU device: scans shorter than 1 ms) | 1 | 2 (every scan) | 0 (off): scan stream(s) with a CU mask of n_cu - 64 CUs, the pre-phase streams
                              // with the other 64 (1: mask bits interleave the XCDs — the amdgpu driver's enumeration; 2: 32 consecutive bits per XCD)
-    int wide_abl = 0;        // development builds only
     int stream_nt = -1;      // stream_nt: -1 default (non-temporal corpus loads, default policy for the query-split grid) | 0 | 1: force
     int wide_mode = 0;       // wide_mode: batches of more than one narrow pass — 1: the register-resident wide kernel, 2: the query-split grid of the
                              // narrow kernel (up to 4 query tiles walk the same panel ranges on CUs of one XCD; any dim / dtype), 0: the measured default

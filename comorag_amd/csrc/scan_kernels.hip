@@ -39,60 +39,15 @@
 // mid-size or large corpus: the sampling scan, its merge and the candidate merge are a chain of dependent launches around a
 // short scan there) — see "finishing stage" in scan_kernel
 #define MODE_FIN 2
-#ifndef CMR_FIN_HINT
-#define CMR_FIN_HINT 1     // finishing stage, hand-counted ring: the READY word is asked for inside the ring's own load sequence and only hints at the proper look (below)
-#endif
 
 // Cache policy of the corpus stream's loads: non-temporal.  Every byte of the corpus is read once per launch by one CU,
-// so keeping the lines in L2 / MALL only evicts what the other kernels of the pipeline use; measured with
-// -DCMR_STREAM_NT=0 / 1 builds: 10 M x 768 bf16, B = 64 step 2.567 -> 2.401 ms, 1 M rows 0.294 -> 0.282 ms (the wide
-// kernel, which is not HBM-bound, does not move).
-#ifndef CMR_STREAM_NT
-#define CMR_STREAM_NT 1
-#endif
-#if CMR_STREAM_NT
+// so keeping the lines in L2 / MALL only evicts what the other kernels of the pipeline use; measured against the default
+// policy: 10 M x 768 bf16, B = 64 step 2.567 -> 2.401 ms, 1 M rows 0.294 -> 0.282 ms (the wide kernel, which is not
+// HBM-bound, does not move).
 #define CMR_STREAM_POLICY " nt"
 #define CMR_STREAM_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define CMR_STREAM_POLICY ""
-#define CMR_STREAM_LOAD(p) (*(p))
-#endif
 // scan_kernel carries the policy as a template parameter (POL = 1: the policy above; 0: default policy — the query-split grid WANTS
 // the corpus lines to stay in L2 until the twins of the other query groups have read them)
-// wide kernel: 1 = all DMA pieces of a group right after its barrier, 0 = one piece per quad of blocks
-#ifndef CMR_WIDE_DMA_BURST
-#define CMR_WIDE_DMA_BURST 0
-#endif
-// Placement of a quad's LDS-DMA piece in the two-tile wide kernel.  0: in front of the quad's eight MFMAs, i.e. directly behind
-// the four ds_read_b128 that refill the read-ahead ring (one boundary of the MFMA stream carries 4 LDS reads + the piece + its
-// SALU: a dozen issue slots in ONE gap).  1: between tile 0's four MFMAs and tile 1's four — the other boundary between chains
-// on DIFFERENT accumulators, 128 cycles behind the ring's reads (MI355X_MICROARCH.md: a gap between MFMAs hides <= 5 single-issue
-// instructions, fillers between MFMAs on the SAME accumulator are never free, and a piece issued beside pending LDS reads
-// costs its wave 100-185 cycles against 25-60 in a quiet gap).
-#ifndef CMR_WIDE_DMA_MID
-#define CMR_WIDE_DMA_MID 1
-#endif
-// M0 around a piece: 0 = saved and restored inside the statement (5 instructions), 1 = written and left (3; hipcc sets M0 itself
-// in front of each of its own uses — v_writelane lane selects in the compaction — and expects nothing of it across an asm)
-#ifndef CMR_WIDE_M0_CLOBBER
-#define CMR_WIDE_M0_CLOBBER 1
-#endif
-// 1: a piece's displacement inside its group comes from the instruction's immediate + a loop-invariant lane offset, M0 is set inside
-// the statement: no compiler-generated SALU per piece (see dma_piece_j)
-#ifndef CMR_WIDE_DMA_IMM
-#define CMR_WIDE_DMA_IMM 1
-#endif
-// 1 (two-tile kernel): both tiles' accumulators live in the VGPR half — their readers (the min / max fold, the slow path) take them as
-// they are, no v_accvgpr_read: 32 fewer instructions per panel — and WIDE_AMOVE_V k-steps of tile 0's B-operands move to the AGPR half in
-// exchange (which then holds 192 + 64 registers of fragments and nothing else)
-#ifndef CMR_WIDE_ACC_VGPR
-#define CMR_WIDE_ACC_VGPR 1
-#endif
-// 1: the read-ahead ring's slot j is refilled directly behind the LAST tile's MFMA j of a quad (the slot's final reader), where the
-// wait state between two MFMAs of one chain is due anyway, instead of four ds_read_b128 in a row behind the quad
-#ifndef CMR_WIDE_READ_INTERLEAVE
-#define CMR_WIDE_READ_INTERLEAVE 1
-#endif
 
 struct ScanP {
     const v4u* corpus;
@@ -226,19 +181,7 @@ __device__ __forceinline__ void fin_threshold(const u64* pmax, int ns, int k, u6
     });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0) atomicOr(ready, 1 << q);
-#ifdef CMR_FIN_DEBUG
-    if (lane == 0) { atomicMin((unsigned*)(ready - CMR_FIN_READY + CMR_FIN_DBG + 2 + 3), (unsigned)wall_clock64()); atomicMax((unsigned*)(ready - CMR_FIN_READY + CMR_FIN_DBG + 2 + 4), (unsigned)wall_clock64()); }      // first / last threshold published
-#endif
 }
-
-// development builds (-DCMR_FIN_DEBUG): a timeline of the finishing stage in 10 ns ticks of the constant clock, slots behind CMR_FIN_DBG + 2
-#ifdef CMR_FIN_DEBUG
-#define CMR_FIN_STAMP_MIN(P, slot) atomicMin((unsigned*)&(P).fin[CMR_FIN_DBG + 2 + (slot)], (unsigned)wall_clock64())
-#define CMR_FIN_STAMP_MAX(P, slot) atomicMax((unsigned*)&(P).fin[CMR_FIN_DBG + 2 + (slot)], (unsigned)wall_clock64())
-#else
-#define CMR_FIN_STAMP_MIN(P, slot) ((void)0)
-#define CMR_FIN_STAMP_MAX(P, slot) ((void)0)
-#endif
 
 template <int DT, int NQT, int CAP, int R, int MODE, int ASMRING, int POL = 1>
 __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
@@ -293,7 +236,6 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
     if (TOPK)
         for (int i = tid; i < CMR_SCAN_WAVES * NQ; i += CMR_SCAN_THREADS) cnt_all[i] = 0;
     if (FIN && tid == 0) { fin_sh[1] = 0; fin_sh[2] = 0; }
-    if constexpr (FIN) { if (tid == 0) { CMR_FIN_STAMP_MIN(P, 0); CMR_FIN_STAMP_MAX(P, 1); } }      // first / last workgroup start
     __syncthreads();
 
     const int W = vgrid * CMR_SCAN_WAVES;
@@ -370,14 +312,6 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
     }
     u64* list_w = TOPK ? P.lists + gwl * NQ * CAP : nullptr;
     int fin_phase = 0;      // FIN: 0 = first panel pending, 1 = waiting for the published thresholds, 2 = adopted
-#ifdef CMR_FIN_DEBUG
-    unsigned dbg_t_slow = 0, dbg_n_slow = 0, dbg_n_whole = 0, dbg_t_thr = 0, dbg_t_epi = 0;      // ticks (10 ns) / counts of this wave
-#define CMR_DBG_T0 const unsigned dbg_t0_ = (unsigned)wall_clock64();
-#define CMR_DBG_ADD(V) V += (unsigned)wall_clock64() - dbg_t0_;
-#else
-#define CMR_DBG_T0
-#define CMR_DBG_ADD(V)
-#endif
     if constexpr (FIN) {
         // The workgroups that do not supply the thresholds look for them before they start: the second round of workgroups (a CU
         // holds one at a time) finds them published and never scans without.  fin_spin > 0 makes wave 0 look again every ~1.5 us
@@ -489,7 +423,7 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
         [[maybe_unused]] bool fin_hint_valid = false;
         asm volatile("" : "+v"(fin_zoff));
         for (long long it = -1; it < ngroups; ++it) {
-            if constexpr (FIN && ASMRING && CMR_FIN_HINT) {
+            if constexpr (FIN && ASMRING) {
                 // A wave that has not adopted the thresholds yet asks for the READY word at the START of a panel's last group — one more load in
                 // the ring's own sequence, nothing waits for it: loads return in order, so the counted waits of the sixteen ring steps that follow
                 // retire it on the way.  At the panel end the value is only a HINT: the proper device-scope load (whose s_waitcnt vmcnt(0) drains
@@ -557,20 +491,12 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                                 for (int r = 0; r < 16; ++r) dst[r] = cmr_make_key(acc[0][r], (unsigned)(row0 + cmr_acc_row(r, lane)));
                                 if (lane < 32) __hip_atomic_store(&cnt_w[ql], c0 + 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                             }
-#ifdef CMR_FIN_DEBUG
-                            ++dbg_n_whole;
-#endif
                             continue;
                         }
                     }
                     if (__any(mx >= tau_f[t])) {
-#ifdef CMR_FIN_DEBUG
-                        ++dbg_n_slow;
-#endif
-                        CMR_DBG_T0
                         topk_slow_path<CAP>(acc[t], row0, P.nrows, P.k, tau_key[t], tau_f[t], cnt_w + t * 32,
                                             list_w + (size_t)t * 32 * CAP, stage, lane);
-                        CMR_DBG_ADD(dbg_t_slow)
                     }
                 }
                 if constexpr (FIN) {
@@ -589,13 +515,10 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                     // held — or spilled — across it)
                     int lane_o = lane;
                     asm volatile("" : "+v"(lane_o));
-                    CMR_DBG_T0
-                    const int fin_phase_was_ = fin_phase;
-                    (void)fin_phase_was_;
                     if (fin_phase == 0) {
                         // the per-query maxima of this wave's first panel go to LDS; the workgroup's last wave takes a ticket, and the first
                         // fin_wgs workgroups to get one — the FASTEST, whichever they are: the slowest of a fixed set of 128 was through its
-                        // first panels at 58-95 us of a 270 us scan, the 64th of all at 31-36 (development build's stamps) — copy their eight
+                        // first panels at 58-95 us of a 270 us scan, the 64th of all at 31-36 (round 6's in-kernel timeline, profiles/r6_measurements.md) — copy their eight
                         // maxima per query to the ticket's slots
                         u64 best = 0ull;
 #pragma unroll
@@ -609,7 +532,6 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                         best = other > best ? other : best;
                         if (lane_o < 32) fin_pm[wave * 32 + lane_o] = lane_o < nq_g ? best : 0ull;
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        if (lane_o == 0) { CMR_FIN_STAMP_MIN(P, 11); }      // the first first panel of a wave is through
                         int o = 0;
                         if (lane_o == 0) o = atomicAdd(&fin_sh[2], 1);
                         o = __builtin_amdgcn_readfirstlane(o);
@@ -618,9 +540,6 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                             int dn = 0;
                             if (lane_o == 0) dn = atomicAdd(&P.fin[CMR_FIN_DONE], 1);
                             dn = __builtin_amdgcn_readfirstlane(dn);
-#ifdef CMR_FIN_DEBUG
-                            if (lane_o == 0) { const int sl = dn == 0 ? 12 : dn == 15 ? 13 : dn == 31 ? 14 : dn == 63 ? 15 : dn == 95 ? 16 : -1; if (sl > 0) P.fin[CMR_FIN_DBG + 2 + sl] = (int)(unsigned)wall_clock64(); }
-#endif
                             if (dn < P.fin_wgs) {
                                 const int ns = P.fin_wgs * CMR_SCAN_WAVES;
                                 if (lane_o < nq_g) {
@@ -635,7 +554,7 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                                 if (pb == P.fin_wgs - 1) {
                                     // every slot is filled: bit 31 says so, and the thresholds are taken query by query by
                                     // whoever claims one — this wave, and every wave that comes past a panel end meanwhile
-                                    if (lane_o == 0) { atomicOr(&P.fin[CMR_FIN_READY], (int)0x80000000u); CMR_FIN_STAMP_MAX(P, 2); }      // every slot of first-panel maxima filled
+                                    if (lane_o == 0) atomicOr(&P.fin[CMR_FIN_READY], (int)0x80000000u);
                                     // (a counted loop, every lane in the atomic: whatever the compiler makes of it, it ends)
                                     for (int it = 0; it < nq_g; ++it) {
                                         int cq = __hip_atomic_fetch_add(&P.fin[CMR_FIN_CLAIM], lane_o == 0 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -650,7 +569,7 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                     }
                     // (a wave whose first panel ends after the thresholds were published adopts them here and now, not a panel later)
                     bool fin_look = fin_phase == 1;
-                    if constexpr (ASMRING && CMR_FIN_HINT) {
+                    if constexpr (ASMRING) {
                         if (fin_look && fin_hint_valid) {        // (the hint of this panel's last group: see the top of the ring loop)
                             unsigned h_ = fin_hint;
                             asm volatile("" : "+v"(h_));
@@ -668,16 +587,12 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                             const u64 gt = q < nq_g ? __hip_atomic_load(&P.fin_tau[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
                             if (q < nq_g && gt > tau_key[0]) { tau_key[0] = gt; tau_f[0] = cmr_key_score(gt); }
                             fin_phase = 2;
-#ifdef CMR_FIN_DEBUG
-                            if (lane_o == 0) { atomicAdd(&P.fin[CMR_FIN_DBG], 1); atomicAdd(&P.fin[CMR_FIN_DBG + 1], p - p0); CMR_FIN_STAMP_MIN(P, 5); CMR_FIN_STAMP_MAX(P, 6); }      // first / last adoption
-#endif
                         } else if (rd < 0) {                      // published, thresholds incomplete: take one
                             int cq = __hip_atomic_fetch_add(&P.fin[CMR_FIN_CLAIM], lane_o == 0 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             cq = __builtin_amdgcn_readfirstlane(cq);
                             if (cq < nq_g) fin_threshold(P.fin_pmax, P.fin_wgs * CMR_SCAN_WAVES, P.k, P.fin_tau, &P.fin[CMR_FIN_READY], stage, cq, lane_o);
                         }
                     }
-                    if constexpr (FIN) { if (fin_phase_was_ != 2) { CMR_DBG_ADD(dbg_t_thr) } }
                 }
             } else {
                 const long long row = row0 + (lane & 31);
@@ -727,14 +642,6 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
         }
     }
     if constexpr (FIN) {
-        if (lane == 0) { CMR_FIN_STAMP_MIN(P, 7); CMR_FIN_STAMP_MAX(P, 8); }      // first / last wave out of its scan loop
-#ifdef CMR_FIN_DEBUG
-        const unsigned dbg_t_p2_ = (unsigned)wall_clock64();
-        if (lane == 0) {
-            atomicAdd((unsigned*)&P.fin[CMR_FIN_DBG2 + 0], dbg_t_slow); atomicAdd((unsigned*)&P.fin[CMR_FIN_DBG2 + 1], dbg_n_slow);
-            atomicAdd((unsigned*)&P.fin[CMR_FIN_DBG2 + 2], dbg_n_whole); atomicAdd((unsigned*)&P.fin[CMR_FIN_DBG2 + 3], dbg_t_thr);
-        }
-#endif
         // Finishing stage, part 2 — the final selection without a merge launch.  Every wave stages the keys of its lists that beat
         // its FINAL threshold (any threshold a wave holds is a valid lower bound of the global k-th best: nothing that can win is
         // dropped) in its LDS scratch; the workgroup appends them to one dense list per query with ONE device atomic per query,
@@ -818,10 +725,6 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
             if (fin_sh[1]) __hip_atomic_store(&P.fin[CMR_FIN_OVER], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             fin_sh[0] = atomicAdd(&P.fin[CMR_FIN_WGS], 1);
-            CMR_FIN_STAMP_MIN(P, 9); CMR_FIN_STAMP_MAX(P, 10);      // first / last ticket
-#ifdef CMR_FIN_DEBUG
-            atomicAdd((unsigned*)&P.fin[CMR_FIN_DBG2 + 4], (unsigned)wall_clock64() - dbg_t_p2_);      // hand-over of this workgroup (its wave 0: scan end -> ticket)
-#endif
         }
         __syncthreads();
         if (fin_sh[0] != (int)gridDim.x - 1) return;
@@ -886,29 +789,6 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
         if (over && lane == 0) fin_sh[1] = 2;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave's results are written through (the caller's buffer may be mapped host memory) before the state says so
         __syncthreads();
-#ifdef CMR_FIN_DEBUG
-        if (tid == 0) {
-            printf("FIN grid %d W %d wgs %d mul %d: done %d ready %d | adoptions %d, panels before adoption (sum) %d | dense[0] %d tau0 %f over %d\n",
-                   (int)gridDim.x, W, P.fin_wgs, P.fin_mul, P.fin[CMR_FIN_DONE], P.fin[CMR_FIN_READY], P.fin[CMR_FIN_DBG], P.fin[CMR_FIN_DBG + 1],
-                   P.fin[CMR_FIN_DCNT(0)], cmr_key_score(P.fin_tau[0]), fin_sh[1]);
-            {
-                const unsigned* T = (const unsigned*)&P.fin[CMR_FIN_DBG + 2];
-                const unsigned t0 = T[0], te = (unsigned)wall_clock64();
-                auto us = [&](unsigned t) { return (t - t0) * 0.01f; };
-                printf("FIN us since the first workgroup started: last start %.1f | maxima published %.1f | thresholds %.1f .. %.1f | adoptions %.1f .. %.1f | "
-                       "waves out of the scan %.1f .. %.1f | tickets %.1f .. %.1f | selection written %.1f\n",
-                       us(T[1]), us(T[2]), us(T[3]), us(T[4]), us(T[5]), us(T[6]), us(T[7]), us(T[8]), us(T[9]), us(T[10]), us(te));
-                printf("FIN    first supplying wave through its first panel %.1f | supplying workgroups complete: 1st %.1f, 16th %.1f, 32nd %.1f, 64th %.1f, 96th %.1f, all %d %.1f\n",
-                       us(T[11]), us(T[12]), us(T[13]), us(T[14]), us(T[15]), us(T[16]), P.fin_wgs, us(T[2]));
-                const unsigned* T2 = (const unsigned*)&P.fin[CMR_FIN_DBG2];
-                printf("FIN    per wave (W = %d): slow-path entries %.2f taking %.2f us, whole panels %.2f, threshold logic %.2f us | hand-over per workgroup %.2f us\n", W,
-                       (float)T2[1] / W, T2[0] * 0.01f / W, (float)T2[2] / W, T2[3] * 0.01f / W, T2[4] * 0.01f / (int)gridDim.x);
-                for (int i = 0; i < 5; ++i) P.fin[CMR_FIN_DBG2 + i] = 0;
-                for (int i = 0; i < 17; ++i) P.fin[CMR_FIN_DBG + 2 + i] = (i == 0 || i == 3 || i == 5 || i == 7 || i == 9 || i == 11) ? -1 : 0;
-            }
-            P.fin[CMR_FIN_DBG] = 0; P.fin[CMR_FIN_DBG + 1] = 0;
-        }
-#endif
         if (tid < 32) P.fin[CMR_FIN_DCNT(tid)] = 0;
         if (tid == 0) {
             P.fin[CMR_FIN_STATE] = fin_sh[1] == 2 ? 2 : 1;
@@ -1013,7 +893,7 @@ static ScanP to_p(const CmrScanGeom& g, const CmrScanArgs& a) {
 //                   GRP x { NT MFMAs, ds_read_b128 ADEPTH blocks ahead },
 //                   with the PPG DMA pieces of group g+NSTG-1 -> stage (g-1) mod NSTG spread between them
 //     Counted waits + raw s_barrier (__syncthreads() would drain the DMA queue, guide §5); the DMAs
-//     are inline asm (§5.7 recipe: M0 = LDS destination, saved/restored inside the statement) with a
+//     are inline asm (§5.7 recipe: M0 = LDS destination, written inside the statement and listed as a clobber) with a
 //     wave-uniform SGPR base, so hipcc neither counts them nor drains them before LDS reads.
 //   * Budget per CU and 32-row panel at 768-d: 4 SIMDs x 96 MFMAs x 32 cycles = 3072 cycles, 192 KiB
 //     of ds_read_b128 = 768 cycles, 48 KiB of HBM = ~4900 cycles at the achievable rate: HBM-bound with
@@ -1025,24 +905,19 @@ static ScanP to_p(const CmrScanGeom& g, const CmrScanArgs& a) {
 // The top-k epilogue, candidate lists and thresholds are the per-wave ones of scan_kernel; list /
 // counter rows are laid out [workgroup][4*NT*32 queries] so merge_query_kernel consumes them with
 // W = gridDim.x.
-#define WIDE_WAVES 4
-#ifndef WIDE_GROUP
-#define WIDE_GROUP 16     // blocks per staged group where 24 does not divide a row's k-steps (1024-d: 64), and for the 8-wave variant
-#endif
-#ifndef WIDE4_NST
-#define WIDE4_NST 8       // stages of the LDS ring at WIDE_GROUP (4-wave kernel): WIDE4_NST x WIDE_GROUP KiB, one stage being refilled
-#endif
-#ifndef WIDE_GROUP3
-#define WIDE_GROUP3 24    // blocks per staged group where 24 divides a row's k-steps (768-d: 48 = two groups, two barriers per panel
-#endif                    // instead of three: 3.907 -> 3.853 ms at 10 M rows, profiles/r3_measurements.md; 8-KiB groups cost +6 %)
-#ifndef WIDE4_NST3
-#define WIDE4_NST3 5      // stages of the ring at WIDE_GROUP3 (120 KiB; 6 stages with half the staging records measured no better)
-#endif
-constexpr int wide_group(int ks, int nw) { return (nw == 4 && ks % WIDE_GROUP3 == 0) ? WIDE_GROUP3 : WIDE_GROUP; }
+
+// Four waves, one per SIMD.  (Two waves per SIMD with one tile each — a partner wave to fill the matrix pipe during the other's
+// epilogue — was measured at 4.198 ms against 3.38-3.44 ms at 10 M rows: every block is read from LDS by eight waves, and hipcc
+// does not fit a tile into 256 registers without spills; profiles/r3_wide_8wave_variant.txt)
+constexpr int WIDE_WAVES = 4;
+constexpr int WIDE_GROUP = 16;     // blocks per staged group where 24 does not divide a row's k-steps (1024-d: 64)
+constexpr int WIDE4_NST = 8;       // stages of the LDS ring at WIDE_GROUP: WIDE4_NST x WIDE_GROUP KiB, one stage being refilled
+constexpr int WIDE_GROUP3 = 24;    // blocks per staged group where 24 divides a row's k-steps (768-d: 48 = two groups, two barriers per panel
+                                   // instead of three: 3.907 -> 3.853 ms at 10 M rows, profiles/r3_measurements.md; 8-KiB groups cost +6 %)
+constexpr int WIDE4_NST3 = 5;      // stages of the ring at WIDE_GROUP3 (120 KiB; 6 stages with half the staging records measured no better)
+constexpr int wide_group(int ks) { return ks % WIDE_GROUP3 == 0 ? WIDE_GROUP3 : WIDE_GROUP; }
 constexpr int wide_nst4(int ks) { return ks % WIDE_GROUP3 == 0 ? WIDE4_NST3 : WIDE4_NST; }
-#ifndef WIDE_ADEPTH
-#define WIDE_ADEPTH 8     // LDS read-ahead ring of a wave, in blocks (two quads: one in use, one landing)
-#endif
+constexpr int WIDE_ADEPTH = 8;     // LDS read-ahead ring of a wave, in blocks (two quads: one in use, one landing)
 
 // Epilogue pieces of the wide kernel.  The wave's register file is full of query fragments, and hipcc's allocator
 // spills the values with the longest live range first — the fragments — whenever ANY block of the loop needs more
@@ -1076,21 +951,10 @@ __device__ __forceinline__ float wide_minmax(const f32x16& acc, float& rmin, flo
     rmax = wide_max3(rmax, mx, mx);
     return mx;
 }
-// One quarter of wide_minmax, issued BETWEEN two MFMAs of the other tile (NT = 2): four accumulator values folded into the
-// panel max / min.  With one wave per SIMD nothing else can use the matrix pipe while this wave runs VALU code, so the
-// epilogue is software-pipelined into the MFMA stream: an independent MFMA occupies the pipe for 8 issue slots, seven of
-// which are free for these eight instructions.
-__device__ __forceinline__ void wide_epi_piece(const f32x16& acc, int i, float& gmax, float& mn) {
-    // one statement: hipcc would otherwise read every accumulator value twice (one AGPR -> VGPR copy per consumer) and
-    // keep all sixteen alive for the (cold) partial-panel branch
-    float a0, a1, a2, a3;
-    asm volatile("v_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7\n\tv_accvgpr_read_b32 %4, %8\n\tv_accvgpr_read_b32 %5, %9\n\t"
-                 "v_max3_f32 %0, %2, %3, %4\n\tv_min3_f32 %1, %1, %2, %3\n\tv_max_f32 %0, %0, %5\n\tv_min3_f32 %1, %1, %4, %5"
-                 : "=&v"(gmax), "+v"(mn), "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3)
-                 : "a"(acc[4 * i]), "a"(acc[4 * i + 1]), "a"(acc[4 * i + 2]), "a"(acc[4 * i + 3]));
-    __builtin_amdgcn_sched_barrier(0);
-}
-// accumulators in VGPRs: the same four-value fold without the reads
+// One quarter of wide_minmax, issued BETWEEN two MFMAs of the other tile (NT = 2, whose accumulators are VGPRs): four accumulator
+// values folded into the panel max / min.  With one wave per SIMD nothing else can use the matrix pipe while this wave runs VALU
+// code, so the epilogue is software-pipelined into the MFMA stream, under an independent MFMA that occupies the pipe meanwhile.
+// (one statement: hipcc would otherwise keep all sixteen values alive for the (cold) partial-panel branch)
 __device__ __forceinline__ void wide_epi_piece_v(const f32x16& acc, int i, float& gmax, float& mn) {
     asm volatile("v_max3_f32 %0, %2, %3, %4\n\tv_min3_f32 %1, %1, %2, %3\n\tv_max_f32 %0, %0, %5\n\tv_min3_f32 %1, %1, %4, %5"
                  : "=&v"(gmax), "+v"(mn)
@@ -1127,19 +991,7 @@ __device__ __forceinline__ float wide_minmax_partial(const f32x16& acc, int nval
 //  * 32-bit rows.  Everything derived from the lane id is made opaque here: hipcc would otherwise hoist sixteen
 //    per-register row offsets and the list pointers out of the panel loop, as loop-invariant values that then live
 //    across the whole scan (and evict query fragments).
-#ifndef WIDE_STG
-#define WIDE_STG 256      // staging records (16 B) per wave (4-wave kernel)
-#endif
-// 8-wave kernel: k-steps of a tile whose B-operand is served from LDS instead of a register (the wave has 256 registers:
-// 192 of fragments + 16 accumulators + a 16-register read-ahead ring leave hipcc too few for everything else)
-#ifndef WIDE8_KLDS
-#define WIDE8_KLDS 8
-#endif
-#ifndef WIDE8_NST
-#define WIDE8_NST 5
-#endif
-#define WIDE8_STG 64
-#define WIDE_AMOVE 8      // NT = 2: k-steps of tile 0 whose B-operand lives in the AGPR half
+constexpr int WIDE_STG = 256;      // staging records (16 B) per wave
 template <int CAP, int STG>
 __device__ __forceinline__ u64 wide_push(const f32x16& acc, unsigned row0, int nvalid, float tau_f, int* cnt_t, u64* list_t, uint4* stg,
                                          int* stg_tail, int lane, int& n_stores) {
@@ -1202,7 +1054,7 @@ __device__ __forceinline__ u64 wide_push(const f32x16& acc, unsigned row0, int n
 // event is kept short: only the accumulator quarters whose maximum (gmax, from the epilogue's fold) reaches the
 // threshold are read back and scanned, one wave-uniform test per register, key compare for the ties, one returning LDS
 // atomic and one store per pushed value; n_stores counts the store instructions.
-template <int CAP, bool ASMREAD>
+template <int CAP>
 __device__ __forceinline__ u64 wide_push_sparse(const f32x16& acc, const float (&gmax)[4], unsigned row0, int nvalid, u64 tau_key, float tau_f,
                                                 int* cnt_t, u64* list_t, int lane, int& n_stores) {
     int ql = lane & 31;
@@ -1217,11 +1069,7 @@ __device__ __forceinline__ u64 wide_push_sparse(const f32x16& acc, const float (
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int r = 4 * gi + j;
-                float v;
-                // ASMREAD (software-pipelined NT = 2 kernel): the read stays inside this branch; otherwise the caller's fold
-                // already holds the sixteen values in VGPRs
-                if constexpr (ASMREAD) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(acc[r]));
-                else v = acc[r];
+                const float v = acc[r];
                 if (__any(v >= tau_f)) {
                     const int cr = (r & 3) + 8 * (r >> 2);
                     const u64 key = cmr_make_key(v, rbase + (unsigned)cr);
@@ -1295,83 +1143,52 @@ __device__ __forceinline__ void wide_compact(u64 need, int k, u64& tau_key, floa
     }
 }
 
-// ABL: developer ablations (development builds, -DCMR_DEV_KNOBS, option "wide_abl"; results are wrong by design): 1 no MFMA, 2 no DMA in the loop, 3 no epilogue,
-// 4 min/max but no threshold test / slow path, 5 no barrier in the loop, 6 = 2 + no LDS reads, 7 = 2 + no barrier
-// NW = waves per workgroup.  4: one wave per SIMD, the whole 512-entry register file, NT = 2 tiles per wave at 768-d.
-// 8: TWO waves per SIMD (256 registers each), one tile per wave (192 registers of fragments at 768-d) — the same 256 queries
-// per workgroup, but every SIMD now has a partner wave whose MFMAs fill the matrix pipe while the other runs its epilogue
-// or sits at a wait / barrier; the price is that every block is read from LDS by eight waves instead of four (128 B/clk of
-// the LDS's 256 B/clk ds_read_b128 rate at full MFMA rate, guide §LDS) and a 4-block read-ahead ring instead of 8.
-template <int DT, int KS, int NT, int CAP, int NSTG, int KLDS, int ABL = 0, int NW = WIDE_WAVES>
-__global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
-    constexpr int GRP = wide_group(KS, NW), NST = NSTG, ADEPTH = NW == 8 ? 4 : (wide_group(KS, NW) % WIDE_ADEPTH == 0 ? WIDE_ADEPTH : 8);
-    constexpr int STG = NW == 8 ? WIDE8_STG : WIDE_STG;         // staging records per wave (LDS budget)
-    static_assert(NW == 4 || (NW == 8 && NT == 1), "8 waves hold one tile each");
-    static_assert(NW == 4 || (size_t)STG * 16 <= (size_t)(CAP + 2) * 8, "8-wave kernel: the staging records live in the compaction stage");
-    static_assert(KS % GRP == 0 && GRP % NW == 0 && GRP % ADEPTH == 0 && ADEPTH % 4 == 0 && NST >= 4, "group geometry (a 3-stage ring was measured with a -DWIDE4_NST3=3 build in round 5 and not kept: no shipped or tested configuration has fewer than 4 stages)");
+// Register budget of a wave (one per SIMD: the whole 512-entry file).
+//  * NT = 2 (768-d): both tiles' accumulators live in the VGPR half — their readers (the min / max fold, the slow path) take them as
+//    they are, no v_accvgpr_read: 32 fewer instructions per panel.  Tile 0's B-operands sit in VGPRs, tile 1's in AGPRs, and AMOVE
+//    k-steps of tile 0's move to the AGPR half in exchange for the accumulators (which then holds 192 + 64 registers of fragments and
+//    nothing else).
+//  * NT = 1 (1024-d): the tile's 256 registers of fragments are split in the middle (VK k-steps in VGPRs, the rest in AGPRs), the
+//    accumulators are AGPRs.
+template <int DT, int KS, int NT, int CAP, int NSTG>
+__global__ __launch_bounds__(WIDE_WAVES * 64, 1) void scan_wide_kernel(ScanP P) {
+    constexpr int NW = WIDE_WAVES;
+    constexpr int GRP = wide_group(KS), NST = NSTG, ADEPTH = WIDE_ADEPTH;
+    constexpr int STG = WIDE_STG;                 // staging records per wave
+    static_assert(NT == 1 || NT == 2, "one or two query tiles per wave");
+    static_assert(KS % GRP == 0 && GRP % NW == 0 && GRP % ADEPTH == 0 && ADEPTH % 4 == 0 && NST >= 4, "group geometry (a 3-stage ring was measured in round 5 and not kept: no shipped or tested configuration has fewer than 4 stages)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int NQB = NW * NT * 32;             // queries per workgroup pass
     constexpr int GPP = KS / GRP;                 // groups per panel
-    constexpr int PPG = GRP / NW;                 // DMA pieces per wave per group
-    constexpr int QPP = (GRP / 4) / PPG;          // quads of blocks per DMA piece of a wave (1 at 4 waves, 2 at 8)
-    static_assert(PPG * QPP == GRP / 4, "DMA pieces spread evenly over the quads of a group");
-    constexpr int KREG = KS - KLDS;               // k-steps of a tile resident in registers; the last KLDS sit in LDS
-    constexpr bool ACCV = NT == 2 && NW == 4 && CMR_WIDE_ACC_VGPR;     // accumulators in the VGPR half (see CMR_WIDE_ACC_VGPR)
-    // the LDS-tail branch of the MFMA chain (ks >= KREG) issues mma_asm with an AGPR accumulator: with ACCV the compiler would wrap every
-    // such MFMA in accvgpr copies around opaque asm (no wait states padded).  No NT = 2 / NW = 4 configuration has an LDS tail today.
-    static_assert(!ACCV || KLDS == 0, "accumulators in VGPRs need every k-step's B-operand in registers (KLDS = 0)");
-    constexpr int AMOVE = ACCV ? 16 : WIDE_AMOVE;                       // NT = 2: k-steps of tile 0 whose B-operand lives in the AGPR half
+    constexpr int PPG = GRP / NW;                 // DMA pieces per wave per group: one per quad of blocks
+    constexpr bool ACCV = NT == 2;                // accumulators in the VGPR half (above)
+    constexpr int AMOVE = 16;                     // NT = 2: k-steps of tile 0 whose B-operand lives in the AGPR half
 // an empty / nop statement that makes an accumulator opaque at this point, whichever register file holds it
 #define CMR_ACC_ASM(TEXT, C) do { if constexpr (ACCV) asm volatile(TEXT : "+v"(C)); else asm volatile(TEXT : "+a"(C)); } while (0)
-    constexpr int VK = NW == 8 ? (KS - KLDS) - 28 : KS / 2;     // NT = 1: k-steps whose B-operand lives in the VGPR half (the rest: AGPRs; hipcc splits a 256-register budget 128 / 128: 16 accumulators + 28 k-steps fill the AGPR half exactly)
+    constexpr int VK = KS / 2;                    // NT = 1: k-steps whose B-operand lives in the VGPR half (the rest: AGPRs)
 
+    // LDS: [NST][GRP][64] ring of staged groups | [NQB] list counters | [WAVES][CAP + 2] compaction stage | [WAVES][STG] staging
+    // records of a push | [WAVES] their tails  (cmr_wide_lds_bytes)
     v4u* stage_lds = reinterpret_cast<v4u*>(smem);                                    // [NST][GRP][64]
     int* cnt_all = reinterpret_cast<int*>(smem + NST * GRP * 1024);                   // [NQB]
     u64* cstage_all = reinterpret_cast<u64*>(cnt_all + NQB);                          // [WAVES][CAP+2]
-    v4u* qlds_all = reinterpret_cast<v4u*>(cstage_all + NW * (CAP + 2));             // [WAVES][NT][KLDS][64]
-    // (8-wave kernel: the staging records of a push are dead once its cooperative stores were issued, and a compaction only
-    //  ever follows a push: the two per-wave scratch areas share their LDS — WIDE8_STG records = CAP + 2 keys at CAP = 128)
-    uint4* stg_all = NW == 8 ? reinterpret_cast<uint4*>(cstage_all) : reinterpret_cast<uint4*>(qlds_all + (size_t)NW * NT * KLDS * 64);   // [WAVES][STG] staging records
-    int* tail_all = reinterpret_cast<int*>(NW == 8 ? reinterpret_cast<unsigned char*>(qlds_all + (size_t)NW * NT * KLDS * 64) : reinterpret_cast<unsigned char*>(stg_all + (size_t)NW * STG));   // [WAVES]
-    v4u* qlds = qlds_all + (size_t)wave * NT * KLDS * 64 + lane;
-    uint4* stg = NW == 8 ? reinterpret_cast<uint4*>(cstage_all + wave * (CAP + 2)) : stg_all + (size_t)wave * STG;
+    uint4* stg_all = reinterpret_cast<uint4*>(cstage_all + NW * (CAP + 2));           // [WAVES][STG] staging records
+    int* tail_all = reinterpret_cast<int*>(stg_all + (size_t)NW * STG);               // [WAVES]
+    uint4* stg = stg_all + (size_t)wave * STG;
     int* stg_tail = tail_all + wave;
     int* cnt_w = cnt_all + wave * NT * 32;
     u64* cstage = cstage_all + wave * (CAP + 2);
     for (int i = tid; i < NQB; i += NW * 64) cnt_all[i] = 0;
 
     // this wave's query fragments -> registers (static indices everywhere below)
-    v4u qreg[NT][KREG];
-    if constexpr (NW == 8) {
-        // 256 registers per wave: the fragment loads are inline asm with a wave-uniform SGPR base, one lane offset and the
-        // destination's register file fixed by the constraint — compiler-generated loads build a 64-bit VGPR address per
-        // few fragments, and that prologue peak alone spills fragments for the whole kernel
-        const unsigned loff = (unsigned)lane * 16u;
+    v4u qreg[NT][KS];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const char* qb = reinterpret_cast<const char*>(P.qfrag) + ((size_t)wave * KS + (size_t)(ks & ~3)) * 1024;   // wave-uniform
-            if (ks < KREG) {
-                if (ks >= VK) asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=a"(qreg[0][ks < KREG ? ks : 0]) : "v"(loff), "s"(qb), "n"((ks & 3) * 1024) : "memory");
-                else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(qreg[0][ks < KREG ? ks : 0]) : "v"(loff), "s"(qb), "n"((ks & 3) * 1024) : "memory");
-            } else {
-                v4u v;
-                asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(loff), "s"(qb), "n"((ks & 3) * 1024) : "memory");
-                qlds[(ks - KREG) * 64] = v;                       // written and read by the same lane only
-            }
-        }
-    } else {
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const v4u v = P.qfrag[((size_t)(wave * NT + t) * KS + ks) * 64 + lane];
-                if (ks < KREG) qreg[t][ks < KREG ? ks : 0] = v;
-                else qlds[(t * KLDS + (ks - KREG)) * 64] = v;        // written and read by the same lane only
-            }
-    }
+        for (int ks = 0; ks < KS; ++ks) qreg[t][ks] = P.qfrag[((size_t)(wave * NT + t) * KS + ks) * 64 + lane];
     // Make hipcc retire every query-fragment load HERE: left alone it defers each wait to the
     // fragment's first use inside the panel loop, where stale low-count s_waitcnt vmcnt(N) would
     // drain the hand-counted DMA ring on every iteration.
@@ -1412,19 +1229,14 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
         const char* last_group = panel_src(s1 - 1) + (GPP - 1) * GRP * 1024;
         const unsigned voff = (unsigned)lane * 16u + (unsigned)wave * 1024u;                    // piece j of wave w = block j*WAVES + w of its group
         const unsigned lds_base = (unsigned)(size_t)((__attribute__((address_space(3))) unsigned char*)smem) + (unsigned)wave * 1024u;
-        // one DMA piece: 1 KiB from (wave-uniform base + voff) to LDS byte address dst
+        // one DMA piece (the ring's prologue): 1 KiB from (wave-uniform base + voff) to LDS byte address dst.  M0 is written and left,
+        // not saved and restored (3 instructions instead of 5): hipcc sets M0 itself in front of each of its own uses — v_writelane
+        // lane selects in the compaction — and expects nothing of it across an asm
         auto dma_piece = [&](const char* base, unsigned dst) {
-#if CMR_WIDE_M0_CLOBBER
             asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" CMR_STREAM_POLICY
                          :: "v"(voff), "s"(base), "s"(dst) : "memory", "m0");
-#else
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" CMR_STREAM_POLICY "\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-#endif
         };
-#if CMR_WIDE_DMA_IMM
-        // Piece j of a group WITHOUT compiler arithmetic around it (4-wave kernel: pieces are 4 KiB apart): the group's source base and
+        // Piece j of a group in the panel loop, WITHOUT compiler arithmetic around it (pieces are 4 KiB apart): the group's source base and
         // LDS destination are two SGPR operands shared by all its pieces; the piece's own displacement is split between three
         // loop-invariant lane offsets (voff + 4 KiB, + 12 KiB, + 20 KiB) and the instruction's signed 13-bit immediate (-4096 / 0), M0
         // takes destination + j * 4 KiB inside the statement.  Three issue slots per piece, none of them hipcc's to place: left to the
@@ -1438,7 +1250,7 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
     asm volatile("s_add_i32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%4" CMR_STREAM_POLICY                      \
                  :: "v"(VO), "s"(gb), "s"(gd), "n"((J) * 4096 - (((J) & 1) ? 0 : -4096)), "n"(((J) & 1) ? 0 : -4096) : "memory", "m0", "scc")
         auto dma_piece_j = [&](int j, const char* gb, unsigned gd) __attribute__((always_inline)) {
-            static_assert(NW != 4 || PPG <= 6, "six pieces per group at most");
+            static_assert(PPG <= 6, "six pieces per group at most");
             switch (j) {            // j is a constant after unrolling: one statement survives
                 case 0: CMR_WIDE_PIECE(0, voj0); break;
                 case 1: CMR_WIDE_PIECE(1, voj0); break;
@@ -1449,7 +1261,6 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
             }
         };
 #undef CMR_WIDE_PIECE
-#endif
         // prologue: groups 0 .. NST-2 of this workgroup's stream (clamped to its last group)
 #pragma unroll
         for (int d = 0; d < NST - 1; ++d) {
@@ -1475,8 +1286,7 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
         // panel's after the loop.  No accumulator is duplicated; the threshold test and the (rare) slow path follow the
         // fold at once, so a tile's pushes still precede the next panel's compare for that tile.
         f32x16 acc[NT];
-        if constexpr (ACCV) asm volatile("" : "=v"(acc[1]));
-        else if constexpr (NT == 2) asm volatile("" : "=a"(acc[1]));   // the very first quad folds (and discards) whatever is there
+        if constexpr (NT == 2) asm volatile("" : "=v"(acc[1]));   // the very first quad folds (and discards) whatever is there
         float eg[4] = {0.0f, 0.0f, 0.0f, 0.0f}, emn = 0.0f;   // quarter maxima / panel min under construction by the interleaved pieces
         unsigned prow0 = 0;                           // the previous panel: tile 1's epilogue is still pending
         int pnvalid = CMR_PANEL_ROWS;
@@ -1497,13 +1307,13 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
             } else {
                 mx = wide_minmax(acc[t], rmin[t], rmax[t], eg);
             }
-            if (ABL != 4 && __any(mx >= tau_f[t])) {
+            if (__any(mx >= tau_f[t])) {
                 // (opaque: hipcc must not hoist the slow path's sixteen accumulator reads in front of the test)
                 if constexpr (decltype(folded)::value) CMR_ACC_ASM("", acc[t]);
                 // sampling pass: dense hits (threshold from a small sample) -> staged push; main pass: sparse hits
                 const u64 need = P.sample_waves > 0
                     ? wide_push<CAP, STG>(acc[t], row0, nvalid, tau_f[t], cnt_w + t * 32, list_w + (size_t)t * 32 * CAP, stg, stg_tail, lane, n_stores)
-                    : wide_push_sparse<CAP, decltype(folded)::value && !ACCV>(acc[t], eg, row0, nvalid, tau_key[t], tau_f[t], cnt_w + t * 32, list_w + (size_t)t * 32 * CAP, lane, n_stores);
+                    : wide_push_sparse<CAP>(acc[t], eg, row0, nvalid, tau_key[t], tau_f[t], cnt_w + t * 32, list_w + (size_t)t * 32 * CAP, lane, n_stores);
                 if (need) {
                     wide_compact<CAP>(need, P.k, tau_key[t], tau_f[t], cnt_w + t * 32, list_w + (size_t)t * 32 * CAP, cstage, lane);
                     compacted = true;
@@ -1522,8 +1332,8 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
                 // The DMA pieces of group g+1 were issued NST-2 groups (two panels) ago; the store instructions issued since
                 // are younger than they are: NT = 1 the last two epilogues'; NT = 2 the same, except that at g = 0 tile 1's
                 // epilogue of the previous panel has not run yet (it sits in this group's first quad).
-                if constexpr (ABL != 2 && ABL != 6 && ABL != 7) wide_wait_group<PPG * (NST - 3)>(st_old + ((NT == 2 && g == 0) ? st_mid : st_new));
-                if constexpr (ABL != 5 && ABL != 7) asm volatile("s_barrier" ::: "memory");
+                wide_wait_group<PPG * (NST - 3)>(st_old + ((NT == 2 && g == 0) ? st_mid : st_new));
+                asm volatile("s_barrier" ::: "memory");
                 // prefetch cursor: group g + NST-1 of the stream, into the stage everybody just left
                 const int dps = s + (g + NST - 1) / GPP;
                 const char* dsrc = dps < s1 ? panel_src(dps) + ((g + NST - 1) % GPP) * GRP * 1024 : last_group;
@@ -1535,29 +1345,21 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
                 // matrix pipe has (tools/probe/mfma_probe.hip: 1.45 PFLOP/s chip-wide against 1.83 for runs of four).
 #pragma unroll
                 for (int qd = 0; qd < GRP / 4; ++qd) {
-                    constexpr bool DMA_MID = NT == 2 && CMR_WIDE_DMA_MID && !CMR_WIDE_DMA_BURST;
-                    auto quad_dma = [&]() __attribute__((always_inline)) {
-                        if (ABL != 2 && ABL != 6 && ABL != 7) {
-                            if (CMR_WIDE_DMA_BURST) {
-                                if (qd == 0)
-                                    for (int j = 0; j < PPG; ++j) dma_piece(dsrc + j * NW * 1024, ddst + (unsigned)j * NW * 1024u);
-                            } else if (qd % QPP == 0) {
-#if CMR_WIDE_DMA_IMM
-                                if constexpr (NW == 4) dma_piece_j(qd / QPP, dsrc, ddst);
-                                else
-#endif
-                                dma_piece(dsrc + (qd / QPP) * NW * 1024, ddst + (unsigned)(qd / QPP) * NW * 1024u);
-                            }
-                        }
-                    };
-                    if constexpr (!DMA_MID) quad_dma();
+                    // One DMA piece per quad (all pieces of a group in a burst behind its barrier was the slower schedule,
+                    // profiles/r5_wide_schedule_ab.txt).  NT = 1: in front of the quad's MFMAs.  NT = 2: between tile 0's four MFMAs and
+                    // tile 1's four — a boundary between chains on DIFFERENT accumulators, 128 cycles behind the read-ahead ring's LDS
+                    // reads — and not in front of the quad, where one gap of the MFMA stream would carry the ring's reads + the piece
+                    // (MI355X_MICROARCH.md: a gap between MFMAs hides <= 5 single-issue instructions, fillers between MFMAs on the SAME
+                    // accumulator are never free, and a piece issued beside pending LDS reads costs its wave 100-185 cycles against
+                    // 25-60 in a quiet gap).
+                    if constexpr (NT == 1) dma_piece_j(qd, dsrc, ddst);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
-                        if constexpr (DMA_MID) {
+                        if constexpr (NT == 2) {
                             if (t == 1) {           // the boundary between the two tiles' chains of this quad
                                 __builtin_amdgcn_sched_barrier(0);
-                                quad_dma();
+                                dma_piece_j(qd, dsrc, ddst);
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                         }
@@ -1566,28 +1368,19 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
                             const int u = qd * 4 + j;
                             const int ks = g * GRP + u;
                             const v4u a_use = a[u % ADEPTH];
-                            // register file of the resident B-operand: tile 0 in VGPRs, tile 1 in AGPRs (NT = 2); first /
-                            // second half of the k-steps (NT = 1).  The accumulators are AGPRs.
-                            // (WIDE_AMOVE of tile 0's operands also sit in AGPRs: the AGPR half has registers to spare)
+                            // register file of the resident B-operand: tile 0 in VGPRs except its last AMOVE k-steps, tile 1 in
+                            // AGPRs (NT = 2); first / second half of the k-steps (NT = 1)
                             const int ab = NT == 2 ? (t == 1 || ks >= KS - AMOVE ? 1 : 0) : (ks >= VK ? 1 : 0);
-                            if constexpr (ABL == 1) {
-                                if (ab) asm volatile("" ::"v"(a_use), "a"(qreg[t][ks < KREG ? ks : 0]));
-                                else asm volatile("" ::"v"(a_use), "v"(qreg[t][ks < KREG ? ks : 0]));
-                                if (ks == 0) { if constexpr (ACCV) asm volatile("" : "=v"(acc[t])); else asm volatile("" : "=a"(acc[t])); }
-                            } else if (ks < KREG) {
-                                if constexpr (ACCV) CmrBlk<DT>::mma_asm_cv(ab, ks == 0, acc[t], a_use, qreg[t][ks < KREG ? ks : 0]);
-                                else CmrBlk<DT>::mma_asm(ab, ks == 0, acc[t], a_use, qreg[t][ks < KREG ? ks : 0]);
-                            } else {
-                                const v4u b = qlds[(t * KLDS + (ks < KREG ? 0 : ks - KREG)) * 64];
-                                CmrBlk<DT>::mma_asm(0, ks == 0, acc[t], a_use, b);
+                            if constexpr (ACCV) CmrBlk<DT>::mma_asm_cv(ab, ks == 0, acc[t], a_use, qreg[t][ks]);
+                            else CmrBlk<DT>::mma_asm(ab, ks == 0, acc[t], a_use, qreg[t][ks]);
+                            // the read-ahead ring's slot takes the block ADEPTH ahead directly behind its final reader (the LAST tile's
+                            // MFMA j of the quad), where the wait state between two MFMAs of one chain is due anyway — not four
+                            // ds_read_b128 in a row behind the quad
+                            if (t == NT - 1) {
+                                const int blk = u + ADEPTH;
+                                a[u % ADEPTH] = blk < GRP ? buf[blk * 64] : bufn[(blk - GRP) * 64];
                             }
-                            if constexpr (CMR_WIDE_READ_INTERLEAVE && ABL != 6) {
-                                if (t == NT - 1) {
-                                    const int blk = u + ADEPTH;
-                                    a[u % ADEPTH] = blk < GRP ? buf[blk * 64] : bufn[(blk - GRP) * 64];
-                                }
-                            }
-                            if constexpr (NT == 2 && ABL != 3) {
+                            if constexpr (NT == 2) {
                                 // (g, qd, t, j are constants after unrolling: at most one of these survives per MFMA)
                                 if (g == 0 && qd == 0 && t == 0) {                  // tile 1 of the PREVIOUS panel, under this panel's first tile-0 MFMAs
                                     __builtin_amdgcn_sched_barrier(0);
@@ -1598,8 +1391,7 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
                                         CMR_ACC_ASM("", acc[NT - 1]);
                                         emn = __builtin_inff();
                                     }
-                                    if constexpr (ACCV) wide_epi_piece_v(acc[NT - 1], j, eg[j], emn);
-                                    else wide_epi_piece(acc[NT - 1], j, eg[j], emn);
+                                    wide_epi_piece_v(acc[NT - 1], j, eg[j], emn);
                                     if (j == 3) {
                                         int n1 = 0;
                                         bool comp = false;
@@ -1621,23 +1413,10 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
                                         CMR_ACC_ASM("s_nop 1", acc[0]);
                                         emn = __builtin_inff();
                                     }
-                                    if constexpr (ACCV) {
-                                        if (j >= 1) wide_epi_piece_v(acc[0], j - 1, eg[j - 1 < 0 ? 0 : j - 1], emn);
-                                        if (j == 3) wide_epi_piece_v(acc[0], 3, eg[3], emn);
-                                    } else {
-                                        if (j >= 1) wide_epi_piece(acc[0], j - 1, eg[j - 1 < 0 ? 0 : j - 1], emn);
-                                        if (j == 3) wide_epi_piece(acc[0], 3, eg[3], emn);
-                                    }
+                                    if (j >= 1) wide_epi_piece_v(acc[0], j - 1, eg[j - 1 < 0 ? 0 : j - 1], emn);
+                                    if (j == 3) wide_epi_piece_v(acc[0], 3, eg[3], emn);
                                 }
                             }
-                        }
-                    }
-                    // the quad's four ring slots take the blocks ADEPTH ahead (they land under the next quad's MFMAs)
-                    if constexpr (ABL != 6 && !CMR_WIDE_READ_INTERLEAVE) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int blk = qd * 4 + j + ADEPTH;
-                            a[(qd * 4 + j) % ADEPTH] = blk < GRP ? buf[blk * 64] : bufn[(blk - GRP) * 64];
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -1645,24 +1424,11 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
                 st = stn;
                 buf = bufn;
             }
-            if constexpr (ABL == 3) {
-                if constexpr (NT == 1) cmr_mfma_drain<NT>(acc);
-                continue;
-            }
             int n_stores = 0;
             bool compacted = false;
             if constexpr (NT == 1) {
                 cmr_mfma_drain<NT>(acc);          // MFMA results -> VALU readers: wait states hipcc does not insert for asm
-                if constexpr (NW == 8) {
-                    // 256 registers per wave: the fold takes the accumulators four at a time through asm reads (wide_epi_piece)
-                    // and the slow path re-reads what it needs — sixteen scores held in VGPRs from the fold to the push do not fit
-                    emn = __builtin_inff();
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) wide_epi_piece(acc[0], j, eg[j], emn);
-                    epi_finish(T0{}, std::true_type{}, row0, nvalid, n_stores, compacted);
-                } else {
-                    epi_finish(T0{}, std::false_type{}, row0, nvalid, n_stores, compacted);
-                }
+                epi_finish(T0{}, std::false_type{}, row0, nvalid, n_stores, compacted);
                 st_old = st_new;
                 st_new = __builtin_amdgcn_readfirstlane(n_stores);
                 if (compacted) {        // its loads already drained the ring; retire its stores too and restart the count
@@ -1681,11 +1447,11 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
                 pnvalid = nvalid;
             }
         }
-        if constexpr (NT == 2 && ABL != 3) {      // tile 1 of the last panel
+        if constexpr (NT == 2) {      // tile 1 of the last panel
             CMR_ACC_ASM("s_nop 15", acc[NT - 1]);
             emn = __builtin_inff();
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { if constexpr (ACCV) wide_epi_piece_v(acc[NT - 1], j, eg[j], emn); else wide_epi_piece(acc[NT - 1], j, eg[j], emn); }
+            for (int j = 0; j < 4; ++j) wide_epi_piece_v(acc[NT - 1], j, eg[j], emn);
             int n1 = 0;
             bool comp = false;
             epi_finish(T1{}, std::true_type{}, prow0, pnvalid, n1, comp);
@@ -1707,31 +1473,18 @@ __global__ __launch_bounds__(NW * 64, 1) void scan_wide_kernel(ScanP P) {
 
 #undef CMR_ACC_ASM
 
-// geometry of the wide kernel per shape: waves per workgroup, query tiles per wave, LDS ring depth
-struct WideCfg { int nw, nt, nst, stg, klds; };
-// Default waves per workgroup at 768-d (ks = 48): measured A/B on MI355X, 10 M x 768 bf16, B = 256 (profiles/r3_wide_ab.txt)
-#ifndef CMR_WIDE_DEFAULT_WAVES
-#define CMR_WIDE_DEFAULT_WAVES 4
-#endif
-static WideCfg wide_cfg(int ks, int cap, int waves) {
-    if (ks == 48) {
-        if (waves == 0) waves = CMR_WIDE_DEFAULT_WAVES;
-        // 8 waves: 16 KiB of staging + 8 compaction stages next to the ring -> 7 stages of 16 KiB for the 256-entry lists
-#ifdef CMR_WIDE8
-        if (waves == 8) return {8, 1, cap > 128 ? WIDE8_NST - 1 : WIDE8_NST, WIDE8_STG, WIDE8_KLDS};
-#endif
-        return {4, 2, wide_nst4(48), WIDE_STG, 0};
-    }
-    return {4, 1, wide_nst4(ks), WIDE_STG, 0};
+// geometry of the wide kernel per shape: query tiles per wave, LDS ring depth
+struct WideCfg { int nt, nst; };
+static constexpr WideCfg wide_cfg(int ks) { return {ks == 48 ? 2 : 1, wide_nst4(ks)}; }
+
+// the kernel's LDS layout: ring of staged groups, list counters, compaction stages, staging records and their tails
+size_t cmr_wide_lds_bytes(int ks, int cap) {
+    const WideCfg c = wide_cfg(ks);
+    return (size_t)c.nst * wide_group(ks) * 1024 + (size_t)WIDE_WAVES * c.nt * 32 * 4 + (size_t)WIDE_WAVES * (cap + 2) * 8 +
+           (size_t)WIDE_WAVES * WIDE_STG * 16 + WIDE_WAVES * 4;
 }
 
-size_t cmr_wide_lds_bytes(int ks, int cap, int waves) {
-    const WideCfg c = wide_cfg(ks, cap, waves);
-    return (size_t)c.nst * wide_group(ks, c.nw) * 1024 + (size_t)c.nw * c.nt * 32 * 4 + (size_t)c.nw * (cap + 2) * 8 + (size_t)c.nw * c.nt * c.klds * 1024 +
-           (c.nw == 8 ? 0 : (size_t)c.nw * c.stg * 16) + c.nw * 4;
-}
-
-// wide kernel availability: 16-bit dtypes at ks = 48 (768-d: 256 queries per pass — 4 waves x 2 tiles or 8 waves x 1 tile of 32),
+// wide kernel availability: 16-bit dtypes at ks = 48 (768-d: 4 waves x 2 tiles x 32 = 256 queries per pass),
 // ks = 64 (1024-d: a tile needs 256 registers -> 4 waves x 1 tile x 32 = 128 queries per pass).  Any other padded dim, and
 // fp32 indexes, run batches of more than 64 queries as ceil(B / 64) passes of the narrow kernel.
 int cmr_wide_queries(int dtype, int dpad) {
@@ -1743,43 +1496,18 @@ int cmr_wide_queries(int dtype, int dpad) {
 
 hipError_t cmr_launch_scan_wide(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s) {
     const ScanP p = to_p(g, a);
-    const WideCfg c = wide_cfg(g.ks, g.cap, g.wide_waves);
-    const size_t lds = cmr_wide_lds_bytes(g.ks, g.cap, g.wide_waves);
+    const size_t lds = cmr_wide_lds_bytes(g.ks, g.cap);
     auto launch = [&](auto kern) -> hipError_t {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(g.grid), dim3(c.nw * 64), lds, s, p);
+        hipLaunchKernelGGL(kern, dim3(g.grid), dim3(WIDE_WAVES * 64), lds, s, p);
         return hipGetLastError();
     };
-#ifdef CMR_DEV_KNOBS
-    // development builds: ablation kernels (results are wrong by design) behind the "wide_abl" option
-    if (g.wide_abl && g.dtype == CMR_DT_BF16 && g.ks == 48 && g.cap == 128 && c.nw == 4) {
-        if (g.wide_abl == 1) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 2, 128, wide_nst4(48), 0, 1>);
-        if (g.wide_abl == 2) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 2, 128, wide_nst4(48), 0, 2>);
-        if (g.wide_abl == 3) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 2, 128, wide_nst4(48), 0, 3>);
-        if (g.wide_abl == 4) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 2, 128, wide_nst4(48), 0, 4>);
-        if (g.wide_abl == 5) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 2, 128, wide_nst4(48), 0, 5>);
-        if (g.wide_abl == 6) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 2, 128, wide_nst4(48), 0, 6>);
-        if (g.wide_abl == 7) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 2, 128, wide_nst4(48), 0, 7>);
-    }
-#endif
-#if defined(CMR_DEV_KNOBS) && defined(CMR_WIDE8)
-    if (g.wide_abl && g.dtype == CMR_DT_BF16 && g.ks == 48 && g.cap == 128 && c.nw == 8) {
-        if (g.wide_abl == 1) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 1, 128, WIDE8_NST, WIDE8_KLDS, 1, 8>);
-        if (g.wide_abl == 2) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 1, 128, WIDE8_NST, WIDE8_KLDS, 2, 8>);
-        if (g.wide_abl == 3) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 1, 128, WIDE8_NST, WIDE8_KLDS, 3, 8>);
-        if (g.wide_abl == 5) return launch(scan_wide_kernel<CMR_DT_BF16, 48, 1, 128, WIDE8_NST, WIDE8_KLDS, 5, 8>);
-    }
-#endif
-#define WCASE(DT, KSV, NTV, CAPV, NSTV, NWV) if (g.dtype == DT && g.ks == KSV && g.cap == CAPV && c.nw == NWV) return launch(scan_wide_kernel<DT, KSV, NTV, CAPV, NSTV, (NWV == 8 ? WIDE8_KLDS : 0), 0, NWV>);
-    WCASE(CMR_DT_BF16, 48, 2, 128, wide_nst4(48), 4) WCASE(CMR_DT_BF16, 48, 2, 256, wide_nst4(48), 4)
-    WCASE(CMR_DT_F16, 48, 2, 128, wide_nst4(48), 4) WCASE(CMR_DT_F16, 48, 2, 256, wide_nst4(48), 4)
-#ifdef CMR_WIDE8     // experimental: two waves per SIMD, one tile each (hipcc does not yet fit it into 256 registers without spills)
-    WCASE(CMR_DT_BF16, 48, 1, 128, WIDE8_NST, 8) WCASE(CMR_DT_BF16, 48, 1, 256, WIDE8_NST - 1, 8)
-    WCASE(CMR_DT_F16, 48, 1, 128, WIDE8_NST, 8) WCASE(CMR_DT_F16, 48, 1, 256, WIDE8_NST - 1, 8)
-#endif
-    WCASE(CMR_DT_BF16, 64, 1, 128, wide_nst4(64), 4) WCASE(CMR_DT_BF16, 64, 1, 256, wide_nst4(64), 4)
-    WCASE(CMR_DT_F16, 64, 1, 128, wide_nst4(64), 4) WCASE(CMR_DT_F16, 64, 1, 256, wide_nst4(64), 4)
+#define WCASE(DT, KSV, CAPV) if (g.dtype == DT && g.ks == KSV && g.cap == CAPV) return launch(scan_wide_kernel<DT, KSV, wide_cfg(KSV).nt, CAPV, wide_cfg(KSV).nst>);
+    WCASE(CMR_DT_BF16, 48, 128) WCASE(CMR_DT_BF16, 48, 256)
+    WCASE(CMR_DT_F16, 48, 128) WCASE(CMR_DT_F16, 48, 256)
+    WCASE(CMR_DT_BF16, 64, 128) WCASE(CMR_DT_BF16, 64, 256)
+    WCASE(CMR_DT_F16, 64, 128) WCASE(CMR_DT_F16, 64, 256)
 #undef WCASE
     return hipErrorInvalidValue;
 }

@@ -100,8 +100,6 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     const long long npanels = idx->npanels();
     int rc = make_geom(idx, quad ? std::min(nqp, idx->narrow_max()) : nqp, k, true, &g);
     if (rc) return rc;
-    g.wide_waves = idx->wide_waves;
-    g.wide_abl = idx->wide_abl;
     const int G = quad ? (nqp + g.nqt * 32 - 1) / (g.nqt * 32) : 1;      // query groups
     p.G = G;
     // the groups' twins re-read each corpus block from L2: default cache policy for them, non-temporal for single-group scans

@@ -175,8 +175,7 @@ int32_t cmr_index_set_id_blocks(cmr_index_t* idx, int32_t n_blocks, const int64_
  * paths), zero_copy, sample_single, sample_single_max, sample_tau_in_scan, sample_div, sample_maxmul, scan_fin (0: small synchronous
  * batches run the sampling / scan / merge chain instead of the scan with the finishing stage) / scan_fin_queries (<= 16) /
  * scan_fin_dense / scan_fin_spin / scan_fin_suppliers / scan_fin_cap, sync_poll (0: synchronous calls wait for the stream), wide_mode (1: register-resident wide kernel | 2: query-split grid of the narrow kernel),
- * stream_nt, pipe_reserve_cus, pipe_slots (2..4), wide_waves (4 | 8:
- * waves per workgroup of the batch-256 kernel at 768-d; 8 only in builds with -DCMR_WIDE8), pipe_cu_mask (0: never | 1 | 2: every scan; default: scans shorter than ~1 ms) and
+ * stream_nt, pipe_reserve_cus, pipe_slots (2..4), pipe_cu_mask (0: never | 1 | 2: every scan; default: scans shorter than ~1 ms) and
  * pipe_dual_scan (0 | 1; default: scans shorter than ~1 ms) — the pipelined search's streams with explicit CU masks (scans
  * of <= 64-query batches on n_cu - 64 CUs, their pre-phases on the other 64) and two alternating scan streams; both must
  * be set before the first pipelined call.

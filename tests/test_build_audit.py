@@ -89,3 +89,44 @@ def test_valu_written_sgpr_in_front_of_an_asm_load_is_flagged_and_five_wait_stat
     spaced = bad.replace("\t;;#ASMSTART", "\ts_mov_b32 s1, 0\n\ts_mov_b32 s2, 0\n\ts_mov_b32 s3, 0\n\ts_mov_b32 s4, 0\n\t;;#ASMSTART")
     assert len(audit_asm_sgpr_hazard(spaced)) == 1
     assert audit_asm_sgpr_hazard(spaced.replace("s_mov_b32 s4, 0", "s_mov_b32 s4, 0\n\ts_mov_b32 s5, 0")) == []
+
+
+# ---- audit_wide: the register-resident wide kernel (scan_wide_kernel<DT, KS, NT, CAP, NSTG>)
+WIDE_HEAD = "_Z16scan_wide_kernelILi1ELi48ELi2ELi128ELi5EEv5ScanP:\n"
+WIDE_KEY = (1, 48, 2, 128, 5)
+
+
+def _wide(extra_front=(), before_last_mfma=(), head=WIDE_HEAD):
+    # two tiles x 48 k-steps: tile 0 accumulates in v[0:15] from VGPR fragments, tile 1 in v[16:31] from AGPR fragments; the streamed
+    # operand comes from the LDS read-ahead ring v[40:71]
+    lines = ["\ts_load_dwordx2 s[0:1], s[4:5], 0x0"] + list(extra_front)
+    for ks in range(48):
+        a = 40 + 4 * (ks % 8)
+        lines += ["\t;;#ASMSTART", f"\tv_mfma_f32_32x32x16_bf16 v[0:15], v[{a}:{a + 3}], v[{100 + 4 * ks}:{103 + 4 * ks}], v[0:15]", "\t;;#ASMEND"]
+        if ks == 47:
+            lines += list(before_last_mfma)
+        lines += ["\t;;#ASMSTART", f"\tv_mfma_f32_32x32x16_bf16 v[16:31], v[{a}:{a + 3}], a[{4 * ks}:{4 * ks + 3}], v[16:31]", "\t;;#ASMEND",
+                  f"\tds_read_b128 v[{a}:{a + 3}], v32 offset:{1024 * ks}"]
+    return head + "\n".join(lines + ["\ts_endpgm"]) + "\n" + TAIL
+
+
+def test_wide_audit_passes_a_clean_two_tile_kernel_and_names_what_is_wrong_with_the_others():
+    from comorag_amd.build import audit_wide
+    assert audit_wide(_wide()) == {WIDE_KEY: ""}
+    spill = audit_wide(_wide(extra_front=["\tscratch_store_dwordx4 off, v[100:103], off offset:16"]))
+    assert set(spill) == {WIDE_KEY} and "scratch" in spill[WIDE_KEY]
+    shuttle = audit_wide(_wide(extra_front=["\tv_accvgpr_write_b32 a0, v100"]))
+    assert set(shuttle) == {WIDE_KEY} and "v_accvgpr_write" in shuttle[WIDE_KEY]
+    # a compiler VALU write of the streamed operand (ring slot 7: v[68:71]) directly in front of the asm MFMA that reads it
+    hazard = audit_wide(_wide(before_last_mfma=["\tv_mov_b32_e32 v68, v33"]))
+    assert set(hazard) == {WIDE_KEY} and "VALU write of an MFMA operand" in hazard[WIDE_KEY]
+    # the same write of a register the MFMA does not read is nobody's hazard
+    assert audit_wide(_wide(before_last_mfma=["\tv_mov_b32_e32 v34, v33"])) == {WIDE_KEY: ""}
+    # too few MFMAs for the shape: the listing is not the kernel the name says
+    assert "MFMAs found" in audit_wide(_wide().replace("v_mfma_f32_32x32x16_bf16 v[16:31]", "v_nop ; v[16:31]", 1))[WIDE_KEY]
+
+
+def test_wide_audit_does_not_match_the_seven_parameter_name_of_the_removed_variants():
+    from comorag_amd.build import audit_wide
+    assert audit_wide(_wide(head="_Z16scan_wide_kernelILi1ELi48ELi2ELi128ELi5ELi0ELi0ELi4EEv5ScanP:\n")) == {}
+    assert audit_wide(_wide(head="_Z16scan_wide_kernelILi1ELi48ELi2ELi128ELi5ELi0ELi0EEv5ScanP:\n")) == {}

@@ -23,7 +23,7 @@ variants = [dict(), dict(CMR_SCAN_NO_WIDE="1"), dict(CMR_SCAN_RING="8"), dict(CM
 if len(sys.argv) > 3:
     variants = [dict(kv.split("=") for kv in v.split(",") if kv) for v in sys.argv[3:]]
 for env in variants:
-    for kk in ("CMR_SCAN_RING", "CMR_SCAN_ASM_RING", "CMR_SCAN_NO_SAMPLE", "CMR_SCAN_GRID", "CMR_SCAN_NO_WIDE", "CMR_PIPE_RESERVE_CUS", "CMR_WIDE_ABL"):
+    for kk in ("CMR_SCAN_RING", "CMR_SCAN_ASM_RING", "CMR_SCAN_NO_SAMPLE", "CMR_SCAN_GRID", "CMR_SCAN_NO_WIDE", "CMR_PIPE_RESERVE_CUS"):
         os.environ.pop(kk, None)
     os.environ.update(env)
     idx = DenseIndex(dim, "bf16", capacity_hint=rows, options=env_options())
