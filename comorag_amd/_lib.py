@@ -70,6 +70,7 @@ SIGNATURES = {
     "cmr_index_search_exact": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),
     "cmr_index_search_exact_pipelined": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _P(_p)]),
     "cmr_index_round_stats": (_i32, [_p, _P(_f32), _P(_f32)]),
+    "cmr_index_prefilter_stats": (_i32, [_p, _P(_f32), _P(_f32)]),
     "cmr_merge_topk": (_i32, [_p, _p, _i32, _i32, _i32, _p, _p]),
     "cmr_merge_topk_dev": (_i32, [_i32, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
     "cmr_graph_create": (_i32, [_i32, _i64, _i64, _p, _p, _p, _P(_p)]),

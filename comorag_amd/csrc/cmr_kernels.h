@@ -176,3 +176,34 @@ size_t cmr_exact_part_bytes(int nq, int kc);
 hipError_t cmr_launch_exact_certify(int dtype, const float* shadow, int dim, long long nrows, long long id_base, const long long* tab, int nb,
                                     const float* q, int nq, const int64_t* cand_ids, const float* cand_sc, int kc, int k, const float* stats,
                                     void* part, int* arrive, int64_t* out_ids, float* out_scores, int* out_exact, hipStream_t s);
+
+// ---- certified int8 pre-filter of the pipelined 16-bit scan (prefilter_kernels.hip)
+// companion of panels [panel0, panel0 + npanels): int8 blocks, (scale, quantisation error norm) per row, and the atomicMax of
+// (max ||x||, max error norm) into stats[2]; rows at or beyond nrows count as zero rows
+hipError_t cmr_launch_q8_quantise(int dtype, const void* corpus, int dpad, long long panel0, long long npanels, long long nrows, void* q8,
+                                  float2* scales, float* stats, hipStream_t s);
+// queries fp32 [nq, dim] -> two int8 parts in block order ([2][tiles][dpad / 32] blocks of 1 KiB) and (a_q, B_q, c_q, 0) per query slot
+hipError_t cmr_launch_q8_pack_queries(int dtype, const float* q, int nq, int dim, int dpad, int tiles, const float* stats, void* qpack,
+                                      float4* qconst, hipStream_t s);
+struct CmrQ8Args {
+    int dtype, dpad, nqt, cap;
+    int grid;                  // filter: workgroups of 8 waves
+    int rescore_grid;          // re-score: workgroups of cmr_q8_rescore_waves() waves; lists / cnt hold one row per wave
+    const void* corpus;        // the 16-bit panels
+    const void* q8;            // the int8 companion
+    const float2* scales;
+    const void* qfrag;         // 16-bit query fragments (prep_queries)
+    const void* qpack;         // int8 query parts
+    const float4* qconst;
+    const u64* tau_init;       // [nqt * 32] thresholds of the sampling passes, or nullptr
+    long long nrows;
+    int npanels, nq, k;
+    int keep_all;              // the filter keeps every row (the re-score path alone)
+    unsigned* cand_row;        // [nrows]
+    unsigned* n_cand;          // zeroed before the filter
+    u64* lists;
+    int* cnt;
+};
+hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s);
+hipError_t cmr_launch_q8_rescore(const CmrQ8Args& a, hipStream_t s);
+int cmr_q8_rescore_waves(void);

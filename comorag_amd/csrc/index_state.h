@@ -24,6 +24,9 @@
 
 namespace {
 
+// prefilter = -1 (the default) takes the pre-filter for scans of 1 ms and longer (DESIGN 4.14 has the measurement behind it)
+constexpr bool kPrefilterAuto = true;
+
 int elem_size(int dtype) { return dtype == CMR_F32 ? 4 : 2; }
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 long long panels_of(long long rows) { return (rows + CMR_PANEL_ROWS - 1) / CMR_PANEL_ROWS; }
@@ -47,6 +50,10 @@ struct Workspace {
     // synchronous search: queries in, (ids | scores | min | max | non-finite flag) out through ONE pinned host buffer and
     // one copy each way — five pageable D2H copies cost more than the search of a small corpus
     DevBuf d_pack;
+    // certified int8 pre-filter: the int8 query parts, the queries' constants, the batch's candidate rows and their
+    // counter; pf_prev: the workspace's last pass ran the re-score, which reads qfrag / tau on the merge stream
+    DevBuf q8_qpack, q8_qconst, q8_cand, q8_ncand;
+    bool pf_prev = false;
     ExactScratch x;              // cmr_index_search_exact
     int* flag_ptr = nullptr;     // the non-finite-query flag the kernels set: flag.p, or the head of d_pack for the host API
     // Synchronous host API with mapped results: the word (device view of the pinned buffer, bytes 4..7) that the search's LAST kernel sets
@@ -80,6 +87,7 @@ struct Workspace {
         fin_ctl.release(); fin_pmax.release(); fin_tau.release(); fin_dense.release(); fin_mm.release();
         d_q.release(); d_ids.release(); d_scores.release(); d_min.release(); d_max.release(); d_cand.release(); d_out.release();
         d_pack.release();
+        q8_qpack.release(); q8_qconst.release(); q8_cand.release(); q8_ncand.release();
         x.release();
         if (h_pin) (void)hipHostFree(h_pin);
         h_pin = nullptr; h_pin_dev = nullptr; h_pin_cap = 0;
@@ -187,6 +195,22 @@ struct cmr_index {
     std::vector<void*> blk_retired;      // earlier tables: in-flight searches may still read them (a few bytes each, freed at destroy)
     int sample_maxmul = 0;   // sample_maxmul: level-1 sample <= sample_maxmul x level 0 (0 = 128 narrow / 512 wide)
     int sample_div = 32;     // sample_div: level-1 sample = 1/sample_div of the panels (clamped to [8, 128] x level 0)
+    // Certified int8 pre-filter of the pipelined 16-bit scan.  prefilter: -1 auto (kPrefilterAuto and a scan of 1 ms
+    // or longer) | 0 off | 1 every eligible call | 2 the same with a filter that keeps every row (the re-score path alone).  The
+    // companion — int8 blocks, (scale, error norm) per row, (max ||x||, max error norm) — covers rows [0, q8_rows) of a corpus buffer
+    // of q8_cap_panels panels; a pipelined call that uses it brings it up to date first, under pipe_mu.
+    int prefilter = -1;
+    int pf_rescore_wgs = 0;              // prefilter_rescore_wgs: workgroups of the re-score (0: one per CU)
+    void* q8 = nullptr;
+    float2* q8_scales = nullptr;
+    float* q8_stats = nullptr;
+    long long q8_cap_panels = 0, q8_rows = 0;
+    long long q8_failed_cap = -1;        // the companion of a corpus buffer of this many panels could not be allocated: the route stays off
+    hipEvent_t q8_ready = nullptr;       // behind the last quantise launch, on q8_stream
+    hipStream_t q8_stream = nullptr;
+    int prefilter_active = 0;            // read-only: did the last pipelined call run the pre-filter
+    const unsigned* q8_last_ncand = nullptr;      // the candidate counter of the last pre-filtered pass
+    size_t q8_bytes() const { return q8 ? (size_t)q8_cap_panels * CMR_PANEL_ROWS * (dpad + sizeof(float2)) + CMR_CORPUS_SLACK : 0; }
     int pipe_slots = 3;      // pipe_slots (2..4): batches in the pipeline.  A third slot lets the pre-phase of batch i+2 start before
                              // scan i has ended: 1 M x 768 bf16, B = 64 step 0.279 -> 0.264 ms; nothing at 10 M rows
     int reserve_cus = -1;    // pipe_reserve_cus: CUs the pipelined main scan leaves free (-1 = by corpus size, see plan_pass)

@@ -71,6 +71,7 @@ struct PassRequest {
     bool single_stream = false;      // pre-phase, scan and merge on ONE stream (a synchronous caller)
     bool pipelined = false;          // the pre-phase has a stream of its own
     int reserve_cus = 0;             // CUs the main scan leaves free (< 0: by corpus size)
+    int prefilter = 0;               // the caller could take the int8 pre-filter (1; 2: with a filter that keeps every row) if the pass is eligible
 };
 
 struct PassPlan {
@@ -78,6 +79,8 @@ struct PassPlan {
     bool wide = false;
     CmrScanGeom g{};                 // the main scan's, g.grid = its launch grid (all query groups)
     bool fin = false;                // scan with the finishing stage: no sampling launches, no merge of its own
+    int prefilter = 0;               // 1 | 2: the int8 filter in the place of the main scan, the re-score in front of the merge (W: the re-score's lists)
+    int rescore_grid = 0;
     int G = 1;                       // query groups of the query-split grid
     int n_levels = 0;                // sampling passes in front of the main scan
     struct Level { long long panels; int grid, Wl, clog, stride; } level[2] = {};      // grid: launch grid (all groups); Wl: candidate lists per query
@@ -134,6 +137,8 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     // Narrow kernel: one sampled panel per wave = one candidate list per panel, and merge_query_kernel takes at
     // most 4096 lists, so S1 is capped there (k > 32 on multi-million-row shards would otherwise overrun it).
     // Wide kernel: the sampling workgroups split the sampled panels among them (one list per workgroup and query).
+    // Certified int8 pre-filter: a narrow pass of a 16-bit index whose thresholds come from tau_init
+    const bool prefilter = rq.prefilter && !wide && G == 1 && !fin && !rq.has_min_score && idx->dtype != CMR_F32;
     long long level_panels[2] = {0, 0};
     int n_levels = 0;
     bool single_level = false;
@@ -145,13 +150,16 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
         // around a short scan: ONE sampling level of 128 panels instead of two saves a scan + merge pair (~45 us of a
         // 0.4 ms call at 1 M rows).  Its threshold lets ~k * npanels / 128 scores per query through — a few slow-path
         // entries per wave as long as queries x panels stays small.
-        single_level = !wide && idx->single_level && k <= 32 && nqp <= 8 && npanels >= 4096 && (long long)nqp * npanels <= idx->single_level_max;
+        // (not with the pre-filter: a pipelined pass hides the second level, and every row a loose threshold lets through is a gather)
+        single_level = !wide && !prefilter && idx->single_level && k <= 32 && nqp <= 8 && npanels >= 4096 && (long long)nqp * npanels <= idx->single_level_max;
         level_panels[n_levels++] = single_level ? 128 : s0;
         if (npanels >= 4096 && !single_level) {
             // wide kernel: 256 queries share a workgroup, so ANY of 8 tiles beating its threshold stalls all four waves at
             // the next barrier — a 4x larger level-1 sample (N/32 rows up to 512 x level 0) took the main pass from 4.09 to
             // 3.76 ms at 10 M rows; the sample itself is cheap there (256 queries per pass over it)
-            const long long maxmul = idx->sample_maxmul > 0 ? idx->sample_maxmul : (wide ? 512 : 128);
+            // pre-filter: every row the threshold lets through costs a gather of 96 cache lines, so the sample is as large as the
+            // merge allows (10 M rows, 2560 -> 4096 panels: 330 K -> 216 K kept rows per batch, step 2.00 -> 1.90 ms)
+            const long long maxmul = idx->sample_maxmul > 0 ? idx->sample_maxmul : (wide ? 512 : prefilter ? kMaxMergeLists : 128);
             long long s1 = std::min<long long>(std::max<long long>(npanels / idx->sample_div, 8 * s0), maxmul * s0);
             if (!wide) s1 = std::min<long long>(s1, kMaxMergeLists);
             if (s1 < npanels / 2) level_panels[n_levels++] = s1;
@@ -216,6 +224,15 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
         if (!idx->force_grid) g.grid = balanced_grid(npanels, g.grid, CMR_SCAN_WAVES);
         NQ = g.nqt * 32; W = g.grid * CMR_SCAN_WAVES; tiles = g.nqt;
     }
+    // Pre-filter: the filter takes the main scan's grid; the candidate lists are the re-score's — a fixed grid of small workgroups, one
+    // per CU by default (4 waves, ~70 registers, 5 KiB of LDS: they fit beside a filter workgroup; its gathers are 16-byte pieces,
+    // one cache line each, and more CUs keep more of them in flight: 92 -> 256 workgroups 2.05 -> 2.01 ms per step at 10 M rows,
+    // nothing beyond).  At most 1024 x 4 = the merge's 4096 lists.
+    if (prefilter) {
+        p.prefilter = rq.prefilter;
+        p.rescore_grid = idx->pf_rescore_wgs > 0 ? idx->pf_rescore_wgs : std::min(idx->n_cu, 1024);
+        W = p.rescore_grid * cmr_q8_rescore_waves();
+    }
     const int NQA = G * NQ;          // query slots of the pass over all groups
     p.NQ = NQ; p.W = W; p.Ws = Ws; p.tiles = tiles; p.NQA = NQA;
     // sample passes and the main pass use separate list buffers: in pipelined mode the next batch's
@@ -246,7 +263,8 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     // the thresholds from these lists themselves (scan_kernel) — no merge launch between the two scans.  Every
     // workgroup reads the whole sample of its queries (32 KiB each): with 8 queries that costs more than the merge
     // launch it saves (1 M rows: 371 -> 405 us per call), with one it wins (344 -> 330 us)
-    p.tau_in_scan = n_levels > 0 && single_level && idx->tau_in_scan && NQ == 32 && nqp <= 2 && k <= 64;
+    // (not with the pre-filter: its filter and re-score take the thresholds from tau_init)
+    p.tau_in_scan = n_levels > 0 && single_level && idx->tau_in_scan && NQ == 32 && nqp <= 2 && k <= 64 && !p.prefilter;
     if (G > 1) g.grid *= G;
     if (fin) {
         p.fin_dcap = idx->fin_dense;

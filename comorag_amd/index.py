@@ -210,7 +210,8 @@ class DenseIndex(HostArrayIndex):
     def get_option(self, name: str) -> int:
         """Readable options (cmr_index_get_option): "last_route" (which path served the last call: CMR_ROUTE_* and the bits beside it in
         include/comorag_hip.h), "pipe_dual_scan_active", "pipe_cu_mask_active", "pipe_scan_cus", "exact_cand", "combine",
-        "combine_wait_us" and the combiner's counters (`combine_stats`)."""
+        "combine_wait_us", the combiner's counters (`combine_stats`), "prefilter" and, of the last pipelined call, "prefilter_active",
+        "prefilter_rows", "prefilter_bytes" and "prefilter_candidates" (waits for the pipeline)."""
         v = C.c_int64(0)
         L.check(L.lib().cmr_index_get_option(self._h, name.encode(), C.byref(v)))
         return v.value
@@ -359,6 +360,12 @@ class DenseIndex(HostArrayIndex):
         """(max ||round(x)||, max ||round(x) - x||) over the appended rows: the maxima the exact search's certificate uses."""
         a, b = C.c_float(0), C.c_float(0)
         L.check(L.lib().cmr_index_round_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def prefilter_stats(self) -> Tuple[float, float]:
+        """(max ||x||, max ||x - a m||) over the rows of the int8 companion (option "prefilter"): the maxima the pre-filter's bound uses."""
+        a, b = C.c_float(0), C.c_float(0)
+        L.check(L.lib().cmr_index_prefilter_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     # -- measurement

@@ -277,6 +277,11 @@ int32_t cmr_index_search_exact_pipelined(cmr_index_t* idx, const float* q_f32_de
 /* The certificate's index-wide maxima in use (ComoRAG.py:958-966 is what they make exact): M_x = max ||round(x)|| and
  * M_dx = max ||round(x) - x|| over every appended row, rounded up; 0 for an fp32 index (E_q = ||dq|| M_x + ||q|| M_dx + ...).   */
 int32_t cmr_index_round_stats(cmr_index_t* idx, float* max_row_norm, float* max_round_err);
+/* The int8 companion behind the option "prefilter" (certified int8 pre-filter of cmr_index_search_pipelined on a 16-bit index:
+ * the main pass streams int8 rows, keeps the rows whose 16-bit score could still reach the threshold by a proven bound and scores
+ * those again from the 16-bit rows — same ids, same score bits): the maxima its bound uses, M_x = max ||x|| and max ||x - a m||
+ * (a, m: a stored row's scale and int8 values) over the rows quantised so far, rounded up; 0 while there is no companion.        */
+int32_t cmr_index_prefilter_stats(cmr_index_t* idx, float* max_row_norm, float* max_quant_err);
 
 /* Gather rows back to the host as fp32 (dequantised), out [n, dim]; ids as returned by search (with the id base). */
 int32_t cmr_index_get_rows(cmr_index_t* idx, const int64_t* ids, int64_t n, float* out);
