@@ -62,8 +62,12 @@ struct Option {
     const char* reject;
     long long (*read)(const cmr_index*);       // nullptr: not readable
 };
-// "prefilter_candidates": rows the last pre-filtered pass kept (waits for the pipeline; -1: the read failed)
+// "prefilter_candidates": rows the last pre-filtered pass handed to the re-score; "prefilter_pairs": the (row, query) records its
+// filter stored, summed over the queries; "prefilter_pair_overflow": queries that offered more than the capacity
+// (all three wait for the pipeline; -1: the read failed)
 long long read_prefilter_candidates(const cmr_index* idx);
+long long read_prefilter_pairs(const cmr_index* idx);
+long long read_prefilter_pair_overflow(const cmr_index* idx);
 #define CMR_STR_(x) #x
 #define CMR_STR(x) CMR_STR_(x)
 #define OPT_FIELD(f) [](cmr_index* i, long long v) { i->f = (decltype(i->f))v; }
@@ -104,10 +108,14 @@ const Option kOptions[] = {
      OPT_READ(i->combine_wait_us.load(std::memory_order_relaxed))},
     {"prefilter", OPT_FIELD(prefilter), Option::range, -1, 2, 0, "prefilter must be -1 (auto), 0 (off), 1 (on) or 2 (on, the filter keeps every row)", OPT_READ(i->prefilter)},
     {"prefilter_rescore_wgs", OPT_FIELD(pf_rescore_wgs), Option::clamp, 0, 1024, 0, nullptr, nullptr},
+    {"prefilter_tighten", OPT_FIELD(pf_tighten), Option::range, 0, 1, 0, "prefilter_tighten must be 0 or 1", OPT_READ(i->pf_tighten)},
+    {"prefilter_pair_cap", OPT_FIELD(pf_pair_cap), Option::clamp, 0, 1 << 20, 0, nullptr, OPT_READ(i->pf_pair_cap)},
     {"prefilter_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->prefilter_active)},
     {"prefilter_rows", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->q8 ? i->q8_rows : 0)},
     {"prefilter_bytes", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ((long long)i->q8_bytes())},
     {"prefilter_candidates", nullptr, Option::any, 0, 0, 0, nullptr, read_prefilter_candidates},
+    {"prefilter_pairs", nullptr, Option::any, 0, 0, 0, nullptr, read_prefilter_pairs},
+    {"prefilter_pair_overflow", nullptr, Option::any, 0, 0, 0, nullptr, read_prefilter_pair_overflow},
     {"last_route", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->last_route.load(std::memory_order_relaxed))},
     {"pipe_dual_scan_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_active)},
     {"pipe_dual_scan_wide_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_wide_active)},
@@ -288,12 +296,17 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
         HIP_TRY(ws->q8_qconst.ensure((size_t)p.NQ * sizeof(float4)));
         HIP_TRY(ws->q8_cand.ensure((size_t)idx->cap_panels * CMR_PANEL_ROWS * sizeof(unsigned)));
         HIP_TRY(ws->q8_ncand.ensure(sizeof(unsigned)));
+        HIP_TRY(ws->q8_pair.ensure(std::max<size_t>((size_t)p.NQ * p.pair_cap * 16, 16)));
+        HIP_TRY(ws->q8_paircnt.ensure((size_t)p.NQ * sizeof(unsigned)));
+        HIP_TRY(ws->q8_keep.ensure((size_t)idx->cap_panels * sizeof(unsigned)));
+        HIP_TRY(ws->q8_tau.ensure((size_t)p.NQ * sizeof(float)));
         if (sp != idx->q8_stream) HIP_TRY(hipStreamWaitEvent(sp, idx->q8_ready, 0));      // the companion's last rows were quantised on another stream
         HIP_TRY(cmr_launch_q8_pack_queries(idx->dtype, q_dev, nqp, idx->dim, idx->dpad, p.tiles, idx->q8_stats, ws->q8_qpack.p, (float4*)ws->q8_qconst.p, sp));
         f.dtype = idx->dtype; f.dpad = idx->dpad; f.nqt = g.nqt; f.cap = g.cap; f.grid = g.grid; f.rescore_grid = p.rescore_grid;
         f.corpus = idx->corpus; f.q8 = idx->q8; f.scales = idx->q8_scales; f.qfrag = ws->qfrag.p; f.qpack = ws->q8_qpack.p; f.qconst = (const float4*)ws->q8_qconst.p;
         f.nrows = idx->n; f.npanels = (int)idx->npanels(); f.nq = nqp; f.k = k; f.keep_all = p.prefilter == 2 ? 1 : 0;
         f.cand_row = (unsigned*)ws->q8_cand.p; f.n_cand = (unsigned*)ws->q8_ncand.p;
+        f.pair = ws->q8_pair.p; f.pair_cnt = (unsigned*)ws->q8_paircnt.p; f.pcap = p.pair_cap; f.keep = (unsigned*)ws->q8_keep.p; f.tau_tight = (float*)ws->q8_tau.p;
     }
     CmrScanArgs a{};
     a.corpus = idx->corpus; a.qfrag = ws->qfrag.p; a.nrows = idx->n; a.npanels = (int)idx->npanels(); a.k = k;
@@ -324,7 +337,9 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
     }
     if (sp != sm) {
         if (st.ev_lists_free) HIP_TRY(hipStreamWaitEvent(sp, st.ev_lists_free, 0));   // previous merge of this slot's lists
-        if (p.prefilter) HIP_TRY(hipMemsetAsync(f.n_cand, 0, sizeof(unsigned), sp));   // (behind that wait: the previous re-score read the counter)
+    }
+    if (p.prefilter) HIP_TRY(hipMemsetAsync(f.pair_cnt, 0, (size_t)p.NQ * sizeof(unsigned), sp));   // (behind that wait: the previous tightening read the counters and the pairs)
+    if (sp != sm) {
         HIP_TRY(hipEventRecord(st.ev_pre, sp));
         HIP_TRY(hipStreamWaitEvent(sm, st.ev_pre, 0));
     }
@@ -363,7 +378,7 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
     if (p.prefilter) {
         f.tau_init = a.tau_init; f.lists = a.lists; f.cnt = a.cnt;
         HIP_TRY(cmr_launch_q8_filter(f, sm));
-        idx->q8_last_ncand = f.n_cand;
+        idx->q8_last_ncand = f.n_cand; idx->q8_last_paircnt = f.pair_cnt; idx->q8_last_nq = nqp; idx->q8_last_pcap = f.pcap;
     } else {
         HIP_TRY(p.wide ? cmr_launch_scan_wide(g, a, sm) : p.fin ? cmr_launch_scan_fin(g, a, sm) : cmr_launch_scan_topk(g, a, sm));
     }
@@ -386,7 +401,13 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
         HIP_TRY(hipEventRecord(st.ev_scan, sm));
         HIP_TRY(hipStreamWaitEvent(sq, st.ev_scan, 0));
     }
-    if (p.prefilter) HIP_TRY(cmr_launch_q8_rescore(f, sq));      // the kept rows, scored by the scan's chain, into the lists the merge reads
+    if (p.prefilter) {
+        // the hits' thresholds tightened into keep[], its bits listed, and those rows scored by the scan's chain into the lists the merge reads
+        if (f.pcap > 0) HIP_TRY(cmr_launch_q8_tighten(f, sq));
+        HIP_TRY(hipMemsetAsync(f.n_cand, 0, sizeof(unsigned), sq));
+        HIP_TRY(cmr_launch_q8_expand(f, sq));
+        HIP_TRY(cmr_launch_q8_rescore(f, sq));
+    }
     HIP_TRY(cmr_launch_merge_query((const u64*)ws->lists.p, (const int*)ws->cnt.p, p.W, p.NQ, g.cap, nqp, k, (const float2*)ws->mm.p,
                                    kernel_id_base(idx), ids_dev, scores_dev, min_dev, max_dev, nullptr, sq, G > 1, fin_state));
     return remap_ids_enqueue(idx, ids_dev, (long long)nqp * k, sq);
@@ -637,6 +658,23 @@ long long read_prefilter_candidates(const cmr_index* cidx) {
     if (hipMemcpy(&h, idx->q8_last_ncand, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return (long long)h;
 }
+
+// the pair counters of the last pre-filtered pass: (stored pairs over all queries, queries that offered more than the capacity)
+bool read_pair_counters(const cmr_index* cidx, long long* stored, long long* overflowed) {
+    cmr_index* idx = const_cast<cmr_index*>(cidx);
+    if (cmr_set_device(idx->device)) return false;
+    std::lock_guard<std::mutex> pl(idx->pipe_mu);
+    *stored = 0; *overflowed = 0;
+    if (!idx->q8_last_paircnt || idx->q8_last_nq <= 0) return true;
+    for (hipStream_t st : idx->pipe.st) if (st && hipStreamSynchronize(st) != hipSuccess) return false;
+    std::vector<unsigned> h((size_t)idx->q8_last_nq);
+    if (hipMemcpy(h.data(), idx->q8_last_paircnt, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    const unsigned cap = (unsigned)idx->q8_last_pcap;
+    for (unsigned c : h) { *stored += std::min(c, cap); *overflowed += c > cap ? 1 : 0; }
+    return true;
+}
+long long read_prefilter_pairs(const cmr_index* idx) { long long s, o; return read_pair_counters(idx, &s, &o) ? s : -1; }
+long long read_prefilter_pair_overflow(const cmr_index* idx) { long long s, o; return read_pair_counters(idx, &s, &o) ? o : -1; }
 
 int scores_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, float* out_dev, long long ld) {
     hipStream_t s = ws->stream;

@@ -50,9 +50,10 @@ struct Workspace {
     // synchronous search: queries in, (ids | scores | min | max | non-finite flag) out through ONE pinned host buffer and
     // one copy each way — five pageable D2H copies cost more than the search of a small corpus
     DevBuf d_pack;
-    // certified int8 pre-filter: the int8 query parts, the queries' constants, the batch's candidate rows and their
-    // counter; pf_prev: the workspace's last pass ran the re-score, which reads qfrag / tau on the merge stream
-    DevBuf q8_qpack, q8_qconst, q8_cand, q8_ncand;
+    // certified int8 pre-filter: the int8 query parts, the queries' constants, the filter's (row, ub, lb) records per
+    // query with their counters, the row mask per panel, the tightened thresholds, the batch's candidate rows and their counter;
+    // pf_prev: the workspace's last pass ran the re-score, which reads qfrag / tau on the merge stream
+    DevBuf q8_qpack, q8_qconst, q8_cand, q8_ncand, q8_pair, q8_paircnt, q8_keep, q8_tau;
     bool pf_prev = false;
     ExactScratch x;              // cmr_index_search_exact
     int* flag_ptr = nullptr;     // the non-finite-query flag the kernels set: flag.p, or the head of d_pack for the host API
@@ -87,7 +88,7 @@ struct Workspace {
         fin_ctl.release(); fin_pmax.release(); fin_tau.release(); fin_dense.release(); fin_mm.release();
         d_q.release(); d_ids.release(); d_scores.release(); d_min.release(); d_max.release(); d_cand.release(); d_out.release();
         d_pack.release();
-        q8_qpack.release(); q8_qconst.release(); q8_cand.release(); q8_ncand.release();
+        q8_qpack.release(); q8_qconst.release(); q8_cand.release(); q8_ncand.release(); q8_pair.release(); q8_paircnt.release(); q8_keep.release(); q8_tau.release();
         x.release();
         if (h_pin) (void)hipHostFree(h_pin);
         h_pin = nullptr; h_pin_dev = nullptr; h_pin_cap = 0;
@@ -201,6 +202,11 @@ struct cmr_index {
     // of q8_cap_panels panels; a pipelined call that uses it brings it up to date first, under pipe_mu.
     int prefilter = -1;
     int pf_rescore_wgs = 0;              // prefilter_rescore_wgs: workgroups of the re-score (0: one per CU)
+    // prefilter_tighten: the k-th largest certified lower bound among a query's hits replaces its sampling threshold before the
+    // re-score (0: every hit is re-scored — the kept set of the route before the tightening, the A/B arm).  prefilter_pair_cap: hit
+    // records per query (16 bytes each: 16 MiB per workspace at 64 queries); a query that offers more keeps the rest directly.
+    int pf_tighten = 1;
+    int pf_pair_cap = 16384;
     void* q8 = nullptr;
     float2* q8_scales = nullptr;
     float* q8_stats = nullptr;
@@ -210,6 +216,8 @@ struct cmr_index {
     hipStream_t q8_stream = nullptr;
     int prefilter_active = 0;            // read-only: did the last pipelined call run the pre-filter
     const unsigned* q8_last_ncand = nullptr;      // the candidate counter of the last pre-filtered pass
+    const unsigned* q8_last_paircnt = nullptr;    // its pair counters (q8_last_nq of them) and the capacity they ran against
+    int q8_last_nq = 0, q8_last_pcap = 0;
     size_t q8_bytes() const { return q8 ? (size_t)q8_cap_panels * CMR_PANEL_ROWS * (dpad + sizeof(float2)) + CMR_CORPUS_SLACK : 0; }
     int pipe_slots = 3;      // pipe_slots (2..4): batches in the pipeline.  A third slot lets the pre-phase of batch i+2 start before
                              // scan i has ended: 1 M x 768 bf16, B = 64 step 0.279 -> 0.264 ms; nothing at 10 M rows

@@ -2,10 +2,13 @@
 //
 // The corpus keeps a half-size companion: every stored row x quantised to int8 with a scale of its own, m = rint(x / a),
 // a = max|x| / 127, and b >= ||x - a m|| beside it.  A batch's main pass streams the companion instead of the 16-bit panels
-// (q8_filter_kernel), keeps the rows whose 16-bit score could still beat the query's sampling threshold — decided with a proven
-// bound on |scan score - int8 score| — and the few rows kept are scored again from the 16-bit panels by the scan's own MFMA
-// chain (q8_rescore_kernel), so the candidate lists hold the same keys, bit for bit, that scan_kernel would have pushed for
-// those rows.  merge_query_kernel then selects as ever.
+// (q8_filter_kernel) and records the (row, query) pairs whose 16-bit score could still beat the query's sampling threshold — decided
+// with a proven bound on |scan score - int8 score| — with their upper and lower bounds.  q8_tighten_kernel raises every query's
+// threshold to the k-th largest LOWER bound among its pairs (k distinct rows score at least that much, so a row whose upper bound
+// is strictly below it cannot be among the k best) and marks the rows still standing in a bit mask per panel, q8_expand_kernel
+// lists the marked rows, and those few are scored again from the 16-bit panels by the scan's own MFMA chain (q8_rescore_kernel),
+// so the candidate lists hold the same keys, bit for bit, that scan_kernel would have pushed for those rows.
+// merge_query_kernel then selects as ever.
 //
 // Layout.  One int8 block = 1 KiB = the A-operand of v_mfma_i32_32x32x32_i8 for 32 rows x 32 k in lane order; a panel of 32
 // rows is dpad / 32 blocks.  Lane l of block kb holds row (l & 31) and the sixteen k of the lane's OWN slots in the 16-bit
@@ -166,15 +169,21 @@ struct FilterP {
     const u64* tau_init;       // per-query threshold keys of the sampling passes, or nullptr (nothing to filter by)
     long long nrows;
     int npanels, KB, nq, keep_all;
-    unsigned* cand_row;        // [nrows] worst case: every row is written at most once
-    unsigned* n_cand;
+    v4u* pair;                 // [nq slots][pcap] records (row, ub, lb, 0)
+    unsigned* pair_cnt;        // [nq slots] pairs offered per query (zeroed before the launch; may run past pcap)
+    unsigned pcap;             // 0: no pairs, every hit is kept directly
+    unsigned* keep;            // [npanels] row masks: every panel's word is written (the rows kept directly, usually none)
 };
 
 // 8 waves per workgroup, each with a contiguous panel range; the two int8 parts of the query tiles in LDS.  Corpus blocks
 // stream through two register buffers of CH blocks (plain non-temporal loads, the compiler counts them): one is in flight
 // while the other feeds the MFMAs — two per block and query tile, hi and lo part.  Panel epilogue: the kept-test on every
-// accumulator element, __any; on a hit the panel's 32-bit row mask over all queries goes to a lane of the wave's entry
-// register, and 64 entries (or the end of the range) are flushed with ONE atomicAdd on the batch's candidate counter.
+// accumulator element, __any; on a hit every lane takes a slot in its query's pair list for each of its own hits (rows at or
+// beyond nrows excepted: a zero padding row scores 0 and must not reach the threshold selection) and writes (row, ub, lb).  A
+// hit that finds the list full is kept directly: its row bit goes into the panel's word of keep[], which the panel's wave —
+// every panel has exactly one — writes for every panel of its range, so the masks need no clearing between batches.  A lane's
+// query per tile is fixed, so a lane that met a full list stops asking (`full`): a batch without a usable threshold costs
+// each lane one refused atomic per tile, not one per hit.
 template <int NQT, int CH>
 __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -223,25 +232,8 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
     };
     load_scales(p0);
 
-    u64 ent = 0ull;            // lane j: the wave's j-th pending entry (panel << 32 | row mask)
-    int nent = 0;
-    auto flush = [&]() {
-        const unsigned mask = (unsigned)ent;
-        const int c = lane < nent ? __popc(mask) : 0;
-        int incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off); if (lane >= off) incl += o; }
-        const int total = __builtin_amdgcn_readlane(incl, 63);
-        unsigned base = 0u;
-        if (lane == 0) base = atomicAdd(P.n_cand, (unsigned)total);
-        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-        unsigned at = base + (unsigned)(incl - c);
-        if (lane < nent) {
-            const unsigned row0 = (unsigned)(ent >> 32) * CMR_PANEL_ROWS;
-            for (unsigned m = mask; m; m &= m - 1u) P.cand_row[at++] = row0 + (unsigned)(__ffs((int)m) - 1);
-        }
-        nent = 0;
-    };
+    unsigned full = P.pcap ? 0u : ~0u;      // bit t: the pair list of this lane's query of tile t is full
+    const int hrow = 4 * (lane >> 5);
 
     const int CPP = KB / CH;
     const long long nchunks = (long long)(p1 - p0) * CPP;
@@ -279,22 +271,33 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
                 if (alive[t] && !(ub < tau[t])) hit |= 1u << (r + 16 * t);
             }
         }
-        if (__any(hit != 0u)) {
-            unsigned rows = 0u;
+        const long long left = P.nrows - (long long)p * CMR_PANEL_ROWS;
+        unsigned rows = 0u;        // the rows of this panel that are kept without a pair
+        if (P.keep_all) rows = ~0u;
+        else if (__any(hit != 0u)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const u64 bal = __ballot((hit & (0x10001u << r)) != 0u);
-                const int i0 = (r & 3) + 8 * (r >> 2);
-                if ((unsigned)bal) rows |= 1u << i0;
-                if ((unsigned)(bal >> 32)) rows |= 1u << (i0 + 4);
+                const int i = (r & 3) + 8 * (r >> 2) + hrow;
+                const float4 s4 = sc[2 * (r >> 2) + ((r & 3) >> 1)];
+                const float ar = (r & 1) ? s4.z : s4.x, br = (r & 1) ? s4.w : s4.y;
+#pragma unroll
+                for (int t = 0; t < NQT; ++t) {
+                    if (!(hit & (1u << (r + 16 * t))) || i >= left) continue;
+                    if (full & (1u << t)) { rows |= 1u << i; continue; }
+                    const int qi = t * 32 + (lane & 31);
+                    const unsigned slot = atomicAdd(&P.pair_cnt[qi], 1u);
+                    if (slot >= P.pcap) { full |= 1u << t; rows |= 1u << i; continue; }
+                    const float ti = fmaf((float)acc[1][t][r], 1.0f / 254.0f, (float)acc[0][t][r]);
+                    const float e = fmaf(Bq[t], br, cq[t]);
+                    const float ub = fmaf(ar * aq[t], ti, e), lb = fmaf(ar * aq[t], ti, -e);
+                    P.pair[(size_t)qi * P.pcap + slot] = (v4u){(unsigned)p * CMR_PANEL_ROWS + (unsigned)i, __float_as_uint(ub), __float_as_uint(lb), 0u};
+                }
             }
-            const long long left = P.nrows - (long long)p * CMR_PANEL_ROWS;
-            if (left < CMR_PANEL_ROWS) rows &= left > 0 ? (1u << left) - 1u : 0u;
-            if (rows) {
-                if (lane == nent) ent = ((u64)(unsigned)p << 32) | rows;
-                if (++nent == 64) flush();
-            }
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) rows |= (unsigned)__shfl_xor((int)rows, off);
         }
+        if (left < CMR_PANEL_ROWS) rows &= left > 0 ? (1u << left) - 1u : 0u;
+        if (lane == 0) P.keep[p] = rows;
         ++p;
         load_scales(p < P.npanels ? p : P.npanels - 1);
 #pragma unroll
@@ -314,7 +317,108 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
             step(bufB);
         }
     }
-    if (nent) flush();
+}
+
+// ------------------------------------------------------------------------------------------ tighten
+struct TightenP {
+    const v4u* pair;
+    const unsigned* pair_cnt;
+    unsigned pcap;
+    const u64* tau_init;       // the sampling thresholds the filter tested against, or nullptr
+    int k;
+    unsigned* keep;
+    float* tau_out;            // [nq] the threshold each query ended with (diagnostics)
+};
+
+// the order-preserving 32-bit image of a non-NaN float, and back
+__device__ __forceinline__ unsigned q8_f2ord(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float q8_ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u); }
+
+// One workgroup per query.  The c = min(pair_cnt, pcap) stored pairs belong to c distinct real rows, and every one of them scores
+// at least its lb in the 16-bit scan; so with c >= k the k-th largest (non-NaN) lb is a score that k rows reach, and a row whose ub
+// is STRICTLY below it is beaten by k others whatever the tie-breaking (a subset of the query's pairs — an overflowed list — only
+// gives a smaller k-th largest, which is as valid).  Radix select, four passes of 8 bits over the image of lb with a 256-bin
+// histogram in LDS; then every stored pair that still stands sets its row's bit in keep[] (the OR also folds the queries that hit one
+// row into one candidate).  Every loop runs to a count read once.
+__global__ __launch_bounds__(256) void q8_tighten_kernel(TightenP P) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned s_bin, s_need;
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const unsigned offered = P.pair_cnt[q];
+    const unsigned c = offered < P.pcap ? offered : P.pcap;
+    const v4u* pr = P.pair + (size_t)q * P.pcap;
+    float tau = -__builtin_inff();
+    if (P.tau_init) {
+        const u64 key = P.tau_init[q];
+        if (key) tau = cmr_key_score(key);
+    }
+    if (c >= (unsigned)P.k) {
+        unsigned prefix = 0u, mask = 0u, need = (unsigned)P.k;
+        bool found = true;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[tid] = 0u;
+            __syncthreads();
+            for (unsigned i = tid; i < c; i += 256u) {
+                const float lb = __uint_as_float(pr[i].z);
+                if (lb == lb) {
+                    const unsigned u = q8_f2ord(lb);
+                    if ((u & mask) == prefix) atomicAdd(&hist[(u >> shift) & 255u], 1u);
+                }
+            }
+            __syncthreads();
+            if (tid < 64) {      // bins in descending order, four per lane: the bin in which the running count reaches `need`
+                unsigned h[4], sum = 0u;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { h[j] = hist[255 - (4 * lane + j)]; sum += h[j]; }
+                unsigned incl = sum;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) { const unsigned o = (unsigned)__shfl_up((int)incl, off); if (lane >= off) incl += o; }
+                const u64 reach = __ballot(incl >= need);
+                if (reach == 0ull) { if (lane == 0) s_bin = 0xFFFFFFFFu; }      // fewer than k lower bounds that are numbers
+                else if (lane == __ffsll((long long)reach) - 1) {
+                    unsigned before = incl - sum;
+                    int j = 0;
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) if (j == t && before + h[t] < need) { before += h[t]; j = t + 1; }
+                    s_bin = 255u - (unsigned)(4 * lane + j);
+                    s_need = need - before;
+                }
+            }
+            __syncthreads();
+            const unsigned bin = s_bin;
+            if (bin == 0xFFFFFFFFu) { found = false; break; }
+            need = s_need;
+            prefix |= bin << shift;
+            mask |= 255u << shift;
+        }
+        if (found) tau = fmaxf(tau, q8_ord2f(prefix));
+    }
+    for (unsigned i = tid; i < c; i += 256u) {
+        const v4u v = pr[i];
+        if (!(__uint_as_float(v.y) < tau)) atomicOr(&P.keep[v.x >> 5], 1u << (v.x & 31u));
+    }
+    if (tid == 0) P.tau_out[q] = tau;
+}
+
+// ------------------------------------------------------------------------------------------ expand
+// keep[0 .. npanels) -> the rows of the set bits in cand_row[], counted in *n_cand (zeroed in front of the launch) with one
+// atomicAdd per wave that has any
+__global__ __launch_bounds__(256) void q8_expand_kernel(const unsigned* __restrict__ keep, int npanels, unsigned* __restrict__ cand_row, unsigned* n_cand) {
+    const int lane = threadIdx.x & 63;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned m = p < npanels ? keep[p] : 0u;
+    const int c = __popc(m);
+    int incl = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+    const int total = __builtin_amdgcn_readlane(incl, 63);
+    if (total == 0) return;
+    unsigned base = 0u;
+    if (lane == 0) base = atomicAdd(n_cand, (unsigned)total);
+    base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+    unsigned at = base + (unsigned)(incl - c);
+    const unsigned row0 = (unsigned)p * CMR_PANEL_ROWS;
+    for (unsigned b = m; b; b &= b - 1u) cand_row[at++] = row0 + (unsigned)(__ffs((int)b) - 1);
 }
 
 // ------------------------------------------------------------------------------------------ re-score
@@ -459,7 +563,7 @@ hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s) {
     p.q8 = reinterpret_cast<const v4u*>(a.q8); p.scales4 = reinterpret_cast<const float4*>(a.scales);
     p.qpack = reinterpret_cast<const v4u*>(a.qpack); p.qconst = a.qconst; p.tau_init = a.tau_init;
     p.nrows = a.nrows; p.npanels = a.npanels; p.KB = a.dpad / 32; p.nq = a.nq; p.keep_all = a.keep_all;
-    p.cand_row = a.cand_row; p.n_cand = a.n_cand;
+    p.pair = reinterpret_cast<v4u*>(a.pair); p.pair_cnt = a.pair_cnt; p.pcap = a.keep_all ? 0u : (unsigned)a.pcap; p.keep = a.keep;
     const size_t lds = cmr_q8_filter_lds(a.dpad, a.nqt);
     auto launch = [&](auto kern) -> hipError_t {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -471,6 +575,19 @@ hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s) {
     if (a.nqt == 2) return ch8 ? launch(q8_filter_kernel<2, 8>) : launch(q8_filter_kernel<2, 4>);
     if (a.nqt == 1) return ch8 ? launch(q8_filter_kernel<1, 8>) : launch(q8_filter_kernel<1, 4>);
     return hipErrorInvalidValue;
+}
+
+hipError_t cmr_launch_q8_tighten(const CmrQ8Args& a, hipStream_t s) {
+    TightenP p;
+    p.pair = reinterpret_cast<const v4u*>(a.pair); p.pair_cnt = a.pair_cnt; p.pcap = (unsigned)a.pcap; p.tau_init = a.tau_init; p.k = a.k;
+    p.keep = a.keep; p.tau_out = a.tau_tight;
+    hipLaunchKernelGGL(q8_tighten_kernel, dim3(a.nq), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t cmr_launch_q8_expand(const CmrQ8Args& a, hipStream_t s) {
+    hipLaunchKernelGGL(q8_expand_kernel, dim3((a.npanels + 255) / 256), dim3(256), 0, s, (const unsigned*)a.keep, a.npanels, a.cand_row, a.n_cand);
+    return hipGetLastError();
 }
 
 hipError_t cmr_launch_q8_rescore(const CmrQ8Args& a, hipStream_t s) {

@@ -81,6 +81,7 @@ struct PassPlan {
     bool fin = false;                // scan with the finishing stage: no sampling launches, no merge of its own
     int prefilter = 0;               // 1 | 2: the int8 filter in the place of the main scan, the re-score in front of the merge (W: the re-score's lists)
     int rescore_grid = 0;
+    int pair_cap = 0;                // pre-filter: hit records per query for the threshold tightening (0: none, every hit is re-scored)
     int G = 1;                       // query groups of the query-split grid
     int n_levels = 0;                // sampling passes in front of the main scan
     struct Level { long long panels; int grid, Wl, clog, stride; } level[2] = {};      // grid: launch grid (all groups); Wl: candidate lists per query
@@ -232,6 +233,7 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
         p.prefilter = rq.prefilter;
         p.rescore_grid = idx->pf_rescore_wgs > 0 ? idx->pf_rescore_wgs : std::min(idx->n_cu, 1024);
         W = p.rescore_grid * cmr_q8_rescore_waves();
+        p.pair_cap = (rq.prefilter == 1 && idx->pf_tighten) ? idx->pf_pair_cap : 0;
     }
     const int NQA = G * NQ;          // query slots of the pass over all groups
     p.NQ = NQ; p.W = W; p.Ws = Ws; p.tiles = tiles; p.NQA = NQA;
