@@ -40,7 +40,7 @@ if os.environ.get("CMR_BUILD_LIB"):          # experiment builds go to their own
 # unrolled size exceeds LLVM's default limit for "#pragma unroll" (16 K) and hipcc silently keeps the loops.
 SCAN_FLAGS = ["-mllvm", "-pragma-unroll-threshold=1048576"]
 SOURCES = ["scan_kernels.hip", "aux_kernels.hip", "prefilter_kernels.hip", "api.hip", "comm.hip", "ppr.hip", "encoder_kernels.hip", "multi.hip"]
-HEADERS = ["cmr_device.h", "cmr_kernels.h", "cmr_internal.h", "combine.h", "cmr_select.h", "cmr_topk.h", "index_state.h", "search_plan.h", os.path.join("..", "..", "include", "comorag_hip.h")]
+HEADERS = ["cmr_device.h", "cmr_kernels.h", "cmr_internal.h", "combine.h", "cmr_select.h", "cmr_topk.h", "index_state.h", "search_plan.h", "prefilter_host.h", os.path.join("..", "..", "include", "comorag_hip.h")]
 
 _KERNEL_RE = re.compile(r"^_Z11scan_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEv5ScanP:")
 

@@ -25,6 +25,7 @@
 #include "cmr_internal.h"
 #include "index_state.h"
 #include "search_plan.h"
+#include "prefilter_host.h"
 
 namespace {
 thread_local std::string g_err;
@@ -62,12 +63,6 @@ struct Option {
     const char* reject;
     long long (*read)(const cmr_index*);       // nullptr: not readable
 };
-// "prefilter_candidates": rows the last pre-filtered pass handed to the re-score; "prefilter_pairs": the (row, query) records its
-// filter stored, summed over the queries; "prefilter_pair_overflow": queries that offered more than the capacity
-// (all three wait for the pipeline; -1: the read failed)
-long long read_prefilter_candidates(const cmr_index* idx);
-long long read_prefilter_pairs(const cmr_index* idx);
-long long read_prefilter_pair_overflow(const cmr_index* idx);
 #define CMR_STR_(x) #x
 #define CMR_STR(x) CMR_STR_(x)
 #define OPT_FIELD(f) [](cmr_index* i, long long v) { i->f = (decltype(i->f))v; }
@@ -111,11 +106,11 @@ const Option kOptions[] = {
     {"prefilter_tighten", OPT_FIELD(pf_tighten), Option::range, 0, 1, 0, "prefilter_tighten must be 0 or 1", OPT_READ(i->pf_tighten)},
     {"prefilter_pair_cap", OPT_FIELD(pf_pair_cap), Option::clamp, 0, 1 << 20, 0, nullptr, OPT_READ(i->pf_pair_cap)},
     {"prefilter_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->prefilter_active)},
-    {"prefilter_rows", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->q8 ? i->q8_rows : 0)},
-    {"prefilter_bytes", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ((long long)i->q8_bytes())},
-    {"prefilter_candidates", nullptr, Option::any, 0, 0, 0, nullptr, read_prefilter_candidates},
-    {"prefilter_pairs", nullptr, Option::any, 0, 0, 0, nullptr, read_prefilter_pairs},
-    {"prefilter_pair_overflow", nullptr, Option::any, 0, 0, 0, nullptr, read_prefilter_pair_overflow},
+    {"prefilter_rows", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->q8c.q8 ? i->q8c.rows : 0)},
+    {"prefilter_bytes", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ((long long)i->q8c.bytes(i->dpad))},
+    {"prefilter_candidates", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::candidates))},
+    {"prefilter_pairs", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::pairs))},
+    {"prefilter_pair_overflow", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::pair_overflow))},
     {"last_route", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->last_route.load(std::memory_order_relaxed))},
     {"pipe_dual_scan_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_active)},
     {"pipe_dual_scan_wide_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_wide_active)},
@@ -287,27 +282,11 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
     }
     HIP_TRY(ws->tau.ensure(p.bytes.tau));
     // the re-score of the workspace's previous pass reads the query fragments and thresholds on the merge stream
-    if (ws->pf_prev && sp != sm && st.ev_lists_free) HIP_TRY(hipStreamWaitEvent(sp, st.ev_lists_free, 0));
-    ws->pf_prev = p.prefilter != 0;
+    if (ws->q8.pf_prev && sp != sm && st.ev_lists_free) HIP_TRY(hipStreamWaitEvent(sp, st.ev_lists_free, 0));
+    ws->q8.pf_prev = p.prefilter != 0;
     HIP_TRY(cmr_launch_prep_queries(idx->dtype, q_dev, nqp, idx->dim, idx->dpad, p.tiles, ws->qfrag.p, ws->flag_ptr, sp));
-    CmrQ8Args f{};
-    if (p.prefilter) {
-        HIP_TRY(ws->q8_qpack.ensure((size_t)2 * p.tiles * (idx->dpad / 32) * 1024));
-        HIP_TRY(ws->q8_qconst.ensure((size_t)p.NQ * sizeof(float4)));
-        HIP_TRY(ws->q8_cand.ensure((size_t)idx->cap_panels * CMR_PANEL_ROWS * sizeof(unsigned)));
-        HIP_TRY(ws->q8_ncand.ensure(sizeof(unsigned)));
-        HIP_TRY(ws->q8_pair.ensure(std::max<size_t>((size_t)p.NQ * p.pair_cap * 16, 16)));
-        HIP_TRY(ws->q8_paircnt.ensure((size_t)p.NQ * sizeof(unsigned)));
-        HIP_TRY(ws->q8_keep.ensure((size_t)idx->cap_panels * sizeof(unsigned)));
-        HIP_TRY(ws->q8_tau.ensure((size_t)p.NQ * sizeof(float)));
-        if (sp != idx->q8_stream) HIP_TRY(hipStreamWaitEvent(sp, idx->q8_ready, 0));      // the companion's last rows were quantised on another stream
-        HIP_TRY(cmr_launch_q8_pack_queries(idx->dtype, q_dev, nqp, idx->dim, idx->dpad, p.tiles, idx->q8_stats, ws->q8_qpack.p, (float4*)ws->q8_qconst.p, sp));
-        f.dtype = idx->dtype; f.dpad = idx->dpad; f.nqt = g.nqt; f.cap = g.cap; f.grid = g.grid; f.rescore_grid = p.rescore_grid;
-        f.corpus = idx->corpus; f.q8 = idx->q8; f.scales = idx->q8_scales; f.qfrag = ws->qfrag.p; f.qpack = ws->q8_qpack.p; f.qconst = (const float4*)ws->q8_qconst.p;
-        f.nrows = idx->n; f.npanels = (int)idx->npanels(); f.nq = nqp; f.k = k; f.keep_all = p.prefilter == 2 ? 1 : 0;
-        f.cand_row = (unsigned*)ws->q8_cand.p; f.n_cand = (unsigned*)ws->q8_ncand.p;
-        f.pair = ws->q8_pair.p; f.pair_cnt = (unsigned*)ws->q8_paircnt.p; f.pcap = p.pair_cap; f.keep = (unsigned*)ws->q8_keep.p; f.tau_tight = (float*)ws->q8_tau.p;
-    }
+    CmrQ8Args f{};      // the pre-filter's launches (prefilter_host.h), where the plan takes that route
+    if (p.prefilter && (rc = q8_prepare(idx, ws, p, q_dev, sp, f))) return rc;
     CmrScanArgs a{};
     a.corpus = idx->corpus; a.qfrag = ws->qfrag.p; a.nrows = idx->n; a.npanels = (int)idx->npanels(); a.k = k;
     a.nq = nqp;
@@ -335,10 +314,8 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
                                        nullptr, nullptr, nullptr, tau_out, sp, G > 1));
         a.tau_init = tau_out;
     }
-    if (sp != sm) {
-        if (st.ev_lists_free) HIP_TRY(hipStreamWaitEvent(sp, st.ev_lists_free, 0));   // previous merge of this slot's lists
-    }
-    if (p.prefilter) HIP_TRY(hipMemsetAsync(f.pair_cnt, 0, (size_t)p.NQ * sizeof(unsigned), sp));   // (behind that wait: the previous tightening read the counters and the pairs)
+    if (sp != sm && st.ev_lists_free) HIP_TRY(hipStreamWaitEvent(sp, st.ev_lists_free, 0));   // previous merge of this slot's lists
+    if (p.prefilter) HIP_TRY(hipMemsetAsync(f.pair_cnt, 0, p.bytes.q8[Q8_PAIRCNT], sp));   // (behind that wait: the previous tightening read the counters and the pairs)
     if (sp != sm) {
         HIP_TRY(hipEventRecord(st.ev_pre, sp));
         HIP_TRY(hipStreamWaitEvent(sm, st.ev_pre, 0));
@@ -375,19 +352,13 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
         // caller's done word and the merge launch — which would return in its first instruction on state 1 — is issued only on state 2
         if (ws->done_ptr && idx->single_block()) a.fin_done = ws->done_ptr;
     }
-    if (p.prefilter) {
-        f.tau_init = a.tau_init; f.lists = a.lists; f.cnt = a.cnt;
-        HIP_TRY(cmr_launch_q8_filter(f, sm));
-        idx->q8_last_ncand = f.n_cand; idx->q8_last_paircnt = f.pair_cnt; idx->q8_last_nq = nqp; idx->q8_last_pcap = f.pcap;
-    } else {
-        HIP_TRY(p.wide ? cmr_launch_scan_wide(g, a, sm) : p.fin ? cmr_launch_scan_fin(g, a, sm) : cmr_launch_scan_topk(g, a, sm));
-    }
+    if (p.prefilter) { if ((rc = q8_filter(idx, f, a, sm))) return rc; }
+    else HIP_TRY(p.wide ? cmr_launch_scan_wide(g, a, sm) : p.fin ? cmr_launch_scan_fin(g, a, sm) : cmr_launch_scan_topk(g, a, sm));
     if (prof) {
         HIP_TRY(hipEventRecord(pe.b, sm));
         std::lock_guard<std::mutex> pg(idx->prof_mu);
         idx->prof_events.push_back(pe);
-        // (the pre-filter: what its launch reads — the int8 companion with its scales and the two int8 query parts)
-        idx->prof_bytes = p.prefilter ? (double)idx->npanels() * CMR_PANEL_ROWS * (idx->dpad + sizeof(float2)) + (double)2 * p.tiles * idx->dpad * 32 : algorithmic_bytes(idx, nqp, k);
+        idx->prof_bytes = p.prefilter ? prefilter_bytes(idx, p) : algorithmic_bytes(idx, nqp, k);
     }
     if (a.fin_done) {
         ws->lazy.due = true;
@@ -401,13 +372,7 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
         HIP_TRY(hipEventRecord(st.ev_scan, sm));
         HIP_TRY(hipStreamWaitEvent(sq, st.ev_scan, 0));
     }
-    if (p.prefilter) {
-        // the hits' thresholds tightened into keep[], its bits listed, and those rows scored by the scan's chain into the lists the merge reads
-        if (f.pcap > 0) HIP_TRY(cmr_launch_q8_tighten(f, sq));
-        HIP_TRY(hipMemsetAsync(f.n_cand, 0, sizeof(unsigned), sq));
-        HIP_TRY(cmr_launch_q8_expand(f, sq));
-        HIP_TRY(cmr_launch_q8_rescore(f, sq));
-    }
+    if (p.prefilter && (rc = q8_rescore(f, sq))) return rc;
     HIP_TRY(cmr_launch_merge_query((const u64*)ws->lists.p, (const int*)ws->cnt.p, p.W, p.NQ, g.cap, nqp, k, (const float2*)ws->mm.p,
                                    kernel_id_base(idx), ids_dev, scores_dev, min_dev, max_dev, nullptr, sq, G > 1, fin_state));
     return remap_ids_enqueue(idx, ids_dev, (long long)nqp * k, sq);
@@ -421,7 +386,6 @@ int plan_and_enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, 
     rq.prefilter = prefilter;
     int rc = plan_pass(idx, rq, &plan);
     if (rc) return rc;
-    if (plan.prefilter) idx->prefilter_active = 1;
     if (ps.q0 == 0)      // (a batch of several passes: its first, and the bit that says more follow)
         idx->last_route.store(route_code(plan, min_score != nullptr) | (ps.nqp < ps.nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
     return enqueue_pass(idx, ws, st, plan, q_dev + (size_t)ps.q0 * idx->dim, min_score, ids_dev + (size_t)ps.q0 * k, scores_dev + (size_t)ps.q0 * k,
@@ -535,48 +499,6 @@ int ensure_pipe(cmr_index* idx) {
     return CMR_OK;
 }
 
-// Brings the int8 companion of the corpus up to date (idx->pipe_mu held): (re)allocated for the corpus buffer's capacity, rows
-// [q8_rows rounded down to a panel, n) quantised on `s`.  false: no companion (allocation failed — the route stays off).
-bool ensure_companion(cmr_index* idx, hipStream_t s) {
-    if (idx->q8_failed_cap == idx->cap_panels) return false;
-    auto give_up = [&]() {
-        if (idx->q8) (void)hipFree(idx->q8);
-        if (idx->q8_scales) (void)hipFree(idx->q8_scales);
-        idx->q8 = nullptr; idx->q8_scales = nullptr; idx->q8_cap_panels = 0; idx->q8_rows = 0;
-        idx->q8_failed_cap = idx->cap_panels;
-        (void)hipGetLastError();
-        return false;
-    };
-    if (!idx->q8_stats) {
-        if (hipMalloc((void**)&idx->q8_stats, 2 * sizeof(float)) != hipSuccess) { idx->q8_stats = nullptr; return give_up(); }
-        if (hipEventCreateWithFlags(&idx->q8_ready, hipEventDisableTiming) != hipSuccess) { idx->q8_ready = nullptr; return give_up(); }
-    }
-    if (!idx->q8_ready) return false;
-    if (!idx->q8 || idx->q8_cap_panels != idx->cap_panels) {
-        // the corpus buffer was replaced (capacity growth): so is the companion, and like grow() only once nothing in flight reads the old one
-        if (idx->q8) {
-            if (hipDeviceSynchronize() != hipSuccess) return give_up();
-            (void)hipFree(idx->q8); (void)hipFree(idx->q8_scales);
-            idx->q8 = nullptr; idx->q8_scales = nullptr;
-        }
-        const size_t bytes = (size_t)idx->cap_panels * CMR_PANEL_ROWS * idx->dpad;
-        if (hipMalloc(&idx->q8, bytes + CMR_CORPUS_SLACK) != hipSuccess) { idx->q8 = nullptr; return give_up(); }
-        if (hipMalloc((void**)&idx->q8_scales, (size_t)idx->cap_panels * CMR_PANEL_ROWS * sizeof(float2)) != hipSuccess) { idx->q8_scales = nullptr; return give_up(); }
-        if (hipMemsetAsync((char*)idx->q8 + bytes, 0, CMR_CORPUS_SLACK, s) != hipSuccess || hipMemsetAsync(idx->q8_stats, 0, 2 * sizeof(float), s) != hipSuccess) return give_up();
-        idx->q8_cap_panels = idx->cap_panels;
-        idx->q8_rows = 0;
-    }
-    idx->q8_rows = std::min(idx->q8_rows, idx->n);
-    if (idx->q8_rows < idx->n) {
-        const long long panel0 = idx->q8_rows / CMR_PANEL_ROWS;
-        if (cmr_launch_q8_quantise(idx->dtype, idx->corpus, idx->dpad, panel0, idx->npanels() - panel0, idx->n, idx->q8, idx->q8_scales, idx->q8_stats, s) != hipSuccess ||
-            hipEventRecord(idx->q8_ready, s) != hipSuccess) return give_up();
-        idx->q8_stream = s;
-        idx->q8_rows = idx->n;
-    }
-    return true;
-}
-
 // Pipelined search: three internal streams.  Pre-phases run on `sp` back to back, candidate merges
 // on `sq`; main scans are serialised on `sm` (two HBM-bound scans at once only slow each other down) and leave
 // `reserve_cus` CUs free, on which the next pass's sampling scans and the merges run concurrently.
@@ -599,12 +521,9 @@ int search_pipelined_enqueue_locked(cmr_index* idx, const float* q_dev, int nq, 
         HIP_TRY(hipStreamWaitEvent(nsp, wait_event, 0));
         if (ps.any_wide()) HIP_TRY(hipStreamWaitEvent(wsp, wait_event, 0));
     }
-    // Certified int8 pre-filter: plain pipelined calls without min / max outputs (the int8 pass cannot give the 16-bit
-    // extremes) on a 16-bit index, when the option says so; the companion is brought up to date in front of the call's pre-phase
-    int prefilter = 0;
-    if (may_prefilter && !min_score && !min_dev && !max_dev && idx->dtype != CMR_F32 && idx->n > 0 && nq <= idx->narrow_max() &&
-        (idx->prefilter > 0 || (idx->prefilter < 0 && kPrefilterAuto && !idx->short_scan())) && ensure_companion(idx, nsp))
-        prefilter = idx->prefilter == 2 ? 2 : 1;
+    // Certified int8 pre-filter (prefilter_host.h): the companion is brought up to date in front of the call's pre-phase
+    int prefilter = prefilter_eligible(idx, min_score != nullptr, min_dev || max_dev, nq, may_prefilter);
+    if (prefilter && !q8_ensure_companion(idx, nsp)) prefilter = 0;
     idx->prefilter_active = 0;
     PipeSlot* last = nullptr;
     while (ps.next()) {
@@ -647,34 +566,6 @@ int search_pipelined_enqueue(cmr_index* idx, const float* q_dev, int nq, int k, 
     std::lock_guard<std::mutex> pl(idx->pipe_mu);
     return search_pipelined_enqueue_locked(idx, q_dev, nq, k, ids_dev, scores_dev, min_dev, max_dev, wait_event, done_event, min_score, may_prefilter);
 }
-
-long long read_prefilter_candidates(const cmr_index* cidx) {
-    cmr_index* idx = const_cast<cmr_index*>(cidx);
-    if (cmr_set_device(idx->device)) return -1;
-    std::lock_guard<std::mutex> pl(idx->pipe_mu);
-    if (!idx->q8_last_ncand) return 0;
-    for (hipStream_t st : idx->pipe.st) if (st && hipStreamSynchronize(st) != hipSuccess) return -1;
-    unsigned h = 0;
-    if (hipMemcpy(&h, idx->q8_last_ncand, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return (long long)h;
-}
-
-// the pair counters of the last pre-filtered pass: (stored pairs over all queries, queries that offered more than the capacity)
-bool read_pair_counters(const cmr_index* cidx, long long* stored, long long* overflowed) {
-    cmr_index* idx = const_cast<cmr_index*>(cidx);
-    if (cmr_set_device(idx->device)) return false;
-    std::lock_guard<std::mutex> pl(idx->pipe_mu);
-    *stored = 0; *overflowed = 0;
-    if (!idx->q8_last_paircnt || idx->q8_last_nq <= 0) return true;
-    for (hipStream_t st : idx->pipe.st) if (st && hipStreamSynchronize(st) != hipSuccess) return false;
-    std::vector<unsigned> h((size_t)idx->q8_last_nq);
-    if (hipMemcpy(h.data(), idx->q8_last_paircnt, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return false;
-    const unsigned cap = (unsigned)idx->q8_last_pcap;
-    for (unsigned c : h) { *stored += std::min(c, cap); *overflowed += c > cap ? 1 : 0; }
-    return true;
-}
-long long read_prefilter_pairs(const cmr_index* idx) { long long s, o; return read_pair_counters(idx, &s, &o) ? s : -1; }
-long long read_prefilter_pair_overflow(const cmr_index* idx) { long long s, o; return read_pair_counters(idx, &s, &o) ? o : -1; }
 
 int scores_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, float* out_dev, long long ld) {
     hipStream_t s = ws->stream;
@@ -907,10 +798,7 @@ int32_t cmr_index_destroy(cmr_index_t* idx) {
         if (idx->shadow) (void)hipFree(idx->shadow);
         if (idx->d_flag) (void)hipFree(idx->d_flag);
         if (idx->d_stats) (void)hipFree(idx->d_stats);
-        if (idx->q8) (void)hipFree(idx->q8);
-        if (idx->q8_scales) (void)hipFree(idx->q8_scales);
-        if (idx->q8_stats) (void)hipFree(idx->q8_stats);
-        if (idx->q8_ready) (void)hipEventDestroy(idx->q8_ready);
+        idx->q8c.release();
         for (ExactScratch& x : idx->x_slot) x.release();
         if (idx->d_blk) (void)hipFree(idx->d_blk);
         for (void* p : idx->blk_retired) (void)hipFree(p);
@@ -1333,7 +1221,7 @@ int cmr_index_truncate(cmr_index_t* idx, long long n_rows) {
     std::unique_lock<std::shared_mutex> lk(idx->mu);
     if (n_rows < 0 || n_rows > idx->n) return fail(CMR_ERR_INVALID, "truncate to %lld rows of %lld", n_rows, idx->n);
     idx->n = n_rows;
-    idx->q8_rows = std::min(idx->q8_rows, n_rows);      // (the next append rewrites the slots behind: their int8 companion is stale then)
+    idx->q8c.rows = std::min(idx->q8c.rows, n_rows);      // (the next append rewrites the slots behind: their int8 companion is stale then)
     return CMR_OK;
 }
 
@@ -1803,9 +1691,9 @@ int32_t cmr_index_prefilter_stats(cmr_index_t* idx, float* max_row_norm, float* 
     if (rc) return rc;
     std::lock_guard<std::mutex> pl(idx->pipe_mu);
     float h[2] = {0.0f, 0.0f};
-    if (idx->q8) {
-        HIP_TRY(hipStreamSynchronize(idx->q8_stream));
-        HIP_TRY(hipMemcpy(h, idx->q8_stats, sizeof(h), hipMemcpyDeviceToHost));
+    if (idx->q8c.q8) {
+        HIP_TRY(hipStreamSynchronize(idx->q8c.stream));
+        HIP_TRY(hipMemcpy(h, idx->q8c.stats, sizeof(h), hipMemcpyDeviceToHost));
     }
     *max_row_norm = h[0];
     *max_quant_err = h[1];

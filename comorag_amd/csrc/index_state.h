@@ -24,9 +24,6 @@
 
 namespace {
 
-// prefilter = -1 (the default) takes the pre-filter for scans of 1 ms and longer (DESIGN 4.14 has the measurement behind it)
-constexpr bool kPrefilterAuto = true;
-
 int elem_size(int dtype) { return dtype == CMR_F32 ? 4 : 2; }
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 long long panels_of(long long rows) { return (rows + CMR_PANEL_ROWS - 1) / CMR_PANEL_ROWS; }
@@ -37,6 +34,27 @@ struct ExactScratch {
     DevBuf ids, sc, part, arrive, oids, osc, oex;
     void release() { ids.release(); sc.release(); part.release(); arrive.release(); oids.release(); osc.release(); oex.release(); }
 };
+
+// ---- certified int8 pre-filter (host side: prefilter_host.h).  The int8 companion of the corpus — int8 blocks, (scale, error norm) per row,
+// (max ||x||, max error norm) — covers rows [0, rows) of a corpus buffer of cap_panels panels; a call that uses it brings it up to date first.  Freed by release() only.
+struct Q8Companion {
+    void* q8 = nullptr; float2* scales = nullptr; float* stats = nullptr;
+    long long cap_panels = 0, rows = 0;
+    long long failed_cap = -1;           // the companion of a corpus buffer of this many panels could not be allocated: the route stays off
+    hipEvent_t ready = nullptr; hipStream_t stream = nullptr;      // the event behind the last quantise launch, and the stream it was recorded on
+    size_t bytes(int dpad) const { return q8 ? (size_t)cap_panels * CMR_PANEL_ROWS * (dpad + sizeof(float2)) + CMR_CORPUS_SLACK : 0; }
+    void release() { (void)hipFree(q8); (void)hipFree(scales); (void)hipFree(stats); if (ready) (void)hipEventDestroy(ready); *this = Q8Companion{}; }
+};
+// A workspace's buffers of a pre-filtered pass, sized by plan_pass (PassPlan::bytes.q8[]): int8 query parts, queries' constants, candidate
+// rows and their counter, the filter's (row, ub, lb) records per query and their counters, row mask per panel, tightened thresholds.
+enum Q8Buf { Q8_QPACK, Q8_QCONST, Q8_CAND, Q8_NCAND, Q8_PAIR, Q8_PAIRCNT, Q8_KEEP, Q8_TAU, Q8_NBUF };
+struct Q8Scratch {
+    DevBuf buf[Q8_NBUF];
+    bool pf_prev = false;                // the workspace's last pass ran the re-score, which reads qfrag / tau on the merge stream
+    hipError_t ensure(const size_t (&bytes)[Q8_NBUF]) { for (int i = 0; i < Q8_NBUF; ++i) if (hipError_t e = buf[i].ensure(bytes[i])) return e; return hipSuccess; }
+    void release() { for (DevBuf& b : buf) b.release(); }
+};
+struct Q8LastPass { const unsigned* ncand = nullptr; const unsigned* paircnt = nullptr; int nq = 0, pcap = 0; };      // candidate counter, nq pair counters, their capacity
 
 // Scratch of one in-flight search.  One per stream (searches on a stream are serialised by it).
 struct Workspace {
@@ -50,11 +68,7 @@ struct Workspace {
     // synchronous search: queries in, (ids | scores | min | max | non-finite flag) out through ONE pinned host buffer and
     // one copy each way — five pageable D2H copies cost more than the search of a small corpus
     DevBuf d_pack;
-    // certified int8 pre-filter: the int8 query parts, the queries' constants, the filter's (row, ub, lb) records per
-    // query with their counters, the row mask per panel, the tightened thresholds, the batch's candidate rows and their counter;
-    // pf_prev: the workspace's last pass ran the re-score, which reads qfrag / tau on the merge stream
-    DevBuf q8_qpack, q8_qconst, q8_cand, q8_ncand, q8_pair, q8_paircnt, q8_keep, q8_tau;
-    bool pf_prev = false;
+    Q8Scratch q8;                // certified int8 pre-filter
     ExactScratch x;              // cmr_index_search_exact
     int* flag_ptr = nullptr;     // the non-finite-query flag the kernels set: flag.p, or the head of d_pack for the host API
     // Synchronous host API with mapped results: the word (device view of the pinned buffer, bytes 4..7) that the search's LAST kernel sets
@@ -88,7 +102,7 @@ struct Workspace {
         fin_ctl.release(); fin_pmax.release(); fin_tau.release(); fin_dense.release(); fin_mm.release();
         d_q.release(); d_ids.release(); d_scores.release(); d_min.release(); d_max.release(); d_cand.release(); d_out.release();
         d_pack.release();
-        q8_qpack.release(); q8_qconst.release(); q8_cand.release(); q8_ncand.release(); q8_pair.release(); q8_paircnt.release(); q8_keep.release(); q8_tau.release();
+        q8.release();
         x.release();
         if (h_pin) (void)hipHostFree(h_pin);
         h_pin = nullptr; h_pin_dev = nullptr; h_pin_cap = 0;
@@ -196,10 +210,8 @@ struct cmr_index {
     std::vector<void*> blk_retired;      // earlier tables: in-flight searches may still read them (a few bytes each, freed at destroy)
     int sample_maxmul = 0;   // sample_maxmul: level-1 sample <= sample_maxmul x level 0 (0 = 128 narrow / 512 wide)
     int sample_div = 32;     // sample_div: level-1 sample = 1/sample_div of the panels (clamped to [8, 128] x level 0)
-    // Certified int8 pre-filter of the pipelined 16-bit scan.  prefilter: -1 auto (kPrefilterAuto and a scan of 1 ms
-    // or longer) | 0 off | 1 every eligible call | 2 the same with a filter that keeps every row (the re-score path alone).  The
-    // companion — int8 blocks, (scale, error norm) per row, (max ||x||, max error norm) — covers rows [0, q8_rows) of a corpus buffer
-    // of q8_cap_panels panels; a pipelined call that uses it brings it up to date first, under pipe_mu.
+    // Certified int8 pre-filter of the pipelined 16-bit scan.  prefilter: -1 auto (kPrefilterAuto, prefilter_host.h, and a scan of 1 ms
+    // or longer) | 0 off | 1 every eligible call | 2 the same with a filter that keeps every row (the re-score path alone).
     int prefilter = -1;
     int pf_rescore_wgs = 0;              // prefilter_rescore_wgs: workgroups of the re-score (0: one per CU)
     // prefilter_tighten: the k-th largest certified lower bound among a query's hits replaces its sampling threshold before the
@@ -207,18 +219,9 @@ struct cmr_index {
     // records per query (16 bytes each: 16 MiB per workspace at 64 queries); a query that offers more keeps the rest directly.
     int pf_tighten = 1;
     int pf_pair_cap = 16384;
-    void* q8 = nullptr;
-    float2* q8_scales = nullptr;
-    float* q8_stats = nullptr;
-    long long q8_cap_panels = 0, q8_rows = 0;
-    long long q8_failed_cap = -1;        // the companion of a corpus buffer of this many panels could not be allocated: the route stays off
-    hipEvent_t q8_ready = nullptr;       // behind the last quantise launch, on q8_stream
-    hipStream_t q8_stream = nullptr;
+    Q8Companion q8c;
     int prefilter_active = 0;            // read-only: did the last pipelined call run the pre-filter
-    const unsigned* q8_last_ncand = nullptr;      // the candidate counter of the last pre-filtered pass
-    const unsigned* q8_last_paircnt = nullptr;    // its pair counters (q8_last_nq of them) and the capacity they ran against
-    int q8_last_nq = 0, q8_last_pcap = 0;
-    size_t q8_bytes() const { return q8 ? (size_t)q8_cap_panels * CMR_PANEL_ROWS * (dpad + sizeof(float2)) + CMR_CORPUS_SLACK : 0; }
+    Q8LastPass q8_last;                  // the last pre-filtered pass's counters (the options prefilter_candidates / _pairs / _pair_overflow read them)
     int pipe_slots = 3;      // pipe_slots (2..4): batches in the pipeline.  A third slot lets the pre-phase of batch i+2 start before
                              // scan i has ended: 1 M x 768 bf16, B = 64 step 0.279 -> 0.264 ms; nothing at 10 M rows
     int reserve_cus = -1;    // pipe_reserve_cus: CUs the pipelined main scan leaves free (-1 = by corpus size, see plan_pass)

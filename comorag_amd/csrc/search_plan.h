@@ -71,7 +71,7 @@ struct PassRequest {
     bool single_stream = false;      // pre-phase, scan and merge on ONE stream (a synchronous caller)
     bool pipelined = false;          // the pre-phase has a stream of its own
     int reserve_cus = 0;             // CUs the main scan leaves free (< 0: by corpus size)
-    int prefilter = 0;               // the caller could take the int8 pre-filter (1; 2: with a filter that keeps every row) if the pass is eligible
+    int prefilter = 0;               // the call may take the int8 pre-filter (prefilter_eligible, prefilter_host.h: 1; 2: with a filter that keeps every row) if the pass is eligible
 };
 
 struct PassPlan {
@@ -91,7 +91,7 @@ struct PassPlan {
     int lists_per_wg = CMR_SCAN_WAVES;
     int NQ = 0, W = 0, Ws = 0, tiles = 0, NQA = 0;      // query slots per group, main / sampling lists per query, query tiles, query slots over all groups
     int fin_first = 0, fin_wgs = 0, fin_mul = 1, fin_dcap = 0, fin_spin = 0;
-    struct { size_t qfrag, lists, cnt, mm, s_lists, s_cnt, s_mm, tau, fin_ctl, fin_pmax, fin_tau, fin_mm, fin_dense; } bytes = {};
+    struct { size_t qfrag, lists, cnt, mm, s_lists, s_cnt, s_mm, tau, fin_ctl, fin_pmax, fin_tau, fin_mm, fin_dense, q8[Q8_NBUF]; } bytes = {};
 };
 
 int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
@@ -138,8 +138,8 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     // Narrow kernel: one sampled panel per wave = one candidate list per panel, and merge_query_kernel takes at
     // most 4096 lists, so S1 is capped there (k > 32 on multi-million-row shards would otherwise overrun it).
     // Wide kernel: the sampling workgroups split the sampled panels among them (one list per workgroup and query).
-    // Certified int8 pre-filter: a narrow pass of a 16-bit index whose thresholds come from tau_init
-    const bool prefilter = rq.prefilter && !wide && G == 1 && !fin && !rq.has_min_score && idx->dtype != CMR_F32;
+    // Certified int8 pre-filter: a narrow pass with thresholds from tau_init (16-bit index, no threshold search: tested by prefilter_eligible)
+    const bool prefilter = rq.prefilter && !wide && G == 1 && !fin;
     long long level_panels[2] = {0, 0};
     int n_levels = 0;
     bool single_level = false;
@@ -234,6 +234,14 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
         p.rescore_grid = idx->pf_rescore_wgs > 0 ? idx->pf_rescore_wgs : std::min(idx->n_cu, 1024);
         W = p.rescore_grid * cmr_q8_rescore_waves();
         p.pair_cap = (rq.prefilter == 1 && idx->pf_tighten) ? idx->pf_pair_cap : 0;
+        p.bytes.q8[Q8_QPACK] = (size_t)2 * tiles * (idx->dpad / 32) * 1024;
+        p.bytes.q8[Q8_QCONST] = (size_t)NQ * sizeof(float4);
+        p.bytes.q8[Q8_CAND] = (size_t)idx->cap_panels * CMR_PANEL_ROWS * sizeof(unsigned);      // (cap_panels: candidate rows and keep masks follow the corpus buffer)
+        p.bytes.q8[Q8_NCAND] = sizeof(unsigned);
+        p.bytes.q8[Q8_PAIR] = std::max<size_t>((size_t)NQ * p.pair_cap * 16, 16);
+        p.bytes.q8[Q8_PAIRCNT] = (size_t)NQ * sizeof(unsigned);
+        p.bytes.q8[Q8_KEEP] = (size_t)idx->cap_panels * sizeof(unsigned);
+        p.bytes.q8[Q8_TAU] = (size_t)NQ * sizeof(float);
     }
     const int NQA = G * NQ;          // query slots of the pass over all groups
     p.NQ = NQ; p.W = W; p.Ws = Ws; p.tiles = tiles; p.NQA = NQA;

@@ -1,54 +1,21 @@
 """Certified int8 pre-filter of the pipelined search on the device: with the option "prefilter" = 1 (filter + re-score)
 and 2 (the re-score alone: the filter keeps every row) a pipelined call returns, bit for bit, the ids and scores of the same index
 with "prefilter" = 0 and of the synchronous search."""
-import functools
-
 import numpy as np
 import pytest
 
 from tests import prefilter_model as pm
-from tests import value_domain_inputs as vd
+from tests.prefilter_gpu_helpers import BATCHES, N_BIG, N_MID, N_SMALL, _data, _enqueue, _index, _same_bits
 
 pytestmark = pytest.mark.gpu
 
-MAX_K = 128      # CMR_MAX_K
-# n: no sampling level / one level, partial last panel / two levels
-N_SMALL, N_MID, N_BIG = 70, 8197, 140_003
-BATCHES = [(1, 1), (33, 20), (64, MAX_K)]
-
-
-@functools.lru_cache(maxsize=None)
-def _data(family, n, d, seed=0):
-    X, Q = pm.family(family, n, d, 64, seed)
-    X.setflags(write=False); Q.setflags(write=False)
-    return X, Q
-
-
-def _index(X, d, dtype, id_base=0, capacity_hint=0):
-    from comorag_amd.index import DenseIndex
-    idx = DenseIndex(d, dtype, capacity_hint=capacity_hint)
-    idx.append(X)
-    if id_base:
-        idx.set_id_base(id_base)
-    return idx
-
 
 def _pipelined(idx, Q, k, mode, minmax=False):
-    import torch
-    dev = torch.device("cuda", idx.device)
     idx.set_option("prefilter", mode)
-    qt = torch.from_numpy(np.ascontiguousarray(Q, np.float32)).to(dev)
-    oi = torch.empty((len(Q), k), dtype=torch.int64, device=dev)
-    os_ = torch.empty((len(Q), k), dtype=torch.float32, device=dev)
-    mn = torch.empty(len(Q), dtype=torch.float32, device=dev) if minmax else None
-    mx = torch.empty(len(Q), dtype=torch.float32, device=dev) if minmax else None
-    idx.sync(idx.search_pipelined(qt, k, oi, os_, mn, mx))
+    done, _, oi, os_ = _enqueue(idx, Q, k, minmax)
+    idx.sync(done)
     assert idx.query_status() is False
     return oi.cpu().numpy(), os_.cpu().numpy()
-
-
-def _same_bits(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
 
 
 def _check_all_modes(idx, Q, k, want_active=True):

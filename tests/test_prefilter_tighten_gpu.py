@@ -13,20 +13,9 @@ import pytest
 from tests import prefilter_model as pm
 from tests import prefilter_tighten_model as tm
 from tests import value_domain_inputs as vd
+from tests.prefilter_gpu_helpers import BATCHES, MAX_K, N_BIG, N_MID, N_SMALL, _data, _enqueue, _index, _same_bits
 
 pytestmark = pytest.mark.gpu
-
-MAX_K = 128      # CMR_MAX_K
-# n: no sampling level / one level, partial last panel / two levels
-N_SMALL, N_MID, N_BIG = 70, 8197, 140_003
-BATCHES = [(1, 1), (33, 20), (64, MAX_K)]
-
-
-@functools.lru_cache(maxsize=None)
-def _data(family, n, d, seed=0):
-    X, Q = pm.family(family, n, d, 64, seed)
-    X.setflags(write=False); Q.setflags(write=False)
-    return X, Q
 
 
 @functools.lru_cache(maxsize=2)
@@ -59,24 +48,6 @@ def _model_count(family, n, d, dtype, nq, k, idx, ref, seed=0, queries=None):
     return int(keep.sum())
 
 
-def _index(X, d, dtype, id_base=0, capacity_hint=0):
-    from comorag_amd.index import DenseIndex
-    idx = DenseIndex(d, dtype, capacity_hint=capacity_hint)
-    idx.append(X)
-    if id_base:
-        idx.set_id_base(id_base)
-    return idx
-
-
-def _enqueue(idx, Q, k):
-    import torch
-    dev = torch.device("cuda", idx.device)
-    qt = torch.from_numpy(np.array(Q, np.float32)).to(dev)
-    oi = torch.empty((len(Q), k), dtype=torch.int64, device=dev)
-    os_ = torch.empty((len(Q), k), dtype=torch.float32, device=dev)
-    return idx.search_pipelined(qt, k, oi, os_), qt, oi, os_
-
-
 def _pipelined(idx, Q, k, prefilter, tighten=1, cap=16384):
     idx.set_option("prefilter", prefilter)
     idx.set_option("prefilter_tighten", tighten)
@@ -86,10 +57,6 @@ def _pipelined(idx, Q, k, prefilter, tighten=1, cap=16384):
     assert idx.query_status() is False
     assert idx.get_option("prefilter_active") == (1 if prefilter else 0)
     return oi.cpu().numpy(), os_.cpu().numpy()
-
-
-def _same_bits(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
 
 
 def _check(idx, Q, k):
@@ -242,6 +209,56 @@ def test_six_calls_in_flight():
             assert _same_bits((oi.cpu().numpy(), os_.cpu().numpy()), idx.search(np.ascontiguousarray(q), k, with_minmax=False)[:2])
     finally:
         idx.close()
+
+
+# ---- the route switching on and off inside one in-flight sequence.  Six calls of one pass each take the pipeline's three slots (the default)
+# in turn, so calls i and i + 3 share a workspace whichever slot is next.  Both sequences grow the pre-filter's scratch in flight (1 -> 64
+# queries); the first, modes 1 0 1 1 0 1, gives every workspace the same mode twice (1 -> 1, 0 -> 0, 1 -> 1: a route's own hand-over); the
+# second, modes 1 0 1 0 1 1, puts an unfiltered pass behind a pre-filtered one (1 -> 0: the pre-phase has to wait for the re-score that
+# still reads the workspace's query fragments), a pre-filtered pass behind an unfiltered one (0 -> 1) and 1 -> 1.
+SWITCH_CALLS = [(1, 1), (64, 20), (33, 20), (64, MAX_K), (5, 20), (33, 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def _switch_queries():
+    """the six batches: disjoint slices of the 64 queries where nq allows, the first nq otherwise"""
+    _, Q = _data("gauss", N_MID, 128)
+    calls, off = [], 0
+    for nq, k in SWITCH_CALLS:
+        lo = off if off + nq <= 64 else 0
+        off = lo + nq if off + nq <= 64 else off
+        calls.append((np.ascontiguousarray(Q[lo:lo + nq]), k))
+    return calls
+
+
+def _check_switching(modes):
+    d, n = 128, N_MID
+    X, _ = _data("gauss", n, d)
+    calls = _switch_queries()
+    idx = _index(X, d, "bf16")
+    try:
+        refs = [_pipelined(idx, q, k, 0) for q, k in calls]      # one call at a time, each waited for
+        inflight = []
+        for (q, k), mode in zip(calls, modes):
+            idx.set_option("prefilter", mode)
+            inflight.append(_enqueue(idx, q, k))
+        idx.sync(inflight[-1][0])
+        for ref, (_, _, oi, os_) in zip(refs, inflight):
+            assert _same_bits((oi.cpu().numpy(), os_.cpu().numpy()), ref)
+        assert idx.query_status() is False
+        assert idx.get_option("prefilter_active") == 1
+        distinct = len(np.unique(refs[-1][0][refs[-1][0] >= 0]))
+        assert distinct <= idx.get_option("prefilter_candidates") <= n
+    finally:
+        idx.close()
+
+
+def test_route_switches_between_calls_in_flight():
+    _check_switching((1, 0, 1, 1, 0, 1))
+
+
+def test_route_switches_on_one_workspace_in_flight():
+    _check_switching((1, 0, 1, 0, 1, 1))
 
 
 # ---- mode 2: the filter keeps every row and stores no pair
