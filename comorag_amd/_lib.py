@@ -22,6 +22,7 @@ ABI_VERSION = 2        # include/comorag_hip.h: CMR_ABI_VERSION
 CMR_MAX_K_2PASS = 4096
 CMR_MAX_K_EXACT = 64      # cmr_index_search_exact
 CMR_PPR_MAX_BATCH = 16    # cmr_graph_ppr_batch / cmr_index_ppr_batch: queries per power iteration
+CMR_PPR_RANK_TILE = 2048  # keys per workgroup of the ranked calls' radix sort
 DTYPES = {"f32": CMR_F32, "fp32": CMR_F32, "float32": CMR_F32, "bf16": CMR_BF16, "bfloat16": CMR_BF16,
           "f16": CMR_F16, "fp16": CMR_F16, "float16": CMR_F16}
 
@@ -80,6 +81,9 @@ SIGNATURES = {
     "cmr_index_ppr": (_i32, [_p, _p, _p, _p, _p, _i32, _f64, _f64, _f64, _i32, _p, _P(_i32)]),
     "cmr_graph_ppr_batch": (_i32, [_p, _p, _i32, _f64, _f64, _i32, _p, _P(_i32)]),
     "cmr_index_ppr_batch": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _f64, _f64, _f64, _i32, _p, _P(_i32)]),
+    "cmr_index_ppr_ranked": (_i32, [_p, _p, _p, _p, _p, _i32, _f64, _f64, _f64, _i32, _i64, _p, _p, _P(_i32)]),
+    "cmr_index_ppr_ranked_batch": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _f64, _f64, _f64, _i32, _i64, _p, _p, _P(_i32)]),
+    "cmr_graph_ppr_ranked_batch": (_i32, [_p, _p, _i32, _f64, _f64, _i32, _i64, _p, _p, _P(_i32)]),
     "cmr_pack_candidates_dev": (_i32, [_p, _p, _i64, _p, _p]),
     "cmr_merge_keys_dev": (_i32, [_p, _i32, _i32, _i32, _p, _p, _p]),
     "cmr_comm_unique_id": (_i32, [_p]),

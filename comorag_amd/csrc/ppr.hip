@@ -47,6 +47,8 @@ struct PprScratch {
     int *seed_v = nullptr, *seed_q = nullptr;
     double* seed_w = nullptr;
     long long seed_cap = 0, out_cap = 0;
+    void* rank = nullptr;              // the ranking's workspace (rank_bytes), allocated and grown by ranked calls only
+    size_t rank_cap = 0;
     // the power iteration of THIS scratch as an instantiated hipGraph (clean + normalise + `iters` steps: every argument is
     // one of this scratch's pointers or a graph constant), keyed by (damping, iters); replayed with one hipGraphLaunch
     hipGraphExec_t iter_exec = nullptr;
@@ -60,7 +62,7 @@ struct PprScratch {
     void release() {
         if (iter_exec) (void)hipGraphExecDestroy(iter_exec);
         if (own) (void)hipStreamDestroy(own);
-        for (void* p : {(void*)reset, (void*)x, (void*)y, (void*)red, (void*)out, (void*)mm, (void*)seed_v, (void*)seed_q, (void*)seed_w})
+        for (void* p : {(void*)reset, (void*)x, (void*)y, (void*)red, (void*)out, (void*)mm, (void*)seed_v, (void*)seed_q, (void*)seed_w, rank})
             if (p) (void)hipFree(p);
     }
 };
@@ -481,6 +483,128 @@ __global__ __launch_bounds__(PPR_T) void ppr_gather_batch_kernel(const double* _
     }
 }
 
+// ---- ranking: every passage of every query by descending score, ties by ascending row — the reference's
+// np.argsort(doc_scores)[::-1] and doc_scores[sorted_doc_ids.tolist()] (ComoRAG.py:1101-1105) without the [nb, n_rows] doubles going to
+// the host first.  A segmented, stable LSD radix sort over the doubles launch_gather left in PprScratch::out: 64-bit keys, the passage row
+// (uint32) as payload, 8-bit digits, 8 passes of histogram -> scan -> scatter.  blockIdx.y = query: one set of launches serves the batch, and
+// a query's tiles, counters and order are those of its single call.  Payloads start ascending, every pass is stable: equal scores come by
+// ascending row.  No floating-point operation beyond the key's canonicalisation.
+#define PPR_RANK_TILE CMR_PPR_RANK_TILE
+#define PPR_RANK_PASSES 8
+
+// ascending key = descending score: the complement of the order-preserving code of the double.  -0.0 counts as +0.0; NaN (ppr_update on a
+// cleaned reset vector yields none) sorts behind everything, so the order stays total
+__device__ __forceinline__ u64 ppr_rank_key(double v) {
+    u64 u = (u64)__double_as_longlong(v);
+    if (v != v) return ~0ull;
+    if (u == 0x8000000000000000ull) u = 0ull;
+    return ~((u >> 63) ? ~u : (u | 0x8000000000000000ull));
+}
+
+__global__ __launch_bounds__(PPR_T) void ppr_rank_init_kernel(const double* __restrict__ doc, unsigned n, u64* __restrict__ key, unsigned* __restrict__ val) {
+    const size_t i = (size_t)blockIdx.x * PPR_T + threadIdx.x;
+    if (i >= n) return;
+    const size_t at = (size_t)blockIdx.y * n + i;
+    key[at] = ppr_rank_key(doc[at]);
+    val[at] = (unsigned)i;
+}
+
+// hist[query][digit][tile] = keys of the tile with that digit
+__global__ __launch_bounds__(PPR_T) void ppr_rank_hist_kernel(const u64* __restrict__ key, unsigned n, int shift, unsigned ntiles, unsigned* __restrict__ hist) {
+    __shared__ unsigned cnt[256];
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const u64* __restrict__ k = key + (size_t)blockIdx.y * n;
+    const size_t base = (size_t)blockIdx.x * PPR_RANK_TILE;
+    for (unsigned j = threadIdx.x; j < PPR_RANK_TILE; j += PPR_T)
+        if (base + j < n) atomicAdd(&cnt[(unsigned)(k[base + j] >> shift) & 255u], 1u);
+    __syncthreads();
+    hist[((size_t)blockIdx.y * 256 + threadIdx.x) * ntiles + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// exclusive scan of a query's m = 256 * ntiles counters, digit-major: a workgroup per query
+__global__ __launch_bounds__(1024) void ppr_rank_scan_kernel(unsigned* __restrict__ hist_all, unsigned m) {
+    __shared__ unsigned wsum[16];
+    __shared__ unsigned carry_s;
+    unsigned* __restrict__ hist = hist_all + (size_t)blockIdx.x * m;
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) carry_s = 0;
+    __syncthreads();
+    for (unsigned base = 0; base < m; base += 1024 * 8) {
+        unsigned v[8], local = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const unsigned i = base + tid * 8 + j; v[j] = i < m ? hist[i] : 0u; local += v[j]; }
+        unsigned incl = local;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        unsigned wbase = 0;
+        for (unsigned w = 0; w < wave; ++w) wbase += wsum[w];
+        unsigned run = carry_s + wbase + incl - local;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const unsigned i = base + tid * 8 + j; if (i < m) hist[i] = run; run += v[j]; }
+        __syncthreads();
+        if (tid == 1023) carry_s = run;
+        __syncthreads();
+    }
+}
+
+// Stable scatter of one tile: slices of PPR_T keys in order, waves of a slice in order, lanes of a wave by ballot rank.  The lanes that hold a
+// lane's digit are the AND over its eight bits of ballot(bit) or its complement: 8 ballots, whatever the digit.
+__global__ __launch_bounds__(PPR_T) void ppr_rank_scatter_kernel(const u64* __restrict__ key_in, const unsigned* __restrict__ val_in, unsigned n, int shift, unsigned ntiles,
+                                                                 const unsigned* __restrict__ offs, u64* __restrict__ key_out, unsigned* __restrict__ val_out) {
+    __shared__ unsigned run[256];                 // where the tile's next key of a digit goes
+    __shared__ unsigned wcnt[PPR_T / 64][256];    // the current slice's keys per wave and digit
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t seg = (size_t)blockIdx.y * n;
+    run[tid] = offs[((size_t)blockIdx.y * 256 + tid) * ntiles + blockIdx.x];
+#pragma unroll
+    for (int w = 0; w < PPR_T / 64; ++w) wcnt[w][tid] = 0;
+    __syncthreads();
+    const u64 lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    for (unsigned s = 0; s < PPR_RANK_TILE; s += PPR_T) {
+        const size_t first = (size_t)blockIdx.x * PPR_RANK_TILE + s;
+        if (first >= n) break;                    // the whole workgroup: the tile ends here
+        const size_t i = first + tid;
+        const bool ok = i < n;
+        const u64 k = ok ? key_in[seg + i] : 0ull;
+        const unsigned d = (unsigned)(k >> shift) & 255u;
+        u64 peers = __ballot(ok);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const bool on = (d >> bit) & 1u;
+            const u64 b = __ballot(on);
+            peers &= on ? b : ~b;
+        }
+        const unsigned rank = (unsigned)__popcll(peers & lt);
+        if (ok && rank == 0) wcnt[wave][d] = (unsigned)__popcll(peers);
+        __syncthreads();
+        if (ok) {
+            unsigned pos = run[d] + rank;
+            for (unsigned w = 0; w < wave; ++w) pos += wcnt[w][d];
+            key_out[seg + pos] = k;               // pos < n: an exclusive prefix of the query's n keys plus the keys ahead of this one
+            val_out[seg + pos] = val_in[seg + i];
+        }
+        __syncthreads();
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < PPR_T / 64; ++w) { t += wcnt[w][tid]; wcnt[w][tid] = 0; }
+        run[tid] += t;
+        __syncthreads();
+    }
+}
+
+// rank r of query b: the row and the bits of its score, gathered from the unranked result — never recomputed
+__global__ __launch_bounds__(PPR_T) void ppr_rank_finish_kernel(const unsigned* __restrict__ val, const double* __restrict__ doc, unsigned n, unsigned n_out,
+                                                                long long* __restrict__ out_ids, double* __restrict__ out_scores) {
+    const size_t r = (size_t)blockIdx.x * PPR_T + threadIdx.x;
+    if (r >= n_out) return;
+    const unsigned id = val[(size_t)blockIdx.y * n + r];
+    out_ids[(size_t)blockIdx.y * n_out + r] = (long long)id;
+    out_scores[(size_t)blockIdx.y * n_out + r] = doc[(size_t)blockIdx.y * n + id];
+}
+
 // ------------------------------------------------------------------------------------------ host
 static unsigned blocks_for(long long n) { return (unsigned)std::max<long long>(1, (n + PPR_T - 1) / PPR_T); }
 static int ppr_width(int nb) { return nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : nb <= 8 ? 8 : 16; }
@@ -647,6 +771,63 @@ static void launch_scatter(cmr_graph* g, PprScratch* sc, const float* scores, lo
                      hipLaunchKernelGGL(ppr_scatter_batch_kernel<BW>, dim3(blocks_for(n)), dim3(PPR_T), 0, s, scores, n, nb, sc->mm_final(), g->vertex_of_row, pnw, sc->reset))
 }
 
+// ---- the ranking tail (kernels: "ranking" above).  What a ranked call asks for: the first n_out ranks of every query.
+struct PprRankOut { int64_t n_out; int64_t* ids; };
+static_assert(PPR_T == 256, "the ranking's kernels give a thread per 8-bit digit");
+
+// Workspace of nb queries of n rows: two key buffers and two payload buffers (the passes alternate) and the counters —
+// 24 bytes per row and query + 1 KiB per tile and query.  After the last pass the keys are dead: the finish kernel writes the ids over
+// the second key buffer and the scores over the first, and the host copies both from there.
+static size_t rank_tiles(long long n) { return (size_t)((n + PPR_RANK_TILE - 1) / PPR_RANK_TILE); }
+static size_t rank_bytes(long long n, int nb) { return (size_t)nb * ((size_t)n * 24 + rank_tiles(n) * 256 * 4); }
+static int ensure_rank(PprScratch* sc, long long n, int nb) {
+    const size_t need = rank_bytes(n, nb);
+    if (need <= sc->rank_cap) return CMR_OK;
+    if (sc->rank) HIP_TRY(hipFree(sc->rank));
+    sc->rank = nullptr; sc->rank_cap = 0;
+    const hipError_t e = hipMalloc(&sc->rank, need);
+    if (e != hipSuccess) return cmr_fail(e == hipErrorOutOfMemory ? CMR_ERR_OOM : CMR_ERR_HIP, "PPR ranking workspace: %s", hipGetErrorString(e));
+    sc->rank_cap = need;
+    return CMR_OK;
+}
+// sc->out [nb][n] -> the host's ids [nb][n_out] and scores [nb][n_out]: 2 + 3 * PPR_RANK_PASSES launches and two copies on `s`
+static int rank_and_copy(PprScratch* sc, long long n, int nb, const PprRankOut& rk, double* out_scores, hipStream_t s) {
+    const size_t rows = (size_t)nb * n;
+    const unsigned un = (unsigned)n, ntiles = (unsigned)rank_tiles(n);
+    u64 *key0 = (u64*)sc->rank, *key1 = key0 + rows;
+    unsigned *val0 = (unsigned*)(key1 + rows), *val1 = val0 + rows, *hist = val1 + rows;
+    hipLaunchKernelGGL(ppr_rank_init_kernel, dim3(blocks_for(n), nb), dim3(PPR_T), 0, s, sc->out, un, key0, val0);
+    u64 *ki = key0, *ko = key1;
+    unsigned *vi = val0, *vo = val1;
+    for (int pass = 0; pass < PPR_RANK_PASSES; ++pass) {
+        hipLaunchKernelGGL(ppr_rank_hist_kernel, dim3(ntiles, nb), dim3(PPR_T), 0, s, ki, un, 8 * pass, ntiles, hist);
+        hipLaunchKernelGGL(ppr_rank_scan_kernel, dim3(nb), dim3(1024), 0, s, hist, 256u * ntiles);
+        hipLaunchKernelGGL(ppr_rank_scatter_kernel, dim3(ntiles, nb), dim3(PPR_T), 0, s, ki, vi, un, 8 * pass, ntiles, hist, ko, vo);
+        std::swap(ki, ko);
+        std::swap(vi, vo);
+    }
+    long long* ids_dev = (long long*)ko;          // the order is in vi; both key buffers are dead: ko == key1, ki == key0 after 8 swaps
+    double* scores_dev = (double*)ki;
+    hipLaunchKernelGGL(ppr_rank_finish_kernel, dim3(blocks_for(rk.n_out), nb), dim3(PPR_T), 0, s, vi, sc->out, un, (unsigned)rk.n_out, ids_dev, scores_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rk.ids, ids_dev, (size_t)nb * rk.n_out * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_scores, scores_dev, (size_t)nb * rk.n_out * 8, hipMemcpyDeviceToHost, s));
+    return CMR_OK;
+}
+// a ranked call's own argument checks: integers and pointers (`early`), then against the passage map
+static int rank_check_early(const PprRankOut* rk) {
+    if (!rk) return CMR_OK;
+    if (!rk->ids) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (rk->n_out < 1) return cmr_fail(CMR_ERR_INVALID, "n_out must be >= 1 (got %lld)", (long long)rk->n_out);
+    return CMR_OK;
+}
+static int rank_check_rows(const PprRankOut* rk, const cmr_graph* g) {
+    if (!rk) return CMR_OK;
+    if (rk->n_out > g->n_rows) return cmr_fail(CMR_ERR_INVALID, "n_out = %lld exceeds the %lld passage rows", (long long)rk->n_out, g->n_rows);
+    if (g->n_rows >= (1ll << 32)) return cmr_fail(CMR_ERR_UNSUPPORTED, "the ranking's payload is a 32-bit row: %lld rows", g->n_rows);
+    return CMR_OK;
+}
+
 static int ensure_seeds(PprScratch* sc, long long n) {
     if (n <= sc->seed_cap) return CMR_OK;
     for (void* p : {(void*)sc->seed_v, (void*)sc->seed_q, (void*)sc->seed_w})
@@ -675,17 +856,25 @@ static void merge_seeds(const int32_t* v, const double* w, int n, std::vector<in
     }
 }
 
-// cmr_graph_ppr (nb == 1) and cmr_graph_ppr_batch: integers and pointers are judged before the handle is touched, every device call
-// comes after both.  A batch of one IS the single call: width 1, the one-query kernels.
-static int ppr_graph_run(cmr_graph* g, const double* reset, int nb, double damping, double tol, int max_iter, double* out_scores, int32_t* iters) {
+// cmr_graph_ppr (nb == 1), cmr_graph_ppr_batch and, with `rk`, cmr_graph_ppr_ranked_batch: integers and pointers are judged before the
+// handle is touched, every device call comes after both.  A batch of one IS the single call: width 1, the one-query kernels.  Unranked:
+// out_scores [nb][nv], every vertex in the caller's order.  Ranked: the passage rows' scores, gathered as the fused call gathers them, then
+// ranked — rk->ids and out_scores [nb][n_out].
+static int ppr_graph_run(cmr_graph* g, const double* reset, int nb, double damping, double tol, int max_iter, double* out_scores, int32_t* iters,
+                         const PprRankOut* rk = nullptr) {
     if (!g || !reset || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (nb < 1) return cmr_fail(CMR_ERR_INVALID, "nb must be >= 1 (got %d)", nb);
     if (nb > CMR_PPR_MAX_BATCH) return cmr_fail(CMR_ERR_UNSUPPORTED, "nb = %d exceeds CMR_PPR_MAX_BATCH (%d): split the batch", nb, CMR_PPR_MAX_BATCH);
+    int rc = rank_check_early(rk);
+    if (rc) return rc;
+    if (rk && !g->vertex_of_row) return cmr_fail(CMR_ERR_INVALID, "cmr_graph_set_passage_vertices was not called");
+    if ((rc = rank_check_rows(rk, g))) return rc;
     HIP_TRY(hipSetDevice(g->device));
     PprScratch* sc = nullptr;
-    int rc = scratch_acquire(g, ppr_width(nb), 0, &sc);
+    rc = scratch_acquire(g, ppr_width(nb), rk ? (long long)nb * g->n_rows : 0, &sc);
     if (rc) return rc;
     ScratchGuard guard{g, sc};
+    if (rk && (rc = ensure_rank(sc, g->n_rows, nb))) return rc;      // before the first launch: growing it frees and allocates
     if (!sc->own) HIP_TRY(hipStreamCreateWithFlags(&sc->own, hipStreamNonBlocking));
     hipStream_t s = sc->own;                                // concurrent callers do not queue behind each other on the null stream
     const long long nv = g->nv;
@@ -697,6 +886,15 @@ static int ppr_graph_run(cmr_graph* g, const double* reset, int nb, double dampi
         double* res = nullptr;
         int rc_ = ppr_iterate(g, sc, damping, tol, max_iter, s, iters, &res);
         if (rc_) return rc_;
+        if (rk) {
+            // (the map cannot be replaced meanwhile: cmr_graph_set_passage_vertices waits for the scratch's holder)
+            const long long n = g->n_rows;
+            if (rk->n_out > n || (long long)nb * n > sc->out_cap || rank_bytes(n, nb) > sc->rank_cap)
+                return cmr_fail(CMR_ERR_INVALID, "the passage-vertex map changed during the call");
+            launch_gather(sc, res, g->vertex_of_row, n, nb, sc->out, s);
+            HIP_TRY(hipGetLastError());
+            return rank_and_copy(sc, n, nb, *rk, out_scores, s);
+        }
         double* tmp = res == sc->x ? sc->y : sc->x;
         launch_gather(sc, res, g->perm, nv, nb, tmp, s);
         HIP_TRY(hipGetLastError());
@@ -712,10 +910,12 @@ static int ppr_graph_run(cmr_graph* g, const double* reset, int nb, double dampi
 // cmr_index_ppr (nb == 1, seed_offsets = {0, n_seeds}) and cmr_index_ppr_batch: plain integers and pointers first, the handles'
 // contents after them, every device call after both.
 static int ppr_index_run(cmr_index_t* idx, cmr_graph* g, const float* q_f32, int nb, const int32_t* seed_offsets, const int32_t* seed_vertices,
-                         const double* seed_weights, double passage_node_weight, double damping, double tol, int max_iter, double* out_doc_scores, int32_t* iters) {
+                         const double* seed_weights, double passage_node_weight, double damping, double tol, int max_iter, double* out_doc_scores, int32_t* iters,
+                         const PprRankOut* rk = nullptr) {
     if (!idx || !g || !q_f32 || !out_doc_scores || !seed_offsets) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (nb < 1) return cmr_fail(CMR_ERR_INVALID, "nb must be >= 1 (got %d)", nb);
     if (nb > CMR_PPR_MAX_BATCH) return cmr_fail(CMR_ERR_UNSUPPORTED, "nb = %d exceeds CMR_PPR_MAX_BATCH (%d): split the batch", nb, CMR_PPR_MAX_BATCH);
+    if (int rc_rk = rank_check_early(rk)) return rc_rk;
     if (seed_offsets[0] < 0) return cmr_fail(CMR_ERR_INVALID, "seed_offsets[0] is negative");
     for (int b = 0; b < nb; ++b)
         if (seed_offsets[b + 1] < seed_offsets[b]) return cmr_fail(CMR_ERR_INVALID, "seed_offsets is not ascending at query %d", b);
@@ -726,6 +926,7 @@ static int ppr_index_run(cmr_index_t* idx, cmr_graph* g, const float* q_f32, int
         const long long rows = cmr_index_row_count(idx);
         if (rows != g->n_rows) return cmr_fail(CMR_ERR_INVALID, "index has %lld rows, the passage-vertex map %lld", rows, g->n_rows);
     }
+    if (int rc_rk = rank_check_rows(rk, g)) return rc_rk;
     for (int i = seed_offsets[0]; i < n_seeds; ++i)
         if (seed_vertices[i] < 0 || seed_vertices[i] >= g->nv) return cmr_fail(CMR_ERR_INVALID, "seed vertex %d outside the graph", seed_vertices[i]);
     const int bw = ppr_width(nb);
@@ -744,6 +945,7 @@ static int ppr_index_run(cmr_index_t* idx, cmr_graph* g, const float* q_f32, int
     int rc = scratch_acquire(g, bw, (long long)nb * g->n_rows, &sc);
     if (rc) return rc;
     ScratchGuard guard{g, sc};
+    if (rk && (rc = ensure_rank(sc, g->n_rows, nb))) return rc;      // before the first launch: growing it frees and allocates
     float* scores = nullptr;
     long long n = 0;
     void* st = nullptr;
@@ -767,6 +969,11 @@ static int ppr_index_run(cmr_index_t* idx, cmr_graph* g, const float* q_f32, int
         if (rc_) return rc_;
         if (n) launch_gather(sc, res, g->vertex_of_row, n, nb, sc->out, s);
         HIP_TRY(hipGetLastError());
+        if (rk) {       // the ranking tail: out_doc_scores is [nb][n_out]
+            if (rk->n_out > n) return cmr_fail(CMR_ERR_INVALID, "n_out = %lld exceeds the %lld passage rows", (long long)rk->n_out, n);
+            if (rank_bytes(n, nb) > sc->rank_cap) return cmr_fail(CMR_ERR_INVALID, "the passage-vertex map changed during the call");
+            return rank_and_copy(sc, n, nb, *rk, out_doc_scores, s);
+        }
         HIP_TRY(hipMemcpyAsync(out_doc_scores, sc->out, (size_t)nb * n * 8, hipMemcpyDeviceToHost, s));
         return CMR_OK;
     };
@@ -912,28 +1119,39 @@ int32_t cmr_graph_ppr_batch(cmr_graph_t* g, const double* reset, int32_t nb, dou
     return ppr_graph_run(g, reset, nb, damping, tol, max_iter, out_scores, iters);
 }
 
-// ---- combined cmr_index_ppr calls (combine.h): concurrent single calls on one index, one graph and one parameter set run as
-// ONE cmr_index_ppr_batch, whose rows hold the bits of the single calls
+int32_t cmr_graph_ppr_ranked_batch(cmr_graph_t* g, const double* reset, int32_t nb, double damping, double tol, int32_t max_iter, int64_t n_out,
+                                   int64_t* out_ids, double* out_scores, int32_t* iters) {
+    const PprRankOut rk{n_out, out_ids};
+    return ppr_graph_run(g, reset, nb, damping, tol, max_iter, out_scores, iters, &rk);
+}
+
+// ---- combined cmr_index_ppr / cmr_index_ppr_ranked calls (combine.h): concurrent single calls on one index, one graph and one
+// parameter set run as ONE cmr_index_ppr_batch / cmr_index_ppr_ranked_batch, whose rows hold the bits of the single calls
 struct CombinedPpr {
     cmr_index_t* idx; cmr_graph* g; const float* q; const int32_t* sv; const double* sw; int n_seeds;
     double pnw, damping, tol; int max_iter; double* out; int32_t* iters;
+    int64_t n_out; int64_t* out_ids;       // a ranked call: out is [n_out]; unranked: n_out = 0, out is [n_rows]
 };
 
 static void combined_ppr_run(void* ctx, cmr_combine::Request** reqs, int n) {
     const int dim = (int)(intptr_t)ctx;
     const CombinedPpr* a0 = (const CombinedPpr*)reqs[0]->args;
     auto answer = [](cmr_combine::Request* r, int rc) { r->rc = rc; if (rc) r->err = cmr_last_error(); };
+    const bool ranked = a0->n_out > 0;
     if (n == 1) {       // the caller's own call, its own arguments
         const int32_t seed_offsets[2] = {0, a0->n_seeds};
-        answer(reqs[0], ppr_index_run(a0->idx, a0->g, a0->q, 1, seed_offsets, a0->sv, a0->sw, a0->pnw, a0->damping, a0->tol, a0->max_iter, a0->out, a0->iters));
+        const PprRankOut rk{a0->n_out, a0->out_ids};
+        answer(reqs[0], ppr_index_run(a0->idx, a0->g, a0->q, 1, seed_offsets, a0->sv, a0->sw, a0->pnw, a0->damping, a0->tol, a0->max_iter, a0->out, a0->iters,
+                                      ranked ? &rk : nullptr));
         return;
     }
     // the participants' seeds in the batch call's CSR form; the row count the results are scattered by is the one the call agreed
     // with (ppr_index_run fails when index and passage-vertex map disagree — for everybody: they share both)
-    const long long rows = a0->g->n_rows;
+    const long long rows = a0->g->n_rows, per = ranked ? a0->n_out : rows;       // doubles per participant (n_out is part of the key)
     std::vector<float> q((size_t)n * dim);
     std::vector<int32_t> off((size_t)n + 1, 0), sv;
-    std::vector<double> sw, out((size_t)n * std::max<long long>(rows, 1));
+    std::vector<double> sw, out((size_t)n * std::max<long long>(per, 1));
+    std::vector<int64_t> ids(ranked ? (size_t)n * per : 0);
     for (int i = 0; i < n; ++i) {
         const CombinedPpr* a = (const CombinedPpr*)reqs[i]->args;
         memcpy(q.data() + (size_t)i * dim, a->q, (size_t)dim * 4);
@@ -942,19 +1160,23 @@ static void combined_ppr_run(void* ctx, cmr_combine::Request** reqs, int n) {
         off[i + 1] = (int32_t)sv.size();
     }
     int32_t it = 0;
-    int rc = ppr_index_run(a0->idx, a0->g, q.data(), n, off.data(), sv.data(), sw.data(), a0->pnw, a0->damping, a0->tol, a0->max_iter, out.data(), &it);
+    const PprRankOut rk{a0->n_out, ids.data()};
+    int rc = ppr_index_run(a0->idx, a0->g, q.data(), n, off.data(), sv.data(), sw.data(), a0->pnw, a0->damping, a0->tol, a0->max_iter, out.data(), &it,
+                           ranked ? &rk : nullptr);
     if (!rc && a0->g->n_rows != rows) rc = cmr_fail(CMR_ERR_INVALID, "the passage-vertex map changed during the call");
     for (int i = 0; i < n; ++i) {
         const CombinedPpr* a = (const CombinedPpr*)reqs[i]->args;
         answer(reqs[i], rc);
         if (rc) continue;
-        memcpy(a->out, out.data() + (size_t)i * rows, (size_t)rows * 8);
+        memcpy(a->out, out.data() + (size_t)i * per, (size_t)per * 8);
+        if (ranked) memcpy(a->out_ids, ids.data() + (size_t)i * per, (size_t)per * 8);
         if (a->iters) *a->iters = it;
     }
 }
 
-int32_t cmr_index_ppr(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, const int32_t* seed_vertices, const double* seed_weights, int32_t n_seeds,
-                      double passage_node_weight, double damping, double tol, int32_t max_iter, double* out_doc_scores, int32_t* iters) {
+// cmr_index_ppr (rk == nullptr) and cmr_index_ppr_ranked: through the combiner where the index has one, else the single call
+static int index_ppr_single(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, const int32_t* seed_vertices, const double* seed_weights, int32_t n_seeds,
+                            double passage_node_weight, double damping, double tol, int32_t max_iter, double* out_doc_scores, int32_t* iters, const PprRankOut* rk) {
     if (n_seeds < 0) return cmr_fail(CMR_ERR_INVALID, "bad argument");
     int dim = 0, dtype = 0;
     const int W = cmr_index_combine_width(idx, &dim, &dtype);
@@ -962,20 +1184,44 @@ int32_t cmr_index_ppr(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, cons
         // what needs no lock is judged here; a call that would be refused, or whose query is not finite (the batch kernels carry one flag per
         // launch), takes the single call below and gets its error there
         bool joins = g && q_f32 && out_doc_scores && (n_seeds == 0 || (seed_vertices && seed_weights)) && cmr_combine::all_finite(q_f32, (size_t)dim, dtype);
+        // (g->n_rows is read without the graph's mutex, as the row-count check of ppr_index_run reads it: a map replaced meanwhile can only
+        // send a call the wrong way here — ppr_index_run judges it again, with the scratch held)
+        if (rk) joins = joins && rk->ids && rk->n_out >= 1 && rk->n_out <= g->n_rows && g->n_rows < (1ll << 32);
         for (int i = 0; joins && i < n_seeds; ++i) joins = seed_vertices[i] >= 0 && seed_vertices[i] < g->nv;
         if (joins) {
-            CombinedPpr a{idx, g, q_f32, seed_vertices, seed_weights, n_seeds, passage_node_weight, damping, tol, max_iter, out_doc_scores, iters};
+            CombinedPpr a{idx, g, q_f32, seed_vertices, seed_weights, n_seeds, passage_node_weight, damping, tol, max_iter, out_doc_scores, iters,
+                          rk ? rk->n_out : 0, rk ? rk->ids : nullptr};
             cmr_combine::Request r;
             r.args = &a;
             cmr_combine::Key key;
-            key.w[0] = 3; key.w[1] = (uint64_t)(uintptr_t)g; key.w[2] = cmr_combine::Key::bits(passage_node_weight); key.w[3] = cmr_combine::Key::bits(damping);
+            // kind 3: unranked; kind 4 with n_out (< 2^32) above it: ranked calls share a batch only with ranked calls of the same n_out
+            key.w[0] = rk ? (4ull | ((uint64_t)rk->n_out << 8)) : 3ull; key.w[1] = (uint64_t)(uintptr_t)g; key.w[2] = cmr_combine::Key::bits(passage_node_weight); key.w[3] = cmr_combine::Key::bits(damping);
             key.w[4] = cmr_combine::Key::bits(tol); key.w[5] = (uint64_t)(int64_t)max_iter;
             cmr_index_combine_submit(idx, key, &r, W, combined_ppr_run, (void*)(intptr_t)dim);
             return r.rc ? cmr_fail(r.rc, "%s", r.err.c_str()) : CMR_OK;
         }
     }
     const int32_t seed_offsets[2] = {0, n_seeds};
-    return ppr_index_run(idx, g, q_f32, 1, seed_offsets, seed_vertices, seed_weights, passage_node_weight, damping, tol, max_iter, out_doc_scores, iters);
+    return ppr_index_run(idx, g, q_f32, 1, seed_offsets, seed_vertices, seed_weights, passage_node_weight, damping, tol, max_iter, out_doc_scores, iters, rk);
+}
+
+int32_t cmr_index_ppr(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, const int32_t* seed_vertices, const double* seed_weights, int32_t n_seeds,
+                      double passage_node_weight, double damping, double tol, int32_t max_iter, double* out_doc_scores, int32_t* iters) {
+    return index_ppr_single(idx, g, q_f32, seed_vertices, seed_weights, n_seeds, passage_node_weight, damping, tol, max_iter, out_doc_scores, iters, nullptr);
+}
+
+int32_t cmr_index_ppr_ranked(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, const int32_t* seed_vertices, const double* seed_weights, int32_t n_seeds,
+                             double passage_node_weight, double damping, double tol, int32_t max_iter, int64_t n_out, int64_t* out_ids, double* out_scores,
+                             int32_t* iters) {
+    const PprRankOut rk{n_out, out_ids};
+    return index_ppr_single(idx, g, q_f32, seed_vertices, seed_weights, n_seeds, passage_node_weight, damping, tol, max_iter, out_scores, iters, &rk);
+}
+
+int32_t cmr_index_ppr_ranked_batch(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, int32_t nb, const int32_t* seed_offsets, const int32_t* seed_vertices,
+                                   const double* seed_weights, double passage_node_weight, double damping, double tol, int32_t max_iter, int64_t n_out,
+                                   int64_t* out_ids, double* out_scores, int32_t* iters) {
+    const PprRankOut rk{n_out, out_ids};
+    return ppr_index_run(idx, g, q_f32, nb, seed_offsets, seed_vertices, seed_weights, passage_node_weight, damping, tol, max_iter, out_scores, iters, &rk);
 }
 
 int32_t cmr_index_ppr_batch(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, int32_t nb, const int32_t* seed_offsets, const int32_t* seed_vertices,

@@ -12,6 +12,7 @@ scope), exactly the numeric call sites of SURVEY.md §8a:
     run_ppr                     ComoRAG.py:1086-1105         → power iteration on a CSR copy of the graph in HBM (no igraph call)
     graph_search_with_fact_entities  :992-1053               → its passage loop + run_ppr fused on the device (cmr_index_ppr)
     graph_search_with_fact_entities_batch  (new method)      → the same for a list of calls, ONE batched PageRank (cmr_index_ppr_batch)
+    the ranking behind both         ComoRAG.py:1101-1105      → on the device from ppr.DEVICE_RANK_MIN_ROWS passages up (cmr_index_ppr_ranked*)
 Everything else (LLM calls, graph construction, clustering) keeps running the reference's code.
 """
 from __future__ import annotations
@@ -159,15 +160,18 @@ def install(rag, index_dtype: Optional[str] = None, device: int = 0, patch_modul
         q, phrase_weights, used_phrases_with_scores = _graph_search_host(self, g, index, query, link_top_k, query_fact_scores, top_k_facts,
                                                                          top_k_fact_indices, passage_node_weight)
         if hasattr(g, "passage_scores"):
-            doc_scores = g.passage_scores(index, q, phrase_weights, passage_node_weight, 0.5)
-        else:
-            from . import ppr
-            doc_scores = ppr.ppr_passage_scores(index, g, q, phrase_weights, passage_node_weight, 0.5)
-        return _ranked(self, doc_scores, used_phrases_with_scores)
+            return _ranked(self, g.passage_scores(index, q, phrase_weights, passage_node_weight, 0.5), used_phrases_with_scores)
+        from . import ppr
+        return _checked(self, *ppr.ppr_passage_ranking(index, g, q, phrase_weights, passage_node_weight, 0.5), used_phrases_with_scores)
 
     def _ranked(self, doc_scores, used_phrases_with_scores):
         sorted_doc_ids = np.argsort(doc_scores)[::-1]
         sorted_doc_scores = doc_scores[sorted_doc_ids.tolist()]
+        return _checked(self, sorted_doc_ids, sorted_doc_scores, used_phrases_with_scores)
+
+    def _checked(self, sorted_doc_ids, sorted_doc_scores, used_phrases_with_scores):
+        """ComoRAG.py:1101-1105: every passage is ranked, whether numpy's two lines (`_ranked`; ppr.ppr_passage_ranking below
+        ppr.DEVICE_RANK_MIN_ROWS passage rows) or the device (from there up) produced the order."""
         assert len(sorted_doc_ids) == len(self.passage_node_idxs)
         return sorted_doc_ids, sorted_doc_scores, used_phrases_with_scores
 
@@ -204,7 +208,7 @@ def install(rag, index_dtype: Optional[str] = None, device: int = 0, patch_modul
         """`calls`: a list of graph_search_with_fact_entities' argument tuples (query, link_top_k, query_fact_scores, top_k_facts,
         top_k_fact_indices[, passage_node_weight]) — what ComoRAG.try_answer's threads (ComoRAG.py:432-453) each pass.  Returns the list
         of what the single method returns for each, bit for bit: the host part runs per call, the device part is ONE batched
-        scan + PageRank per distinct passage_node_weight (comorag_amd.ppr.ppr_passage_scores_batch).  A graph object that brings its own
+        scan + PageRank per distinct passage_node_weight (comorag_amd.ppr.ppr_passage_ranking_batch).  A graph object that brings its own
         `passage_scores` and nothing batched is served call by call."""
         g, index = self._hip["graph"], self._hip["passage"]
         calls = [tuple(c) for c in calls]
@@ -218,12 +222,12 @@ def install(rag, index_dtype: Optional[str] = None, device: int = 0, patch_modul
             Q = np.stack([np.asarray(host[i][0], dtype=np.float32).reshape(-1) for i in sel])
             pw = [host[i][1] for i in sel]
             if hasattr(g, "passage_scores_batch"):
-                scores = g.passage_scores_batch(index, Q, pw, pnw, 0.5)
+                for i, doc_scores in zip(sel, g.passage_scores_batch(index, Q, pw, pnw, 0.5)):
+                    out[i] = _ranked(self, np.asarray(doc_scores), host[i][2])
             else:
                 from . import ppr
-                scores = ppr.ppr_passage_scores_batch(index, g, Q, pw, pnw, 0.5)
-            for i, doc_scores in zip(sel, scores):
-                out[i] = _ranked(self, np.asarray(doc_scores), host[i][2])
+                for i, (ids, sc) in zip(sel, ppr.ppr_passage_ranking_batch(index, g, Q, pw, pnw, 0.5)):
+                    out[i] = _checked(self, ids, sc, host[i][2])
         return out
 
     fns = [prepare_retrieval_objects, get_query_embeddings, get_fact_scores, dense_passage_retrieval]

@@ -6,6 +6,8 @@ vector and hands that to igraph's prpack PageRank.  Here the graph lives in HBM 
 `ppr_passage_scores` keeps scan -> min-max -> scatter -> power iteration -> gather on the device: only n_passages
 doubles come back.  igraph itself is not needed (it is absent from this image): `DeviceGraph.from_igraph` only reads an
 edge list + weights from anything that offers `vcount() / get_edgelist() / es['weight']`.
+`ppr_passage_ranked(_batch)` / `DeviceGraph.ppr_ranked_batch` also rank the passages on the device (ComoRAG.py:1101-1105; DESIGN §4.9c);
+`run_ppr` and `ppr_passage_ranking(_batch)` switch to them at DEVICE_RANK_MIN_ROWS passage rows (None: never).
 """
 from __future__ import annotations
 
@@ -15,6 +17,21 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib as L
+
+# From this many passage rows up the ranking of the PageRank scores (ComoRAG.py:1101-1105) runs on the device (cmr_*_ppr_ranked*, DESIGN
+# §4.9c); below it the reference's two numpy lines run on the host, unchanged.  The measured crossover of `tools/ppr_batch_bench.py
+# --rank`'s sweep (profiles/ppr_rank.json: the ranked call takes 1.14 of the host path at 4096 rows, 0.86 at 8192, 0.27 at 65536), rounded up
+# to a multiple of 1024 and never below 8192.  None switches it off: run_ppr, ppr_passage_ranking(_batch) and the hooks then keep the host
+# lines at every size.  From the threshold up, rows with equal fp64 scores come by ascending row, where numpy's argsort leaves their order
+# unspecified; scores, and ids wherever scores differ, are the same.
+DEVICE_RANK_MIN_ROWS: Optional[int] = 8192
+
+
+def _n_out(n_out, n_rows: int) -> int:
+    n = int(n_rows) if n_out is None else int(n_out)
+    if not 1 <= n <= int(n_rows):
+        raise ValueError(f"n_out must be in [1, {int(n_rows)}] (got {n})")
+    return n
 
 
 class DeviceGraph:
@@ -77,6 +94,26 @@ class DeviceGraph:
             self.last_iters = it.value
         return out
 
+    def ppr_ranked_batch(self, resets, n_out: Optional[int] = None, damping: float = 0.5, tol: float = 1e-12,
+                         max_iter: int = 200) -> Tuple[np.ndarray, np.ndarray]:
+        """`ppr_batch`, then pagerank[passage vertices] ranked on the device (ComoRAG.py:1101-1105): (ids [B, n_out] int64 passage rows,
+        scores [B, n_out] float64), score descending, equal scores by ascending row; n_out = None: every row.  ids[b] equals
+        np.argsort(-doc, kind="stable") and scores[b] equals doc[ids[b]] bit for bit, doc = ppr(resets[b])[passage vertices].  Needs
+        `set_passage_vertices`; B above CMR_PPR_MAX_BATCH goes in chunks."""
+        r = np.ascontiguousarray(resets, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != self.n_vertices:
+            raise ValueError(f"resets must be [B, {self.n_vertices}]")
+        n = _n_out(n_out, self.n_rows)
+        ids = np.empty((r.shape[0], n), dtype=np.int64)
+        sc = np.empty((r.shape[0], n), dtype=np.float64)
+        it = C.c_int32(0)
+        for b0 in range(0, r.shape[0], L.CMR_PPR_MAX_BATCH):
+            nb = min(L.CMR_PPR_MAX_BATCH, r.shape[0] - b0)
+            L.check(L.lib().cmr_graph_ppr_ranked_batch(self._h, r[b0:b0 + nb].ctypes.data_as(C.c_void_p), nb, float(damping), float(tol), int(max_iter), n,
+                                                       ids[b0:b0 + nb].ctypes.data_as(C.c_void_p), sc[b0:b0 + nb].ctypes.data_as(C.c_void_p), C.byref(it)))
+            self.last_iters = it.value
+        return ids, sc
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             L.lib().cmr_graph_destroy(self._h)
@@ -93,6 +130,9 @@ def run_ppr(graph: DeviceGraph, reset_prob, passage_node_idxs, damping: Optional
     """ComoRAG.run_ppr (ComoRAG.py:1086-1105) with the PageRank itself on the device; the last three lines are the reference's."""
     if damping is None:
         damping = 0.5
+    if _device_rank(graph, len(passage_node_idxs)) and np.array_equal(getattr(graph, "passage_vertices", None), np.asarray(passage_node_idxs)):
+        ids, sc = graph.ppr_ranked_batch(np.asarray(reset_prob, dtype=np.float64)[None, :], damping=damping)
+        return ids[0], sc[0]
     pagerank_scores = graph.ppr(np.asarray(reset_prob, dtype=np.float64), damping=damping)
     doc_scores = np.array([pagerank_scores[idx] for idx in passage_node_idxs])
     sorted_doc_ids = np.argsort(doc_scores)[::-1]
@@ -109,6 +149,12 @@ def _seed_arrays(phrase_weights) -> Tuple[np.ndarray, np.ndarray]:
     pw = np.asarray(phrase_weights, dtype=np.float64)
     sv = np.flatnonzero(pw != 0).astype(np.int32)
     return sv, np.ascontiguousarray(pw[sv])
+
+
+def _device_rank(graph, n_rows: int) -> bool:
+    """Rank on the device?  From DEVICE_RANK_MIN_ROWS passage rows up, for a graph object that can (the numpy stand-ins and custom graph
+    objects without `ppr_ranked_batch` always take the host lines, as `_graph_ppr_batch` falls back)."""
+    return DEVICE_RANK_MIN_ROWS is not None and n_rows >= DEVICE_RANK_MIN_ROWS and n_rows > 0 and hasattr(graph, "ppr_ranked_batch")
 
 
 def _host_branch(index) -> bool:
@@ -152,7 +198,10 @@ def ppr_passage_scores(index, graph: DeviceGraph, query_embedding, phrase_weight
 
 def ppr_passage_ranking(index, graph: DeviceGraph, query_embedding, phrase_weights=None, passage_node_weight: float = 0.05,
                         damping: float = 0.5) -> Tuple[np.ndarray, np.ndarray]:
-    """(sorted_doc_ids, sorted_doc_scores) exactly as ComoRAG.run_ppr returns them (ComoRAG.py:1101-1105)."""
+    """(sorted_doc_ids, sorted_doc_scores) exactly as ComoRAG.run_ppr returns them (ComoRAG.py:1101-1105); from DEVICE_RANK_MIN_ROWS
+    passage rows up the device ranks (`ppr_passage_ranked`: equal scores by ascending row)."""
+    if _device_rank(graph, getattr(graph, "n_rows", 0)):
+        return ppr_passage_ranked(index, graph, query_embedding, phrase_weights, passage_node_weight, damping)
     doc_scores = ppr_passage_scores(index, graph, query_embedding, phrase_weights, passage_node_weight, damping)
     sorted_doc_ids = np.argsort(doc_scores)[::-1]
     return sorted_doc_ids, doc_scores[sorted_doc_ids.tolist()]
@@ -203,9 +252,73 @@ def _graph_ppr_batch(graph, resets: np.ndarray, damping: float, tol: float, max_
 
 def ppr_passage_ranking_batch(index, graph, query_embeddings, phrase_weights: Optional[Sequence] = None, passage_node_weight: float = 0.05,
                               damping: float = 0.5) -> list:
-    """[(sorted_doc_ids, sorted_doc_scores)] per query, each exactly as ComoRAG.run_ppr returns them (ComoRAG.py:1101-1105)."""
+    """[(sorted_doc_ids, sorted_doc_scores)] per query, each exactly as ComoRAG.run_ppr returns them (ComoRAG.py:1101-1105); from
+    DEVICE_RANK_MIN_ROWS passage rows up the device ranks (`ppr_passage_ranked_batch`)."""
+    if _device_rank(graph, getattr(graph, "n_rows", 0)):
+        ids, sc = ppr_passage_ranked_batch(index, graph, query_embeddings, phrase_weights, passage_node_weight, damping)
+        return [(ids[b], sc[b]) for b in range(len(ids))]
     out = []
     for doc_scores in ppr_passage_scores_batch(index, graph, query_embeddings, phrase_weights, passage_node_weight, damping):
         sorted_doc_ids = np.argsort(doc_scores)[::-1]
         out.append((sorted_doc_ids, doc_scores[sorted_doc_ids.tolist()]))
     return out
+
+
+def ppr_passage_ranked_batch(index, graph, query_embeddings, phrase_weights: Optional[Sequence] = None, passage_node_weight: float = 0.05,
+                             damping: float = 0.5, n_out: Optional[int] = None, tol: float = 1e-12, max_iter: int = 200) -> Tuple[np.ndarray, np.ndarray]:
+    """`ppr_passage_scores_batch` with the ranking on the device (ComoRAG.py:1101-1105): (ids [B, n_out] int64 passage rows, scores
+    [B, n_out] float64) by descending score, equal scores by ascending row; n_out = None: all n_rows.  ids[b] = np.argsort(-doc, kind="stable")
+    [:n_out] and scores[b] = doc[ids[b]] bit for bit, doc = ppr_passage_scores(Q[b], phrase_weights[b]).  A row-sharded index builds the reset
+    vectors on the host as `ppr_passage_scores_batch` does and ranks through `graph.ppr_ranked_batch`."""
+    Q = np.ascontiguousarray(np.asarray(query_embeddings, dtype=np.float32))
+    if Q.ndim != 2:
+        raise ValueError("query_embeddings must be [B, d]")
+    B = Q.shape[0]
+    pws = [None] * B if phrase_weights is None else list(phrase_weights)
+    if len(pws) != B:
+        raise ValueError(f"{len(pws)} phrase-weight entries for {B} queries")
+    n = _n_out(n_out, graph.n_rows)
+    if B == 0:
+        return np.empty((0, n), np.int64), np.empty((0, n), np.float64)
+    if _host_branch(index):
+        S = index.scores(Q)
+        resets = np.zeros((B, graph.n_vertices), dtype=np.float64)
+        for b in range(B):
+            resets[b] = _host_reset(graph, S[b], pws[b], passage_node_weight)
+        return graph.ppr_ranked_batch(resets, n_out=n, damping=damping, tol=tol, max_iter=max_iter)
+    ids = np.empty((B, n), dtype=np.int64)
+    sc = np.empty((B, n), dtype=np.float64)
+    it = C.c_int32(0)
+    for b0 in range(0, B, L.CMR_PPR_MAX_BATCH):
+        nb = min(L.CMR_PPR_MAX_BATCH, B - b0)
+        seeds = [_seed_arrays(pw) for pw in pws[b0:b0 + nb]]
+        off = np.zeros(nb + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(v) for v, _ in seeds])
+        sv = np.ascontiguousarray(np.concatenate([v for v, _ in seeds]), dtype=np.int32)
+        sw = np.ascontiguousarray(np.concatenate([w for _, w in seeds]), dtype=np.float64)
+        L.check(L.lib().cmr_index_ppr_ranked_batch(index._h, graph._h, Q[b0:b0 + nb].ctypes.data_as(C.c_void_p), nb, off.ctypes.data_as(C.c_void_p),
+                                                   sv.ctypes.data_as(C.c_void_p), sw.ctypes.data_as(C.c_void_p), float(passage_node_weight), float(damping),
+                                                   float(tol), int(max_iter), n, ids[b0:b0 + nb].ctypes.data_as(C.c_void_p),
+                                                   sc[b0:b0 + nb].ctypes.data_as(C.c_void_p), C.byref(it)))
+        graph.last_iters = it.value
+    return ids, sc
+
+
+def ppr_passage_ranked(index, graph, query_embedding, phrase_weights=None, passage_node_weight: float = 0.05, damping: float = 0.5,
+                       n_out: Optional[int] = None, tol: float = 1e-12, max_iter: int = 200) -> Tuple[np.ndarray, np.ndarray]:
+    """`ppr_passage_ranked_batch` for one query: (ids [n_out] int64, scores [n_out] float64).  On a device index this is
+    cmr_index_ppr_ranked, which joins the index's combine queue as cmr_index_ppr does."""
+    q = np.ascontiguousarray(np.asarray(query_embedding, dtype=np.float32).reshape(-1))
+    if _host_branch(index):
+        ids, sc = ppr_passage_ranked_batch(index, graph, q[None, :], [phrase_weights], passage_node_weight, damping, n_out, tol, max_iter)
+        return ids[0], sc[0]
+    n = _n_out(n_out, graph.n_rows)
+    sv, sw = _seed_arrays(phrase_weights)
+    ids = np.empty(n, dtype=np.int64)
+    sc = np.empty(n, dtype=np.float64)
+    it = C.c_int32(0)
+    L.check(L.lib().cmr_index_ppr_ranked(index._h, graph._h, q.ctypes.data_as(C.c_void_p), sv.ctypes.data_as(C.c_void_p), sw.ctypes.data_as(C.c_void_p),
+                                         len(sv), float(passage_node_weight), float(damping), float(tol), int(max_iter), n,
+                                         ids.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), C.byref(it)))
+    graph.last_iters = it.value
+    return ids, sc

@@ -195,7 +195,8 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  * calls that several threads issue on this index at the same time share ONE batched call of up to W queries and each caller gets the bits of
  * its own call —
  *   cmr_index_search  (same k, k <= CMR_MAX_K, nq < W),  cmr_index_scores  (nq < W),
- *   cmr_index_ppr     (same graph, passage_node_weight, damping, tol, max_iter; runs as cmr_index_ppr_batch).
+ *   cmr_index_ppr     (same graph, passage_node_weight, damping, tol, max_iter; runs as cmr_index_ppr_batch),
+ *   cmr_index_ppr_ranked  (the same and the same n_out; runs as cmr_index_ppr_ranked_batch).
  * "combine_wait_us" (default 0): the gather window — the first caller waits until W queries have joined or the window has passed; at 0
  * batches form only from calls that arrive while an earlier batch is on the device, and a caller alone runs its unchanged single call.
  * A call with a NaN / Inf query, or with arguments the call refuses, never joins a batch: it gets its own error.
@@ -315,7 +316,8 @@ int32_t cmr_merge_topk_dev(int32_t device_id, const int64_t* ids_dev, const floa
  *                              scattered into the reset vector on the device, + the (few) phrase seeds (duplicate seed
  *                              vertices are SUMMED; ComoRAG's own loop assigns, last wins, :1019-1021 — resolve before the call) -> PPR ->
  *                              out_doc_scores [n_rows] = pagerank[vertex of row]; 8 * n_rows bytes come back instead of
- *                              the 12 * N of the full ranking.  The caller sorts (np.argsort(doc_scores)[::-1], :1102).
+ *                              the 12 * N of the full ranking.  The caller sorts (np.argsort(doc_scores)[::-1], :1102) — or calls
+ *                              cmr_index_ppr_ranked below, which sorts on the device.
  * Power iteration in fp64, ceil(log(tol/2)/log(damping)) steps (<= max_iter; *iters = steps taken), fixed summation
  * order.  prpack solves the same linear system directly to ~1e-10.                                                     */
 typedef struct cmr_graph cmr_graph_t;
@@ -344,6 +346,34 @@ int32_t cmr_graph_ppr_batch(cmr_graph_t* g, const double* reset, int32_t nb, dou
 int32_t cmr_index_ppr_batch(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, int32_t nb, const int32_t* seed_offsets,
                             const int32_t* seed_vertices, const double* seed_weights, double passage_node_weight,
                             double damping, double tol, int32_t max_iter, double* out_doc_scores, int32_t* iters);
+/* The same calls with the ranking done on the device: every passage row by descending PageRank score — the reference's
+ * `sorted_doc_ids = np.argsort(doc_scores)[::-1]` and `sorted_doc_scores = doc_scores[sorted_doc_ids.tolist()]` (ComoRAG.py:1101-1105),
+ * which must cover every passage (`len(sorted_doc_ids) == len(passage_node_idxs)`).  A segmented stable radix sort of the fp64 scores
+ *  runs behind the power iteration on the call's stream; the [nb, n_rows] doubles never reach the host unsorted.
+ *   out_ids    [nb, n_out] int64 passage ROWS — positions in the unranked call's out_doc_scores, what np.argsort(doc_scores) indexes;
+ *              neither cmr_index_set_id_base nor the id block table is applied.
+ *   out_scores [nb, n_out] double, out_scores[b, r] = doc_scores[b, out_ids[b, r]] bit for bit (gathered, not recomputed).
+ *   1 <= n_out <= n_rows; n_out = n_rows is the reference's full ranking, a smaller n_out shortens only the last kernel and the copy.
+ * Order: score descending (-0.0 = +0.0; a NaN, which the iteration cannot produce, last), equal scores by ascending row — where numpy's
+ * argsort leaves the order of equal scores unspecified.  Row b of a batch equals the single call bit for bit.
+ *   cmr_index_ppr_ranked        cmr_index_ppr + ranking (ComoRAG.py:1034-1044, :1086-1105 with :1101-1105 on the device); combined like
+ *                               cmr_index_ppr where the index's "combine" option is set (same n_out as well).
+ *   cmr_index_ppr_ranked_batch  cmr_index_ppr_batch + ranking (:1101-1105 for each of the nb queries, one set of launches).
+ *   cmr_graph_ppr_ranked_batch  cmr_graph_ppr_batch, then pagerank[vertex of row] ranked (:1101-1105): needs cmr_graph_set_passage_vertices;
+ *                               nb = 1 is the single call.
+ * Arguments are checked before any device call: NULL, n_out out of range, no passage map -> CMR_ERR_INVALID; nb > CMR_PPR_MAX_BATCH or
+ * n_rows >= 2^32 -> CMR_ERR_UNSUPPORTED.                                                                                              
+ * CMR_PPR_RANK_TILE: keys per workgroup of the sort (sizes around it are where its paths change).                                    */
+#define CMR_PPR_RANK_TILE 2048
+int32_t cmr_index_ppr_ranked(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, const int32_t* seed_vertices,
+                             const double* seed_weights, int32_t n_seeds, double passage_node_weight, double damping, double tol,
+                             int32_t max_iter, int64_t n_out, int64_t* out_ids, double* out_scores, int32_t* iters);
+int32_t cmr_index_ppr_ranked_batch(cmr_index_t* idx, cmr_graph_t* g, const float* q_f32, int32_t nb, const int32_t* seed_offsets,
+                                   const int32_t* seed_vertices, const double* seed_weights, double passage_node_weight,
+                                   double damping, double tol, int32_t max_iter, int64_t n_out, int64_t* out_ids,
+                                   double* out_scores, int32_t* iters);
+int32_t cmr_graph_ppr_ranked_batch(cmr_graph_t* g, const double* reset, int32_t nb, double damping, double tol, int32_t max_iter,
+                                   int64_t n_out, int64_t* out_ids, double* out_scores, int32_t* iters);
 
 /* ---- row-shard exchange ------------------------------------------------------------------
  * One process per GPU, each with a row shard (cmr_index_set_id_base makes its searches return global ids).  Per query
