@@ -4,10 +4,13 @@
 //                     fp32 scores and accumulators, keys beyond the sequence's length masked (right-padded mini-batches).
 //                     Replaces the scaled-dot-product-attention call inside transformers' BertSelfAttention, i.e. part of
 //                     `self.embedding_model(**inputs)` at embedding_model/BGEEmbedding.py:119.
+//   attn_fwd_f32_kernel   the same for fp32 tensors, fp32 end to end, both products on the exact f32-input MFMA (comment at the kernel).
 //   add_ln_kernel     LayerNorm(y + bias + residual) * gamma + beta, one wave per token: BertSelfOutput / BertOutput minus
 //                     their GEMM (dense bias add, residual add and LayerNorm are three kernels and five passes over the
 //                     activations in PyTorch; here one read of y and the residual, one write).
 //   embed_ln_kernel   BertEmbeddings: the word / position / token-type gathers, their sum and the LayerNorm in one pass.
+// The LayerNorm and embedding kernels are templates over the element type: bf16, fp16 and — written unrounded, 16-byte lane vectors of
+// four floats — fp32 (EncVec below).
 //
 // Attention layout.  Q, K, V are column slices of ONE packed projection output qkv[b*L, 3*hidden] (the host side multiplies by
 // the concatenated query/key/value weights once): head h reads columns h*64 (Q), hidden + h*64 (K), 2*hidden + h*64 (V).
@@ -48,6 +51,56 @@ template <int DT> __device__ __forceinline__ void enc_unpack2(unsigned u, float&
         enc_f16x2 t = __builtin_bit_cast(enc_f16x2, u);
         a = (float)t[0];
         b = (float)t[1];
+    }
+}
+
+// One lane-vector of four / eight elements of a row: 8 / 16 bytes of a 16-bit tensor; four floats (16 bytes) / two such vectors of an
+// fp32 one.  enc_get* widen to fp32 (exact), enc_put* round once (16-bit) or store the floats as they are (fp32).
+struct enc_f32x8 { float4 lo, hi; };
+template <int DT> struct EncVec { typedef uint2 V4; typedef uint4 V8; };
+template <> struct EncVec<CMR_DT_F32> { typedef float4 V4; typedef enc_f32x8 V8; };
+template <int DT> __device__ __forceinline__ void enc_get4(float (&t)[4], typename EncVec<DT>::V4 a) {
+    if constexpr (DT == CMR_DT_F32) {
+        t[0] = a.x; t[1] = a.y; t[2] = a.z; t[3] = a.w;
+    } else {
+        enc_unpack2<DT>(a.x, t[0], t[1]);
+        enc_unpack2<DT>(a.y, t[2], t[3]);
+    }
+}
+template <int DT> __device__ __forceinline__ void enc_get8(float (&t)[8], typename EncVec<DT>::V8 a) {
+    if constexpr (DT == CMR_DT_F32) {
+        t[0] = a.lo.x; t[1] = a.lo.y; t[2] = a.lo.z; t[3] = a.lo.w;
+        t[4] = a.hi.x; t[5] = a.hi.y; t[6] = a.hi.z; t[7] = a.hi.w;
+    } else {
+        enc_unpack2<DT>(a.x, t[0], t[1]);
+        enc_unpack2<DT>(a.y, t[2], t[3]);
+        enc_unpack2<DT>(a.z, t[4], t[5]);
+        enc_unpack2<DT>(a.w, t[6], t[7]);
+    }
+}
+template <int DT> __device__ __forceinline__ typename EncVec<DT>::V4 enc_put4(float a, float b, float c, float d) {
+    if constexpr (DT == CMR_DT_F32) {
+        return make_float4(a, b, c, d);
+    } else {
+        uint2 w;
+        w.x = enc_pack2<DT>(a, b);
+        w.y = enc_pack2<DT>(c, d);
+        return w;
+    }
+}
+template <int DT> __device__ __forceinline__ typename EncVec<DT>::V8 enc_put8(const float (&t)[8]) {
+    if constexpr (DT == CMR_DT_F32) {
+        enc_f32x8 w;
+        w.lo = make_float4(t[0], t[1], t[2], t[3]);
+        w.hi = make_float4(t[4], t[5], t[6], t[7]);
+        return w;
+    } else {
+        uint4 w;
+        w.x = enc_pack2<DT>(t[0], t[1]);
+        w.y = enc_pack2<DT>(t[2], t[3]);
+        w.z = enc_pack2<DT>(t[4], t[5]);
+        w.w = enc_pack2<DT>(t[6], t[7]);
+        return w;
     }
 }
 
@@ -378,6 +431,185 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
     }
 }
 
+// The same attention for fp32 tensors, fp32 end to end: both products run on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32: every
+// result a k-ordered fmaf chain), nothing is rounded to 16 bits.  Same orientation, S^T = K Q^T, so the statistics code is the 16-bit
+// kernel's (the C/D lane map does not depend on the input type).  The operands of this MFMA are ONE float per lane, k = lane >> 5:
+//   * QK^T: the order of d inside the sum is free as long as K and Q agree.  k-step (j, e), j = 0..7, e = 0..3, takes d = 8j + 4g + e
+//     of lane half g, so a lane reads K from LDS — and its Q row from global memory, once — as 16-byte vectors [8j + 4g, + 4).
+//     K rows are 68 floats apart in LDS (272 B: sixteen consecutive rows of a ds_read_b128 start in sixteen different 16-byte slots).
+//   * PV, O^T = V^T P^T: register r of a score tile holds key (r & 3) + 8 (r >> 2) in lane half 0 and that key + 4 in lane half 1
+//     (cmr_acc_row), which IS the B operand of a k-step over that key pair — no conversion, no lane movement.  The A operand of lane
+//     (c, g) is V[key + 4g][32 dt + c]: 32 consecutive floats per lane half; V rows are 72 floats apart (4 rows = 288 floats = 32
+//     banks mod 64: the two halves of a ds_read_b32 use disjoint banks).
+// 128 MFMAs of 64 cycles per 64-key chunk and wave against ~140 VALU instructions: the matrix pipe is the long leg here (the 16-bit
+// kernel's is the softmax), so K / V chunks are SINGLE-buffered in LDS (35 KiB per workgroup, the next chunk's global loads in flight in
+// registers while this one is multiplied, two barriers per chunk) and one workgroup shape (4 waves, 128 query rows) serves every l.
+// The exponent is (s - max) * sc, not fma(s, sc, -max * sc): the difference is rounded where it is small, so the weights of the keys
+// that matter carry no rounding error of the (large) maximum — 32 more VALU instructions per chunk next to 8192 MFMA cycles.
+#define ATT32_KSTR 68
+#define ATT32_VSTR 72
+__global__ __launch_bounds__(256, 2) void attn_fwd_f32_kernel(const float* __restrict__ qkv, const int* __restrict__ lens, int L, int hidden, int n_heads,
+                                                              int n_qblocks, int total, float sc /* log2(e) / sqrt(64) */, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float k_lds[ATT_CHUNK * ATT32_KSTR];
+    __shared__ __attribute__((aligned(16))) float v_lds[ATT_CHUNK * ATT32_VSTR];
+    // workgroup id -> (sequence, head, query block): as attn_fwd_kernel
+    const int xcd = (int)(blockIdx.x & 7), j0 = (int)(blockIdx.x >> 3);
+    const int pair = (j0 / n_qblocks) * 8 + xcd;
+    if (pair >= total / n_qblocks) return;
+    const int qb = j0 % n_qblocks, head = pair % n_heads, seq = total / (n_qblocks * n_heads) - 1 - pair / n_heads;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
+    const int q0 = qb * ATT_QBLOCK;
+    int len = lens[seq];
+    len = len < L ? len : L;
+    const size_t rs = (size_t)3 * hidden;
+    const float* qbase = qkv + (size_t)seq * L * rs + (size_t)head * 64;
+    const float* kbase = qbase + hidden;
+    const float* vbase = qbase + 2 * (size_t)hidden;
+    float* obase = out + (size_t)seq * L * hidden + (size_t)head * 64;
+
+    if (q0 >= len) {                                   // a block of padding rows only: zeros
+        const int row = q0 + (tid >> 1);
+        if (row < L) {
+            float4* dst = reinterpret_cast<float4*>(obase + (size_t)row * hidden + (tid & 1) * 32);
+            const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dst[i] = z;
+        }
+        return;
+    }
+
+    // the wave's 32 query rows as B operands: lane (c, g) holds d = 8j + 4g + [0,4) of row q0 + 32 wave + c in qf[j]
+    const int qrow = q0 + wave * 32 + c;
+    float4 qf[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        qf[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (qrow < L) qf[j] = *reinterpret_cast<const float4*>(qbase + (size_t)qrow * rs + 8 * j + 4 * g);
+    }
+
+    // chunk staging: thread -> 16-byte segment sseg of rows srow + 16 h, h = 0..3, of K and of V; rows behind the sequence's end are zeros
+    const int srow = tid >> 4, sseg = tid & 15;
+    float4 kreg[4], vreg[4];
+    auto load_chunk = [&](int ch) {
+        const int k0 = ch * ATT_CHUNK;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int key = k0 + srow + 16 * h;
+            kreg[h] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            vreg[h] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (key < len) {
+                kreg[h] = *reinterpret_cast<const float4*>(kbase + (size_t)key * rs + sseg * 4);
+                vreg[h] = *reinterpret_cast<const float4*>(vbase + (size_t)key * rs + sseg * 4);
+            }
+        }
+    };
+    auto store_chunk = [&]() {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            *reinterpret_cast<float4*>(&k_lds[(srow + 16 * h) * ATT32_KSTR + sseg * 4]) = kreg[h];
+            *reinterpret_cast<float4*>(&v_lds[(srow + 16 * h) * ATT32_VSTR + sseg * 4]) = vreg[h];
+        }
+    };
+
+    f32x16 o[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o[0][r] = 0.0f; o[1][r] = 0.0f; }
+    float m = ATT_NEG, lsum = 0.0f;
+    const int nch = (len + ATT_CHUNK - 1) / ATT_CHUNK;
+    load_chunk(0);
+    for (int ch = 0; ch < nch; ++ch) {
+        store_chunk();
+        __syncthreads();
+        if (ch + 1 < nch) load_chunk(ch + 1);
+        // S^T tiles: keys t*32 + [0,32) of the chunk x the wave's 32 queries
+        f32x16 s[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[t][r] = 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const float4 kf = *reinterpret_cast<const float4*>(&k_lds[(t * 32 + c) * ATT32_KSTR + 8 * j + 4 * g]);
+                s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[j].x, s[t], 0, 0, 0);
+                s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[j].y, s[t], 0, 0, 0);
+                s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[j].z, s[t], 0, 0, 0);
+                s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[j].w, s[t], 0, 0, 0);
+            }
+        }
+        const int k0 = ch * ATT_CHUNK;
+        if (k0 + ATT_CHUNK > len) {                    // the chunk holding the end of the sequence (wave-uniform)
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (k0 + t * 32 + cmr_acc_row(r, lane) >= len) s[t][r] = ATT_NEG;
+        }
+        float cm = ATT_NEG;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) cm = fmaxf(cm, s[t][r]);
+        cm = fmaxf(cm, __shfl_xor(cm, 32));
+        const float mn = fmaxf(m, cm);
+        const float alpha = __builtin_amdgcn_exp2f((m - mn) * sc);
+        typedef float att_f2 __attribute__((ext_vector_type(2)));
+        att_f2 ps2 = {0.0f, 0.0f};
+        const att_f2 sc2 = {sc, sc}, mn2 = {mn, mn};
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                att_f2 x = {s[t][r], s[t][r + 1]};
+                x = (x - mn2) * sc2;
+                x[0] = __builtin_amdgcn_exp2f(x[0]);
+                x[1] = __builtin_amdgcn_exp2f(x[1]);
+                s[t][r] = x[0];
+                s[t][r + 1] = x[1];
+                ps2 += x;
+            }
+        lsum = fmaf(lsum, alpha, ps2[0] + ps2[1]);
+        m = mn;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
+        // O^T += V^T P^T: register r of tile t is the B operand of the k-step over keys {row(r), row(r) + 4} of the tile
+        const float* vp = &v_lds[4 * g * ATT32_VSTR + c];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int kr = t * 32 + (r & 3) + 8 * (r >> 2);
+                o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[kr * ATT32_VSTR], s[t][r], o[0], 0, 0, 0);
+                o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[kr * ATT32_VSTR + 32], s[t][r], o[1], 0, 0, 0);
+            }
+        __syncthreads();                               // everybody has read this chunk: the next one may overwrite it
+    }
+    const float inv = 1.0f / (lsum + __shfl_xor(lsum, 32));
+    if (qrow < L) {
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)             // registers 4*rr .. 4*rr + 3 = d columns dt*32 + 8*rr + 4*g + [0,4)
+                *reinterpret_cast<float4*>(obase + (size_t)qrow * hidden + dt * 32 + 8 * rr + 4 * g) =
+                    make_float4(o[dt][4 * rr + 0] * inv, o[dt][4 * rr + 1] * inv, o[dt][4 * rr + 2] * inv, o[dt][4 * rr + 3] * inv);
+    }
+}
+
+static hipError_t launch_attention_f32(const void* qkv, const int* lens, int b, int L, int n_heads, void* out, hipStream_t s) {
+    const int hidden = n_heads * 64;
+    const int n_qblocks = (L + ATT_QBLOCK - 1) / ATT_QBLOCK;
+    const long long total = (long long)n_qblocks * n_heads * b;
+    if (total > (1LL << 28)) return hipErrorInvalidValue;
+    const long long pairs = (long long)n_heads * b;
+    const int per = (int)((pairs + 7) / 8) * n_qblocks;
+    const float sc = 1.4426950408889634f * 0.125f;
+    hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3((unsigned)(per * 8)), dim3(256), 0, s, reinterpret_cast<const float*>(qkv), lens, L, hidden, n_heads, n_qblocks,
+                       (int)total, sc, reinterpret_cast<float*>(out));
+    return hipGetLastError();
+}
+
 #ifndef ATT_WAVES_MODE
 #define ATT_WAVES_MODE 0      // 0: eight waves per workgroup for mini-batches of >= 256 (padded) tokens, four below; 4 / 8: always
 #endif
@@ -397,6 +629,7 @@ static hipError_t launch_attention(const void* qkv, const int* lens, int b, int 
 }
 
 hipError_t cmr_launch_attention(const void* qkv, int dtype, const int* lens, int b, int L, int n_heads, void* out, hipStream_t s) {
+    if (dtype == CMR_DT_F32) return launch_attention_f32(qkv, lens, b, L, n_heads, out, s);
     const bool eight = ATT_VTR && (ATT_WAVES_MODE == 8 || (ATT_WAVES_MODE == 0 && L >= 256));
     if (dtype == CMR_DT_BF16) return eight ? launch_attention<CMR_DT_BF16, (ATT_VTR ? 8 : 4)>(qkv, lens, b, L, n_heads, out, s) : launch_attention<CMR_DT_BF16, 4>(qkv, lens, b, L, n_heads, out, s);
     return eight ? launch_attention<CMR_DT_F16, (ATT_VTR ? 8 : 4)>(qkv, lens, b, L, n_heads, out, s) : launch_attention<CMR_DT_F16, 4>(qkv, lens, b, L, n_heads, out, s);
@@ -409,8 +642,8 @@ hipError_t cmr_launch_attention(const void* qkv, int dtype, const int* lens, int
 // v[VPL][4] = the lane's elements of one row (vector i = j*64 + lane, valid while i < d4): mean / variance over the wave, then
 // (v - mean) * rstd * gamma + beta, rounded once, written as 8-byte vectors
 template <int DT, int VPL>
-__device__ __forceinline__ void enc_ln_store(float (&v)[VPL][4], float sum, int lane, int d4, const uint2* __restrict__ gamma,
-                                             const uint2* __restrict__ beta, float eps, uint2* __restrict__ out_row) {
+__device__ __forceinline__ void enc_ln_store(float (&v)[VPL][4], float sum, int lane, int d4, const typename EncVec<DT>::V4* __restrict__ gamma,
+                                             const typename EncVec<DT>::V4* __restrict__ beta, float eps, typename EncVec<DT>::V4* __restrict__ out_row) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
     const float inv_d = 1.0f / (float)(4 * d4);
@@ -429,31 +662,25 @@ __device__ __forceinline__ void enc_ln_store(float (&v)[VPL][4], float sum, int 
     for (int j = 0; j < VPL; ++j) {
         const int i = j * 64 + lane;
         if (i < d4) {
-            const uint2 gg = gamma[i], be = beta[i];
             float gm[4], bt[4];
-            enc_unpack2<DT>(gg.x, gm[0], gm[1]);
-            enc_unpack2<DT>(gg.y, gm[2], gm[3]);
-            enc_unpack2<DT>(be.x, bt[0], bt[1]);
-            enc_unpack2<DT>(be.y, bt[2], bt[3]);
-            uint2 w;
-            w.x = enc_pack2<DT>(fmaf((v[j][0] - mean) * rstd, gm[0], bt[0]), fmaf((v[j][1] - mean) * rstd, gm[1], bt[1]));
-            w.y = enc_pack2<DT>(fmaf((v[j][2] - mean) * rstd, gm[2], bt[2]), fmaf((v[j][3] - mean) * rstd, gm[3], bt[3]));
-            out_row[i] = w;
+            enc_get4<DT>(gm, gamma[i]);
+            enc_get4<DT>(bt, beta[i]);
+            out_row[i] = enc_put4<DT>(fmaf((v[j][0] - mean) * rstd, gm[0], bt[0]), fmaf((v[j][1] - mean) * rstd, gm[1], bt[1]),
+                                      fmaf((v[j][2] - mean) * rstd, gm[2], bt[2]), fmaf((v[j][3] - mean) * rstd, gm[3], bt[3]));
         }
     }
 }
-template <int DT> __device__ __forceinline__ void enc_acc4(float (&f)[4], uint2 a) {
+template <int DT> __device__ __forceinline__ void enc_acc4(float (&f)[4], typename EncVec<DT>::V4 a) {
     float t[4];
-    enc_unpack2<DT>(a.x, t[0], t[1]);
-    enc_unpack2<DT>(a.y, t[2], t[3]);
+    enc_get4<DT>(t, a);
 #pragma unroll
     for (int e = 0; e < 4; ++e) f[e] += t[e];
 }
 
 template <int DT, int VPL>
-__global__ __launch_bounds__(256) void add_ln_kernel(const uint2* __restrict__ y, const uint2* __restrict__ bias, const uint2* __restrict__ res,
-                                                     const uint2* __restrict__ gamma, const uint2* __restrict__ beta, float eps, long long rows,
-                                                     int d4, uint2* __restrict__ out) {
+__global__ __launch_bounds__(256) void add_ln_kernel(const typename EncVec<DT>::V4* __restrict__ y, const typename EncVec<DT>::V4* __restrict__ bias, const typename EncVec<DT>::V4* __restrict__ res,
+                                                     const typename EncVec<DT>::V4* __restrict__ gamma, const typename EncVec<DT>::V4* __restrict__ beta, float eps, long long rows,
+                                                     int d4, typename EncVec<DT>::V4* __restrict__ out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long row = (long long)blockIdx.x * 4 + wave;
     if (row >= rows) return;
@@ -476,19 +703,16 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const uint2* __restrict__ y
 // The same for d % 8 == 0 with 16-byte vectors: sixteen lanes per token row, four rows per wave (a wave instruction still reads
 // contiguous 256-byte pieces, and each lane has 2 * VPL 16-byte loads in flight instead of 8-byte ones: the one-row-per-wave
 // form above ran at 4.5 TB/s of algorithmic traffic at 768 columns).
-template <int DT> __device__ __forceinline__ void enc_acc8(float (&f)[8], uint4 a) {
+template <int DT> __device__ __forceinline__ void enc_acc8(float (&f)[8], typename EncVec<DT>::V8 a) {
     float t[8];
-    enc_unpack2<DT>(a.x, t[0], t[1]);
-    enc_unpack2<DT>(a.y, t[2], t[3]);
-    enc_unpack2<DT>(a.z, t[4], t[5]);
-    enc_unpack2<DT>(a.w, t[6], t[7]);
+    enc_get8<DT>(t, a);
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] += t[e];
 }
 template <int DT, int VPL>
-__global__ __launch_bounds__(256) void add_ln16_kernel(const uint4* __restrict__ y, const uint4* __restrict__ bias, const uint4* __restrict__ res,
-                                                       const uint4* __restrict__ gamma, const uint4* __restrict__ beta, float eps, long long rows,
-                                                       int d8, uint4* __restrict__ out) {
+__global__ __launch_bounds__(256) void add_ln16_kernel(const typename EncVec<DT>::V8* __restrict__ y, const typename EncVec<DT>::V8* __restrict__ bias, const typename EncVec<DT>::V8* __restrict__ res,
+                                                       const typename EncVec<DT>::V8* __restrict__ gamma, const typename EncVec<DT>::V8* __restrict__ beta, float eps, long long rows,
+                                                       int d8, typename EncVec<DT>::V8* __restrict__ out) {
     const int sub = threadIdx.x & 15;
     const long long row = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     if (row >= rows) return;                           // whole 16-lane groups leave together: the shuffles below stay inside a group
@@ -524,15 +748,13 @@ __global__ __launch_bounds__(256) void add_ln16_kernel(const uint4* __restrict__
     for (int j = 0; j < VPL; ++j) {
         const int i = j * 16 + sub;
         if (i < d8) {
-            float gm[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            enc_acc8<DT>(gm, gamma[i]);
-            enc_acc8<DT>(bt, beta[i]);
-            uint4 w;
-            w.x = enc_pack2<DT>(fmaf((v[j][0] - mean) * rstd, gm[0], bt[0]), fmaf((v[j][1] - mean) * rstd, gm[1], bt[1]));
-            w.y = enc_pack2<DT>(fmaf((v[j][2] - mean) * rstd, gm[2], bt[2]), fmaf((v[j][3] - mean) * rstd, gm[3], bt[3]));
-            w.z = enc_pack2<DT>(fmaf((v[j][4] - mean) * rstd, gm[4], bt[4]), fmaf((v[j][5] - mean) * rstd, gm[5], bt[5]));
-            w.w = enc_pack2<DT>(fmaf((v[j][6] - mean) * rstd, gm[6], bt[6]), fmaf((v[j][7] - mean) * rstd, gm[7], bt[7]));
-            out[row * d8 + i] = w;
+            float gm[8], bt[8];
+            enc_get8<DT>(gm, gamma[i]);
+            enc_get8<DT>(bt, beta[i]);
+            float w[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) w[e] = fmaf((v[j][e] - mean) * rstd, gm[e], bt[e]);
+            out[row * d8 + i] = enc_put8<DT>(w);
         }
     }
 }
@@ -545,8 +767,8 @@ __global__ __launch_bounds__(256) void add_ln16_kernel(const uint4* __restrict__
 // write, and nothing is read back but these partials.  Blocks that hold only padding leave at once (no loads, no partial).
 // pool_finish_kernel then adds a sequence's partials in block order, divides by the token count and L2-normalises (eps 1e-12).
 template <int DT, int VPL>
-__global__ __launch_bounds__(256) void add_ln16_pool_kernel(const uint4* __restrict__ y, const uint4* __restrict__ bias, const uint4* __restrict__ res,
-                                                            const uint4* __restrict__ gamma, const uint4* __restrict__ beta, float eps, int l, int d8,
+__global__ __launch_bounds__(256) void add_ln16_pool_kernel(const typename EncVec<DT>::V8* __restrict__ y, const typename EncVec<DT>::V8* __restrict__ bias, const typename EncVec<DT>::V8* __restrict__ res,
+                                                            const typename EncVec<DT>::V8* __restrict__ gamma, const typename EncVec<DT>::V8* __restrict__ beta, float eps, int l, int d8,
                                                             const int* __restrict__ lens, float* __restrict__ partial) {
     __shared__ float red[4][16 * VPL * 8];
     const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4, wave = threadIdx.x >> 6;
@@ -587,13 +809,18 @@ __global__ __launch_bounds__(256) void add_ln16_pool_kernel(const uint4* __restr
     for (int j = 0; j < VPL; ++j) {
         const int i = j * 16 + sub;
         if (i < d8) {
-            float gm[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            enc_acc8<DT>(gm, gamma[i]);
-            enc_acc8<DT>(bt, beta[i]);
+            float gm[8], bt[8];
+            enc_get8<DT>(gm, gamma[i]);
+            enc_get8<DT>(bt, beta[i]);
 #pragma unroll
-            for (int e = 0; e < 8; e += 2) {      // round to 16 bits as the stored hidden state would be, then back
-                const unsigned w = enc_pack2<DT>(fmaf((v[j][e] - mean) * rstd, gm[e], bt[e]), fmaf((v[j][e + 1] - mean) * rstd, gm[e + 1], bt[e + 1]));
-                enc_unpack2<DT>(w, v[j][e], v[j][e + 1]);
+            for (int e = 0; e < 8; e += 2) {
+                const float w0 = fmaf((v[j][e] - mean) * rstd, gm[e], bt[e]), w1 = fmaf((v[j][e + 1] - mean) * rstd, gm[e + 1], bt[e + 1]);
+                if constexpr (DT == CMR_DT_F32) {      // the stored hidden state would have held these floats: nothing to round
+                    v[j][e] = w0;
+                    v[j][e + 1] = w1;
+                } else {                               // round to 16 bits as the stored hidden state would be, then back
+                    enc_unpack2<DT>(enc_pack2<DT>(w0, w1), v[j][e], v[j][e + 1]);
+                }
             }
         }
 #pragma unroll
@@ -662,9 +889,9 @@ __global__ __launch_bounds__(256) void pool_finish_kernel(const float* __restric
 // Ids outside the tables are clamped into them (PyTorch's gather would fault the device instead).
 template <int DT, int VPL>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const long long* __restrict__ ids, const long long* __restrict__ tt,
-                                                       const uint2* __restrict__ word, const uint2* __restrict__ pos, const uint2* __restrict__ type,
-                                                       const uint2* __restrict__ gamma, const uint2* __restrict__ beta, float eps, long long rows,
-                                                       int L, int d4, int vocab, int n_pos, int n_types, int pos_off, uint2* __restrict__ out) {
+                                                       const typename EncVec<DT>::V4* __restrict__ word, const typename EncVec<DT>::V4* __restrict__ pos, const typename EncVec<DT>::V4* __restrict__ type,
+                                                       const typename EncVec<DT>::V4* __restrict__ gamma, const typename EncVec<DT>::V4* __restrict__ beta, float eps, long long rows,
+                                                       int L, int d4, int vocab, int n_pos, int n_types, int pos_off, typename EncVec<DT>::V4* __restrict__ out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long row = (long long)blockIdx.x * 4 + wave;
     if (row >= rows) return;
@@ -694,10 +921,10 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const long long* __restri
 // attention masks them as keys, the pooling leaves them out).  No padded id / mask / token-type tensors exist on either side of
 // the link: the host concatenates the tokenizer's output and ships lens | offsets | ids in ONE copy.  Token type 0 (one segment).
 template <int DT, int VPL>
-__global__ __launch_bounds__(256) void embed_ln_ragged_kernel(const int* __restrict__ ids32, const int* __restrict__ off, const uint2* __restrict__ word,
-                                                              const uint2* __restrict__ pos, const uint2* __restrict__ type, const uint2* __restrict__ gamma,
-                                                              const uint2* __restrict__ beta, float eps, long long rows, int L, int d4, int vocab, int n_pos,
-                                                              int pos_off, uint2* __restrict__ out) {
+__global__ __launch_bounds__(256) void embed_ln_ragged_kernel(const int* __restrict__ ids32, const int* __restrict__ off, const typename EncVec<DT>::V4* __restrict__ word,
+                                                              const typename EncVec<DT>::V4* __restrict__ pos, const typename EncVec<DT>::V4* __restrict__ type, const typename EncVec<DT>::V4* __restrict__ gamma,
+                                                              const typename EncVec<DT>::V4* __restrict__ beta, float eps, long long rows, int L, int d4, int vocab, int n_pos,
+                                                              int pos_off, typename EncVec<DT>::V4* __restrict__ out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long row = (long long)blockIdx.x * 4 + wave;
     if (row >= rows) return;
@@ -729,9 +956,9 @@ static hipError_t launch_embed_ln_ragged(const int* ids32, const int* off, const
     const int d4 = d / 4, vpl = (d4 + 63) / 64;
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
 #define ENC_EMBR(V)                                                                                                                       \
-    hipLaunchKernelGGL((embed_ln_ragged_kernel<DT, V>), grid, block, 0, s, ids32, off, reinterpret_cast<const uint2*>(word), reinterpret_cast<const uint2*>(pos), \
-                       reinterpret_cast<const uint2*>(type), reinterpret_cast<const uint2*>(gamma), reinterpret_cast<const uint2*>(beta), eps, rows, \
-                       L, d4, vocab, n_pos, pos_off, reinterpret_cast<uint2*>(out))
+    hipLaunchKernelGGL((embed_ln_ragged_kernel<DT, V>), grid, block, 0, s, ids32, off, reinterpret_cast<const typename EncVec<DT>::V4*>(word), reinterpret_cast<const typename EncVec<DT>::V4*>(pos), \
+                       reinterpret_cast<const typename EncVec<DT>::V4*>(type), reinterpret_cast<const typename EncVec<DT>::V4*>(gamma), reinterpret_cast<const typename EncVec<DT>::V4*>(beta), eps, rows, \
+                       L, d4, vocab, n_pos, pos_off, reinterpret_cast<typename EncVec<DT>::V4*>(out))
     switch (vpl) {
         case 1: ENC_EMBR(1); break;
         case 2: ENC_EMBR(2); break;
@@ -749,6 +976,7 @@ hipError_t cmr_launch_embed_layernorm_ragged(const int* ids32, const int* off, c
                                              const void* beta, float eps, long long rows, int L, int d, int vocab, int n_pos, int pos_off, int dtype,
                                              void* out, hipStream_t s) {
     if (dtype == CMR_DT_BF16) return launch_embed_ln_ragged<CMR_DT_BF16>(ids32, off, word, pos, type, gamma, beta, eps, rows, L, d, vocab, n_pos, pos_off, out, s);
+    if (dtype == CMR_DT_F32) return launch_embed_ln_ragged<CMR_DT_F32>(ids32, off, word, pos, type, gamma, beta, eps, rows, L, d, vocab, n_pos, pos_off, out, s);
     return launch_embed_ln_ragged<CMR_DT_F16>(ids32, off, word, pos, type, gamma, beta, eps, rows, L, d, vocab, n_pos, pos_off, out, s);
 }
 
@@ -767,9 +995,9 @@ static hipError_t launch_add_ln(const void* y, const void* bias, const void* res
         const int d8 = d / 8, vpl16 = (d8 + 15) / 16;
         const dim3 grid16((unsigned)((rows + 15) / 16)), block16(256);
 #define ENC_LN16(V)                                                                                                                       \
-    hipLaunchKernelGGL((add_ln16_kernel<DT, V>), grid16, block16, 0, s, reinterpret_cast<const uint4*>(y), reinterpret_cast<const uint4*>(bias), \
-                       reinterpret_cast<const uint4*>(res), reinterpret_cast<const uint4*>(gamma), reinterpret_cast<const uint4*>(beta), eps, \
-                       rows, d8, reinterpret_cast<uint4*>(out))
+    hipLaunchKernelGGL((add_ln16_kernel<DT, V>), grid16, block16, 0, s, reinterpret_cast<const typename EncVec<DT>::V8*>(y), reinterpret_cast<const typename EncVec<DT>::V8*>(bias), \
+                       reinterpret_cast<const typename EncVec<DT>::V8*>(res), reinterpret_cast<const typename EncVec<DT>::V8*>(gamma), reinterpret_cast<const typename EncVec<DT>::V8*>(beta), eps, \
+                       rows, d8, reinterpret_cast<typename EncVec<DT>::V8*>(out))
         switch (vpl16) {
             case 1: ENC_LN16(1); break;
             case 2: ENC_LN16(2); break;
@@ -786,9 +1014,9 @@ static hipError_t launch_add_ln(const void* y, const void* bias, const void* res
     const int d4 = d / 4, vpl = (d4 + 63) / 64;
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
 #define ENC_LN(V)                                                                                                                     \
-    hipLaunchKernelGGL((add_ln_kernel<DT, V>), grid, block, 0, s, reinterpret_cast<const uint2*>(y), reinterpret_cast<const uint2*>(bias), \
-                       reinterpret_cast<const uint2*>(res), reinterpret_cast<const uint2*>(gamma), reinterpret_cast<const uint2*>(beta), eps, \
-                       rows, d4, reinterpret_cast<uint2*>(out))
+    hipLaunchKernelGGL((add_ln_kernel<DT, V>), grid, block, 0, s, reinterpret_cast<const typename EncVec<DT>::V4*>(y), reinterpret_cast<const typename EncVec<DT>::V4*>(bias), \
+                       reinterpret_cast<const typename EncVec<DT>::V4*>(res), reinterpret_cast<const typename EncVec<DT>::V4*>(gamma), reinterpret_cast<const typename EncVec<DT>::V4*>(beta), eps, \
+                       rows, d4, reinterpret_cast<typename EncVec<DT>::V4*>(out))
     switch (vpl) {
         case 1: ENC_LN(1); break;
         case 2: ENC_LN(2); break;
@@ -809,9 +1037,9 @@ static hipError_t launch_embed_ln(const long long* ids, const long long* tt, con
     const int d4 = d / 4, vpl = (d4 + 63) / 64;
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
 #define ENC_EMB(V)                                                                                                                       \
-    hipLaunchKernelGGL((embed_ln_kernel<DT, V>), grid, block, 0, s, ids, tt, reinterpret_cast<const uint2*>(word), reinterpret_cast<const uint2*>(pos), \
-                       reinterpret_cast<const uint2*>(type), reinterpret_cast<const uint2*>(gamma), reinterpret_cast<const uint2*>(beta), eps, rows, \
-                       L, d4, vocab, n_pos, n_types, pos_off, reinterpret_cast<uint2*>(out))
+    hipLaunchKernelGGL((embed_ln_kernel<DT, V>), grid, block, 0, s, ids, tt, reinterpret_cast<const typename EncVec<DT>::V4*>(word), reinterpret_cast<const typename EncVec<DT>::V4*>(pos), \
+                       reinterpret_cast<const typename EncVec<DT>::V4*>(type), reinterpret_cast<const typename EncVec<DT>::V4*>(gamma), reinterpret_cast<const typename EncVec<DT>::V4*>(beta), eps, rows, \
+                       L, d4, vocab, n_pos, n_types, pos_off, reinterpret_cast<typename EncVec<DT>::V4*>(out))
     switch (vpl) {
         case 1: ENC_EMB(1); break;
         case 2: ENC_EMB(2); break;
@@ -831,8 +1059,8 @@ static hipError_t launch_add_ln_pool(const void* y, const void* bias, const void
     const int d8 = d / 8, vpl16 = (d8 + 15) / 16;
     const dim3 grid((unsigned)(l / 16), (unsigned)b), block(256);
 #define ENC_LNP(V)                                                                                                                        \
-    hipLaunchKernelGGL((add_ln16_pool_kernel<DT, V>), grid, block, 0, s, reinterpret_cast<const uint4*>(y), reinterpret_cast<const uint4*>(bias), \
-                       reinterpret_cast<const uint4*>(res), reinterpret_cast<const uint4*>(gamma), reinterpret_cast<const uint4*>(beta), eps, l, \
+    hipLaunchKernelGGL((add_ln16_pool_kernel<DT, V>), grid, block, 0, s, reinterpret_cast<const typename EncVec<DT>::V8*>(y), reinterpret_cast<const typename EncVec<DT>::V8*>(bias), \
+                       reinterpret_cast<const typename EncVec<DT>::V8*>(res), reinterpret_cast<const typename EncVec<DT>::V8*>(gamma), reinterpret_cast<const typename EncVec<DT>::V8*>(beta), eps, l, \
                        d8, lens, partial)
     switch (vpl16) {
         case 1: ENC_LNP(1); break;
@@ -856,6 +1084,7 @@ static hipError_t launch_add_ln_pool(const void* y, const void* bias, const void
 hipError_t cmr_launch_add_layernorm_pool(const void* y, const void* bias, const void* res, const void* gamma, const void* beta, float eps, int b, int l,
                                          int d, int dtype, const int* lens, int normalize, float* partial, float* out, hipStream_t s) {
     if (dtype == CMR_DT_BF16) return launch_add_ln_pool<CMR_DT_BF16>(y, bias, res, gamma, beta, eps, b, l, d, lens, normalize, partial, out, s);
+    if (dtype == CMR_DT_F32) return launch_add_ln_pool<CMR_DT_F32>(y, bias, res, gamma, beta, eps, b, l, d, lens, normalize, partial, out, s);
     return launch_add_ln_pool<CMR_DT_F16>(y, bias, res, gamma, beta, eps, b, l, d, lens, normalize, partial, out, s);
 }
 
@@ -863,12 +1092,14 @@ hipError_t cmr_launch_embed_layernorm(const long long* ids, const long long* tt,
                                       const void* gamma, const void* beta, float eps, long long rows, int L, int d, int vocab, int n_pos,
                                       int n_types, int pos_off, int dtype, void* out, hipStream_t s) {
     if (dtype == CMR_DT_BF16) return launch_embed_ln<CMR_DT_BF16>(ids, tt, word, pos, type, gamma, beta, eps, rows, L, d, vocab, n_pos, n_types, pos_off, out, s);
+    if (dtype == CMR_DT_F32) return launch_embed_ln<CMR_DT_F32>(ids, tt, word, pos, type, gamma, beta, eps, rows, L, d, vocab, n_pos, n_types, pos_off, out, s);
     return launch_embed_ln<CMR_DT_F16>(ids, tt, word, pos, type, gamma, beta, eps, rows, L, d, vocab, n_pos, n_types, pos_off, out, s);
 }
 
 hipError_t cmr_launch_add_layernorm(const void* y, const void* bias, const void* res, const void* gamma, const void* beta, float eps, long long rows,
                                     int d, int dtype, void* out, hipStream_t s) {
     if (dtype == CMR_DT_BF16) return launch_add_ln<CMR_DT_BF16>(y, bias, res, gamma, beta, eps, rows, d, out, s);
+    if (dtype == CMR_DT_F32) return launch_add_ln<CMR_DT_F32>(y, bias, res, gamma, beta, eps, rows, d, out, s);
     return launch_add_ln<CMR_DT_F16>(y, bias, res, gamma, beta, eps, rows, d, out, s);
 }
 
@@ -881,7 +1112,7 @@ int32_t cmr_encoder_attention(int32_t device_id, const void* qkv_dev, int32_t dt
     if (!qkv_dev || !lens_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (b <= 0 || l <= 0 || n_heads <= 0) return cmr_fail(CMR_ERR_INVALID, "b, l, n_heads must be > 0");
     if (head_dim != 64) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: head_dim must be 64 (BERT-base / BERT-large heads)");
-    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: dtype must be bf16 or f16");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: dtype must be bf16 or f16 or f32");
     if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & 15) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: buffers must be 16-byte aligned");
     int rc = cmr_check_device(device_id);
     if (rc) return rc;
@@ -895,9 +1126,9 @@ int32_t cmr_encoder_add_layernorm(int32_t device_id, const void* y_dev, const vo
                                   const void* beta_dev, float eps, int64_t rows, int32_t d, int32_t dtype, void* out_dev, void* stream) {
     if (!y_dev || !gamma_dev || !beta_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (rows <= 0 || d <= 0 || d % 4 || d > 2048) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm: rows > 0, d a multiple of 4, d <= 2048");
-    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm: dtype must be bf16 or f16");
-    if (((uintptr_t)y_dev | (uintptr_t)bias_dev | (uintptr_t)residual_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & 7)
-        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm: buffers must be 8-byte aligned");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm: dtype must be bf16 or f16 or f32");
+    if (((uintptr_t)y_dev | (uintptr_t)bias_dev | (uintptr_t)residual_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & (dtype == CMR_F32 ? 15 : 7))
+        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm: buffers must be 8-byte aligned (16-byte for f32)");
     int rc = cmr_check_device(device_id);
     if (rc) return rc;
     rc = cmr_set_device(device_id);
@@ -912,7 +1143,7 @@ int32_t cmr_encoder_add_layernorm_pool(int32_t device_id, const void* y_dev, con
     if (!y_dev || !gamma_dev || !beta_dev || !lens_dev || !partial_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (b <= 0 || l <= 0 || d <= 0) return cmr_fail(CMR_ERR_INVALID, "b, l, d must be > 0");
     if (l % 16 || d % 8 || d > 2048) return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_pool: l must be a multiple of 16, d a multiple of 8 and <= 2048");
-    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm_pool: dtype must be bf16 or f16");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm_pool: dtype must be bf16 or f16 or f32");
     if (((uintptr_t)y_dev | (uintptr_t)bias_dev | (uintptr_t)residual_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)partial_dev | (uintptr_t)out_dev) & 15)
         return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_pool: buffers must be 16-byte aligned");
     int rc = cmr_check_device(device_id);
@@ -930,9 +1161,9 @@ int32_t cmr_encoder_embed_layernorm(int32_t device_id, const int64_t* ids_dev, c
     if (!ids_dev || !word_dev || !pos_dev || !type_dev || !gamma_dev || !beta_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (rows <= 0 || l <= 0 || d <= 0 || d % 4 || d > 2048) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: rows, l > 0, d a multiple of 4, d <= 2048");
     if (vocab <= 0 || n_positions <= 0 || n_types <= 0 || position_offset < 0) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: empty embedding table / negative position offset");
-    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: dtype must be bf16 or f16");
-    if (((uintptr_t)word_dev | (uintptr_t)pos_dev | (uintptr_t)type_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & 7)
-        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: buffers must be 8-byte aligned");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: dtype must be bf16 or f16 or f32");
+    if (((uintptr_t)word_dev | (uintptr_t)pos_dev | (uintptr_t)type_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & (dtype == CMR_F32 ? 15 : 7))
+        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm: buffers must be 8-byte aligned (16-byte for f32)");
     int rc = cmr_check_device(device_id);
     if (rc) return rc;
     rc = cmr_set_device(device_id);
@@ -948,9 +1179,9 @@ int32_t cmr_encoder_embed_layernorm_ragged(int32_t device_id, const int32_t* ids
     if (!ids32_dev || !offsets_dev || !word_dev || !pos_dev || !type_dev || !gamma_dev || !beta_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (b <= 0 || l <= 0 || d <= 0 || d % 4 || d > 2048) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: b, l > 0, d a multiple of 4, d <= 2048");
     if (vocab <= 0 || n_positions <= 0 || position_offset < 0) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: empty embedding table / negative position offset");
-    if (dtype != CMR_BF16 && dtype != CMR_F16) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: dtype must be bf16 or f16");
-    if (((uintptr_t)word_dev | (uintptr_t)pos_dev | (uintptr_t)type_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & 7)
-        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: buffers must be 8-byte aligned");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: dtype must be bf16 or f16 or f32");
+    if (((uintptr_t)word_dev | (uintptr_t)pos_dev | (uintptr_t)type_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & (dtype == CMR_F32 ? 15 : 7))
+        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_embed_layernorm_ragged: buffers must be 8-byte aligned (16-byte for f32)");
     int rc = cmr_check_device(device_id);
     if (rc) return rc;
     rc = cmr_set_device(device_id);

@@ -100,7 +100,8 @@ class _EncodeReplica:
             same = device == owner.device
             self.model = owner.embedding_model if same else copy.deepcopy(owner.embedding_model).to(device).eval()
             with torch.cuda.device(device):
-                self.fused = fused_bert.FusedBertLayers(self.model, graphs=owner._fused.graphs, gelu="epilogue" if owner._fused.gelu_path.startswith("hipblaslt") else "exact")
+                self.fused = fused_bert.FusedBertLayers(self.model, graphs=owner._fused.graphs, gelu="epilogue" if owner._fused.gelu_path.startswith("hipblaslt") else "exact",
+                                                        fp32=owner._fused.dtype == torch.float32)
         self.stream = torch.cuda.Stream(device)
         self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=f"cmr-enc-{device.index}")
         self.first = first
@@ -146,12 +147,13 @@ class HipBGEEmbeddingModel(BaseEmbeddingModel):
         self._fused, self.encoder_path = None, "transformers"
         if bool(cfg_get(self.global_config, "embedding_fused_encoder", True)):
             from . import fused_bert
-            reason = fused_bert.why_not(self.embedding_model)
+            fp32 = bool(cfg_get(self.global_config, "embedding_fused_fp32", False))       # opt-in: fp32 models through the fp32 kernels
+            reason = fused_bert.why_not(self.embedding_model, fp32=fp32)
             if reason is None and getattr(tokenizer, "padding_side", "right") != "right":
                 reason = "left-padding tokenizer"
             if reason is None:
                 self._fused = fused_bert.FusedBertLayers(self.embedding_model, graphs=int(cfg_get(self.global_config, "embedding_hip_graphs", 24)),
-                                                         gelu=str(cfg_get(self.global_config, "embedding_gelu", "exact")))
+                                                         gelu=str(cfg_get(self.global_config, "embedding_gelu", "exact")), fp32=fp32)
                 self.encoder_path = "hip-fused-layers"
             else:
                 self.encoder_path = f"transformers ({reason})"

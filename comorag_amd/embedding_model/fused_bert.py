@@ -1,4 +1,5 @@
-"""The encoder stack behind `self.embedding_model(**inputs)` (embedding_model/BGEEmbedding.py:119) for 16-bit BERT encoders.
+"""The encoder stack behind `self.embedding_model(**inputs)` (embedding_model/BGEEmbedding.py:119) for 16-bit BERT encoders — and,
+opt-in (`fp32=True`, config `embedding_fused_fp32`), for fp32 ones: the same stages with fp32 tensors, fp32 GEMMs and fp32 HIP kernels.
 
 transformers' BertLayer is ~20 kernels and as many Python module calls per layer: three projection GEMMs, SDPA with an additive
 mask, the output GEMM, bias / residual adds, LayerNorm, the FFN GEMMs and GELU.  Here a layer is
@@ -83,8 +84,9 @@ def position_offset(model) -> int:
     return int(pad) + 1
 
 
-def why_not(model) -> Optional[str]:
-    """None if the fused layer stack can run this model, else the reason it cannot."""
+def why_not(model, fp32: bool = False) -> Optional[str]:
+    """None if the fused layer stack can run this model, else the reason it cannot.  fp32 = True also accepts torch.float32 weights
+    (the fp32 kernels, opt-in); every other reason applies unchanged."""
     import torch
     cfg = getattr(model, "config", None)
     if cfg is None or getattr(cfg, "model_type", "") not in ENCODER_TYPES:
@@ -103,6 +105,8 @@ def why_not(model) -> Optional[str]:
     if cfg.hidden_size % 4 or cfg.hidden_size > 2048 or cfg.intermediate_size % 4:
         return "hidden size not supported by the LayerNorm kernel"
     dt = next(model.parameters()).dtype
+    if fp32 and dt == torch.float32:
+        return None
     if dt not in (torch.bfloat16, torch.float16):
         return f"{dt} weights (the fused layers are 16-bit)"
     return None
@@ -155,7 +159,7 @@ def gelu_epilogue_available(device, dtype) -> bool:
 
 
 class FusedBertLayers:
-    def __init__(self, model, graphs: int = 0, gelu: str = "exact"):
+    def __init__(self, model, graphs: int = 0, gelu: str = "exact", fp32: bool = False):
         """gelu = "exact" (default): FFN-up GEMM + bias in hipBLASLt, then PyTorch's erf-form GELU kernel — the function the model
         was trained with and the reference runs (BGEEmbedding.py:119-120, `hidden_act = "gelu"`).
         gelu = "epilogue" (opt-in, `embedding_gelu`): projection, bias and GELU are ONE hipBLASLt GEMM (`torch._addmm_activation`) —
@@ -164,9 +168,12 @@ class FusedBertLayers:
         itself is ~1e-2: for small outputs the difference exceeds the 16-bit rounding step — bf16 ulp at 0.009 is 6e-5, fp16's 8e-6).
         Measured inside north_star's 1e-3 cosine bar on seed-initialised BERT shapes and on heavy-tailed pre-activations
         (tests/test_encoder_fused_gpu.py), not on real BGE weights (absent from the image) — hence not the default.  Falls back to
-        "exact" when the build does not fuse it into a single launch (`gelu_path` says which one runs)."""
+        "exact" when the build does not fuse it into a single launch (`gelu_path` says which one runs).
+        fp32 = True admits an fp32 model: fp32 tensors through every stage (cmr_dtype = CMR_F32: exact f32-input MFMA attention,
+        LayerNorm written unrounded), F.linear in fp32 as the transformers forward calls it.  gelu = "epilogue" then runs the exact
+        kernel too: the tanh epilogue was validated against 16-bit rounding steps only."""
         import torch
-        reason = why_not(model)
+        reason = why_not(model, fp32=fp32)
         if reason is not None:
             raise ValueError("FusedBertLayers: " + reason)
         if gelu not in ("epilogue", "exact"):
@@ -175,7 +182,9 @@ class FusedBertLayers:
         cfg = model.config
         self.hidden, self.n_heads, self.eps = int(cfg.hidden_size), int(cfg.num_attention_heads), float(cfg.layer_norm_eps)
         self.dtype = next(model.parameters()).dtype
-        self.cmr_dtype = L.CMR_BF16 if self.dtype == torch.bfloat16 else L.CMR_F16
+        self.cmr_dtype = {torch.bfloat16: L.CMR_BF16, torch.float16: L.CMR_F16, torch.float32: L.CMR_F32}[self.dtype]
+        if self.dtype == torch.float32:
+            gelu = "exact"
         self.device = next(model.parameters()).device
         emb = model.embeddings
         self.emb = tuple(t.detach().contiguous() for t in (emb.word_embeddings.weight, emb.position_embeddings.weight,

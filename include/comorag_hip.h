@@ -479,8 +479,9 @@ int32_t cmr_pool_l2norm(int32_t device_id, const void* hidden_dev, int32_t hidde
 
 /* ---- encoder layer pieces -----------------------------------------------------------------
  * The two non-GEMM stages of a BERT layer inside `self.embedding_model(**inputs)` (embedding_model/BGEEmbedding.py:119; the
- * GEMMs stay PyTorch-ROCm / hipBLASLt as north_star prescribes).  Both take device pointers of 16-bit tensors (dtype =
- * CMR_BF16 or CMR_F16) and run on `stream`.
+ * GEMMs stay PyTorch-ROCm / hipBLASLt as north_star prescribes).  They take device pointers of bf16, fp16 or fp32 tensors (dtype =
+ * CMR_BF16, CMR_F16 or CMR_F32: every tensor of a call has that type) and run on `stream`.  CMR_F32 is fp32 end to end (fp32 in, exact
+ * f32-input MFMA products, fp32 out, nothing rounded to 16 bits); its buffers must be 16-byte aligned in every entry point.
  *
  * cmr_encoder_attention: out[b*l, hidden] = softmax(Q K^T / sqrt(head_dim), keys >= lens[s] masked) V per sequence and head,
  *   with Q | K | V the three hidden-wide column groups of ONE packed projection qkv_dev[b*l, 3*hidden] (hidden = n_heads *
@@ -497,8 +498,8 @@ int32_t cmr_pool_l2norm(int32_t device_id, const void* hidden_dev, int32_t hidde
 /* The LAST layer's cmr_encoder_add_layernorm with the encoder tail folded in — mean_pooling over the tokens < lens[s]
  * (embedding_model/BGEEmbedding.py:15-28) and F.normalize (:126-127, eps 1e-12; normalize = 0: the plain masked mean) of the
  * [b, l, d] mini-batch it would have written: out_dev [b, d] fp32; the hidden state itself is never stored (a 16-token block per
- * workgroup -> one fp32 partial row, summed in block order by a small second launch; every value is rounded to 16 bits before it
- * is added, as the stored hidden state would have been).  l % 16 == 0, d % 8 == 0, d <= 2048, 16-byte aligned buffers, right-padded
+ * workgroup -> one fp32 partial row, summed in block order by a small second launch; a 16-bit dtype's values are rounded to 16 bits before
+ * they are added, as the stored hidden state would have been; CMR_F32 adds them as they are).  l % 16 == 0, d % 8 == 0, d <= 2048, 16-byte aligned buffers, right-padded
  * sequences (lens_dev [b] int32): CMR_ERR_UNSUPPORTED otherwise — callers then run add_layernorm + cmr_pool_l2norm.             */
 int32_t cmr_encoder_add_layernorm_pool(int32_t device_id, const void* y_dev, const void* bias_dev, const void* residual_dev,
                                        const void* gamma_dev, const void* beta_dev, float eps, int32_t b, int32_t l, int32_t d,

@@ -1,5 +1,7 @@
 """Corpus-embed rate and per-stage breakdown of the encoder path (tools/bench_extras.encode_breakdown) for the BERT-base bf16 and
-BERT-large fp16 shapes, fused layer stack against the transformers forward.  `python -m tools.encoder_bench [--quick]`."""
+BERT-large fp16 shapes, fused layer stack against the transformers forward.  `python -m tools.encoder_bench [--quick]`.
+`python -m tools.encoder_bench --fp32 [--out FILE]`: the fp32 rows (`embedding_model_dtype = "auto"`, `embedding_fused_fp32` on and off in the
+same run) — one short query, the corpus forward at 512 tokens, and the fp32 attention kernel next to PyTorch's SDPA on the same tensors."""
 import json
 import sys
 
@@ -31,7 +33,87 @@ def query_latency(kind, dtype, dev, reps=40):
     return out
 
 
+def _timed(fn, reps, warm=3):
+    """Seconds per call: `reps` calls back to back between two device synchronisations (launches overlap the device work)."""
+    import time
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps
+
+
+def fp32_report(dev, reps=60):
+    """The fp32 opt-in (`embedding_fused_fp32`) against the transformers fp32 forward of the same model, same process, same run."""
+    import time
+    import numpy as np
+    from comorag_amd.embedding_model.bge import HipBGEEmbeddingModel
+    from comorag_amd.utils.config_utils import BaseConfig
+    from tools.synthetic import random_bert, synthetic_chunks, synthetic_wordpiece_tokenizer
+    tok, words = synthetic_wordpiece_tokenizer()
+    q = " ".join(words[:12])
+    out = {"what": "fp32 encoder (embedding_model_dtype auto = fp32 weights): fused fp32 stack (embedding_fused_fp32 = True) vs the transformers fp32 forward",
+           "single_query_encode_us": {}, "corpus": {}, "attention": {}}
+    for kind in ("base", "large"):
+        row = {}
+        for flag in (True, False):
+            cfg = BaseConfig(embedding_model_name=f"bge-{kind}-random-init", embedding_model_dtype="auto", device=dev.index or 0,
+                             embedding_fused_fp32=flag, embedding_query_cache=0)                       # (every call a forward)
+            em = HipBGEEmbeddingModel(cfg, cfg.embedding_model_name, model=random_bert(kind, vocab_size=len(tok)), tokenizer=tok)
+            assert em.encoder_path.startswith("hip-fused-layers" if flag else "transformers (")
+            for _ in range(8):
+                em.batch_encode(q)
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter(); em.batch_encode(q); ts.append(time.perf_counter() - t0)
+            row["fused_fp32" if flag else "transformers_fp32"] = {"median": float(np.median(ts) * 1e6), "min": float(np.min(ts) * 1e6)}
+            if kind == "base":
+                # corpus forward: 32 chunks of 512 tokens, inputs on the device; and batch_encode of 128 chunks end to end
+                chunks = synthetic_chunks(words, 128, tokens_per_chunk=560)
+                host = em._tokenize(chunks[:32], 512)
+                inp = {k: v.to(dev) for k, v in host.items()}
+                lens = host["attention_mask"].numpy().sum(1).astype(np.int32)
+                with torch.no_grad():
+                    if flag:
+                        dt = _timed(lambda: em._fused(inp["input_ids"], lens, token_type_ids=inp.get("token_type_ids"), pool=True), 5, warm=2)
+                    else:
+                        dt = _timed(lambda: em.embedding_model(**inp).last_hidden_state, 5, warm=2)
+                em.batch_encode(chunks[:64])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter(); em.batch_encode(chunks); torch.cuda.synchronize(); dt_e2e = time.perf_counter() - t0
+                out["corpus"]["fused_fp32" if flag else "transformers_fp32"] = {
+                    "forward_only_chunks_per_s": 32 / dt, "end_to_end_chunks_per_s": len(chunks) / dt_e2e, "tokens_per_chunk": int(inp["input_ids"].shape[1])}
+                if flag:
+                    # the attention kernel alone at 32 x 512 x 12 heads, every sequence full, next to SDPA on the same tensors (its inputs
+                    # already split and head-major, which the transformers forward pays for with three more copies)
+                    fz, b, l = em._fused, 32, 512
+                    qkv = torch.randn((b * l, 3 * fz.hidden), device=dev) * 1.5
+                    lens_dev = torch.full((b,), l, dtype=torch.int32, device=dev)
+                    x = qkv.view(b, l, 3, fz.n_heads, 64)
+                    qh, kh, vh = (x[:, :, i].permute(0, 2, 1, 3).contiguous() for i in range(3))
+                    dt_k = _timed(lambda: fz.attention(qkv, lens_dev, b, l), 20)
+                    dt_s = _timed(lambda: torch.nn.functional.scaled_dot_product_attention(qh, kh, vh), 20)
+                    flops = 4.0 * b * l * l * fz.hidden
+                    out["attention"] = {"shape": "32 x 512 tokens x 12 heads x 64, fp32, full sequences", "timing": "20 launches back to back between two synchronisations",
+                                        "hip_fp32_kernel_us": dt_k * 1e6, "torch_sdpa_fp32_us": dt_s * 1e6, "hip_TFLOPs": flops / dt_k / 1e12,
+                                        "frac_of_155TF_f32_mfma": flops / dt_k / 1e12 / 155.0}
+            em.close()
+        out["single_query_encode_us"][kind] = row
+    return out
+
+
 def main():
+    if "--fp32" in sys.argv:
+        rep = fp32_report(torch.device("cuda", 0))
+        text = json.dumps(rep, indent=1)
+        print(text)
+        if "--out" in sys.argv:
+            with open(sys.argv[sys.argv.index("--out") + 1], "w") as f:
+                f.write(text + "\n")
+        return
     quick = "--quick" in sys.argv
     dev = torch.device("cuda", 0)
     cases = [("base", "bf16", 256, 0), ("base", "bf16", 256, 4), ("large", "fp16", 256, 0)]

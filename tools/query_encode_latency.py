@@ -19,8 +19,10 @@ def med(f, n):
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
     tok, words = synthetic_wordpiece_tokenizer()
-    for kind, dtype in (("base", "bf16"), ("large", "fp16")):
-        cfg = BaseConfig(embedding_model_name=f"bge-{kind}-random-init", embedding_model_dtype=dtype, embedding_query_cache=0)      # (every call a forward: the product keeps the last 256 single-string rows)
+    # (the "auto" rows: fp32 weights as stored — the transformers fp32 forward, then the fused fp32 stack, `embedding_fused_fp32`)
+    for kind, dtype, fp32 in (("base", "bf16", False), ("large", "fp16", False), ("base", "auto", False), ("base", "auto", True), ("large", "auto", False), ("large", "auto", True)):
+        cfg = BaseConfig(embedding_model_name=f"bge-{kind}-random-init", embedding_model_dtype=dtype, embedding_query_cache=0,      # (every call a forward: the product keeps the last 256 single-string rows)
+                         embedding_fused_fp32=fp32)
         em = HipBGEEmbeddingModel(cfg, cfg.embedding_model_name, model=random_bert(kind, vocab_size=len(tok)), tokenizer=tok)
         q = " ".join(words[:12])
         for _ in range(8):
