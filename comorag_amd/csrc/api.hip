@@ -1432,7 +1432,7 @@ int32_t cmr_index_sorted_scores(cmr_index_t* idx, const float* q, int32_t nq, in
     hipStream_t const s = call.s;
     HIP_TRY(ws->d_q.ensure((size_t)nq * idx->dim * 4));
     HIP_TRY(ws->d_out.ensure((size_t)n * 4));
-    HIP_TRY(ws->d_cand.ensure(cmr_sort_workspace_bytes(n)));
+    HIP_TRY(ws->d_cand.ensure(cmr_sort_workspace_bytes(n, 1, 4)));
     HIP_TRY(hipMemcpyAsync(ws->d_q.p, q, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, s));
     idx->last_route.store(route_code(CMR_ROUTE_SORTED), std::memory_order_relaxed);
     // Several queries: scan + sort of query i + 1 run while the 12 N bytes of query i cross the link on a second stream

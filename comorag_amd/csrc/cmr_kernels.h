@@ -1,4 +1,4 @@
-// Host-callable launchers of the gfx950 kernels (defined in scan_kernels.hip / aux_kernels.hip).
+// Host-callable launchers of the gfx950 kernels (defined in scan_kernels.hip / aux_kernels.hip / sort_kernels.hip).
 // All launchers enqueue on `stream` and return the hipError_t of the launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -128,10 +128,14 @@ hipError_t cmr_launch_tiny_scores(int dtype, const void* corpus, const float* q,
 // per-row top-k (k <= 4096) of a materialised score matrix [nq, ld]
 hipError_t cmr_launch_topk_rows(const float* scores, long long ld, int n, int nq, int k, long long id_base,
                                 int64_t* out_ids, float* out_scores, float* out_min, float* out_max, hipStream_t s);
-// full descending sort of one query's scores (stable LSD radix sort; ties by ascending row)
-size_t cmr_sort_workspace_bytes(long long n);
+// complete ranking by descending score (sort_kernels.hip: one stable LSD radix sort; ties by ascending row).  Workspace of nb segments of
+// n rows, score_bytes 4 (fp32) or 8 (fp64).  fp32: one query, ids (+ id_base) and scores to the caller's buffers.  fp64: scores [nb][n], the
+// first n_out ranks of every query stay in the workspace, at *ids_at [nb][n_out] and *scores_at [nb][n_out].
+size_t cmr_sort_workspace_bytes(long long n, int nb, int score_bytes);
 hipError_t cmr_launch_sort_scores(const float* scores, long long n, long long id_base, void* workspace, int64_t* out_ids,
                                   float* out_scores, hipStream_t s);
+hipError_t cmr_launch_sort_scores_f64(const double* scores, long long n, int nb, long long n_out, void* workspace, int64_t** ids_at,
+                                      double** scores_at, hipStream_t s);
 // shard merge: ids/scores [S][nq][k] -> [nq][k]
 hipError_t cmr_launch_merge_shards(const int64_t* ids, const float* scores, int S, int nq, int k,
                                    int64_t* out_ids, float* out_scores, hipStream_t s);

@@ -47,7 +47,7 @@ struct PprScratch {
     int *seed_v = nullptr, *seed_q = nullptr;
     double* seed_w = nullptr;
     long long seed_cap = 0, out_cap = 0;
-    void* rank = nullptr;              // the ranking's workspace (rank_bytes), allocated and grown by ranked calls only
+    void* rank = nullptr;              // the ranking's workspace (cmr_sort_workspace_bytes), allocated and grown by ranked calls only
     size_t rank_cap = 0;
     // the power iteration of THIS scratch as an instantiated hipGraph (clean + normalise + `iters` steps: every argument is
     // one of this scratch's pointers or a graph constant), keyed by (damping, iters); replayed with one hipGraphLaunch
@@ -483,128 +483,6 @@ __global__ __launch_bounds__(PPR_T) void ppr_gather_batch_kernel(const double* _
     }
 }
 
-// ---- ranking: every passage of every query by descending score, ties by ascending row — the reference's
-// np.argsort(doc_scores)[::-1] and doc_scores[sorted_doc_ids.tolist()] (ComoRAG.py:1101-1105) without the [nb, n_rows] doubles going to
-// the host first.  A segmented, stable LSD radix sort over the doubles launch_gather left in PprScratch::out: 64-bit keys, the passage row
-// (uint32) as payload, 8-bit digits, 8 passes of histogram -> scan -> scatter.  blockIdx.y = query: one set of launches serves the batch, and
-// a query's tiles, counters and order are those of its single call.  Payloads start ascending, every pass is stable: equal scores come by
-// ascending row.  No floating-point operation beyond the key's canonicalisation.
-#define PPR_RANK_TILE CMR_PPR_RANK_TILE
-#define PPR_RANK_PASSES 8
-
-// ascending key = descending score: the complement of the order-preserving code of the double.  -0.0 counts as +0.0; NaN (ppr_update on a
-// cleaned reset vector yields none) sorts behind everything, so the order stays total
-__device__ __forceinline__ u64 ppr_rank_key(double v) {
-    u64 u = (u64)__double_as_longlong(v);
-    if (v != v) return ~0ull;
-    if (u == 0x8000000000000000ull) u = 0ull;
-    return ~((u >> 63) ? ~u : (u | 0x8000000000000000ull));
-}
-
-__global__ __launch_bounds__(PPR_T) void ppr_rank_init_kernel(const double* __restrict__ doc, unsigned n, u64* __restrict__ key, unsigned* __restrict__ val) {
-    const size_t i = (size_t)blockIdx.x * PPR_T + threadIdx.x;
-    if (i >= n) return;
-    const size_t at = (size_t)blockIdx.y * n + i;
-    key[at] = ppr_rank_key(doc[at]);
-    val[at] = (unsigned)i;
-}
-
-// hist[query][digit][tile] = keys of the tile with that digit
-__global__ __launch_bounds__(PPR_T) void ppr_rank_hist_kernel(const u64* __restrict__ key, unsigned n, int shift, unsigned ntiles, unsigned* __restrict__ hist) {
-    __shared__ unsigned cnt[256];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const u64* __restrict__ k = key + (size_t)blockIdx.y * n;
-    const size_t base = (size_t)blockIdx.x * PPR_RANK_TILE;
-    for (unsigned j = threadIdx.x; j < PPR_RANK_TILE; j += PPR_T)
-        if (base + j < n) atomicAdd(&cnt[(unsigned)(k[base + j] >> shift) & 255u], 1u);
-    __syncthreads();
-    hist[((size_t)blockIdx.y * 256 + threadIdx.x) * ntiles + blockIdx.x] = cnt[threadIdx.x];
-}
-
-// exclusive scan of a query's m = 256 * ntiles counters, digit-major: a workgroup per query
-__global__ __launch_bounds__(1024) void ppr_rank_scan_kernel(unsigned* __restrict__ hist_all, unsigned m) {
-    __shared__ unsigned wsum[16];
-    __shared__ unsigned carry_s;
-    unsigned* __restrict__ hist = hist_all + (size_t)blockIdx.x * m;
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (unsigned base = 0; base < m; base += 1024 * 8) {
-        unsigned v[8], local = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const unsigned i = base + tid * 8 + j; v[j] = i < m ? hist[i] : 0u; local += v[j]; }
-        unsigned incl = local;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(incl, off); if (lane >= off) incl += o; }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        unsigned wbase = 0;
-        for (unsigned w = 0; w < wave; ++w) wbase += wsum[w];
-        unsigned run = carry_s + wbase + incl - local;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const unsigned i = base + tid * 8 + j; if (i < m) hist[i] = run; run += v[j]; }
-        __syncthreads();
-        if (tid == 1023) carry_s = run;
-        __syncthreads();
-    }
-}
-
-// Stable scatter of one tile: slices of PPR_T keys in order, waves of a slice in order, lanes of a wave by ballot rank.  The lanes that hold a
-// lane's digit are the AND over its eight bits of ballot(bit) or its complement: 8 ballots, whatever the digit.
-__global__ __launch_bounds__(PPR_T) void ppr_rank_scatter_kernel(const u64* __restrict__ key_in, const unsigned* __restrict__ val_in, unsigned n, int shift, unsigned ntiles,
-                                                                 const unsigned* __restrict__ offs, u64* __restrict__ key_out, unsigned* __restrict__ val_out) {
-    __shared__ unsigned run[256];                 // where the tile's next key of a digit goes
-    __shared__ unsigned wcnt[PPR_T / 64][256];    // the current slice's keys per wave and digit
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t seg = (size_t)blockIdx.y * n;
-    run[tid] = offs[((size_t)blockIdx.y * 256 + tid) * ntiles + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < PPR_T / 64; ++w) wcnt[w][tid] = 0;
-    __syncthreads();
-    const u64 lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    for (unsigned s = 0; s < PPR_RANK_TILE; s += PPR_T) {
-        const size_t first = (size_t)blockIdx.x * PPR_RANK_TILE + s;
-        if (first >= n) break;                    // the whole workgroup: the tile ends here
-        const size_t i = first + tid;
-        const bool ok = i < n;
-        const u64 k = ok ? key_in[seg + i] : 0ull;
-        const unsigned d = (unsigned)(k >> shift) & 255u;
-        u64 peers = __ballot(ok);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool on = (d >> bit) & 1u;
-            const u64 b = __ballot(on);
-            peers &= on ? b : ~b;
-        }
-        const unsigned rank = (unsigned)__popcll(peers & lt);
-        if (ok && rank == 0) wcnt[wave][d] = (unsigned)__popcll(peers);
-        __syncthreads();
-        if (ok) {
-            unsigned pos = run[d] + rank;
-            for (unsigned w = 0; w < wave; ++w) pos += wcnt[w][d];
-            key_out[seg + pos] = k;               // pos < n: an exclusive prefix of the query's n keys plus the keys ahead of this one
-            val_out[seg + pos] = val_in[seg + i];
-        }
-        __syncthreads();
-        unsigned t = 0;
-#pragma unroll
-        for (int w = 0; w < PPR_T / 64; ++w) { t += wcnt[w][tid]; wcnt[w][tid] = 0; }
-        run[tid] += t;
-        __syncthreads();
-    }
-}
-
-// rank r of query b: the row and the bits of its score, gathered from the unranked result — never recomputed
-__global__ __launch_bounds__(PPR_T) void ppr_rank_finish_kernel(const unsigned* __restrict__ val, const double* __restrict__ doc, unsigned n, unsigned n_out,
-                                                                long long* __restrict__ out_ids, double* __restrict__ out_scores) {
-    const size_t r = (size_t)blockIdx.x * PPR_T + threadIdx.x;
-    if (r >= n_out) return;
-    const unsigned id = val[(size_t)blockIdx.y * n + r];
-    out_ids[(size_t)blockIdx.y * n_out + r] = (long long)id;
-    out_scores[(size_t)blockIdx.y * n_out + r] = doc[(size_t)blockIdx.y * n + id];
-}
-
 // ------------------------------------------------------------------------------------------ host
 static unsigned blocks_for(long long n) { return (unsigned)std::max<long long>(1, (n + PPR_T - 1) / PPR_T); }
 static int ppr_width(int nb) { return nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : nb <= 8 ? 8 : 16; }
@@ -771,17 +649,12 @@ static void launch_scatter(cmr_graph* g, PprScratch* sc, const float* scores, lo
                      hipLaunchKernelGGL(ppr_scatter_batch_kernel<BW>, dim3(blocks_for(n)), dim3(PPR_T), 0, s, scores, n, nb, sc->mm_final(), g->vertex_of_row, pnw, sc->reset))
 }
 
-// ---- the ranking tail (kernels: "ranking" above).  What a ranked call asks for: the first n_out ranks of every query.
+// ---- the ranking tail (the sort: sort_kernels.hip).  What a ranked call asks for: the first n_out ranks of every query by
+// descending score, ties by ascending row, without the [nb, n_rows] doubles going to the host first.
 struct PprRankOut { int64_t n_out; int64_t* ids; };
-static_assert(PPR_T == 256, "the ranking's kernels give a thread per 8-bit digit");
 
-// Workspace of nb queries of n rows: two key buffers and two payload buffers (the passes alternate) and the counters —
-// 24 bytes per row and query + 1 KiB per tile and query.  After the last pass the keys are dead: the finish kernel writes the ids over
-// the second key buffer and the scores over the first, and the host copies both from there.
-static size_t rank_tiles(long long n) { return (size_t)((n + PPR_RANK_TILE - 1) / PPR_RANK_TILE); }
-static size_t rank_bytes(long long n, int nb) { return (size_t)nb * ((size_t)n * 24 + rank_tiles(n) * 256 * 4); }
 static int ensure_rank(PprScratch* sc, long long n, int nb) {
-    const size_t need = rank_bytes(n, nb);
+    const size_t need = cmr_sort_workspace_bytes(n, nb, 8);
     if (need <= sc->rank_cap) return CMR_OK;
     if (sc->rank) HIP_TRY(hipFree(sc->rank));
     sc->rank = nullptr; sc->rank_cap = 0;
@@ -790,26 +663,11 @@ static int ensure_rank(PprScratch* sc, long long n, int nb) {
     sc->rank_cap = need;
     return CMR_OK;
 }
-// sc->out [nb][n] -> the host's ids [nb][n_out] and scores [nb][n_out]: 2 + 3 * PPR_RANK_PASSES launches and two copies on `s`
+// sc->out [nb][n] -> the host's ids [nb][n_out] and scores [nb][n_out]: the sort's launches and two copies on `s`
 static int rank_and_copy(PprScratch* sc, long long n, int nb, const PprRankOut& rk, double* out_scores, hipStream_t s) {
-    const size_t rows = (size_t)nb * n;
-    const unsigned un = (unsigned)n, ntiles = (unsigned)rank_tiles(n);
-    u64 *key0 = (u64*)sc->rank, *key1 = key0 + rows;
-    unsigned *val0 = (unsigned*)(key1 + rows), *val1 = val0 + rows, *hist = val1 + rows;
-    hipLaunchKernelGGL(ppr_rank_init_kernel, dim3(blocks_for(n), nb), dim3(PPR_T), 0, s, sc->out, un, key0, val0);
-    u64 *ki = key0, *ko = key1;
-    unsigned *vi = val0, *vo = val1;
-    for (int pass = 0; pass < PPR_RANK_PASSES; ++pass) {
-        hipLaunchKernelGGL(ppr_rank_hist_kernel, dim3(ntiles, nb), dim3(PPR_T), 0, s, ki, un, 8 * pass, ntiles, hist);
-        hipLaunchKernelGGL(ppr_rank_scan_kernel, dim3(nb), dim3(1024), 0, s, hist, 256u * ntiles);
-        hipLaunchKernelGGL(ppr_rank_scatter_kernel, dim3(ntiles, nb), dim3(PPR_T), 0, s, ki, vi, un, 8 * pass, ntiles, hist, ko, vo);
-        std::swap(ki, ko);
-        std::swap(vi, vo);
-    }
-    long long* ids_dev = (long long*)ko;          // the order is in vi; both key buffers are dead: ko == key1, ki == key0 after 8 swaps
-    double* scores_dev = (double*)ki;
-    hipLaunchKernelGGL(ppr_rank_finish_kernel, dim3(blocks_for(rk.n_out), nb), dim3(PPR_T), 0, s, vi, sc->out, un, (unsigned)rk.n_out, ids_dev, scores_dev);
-    HIP_TRY(hipGetLastError());
+    int64_t* ids_dev = nullptr;
+    double* scores_dev = nullptr;
+    HIP_TRY(cmr_launch_sort_scores_f64(sc->out, n, nb, rk.n_out, sc->rank, &ids_dev, &scores_dev, s));
     HIP_TRY(hipMemcpyAsync(rk.ids, ids_dev, (size_t)nb * rk.n_out * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out_scores, scores_dev, (size_t)nb * rk.n_out * 8, hipMemcpyDeviceToHost, s));
     return CMR_OK;
@@ -889,7 +747,7 @@ static int ppr_graph_run(cmr_graph* g, const double* reset, int nb, double dampi
         if (rk) {
             // (the map cannot be replaced meanwhile: cmr_graph_set_passage_vertices waits for the scratch's holder)
             const long long n = g->n_rows;
-            if (rk->n_out > n || (long long)nb * n > sc->out_cap || rank_bytes(n, nb) > sc->rank_cap)
+            if (rk->n_out > n || (long long)nb * n > sc->out_cap || cmr_sort_workspace_bytes(n, nb, 8) > sc->rank_cap)
                 return cmr_fail(CMR_ERR_INVALID, "the passage-vertex map changed during the call");
             launch_gather(sc, res, g->vertex_of_row, n, nb, sc->out, s);
             HIP_TRY(hipGetLastError());
@@ -971,7 +829,7 @@ static int ppr_index_run(cmr_index_t* idx, cmr_graph* g, const float* q_f32, int
         HIP_TRY(hipGetLastError());
         if (rk) {       // the ranking tail: out_doc_scores is [nb][n_out]
             if (rk->n_out > n) return cmr_fail(CMR_ERR_INVALID, "n_out = %lld exceeds the %lld passage rows", (long long)rk->n_out, n);
-            if (rank_bytes(n, nb) > sc->rank_cap) return cmr_fail(CMR_ERR_INVALID, "the passage-vertex map changed during the call");
+            if (cmr_sort_workspace_bytes(n, nb, 8) > sc->rank_cap) return cmr_fail(CMR_ERR_INVALID, "the passage-vertex map changed during the call");
             return rank_and_copy(sc, n, nb, *rk, out_doc_scores, s);
         }
         HIP_TRY(hipMemcpyAsync(out_doc_scores, sc->out, (size_t)nb * n * 8, hipMemcpyDeviceToHost, s));

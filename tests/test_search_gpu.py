@@ -367,20 +367,15 @@ def test_full_scores(dtype):
     idx.close()
 
 
-@pytest.mark.parametrize("dtype,n", [("bf16", 1), ("bf16", 2047), ("bf16", 2049), ("f32", 70001), ("bf16", 300017)])
-def test_sorted_scores_full_ranking(dtype, n):
-    """cmr_index_sorted_scores: all N rows, score descending, ties by ascending row — bit-identical
-    to sorting the library's own full-score vector with the exported rule."""
+def _assert_full_ranking(dtype, X, Q):
+    """sorted_scores(Q) against the exported rule applied to the library's own scores(Q); returns the ids"""
     from comorag_amd.index import DenseIndex
-    d = 64
-    X, Q = _mk(n, d, 3, seed=21)
-    if n > 100:                         # exact ties: duplicate rows far apart, plus a block of identical rows
-        X[n // 2] = X[7]; X[n - 1] = X[7]; X[40:60] = X[40]
-    idx = DenseIndex(d, dtype); idx.append(X)
+    n, nq = len(X), len(Q)
+    idx = DenseIndex(X.shape[1], dtype); idx.append(X)
     s = idx.scores(Q)
     ids, sc, mn, mx = idx.sorted_scores(Q)
-    assert ids.shape == (3, n) and sc.shape == (3, n)
-    for i in range(3):
+    assert ids.shape == (nq, n) and sc.shape == (nq, n)
+    for i in range(nq):
         order = np.lexsort((np.arange(n), -s[i].astype(np.float64)))      # score desc, row asc
         np.testing.assert_array_equal(ids[i], order)
         np.testing.assert_array_equal(sc[i], s[i][order])
@@ -388,6 +383,39 @@ def test_sorted_scores_full_ranking(dtype, n):
     exact = orc.exact_scores_f64(ROUND[dtype](X), ROUND[dtype](Q))
     np.testing.assert_allclose(sc, np.take_along_axis(exact, ids, 1), atol=ERR, rtol=0)
     idx.close()
+    return ids
+
+
+# sizes around the places where the sort's paths change: a wave (64), a slice (256), a tile (2048), several tiles with a ragged end
+@pytest.mark.parametrize("dtype,n", [("bf16", 1), ("bf16", 2), ("bf16", 63), ("bf16", 64), ("bf16", 65), ("bf16", 255), ("bf16", 256), ("bf16", 257),
+                                     ("f32", 257), ("bf16", 2047), ("bf16", 2048), ("bf16", 2049), ("bf16", 3 * 2048 + 5), ("f32", 3 * 2048 + 5),
+                                     ("f32", 70001), ("bf16", 300017)])
+def test_sorted_scores_full_ranking(dtype, n):
+    """cmr_index_sorted_scores: all N rows, score descending, ties by ascending row — bit-identical
+    to sorting the library's own full-score vector with the exported rule."""
+    X, Q = _mk(n, 64, 3, seed=21)
+    if n > 100:                         # exact ties: duplicate rows far apart, plus a block of identical rows
+        X[n // 2] = X[7]; X[n - 1] = X[7]; X[40:60] = X[40]
+    _assert_full_ranking(dtype, X, Q)
+
+
+@pytest.mark.parametrize("n", [2049, 3 * 2048 + 5])
+def test_sorted_scores_every_row_identical(n):
+    """Every key equal: each pass has a single digit and every lane of a wave is every other lane's peer — the order is the rows' own."""
+    X, Q = _mk(n, 64, 3, seed=23)
+    X[:] = X[0]
+    ids = _assert_full_ranking("bf16", X, Q)
+    for i in range(3):
+        np.testing.assert_array_equal(ids[i], np.arange(n))
+
+
+def test_sorted_scores_one_signed():
+    """Rows abs(X) with the queries +abs(q) and -abs(q): the sign bit is constant over a query (the top digit is a single bucket), and the
+    second query takes the negative branch of the float code on all of its rows."""
+    X, Q = _mk(257, 64, 1, seed=24)
+    X = np.abs(X)
+    X[200] = X[7]; X[40:60] = X[40]
+    _assert_full_ranking("f32", X, np.concatenate([np.abs(Q), -np.abs(Q)]))
 
 
 def test_dense_passage_retrieval_device_sort_matches_reference_lines():
