@@ -155,7 +155,7 @@ hipError_t cmr_launch_pool(const void* hidden, int hidden_dtype, const int64_t* 
 int cmr_pool_splits(int b, int l, int d);
 // encoder layer pieces (encoder_kernels.hip): masked attention over a packed [b*L, 3*hidden] projection (head width 64; bf16 / fp16,
 // or fp32 end to end on the f32-input MFMA), LayerNorm(y + bias + residual) (bf16 / fp16 / fp32, d % 4 == 0, d <= 2048; bias / residual may be NULL)
-hipError_t cmr_launch_attention(const void* qkv, int dtype, const int* lens, int b, int L, int n_heads, void* out, hipStream_t s);
+hipError_t cmr_launch_attention(const void* qkv, int dtype, const int* lens, int b, int L, int n_heads, int head_dim /* 64 or 32 */, void* out, hipStream_t s);
 hipError_t cmr_launch_embed_layernorm(const long long* ids, const long long* tt, const void* word, const void* pos, const void* type,
                                       const void* gamma, const void* beta, float eps, long long rows, int L, int d, int vocab, int n_pos,
                                       int n_types, int pos_off, int dtype, void* out, hipStream_t s);

@@ -1,6 +1,6 @@
 // Encoder-side gfx950 kernels of libcomorag_hip.so: the two memory-/latency-shaped pieces of a BERT layer that are not GEMMs.
 //
-//   attn_fwd_kernel   softmax(Q K^T / sqrt(64)) V of one (sequence, head, 128-query block) per workgroup, 16-bit in / out,
+//   attn_fwd_kernel   softmax(Q K^T / sqrt(HD)) V of one (sequence, head, 128-query block) per workgroup, heads HD = 64 or 32 wide, 16-bit in / out,
 //                     fp32 scores and accumulators, keys beyond the sequence's length masked (right-padded mini-batches).
 //                     Replaces the scaled-dot-product-attention call inside transformers' BertSelfAttention, i.e. part of
 //                     `self.embedding_model(**inputs)` at embedding_model/BGEEmbedding.py:119.
@@ -13,7 +13,7 @@
 // four floats — fp32 (EncVec below).
 //
 // Attention layout.  Q, K, V are column slices of ONE packed projection output qkv[b*L, 3*hidden] (the host side multiplies by
-// the concatenated query/key/value weights once): head h reads columns h*64 (Q), hidden + h*64 (K), 2*hidden + h*64 (V).
+// the concatenated query/key/value weights once): head h reads columns h*HD (Q), hidden + h*HD (K), 2*hidden + h*HD (V); below for HD = 64.
 // A wave owns 32 query rows.  Scores are computed TRANSPOSED, S^T = K Q^T (A operand = a 32-key tile read from LDS, B operand
 // = the wave's Q rows, loaded once from global memory in MFMA lane order), so that in the 32x32 accumulator layout
 // (cmr_acc_row) lane l holds column q = l & 31: every softmax statistic of a query row is lane-local except one cross-half
@@ -156,10 +156,29 @@ typedef short att_v4s __attribute__((ext_vector_type(4)));
 // -> LDS, one barrier) is the longest leg of this kernel (26 % at 4 waves: DESIGN 4.10) and costs the same per chunk however many
 // query rows consume it; every thread then stages ONE 16-byte segment of K and of V instead of two.  Used for sequences of >= 256
 // (padded) tokens; shorter mini-batches keep 4 waves (half of an 8-wave workgroup would hold padding rows only).
-template <int DT, int NW>
+//
+// HD = head width, 64 or 32 (bge-small / MiniLM / e5-small: 384 hidden, 12 heads).  Same algorithm and data flow; with HD = 32 the wave's Q rows
+// are TWO k-steps (qf[2]), a score tile costs 2 MFMAs, and PV has ONE 32-column output tile (o[1]): 8 MFMAs per tile pair and chunk
+// instead of 16, 16 accumulator registers instead of 32.  A K / V row is 64 B — four 16-byte segments — so a 64-key chunk is 256 segments
+// of K and of V: one staging pass of 4 waves (thread -> row tid >> 2, segment tid & 3).  HD = 32 runs on 4 waves for every l: an 8-wave
+// workgroup would leave half its threads without a segment to stage, and the staging it amortises is half the 64-wide kernel's already.
+#define ATT_KSTR32 40         // HD = 32, K rows in LDS: 32 elements + 8 of padding (80 B = 5 slots of 16 B, odd: ds_read_b128 of 16 consecutive rows hit 16 different slots)
+#ifndef ATT_VSTR32
+#define ATT_VSTR32 32         // HD = 32, V rows in LDS: NO padding (64 B).  A 32-lane group of ds_read_b64_tr_b16 reads ALL 32 d of four consecutive keys:
+#endif                        // with 64-byte rows that is 256 contiguous bytes = the 64 banks once each; ds_write_b128 of 8 lanes covers two whole rows (128 B, 32 banks).
+                              // Any multiple of 8 elements >= 32 is correct (8-byte reads, 16-byte writes).  Measured, us per call at 32 x 512 x 12 heads, full sequences,
+                              // bf16 / f16, medians of 9 regions x 40 calls, two processes each on one box: 32: 32.9, 31.9 / 31.4, 31.4   40: 32.5, 32.6 / 31.5, 32.1
+                              // 48: 33.3, 33.3 / 31.7, 31.6 — inside the regions' own spread (bf16 min .. max 31.1 .. 38.6): the smallest footprint stays.
+template <int DT, int NW, int HD>
 __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_kernel(const unsigned short* __restrict__ qkv, const int* __restrict__ lens, int L, int hidden,
-                                                           int n_heads, int n_qblocks, int total, float sc /* log2(e) / sqrt(64) */,
+                                                           int n_heads, int n_qblocks, int total, float sc /* log2(e) / sqrt(HD) */,
                                                            unsigned short* __restrict__ out) {
+    static_assert(HD == 64 || HD == 32, "head width 64 or 32");
+    static_assert(HD == 64 || (ATT_VTR && !ATT_SWZL && !ATT_DMA), "the development layouts (ATT_VTR = 0, ATT_SWZL, ATT_DMA) are written for 64-wide heads");
+    static_assert(HD == 64 || NW == 4, "32-wide heads: a chunk is one staging pass of 4 waves");
+    static_assert(ATT_VSTR32 >= 32 && ATT_VSTR32 % 8 == 0, "V rows of 32 elements, 16-byte aligned");
+    constexpr int KSTR = HD == 64 ? ATT_KSTR : ATT_KSTR32, VSTR = HD == 64 ? ATT_VSTR : ATT_VSTR32;      // LDS row strides, elements
+    constexpr int KS = HD / 16, DTN = HD / 32, SEGS = HD / 8;      // k-steps of QK^T; 32-column output tiles of PV; 16-byte segments of a K / V row
 #if ATT_SWZL
     // [key][64 d] unpadded (two rows per 256-byte bank row), 16-byte segment sg of row r at slot sg ^ f(r), f = ATT_SWZ: a DMA instruction lands
     // 8 rows x 128 B lane-linear (the lane picks the SOURCE segment that belongs in its slot).  f permutes the bits of u = (r >> 1) & 7 —
@@ -173,8 +192,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
     __shared__ __attribute__((aligned(1024))) unsigned short k_lds[2][ATT_CHUNK * 64];
     __shared__ __attribute__((aligned(1024))) unsigned short v_lds[2][ATT_CHUNK * 64];
 #else
-    __shared__ __attribute__((aligned(16))) unsigned short k_lds[2][ATT_CHUNK * ATT_KSTR];
-    __shared__ __attribute__((aligned(16))) unsigned short v_lds[2][64 * ATT_VSTR];      // ATT_VTR: [key][d], else [d][key]
+    __shared__ __attribute__((aligned(16))) unsigned short k_lds[2][ATT_CHUNK * KSTR];
+    __shared__ __attribute__((aligned(16))) unsigned short v_lds[2][64 * VSTR];      // ATT_VTR: [key][d], else [d][key]
 #endif
     // workgroup id -> work item.  Hardware deals workgroup ids round-robin over the 8 XCDs: the query blocks of one (sequence, head)
     // pair stay on ONE XCD, so the pair's K / V come out of that XCD's L2 after the first block; the PAIRS go round the XCDs, so every
@@ -187,31 +206,32 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
     //  leaves the short ones to fill the tail)
     const int qb = j % n_qblocks, head = pair % n_heads, seq = total / (n_qblocks * n_heads) - 1 - pair / n_heads;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5, c = lane & 31;
-    constexpr int QBLOCK = NW * 32, PASSES = 8 / NW, PROWS = NW * 8;      // rows per workgroup; staging passes of PROWS K / V rows each
+    constexpr int QBLOCK = NW * 32, PROWS = NW * 64 / SEGS, PASSES = ATT_CHUNK / PROWS;      // rows per workgroup; staging passes of PROWS K / V rows each
     const int q0 = qb * QBLOCK;
     int len = lens[seq];
     len = len < L ? len : L;
     const size_t rs = (size_t)3 * hidden;
-    const unsigned short* qbase = qkv + (size_t)seq * L * rs + (size_t)head * 64;
+    const unsigned short* qbase = qkv + (size_t)seq * L * rs + (size_t)head * HD;
     const unsigned short* kbase = qbase + hidden;
     const unsigned short* vbase = qbase + 2 * (size_t)hidden;
-    unsigned short* obase = out + (size_t)seq * L * hidden + (size_t)head * 64;
+    unsigned short* obase = out + (size_t)seq * L * hidden + (size_t)head * HD;
 
     if (q0 >= len) {                                   // a block of padding rows only: zeros, nothing reads them but LayerNorm
-        const int row = q0 + (tid >> 1);
+        const int row = q0 + (tid >> 1);               // (two threads per row, half a head row each)
         if (row < L) {
-            uint4* dst = reinterpret_cast<uint4*>(obase + (size_t)row * hidden + (tid & 1) * 32);
+            uint4* dst = reinterpret_cast<uint4*>(obase + (size_t)row * hidden + (tid & 1) * (HD / 2));
             const uint4 z = make_uint4(0, 0, 0, 0);
-            dst[0] = z; dst[1] = z; dst[2] = z; dst[3] = z;
+#pragma unroll
+            for (int i = 0; i < HD / 16; ++i) dst[i] = z;
         }
         return;
     }
 
-    // the wave's 32 query rows as B operands of the four k-steps over d (lane: row c, d = 16*ks + 8*g + [0,8))
+    // the wave's 32 query rows as B operands of the KS k-steps over d (lane: row c, d = 16*ks + 8*g + [0,8))
     const int qrow = q0 + wave * 32 + c;
-    v4u qf[4];
+    v4u qf[KS];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
+    for (int ks = 0; ks < KS; ++ks) {
         qf[ks] = v4u{0, 0, 0, 0};
         if (qrow < L) qf[ks] = *reinterpret_cast<const v4u*>(qbase + (size_t)qrow * rs + ks * 16 + g * 8);
     }
@@ -239,8 +259,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
         }
     };
 #endif
-    // chunk staging.  K: thread -> rows r and r + 32, 16-byte segment seg.  V: thread -> the key pair pi, d segment dseg.
-    const int kr = tid >> 3, kseg = tid & 7;
+    // chunk staging.  K: thread -> rows r and r + 32, 16-byte segment seg (HD = 32: the one row tid >> 2, segment tid & 3).  V: thread -> the key pair pi, d segment dseg.
+    const int kr = tid >> (HD == 64 ? 3 : 2), kseg = tid & (SEGS - 1);
     const int pi = wave * 8 + (lane & 7), dseg = lane >> 3;
     v4u kreg[PASSES], vreg[PASSES];
     auto load_chunk = [&](int ch) {
@@ -262,9 +282,9 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
 #pragma unroll
         for (int h = 0; h < (ATT_ABL == 6 ? 0 : PASSES); ++h) *reinterpret_cast<v4u*>(&v_lds[buf][(kr + PROWS * h) * 64 + ((kseg ^ ATT_SWZ(kr + PROWS * h)) * 8)]) = vreg[h];
 #elif ATT_VTR
-        for (int h = 0; h < PASSES; ++h) *reinterpret_cast<v4u*>(&k_lds[buf][(kr + PROWS * h) * ATT_KSTR + kseg * 8]) = kreg[h];
+        for (int h = 0; h < PASSES; ++h) *reinterpret_cast<v4u*>(&k_lds[buf][(kr + PROWS * h) * KSTR + kseg * 8]) = kreg[h];
 #pragma unroll
-        for (int h = 0; h < (ATT_ABL == 6 ? 0 : PASSES); ++h) *reinterpret_cast<v4u*>(&v_lds[buf][(kr + PROWS * h) * ATT_VSTR + kseg * 8]) = vreg[h];
+        for (int h = 0; h < (ATT_ABL == 6 ? 0 : PASSES); ++h) *reinterpret_cast<v4u*>(&v_lds[buf][(kr + PROWS * h) * VSTR + kseg * 8]) = vreg[h];
 #else
         for (int h = 0; h < PASSES; ++h) *reinterpret_cast<v4u*>(&k_lds[buf][(kr + PROWS * h) * ATT_KSTR + kseg * 8]) = kreg[h];
 #pragma unroll
@@ -276,9 +296,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
 #endif
     };
 
-    f32x16 o[2];
+    f32x16 o[DTN];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { o[0][r] = 0.0f; o[1][r] = 0.0f; }
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+        for (int dt = 0; dt < DTN; ++dt) o[dt][r] = 0.0f;
     float m = ATT_NEG, lsum = 0.0f;
     const int nch = (len + ATT_CHUNK - 1) / ATT_CHUNK;
 #if ATT_DMA
@@ -303,11 +325,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[t][r] = 0.0f;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
+            for (int ks = 0; ks < KS; ++ks) {
 #if ATT_SWZL
                 const v4u kf = *reinterpret_cast<const v4u*>(&k_lds[ATT_ABL == 4 ? 0 : cur][(t * 32 + c) * 64 + (((ks * 2 + g) ^ ATT_SWZ(c)) * 8)]);
 #else
-                const v4u kf = *reinterpret_cast<const v4u*>(&k_lds[ATT_ABL == 4 ? 0 : cur][(t * 32 + c) * ATT_KSTR + ks * 16 + g * 8]);
+                const v4u kf = *reinterpret_cast<const v4u*>(&k_lds[ATT_ABL == 4 ? 0 : cur][(t * 32 + c) * KSTR + ks * 16 + g * 8]);
 #endif
                 if (ATT_ABL != 2) s[t] = CmrBlk<DT>::mma(kf, qf[ks], s[t]);
                 else s[t][ks] += __uint_as_float(kf[0] & 0x3F800000u);
@@ -364,11 +386,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
             lsum = fmaf(lsum, alpha, ps);
             m = mn;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int dt = 0; dt < DTN; ++dt) o[dt][r] *= alpha;
         } else {
             lsum += ps;
         }
-        // O^T += V^T P^T: four k-steps of 16 keys; the P registers 8*sp .. 8*sp + 7 of tile t are the B operand as they are
+        // O^T += V^T P^T: four k-steps of 16 keys, DTN output tiles each; the P registers 8*sp .. 8*sp + 7 of tile t are the B operand as they are
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -380,7 +404,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
                 pb[3] = enc_pack2<DT>(s[t][8 * sp + 6], s[t][8 * sp + 7]);
                 const int kb = t * 32 + sp * 16 + 4 * g;
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
+                for (int dt = 0; dt < DTN; ++dt) {
 #if ATT_VTR
                     // the A operand of lane l: V[kb + {0..3, 8..11}][dt*32 + c].  A transposing read hands lane i of a 16-lane group column i of the
                     // 4 x 16 block whose row (i >> 2), columns 4 * (i & 3) .. + 3 that lane addresses (tools/probe/tr_probe.hip): rows = keys
@@ -392,8 +416,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
                     const unsigned short* vblk = &v_lds[cur][vrow_ * 64 + vslot_ * 8 + 4 * (lane & 1)];
                     const unsigned short* vblk8 = &v_lds[cur][(vrow_ + 8) * 64 + (vslot_ ^ 2) * 8 + 4 * (lane & 1)];
 #else
-                    const unsigned short* vblk = &v_lds[cur][(kb + ((lane & 15) >> 2)) * ATT_VSTR + dt * 32 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3)];
-                    const unsigned short* vblk8 = vblk + 8 * ATT_VSTR;
+                    const unsigned short* vblk = &v_lds[cur][(kb + ((lane & 15) >> 2)) * VSTR + dt * 32 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3)];
+                    const unsigned short* vblk8 = vblk + 8 * VSTR;
 #endif
                     typedef __attribute__((address_space(3))) att_v4s* lds_v4s;
                     const att_v4s lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s)vblk);
@@ -420,7 +444,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
     const float inv = 1.0f / (lsum + __shfl_xor(lsum, 32));
     if (qrow < L) {
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
+        for (int dt = 0; dt < DTN; ++dt)
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {           // registers 4*rr .. 4*rr + 3 = d columns dt*32 + 8*rr + 4*g + [0,4)
                 uint2 w;
@@ -446,12 +470,22 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : ATT_MIN_WG) void attn_fwd_ke
 // registers while this one is multiplied, two barriers per chunk) and one workgroup shape (4 waves, 128 query rows) serves every l.
 // The exponent is (s - max) * sc, not fma(s, sc, -max * sc): the difference is rounded where it is small, so the weights of the keys
 // that matter carry no rounding error of the (large) maximum — 32 more VALU instructions per chunk next to 8192 MFMA cycles.
+// HD = 32 (the 384-hidden tier): j runs 0..3 over the same d = 8j + 4g + e, PV has one output tile (o[1]) — 64 + 32 MFMAs per chunk and wave
+// instead of 128 + 128; a row is eight 16-byte segments, so a chunk is two staging passes of 32 rows.  K rows 36 floats apart (144 B = 9 slots
+// of 16 B, odd: sixteen different slots again), V rows 40 floats apart (4 rows = 160 floats = 32 banks mod 64, as 72).  19 KiB of LDS.
 #define ATT32_KSTR 68
 #define ATT32_VSTR 72
+#define ATT32_KSTR_HD32 36
+#define ATT32_VSTR_HD32 40
+template <int HD>
 __global__ __launch_bounds__(256, 2) void attn_fwd_f32_kernel(const float* __restrict__ qkv, const int* __restrict__ lens, int L, int hidden, int n_heads,
-                                                              int n_qblocks, int total, float sc /* log2(e) / sqrt(64) */, float* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float k_lds[ATT_CHUNK * ATT32_KSTR];
-    __shared__ __attribute__((aligned(16))) float v_lds[ATT_CHUNK * ATT32_VSTR];
+                                                              int n_qblocks, int total, float sc /* log2(e) / sqrt(HD) */, float* __restrict__ out) {
+    static_assert(HD == 64 || HD == 32, "head width 64 or 32");
+    constexpr int KSTR = HD == 64 ? ATT32_KSTR : ATT32_KSTR_HD32, VSTR = HD == 64 ? ATT32_VSTR : ATT32_VSTR_HD32;      // LDS row strides, floats
+    constexpr int NJ = HD / 8, DTN = HD / 32, SEGS = HD / 4;       // QK^T steps of 4 + 4 d; 32-column output tiles of PV; 16-byte segments of a K / V row
+    constexpr int SROWS = 256 / SEGS, PASSES = ATT_CHUNK / SROWS;  // staging passes of SROWS K / V rows each
+    __shared__ __attribute__((aligned(16))) float k_lds[ATT_CHUNK * KSTR];
+    __shared__ __attribute__((aligned(16))) float v_lds[ATT_CHUNK * VSTR];
     // workgroup id -> (sequence, head, query block): as attn_fwd_kernel
     const int xcd = (int)(blockIdx.x & 7), j0 = (int)(blockIdx.x >> 3);
     const int pair = (j0 / n_qblocks) * 8 + xcd;
@@ -462,39 +496,40 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_kernel(const float* __res
     int len = lens[seq];
     len = len < L ? len : L;
     const size_t rs = (size_t)3 * hidden;
-    const float* qbase = qkv + (size_t)seq * L * rs + (size_t)head * 64;
+    const float* qbase = qkv + (size_t)seq * L * rs + (size_t)head * HD;
     const float* kbase = qbase + hidden;
     const float* vbase = qbase + 2 * (size_t)hidden;
-    float* obase = out + (size_t)seq * L * hidden + (size_t)head * 64;
+    float* obase = out + (size_t)seq * L * hidden + (size_t)head * HD;
 
     if (q0 >= len) {                                   // a block of padding rows only: zeros
         const int row = q0 + (tid >> 1);
         if (row < L) {
-            float4* dst = reinterpret_cast<float4*>(obase + (size_t)row * hidden + (tid & 1) * 32);
+            float4* dst = reinterpret_cast<float4*>(obase + (size_t)row * hidden + (tid & 1) * (HD / 2));
             const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) dst[i] = z;
+            for (int i = 0; i < HD / 8; ++i) dst[i] = z;
         }
         return;
     }
 
     // the wave's 32 query rows as B operands: lane (c, g) holds d = 8j + 4g + [0,4) of row q0 + 32 wave + c in qf[j]
     const int qrow = q0 + wave * 32 + c;
-    float4 qf[8];
+    float4 qf[NJ];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < NJ; ++j) {
         qf[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (qrow < L) qf[j] = *reinterpret_cast<const float4*>(qbase + (size_t)qrow * rs + 8 * j + 4 * g);
     }
 
-    // chunk staging: thread -> 16-byte segment sseg of rows srow + 16 h, h = 0..3, of K and of V; rows behind the sequence's end are zeros
-    const int srow = tid >> 4, sseg = tid & 15;
-    float4 kreg[4], vreg[4];
+    // chunk staging: thread -> 16-byte segment sseg of rows srow + SROWS h (16 h, h = 0..3; HD = 32: 32 h, h = 0..1) of K and of V; rows behind
+    // the sequence's end are zeros
+    const int srow = tid >> (HD == 64 ? 4 : 3), sseg = tid & (SEGS - 1);
+    float4 kreg[PASSES], vreg[PASSES];
     auto load_chunk = [&](int ch) {
         const int k0 = ch * ATT_CHUNK;
 #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int key = k0 + srow + 16 * h;
+        for (int h = 0; h < PASSES; ++h) {
+            const int key = k0 + srow + SROWS * h;
             kreg[h] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             vreg[h] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (key < len) {
@@ -505,15 +540,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_kernel(const float* __res
     };
     auto store_chunk = [&]() {
 #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            *reinterpret_cast<float4*>(&k_lds[(srow + 16 * h) * ATT32_KSTR + sseg * 4]) = kreg[h];
-            *reinterpret_cast<float4*>(&v_lds[(srow + 16 * h) * ATT32_VSTR + sseg * 4]) = vreg[h];
+        for (int h = 0; h < PASSES; ++h) {
+            *reinterpret_cast<float4*>(&k_lds[(srow + SROWS * h) * KSTR + sseg * 4]) = kreg[h];
+            *reinterpret_cast<float4*>(&v_lds[(srow + SROWS * h) * VSTR + sseg * 4]) = vreg[h];
         }
     };
 
-    f32x16 o[2];
+    f32x16 o[DTN];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { o[0][r] = 0.0f; o[1][r] = 0.0f; }
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+        for (int dt = 0; dt < DTN; ++dt) o[dt][r] = 0.0f;
     float m = ATT_NEG, lsum = 0.0f;
     const int nch = (len + ATT_CHUNK - 1) / ATT_CHUNK;
     load_chunk(0);
@@ -529,10 +566,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_kernel(const float* __res
             for (int r = 0; r < 16; ++r) s[t][r] = 0.0f;
         }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < NJ; ++j) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const float4 kf = *reinterpret_cast<const float4*>(&k_lds[(t * 32 + c) * ATT32_KSTR + 8 * j + 4 * g]);
+                const float4 kf = *reinterpret_cast<const float4*>(&k_lds[(t * 32 + c) * KSTR + 8 * j + 4 * g]);
                 s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[j].x, s[t], 0, 0, 0);
                 s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[j].y, s[t], 0, 0, 0);
                 s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[j].z, s[t], 0, 0, 0);
@@ -573,23 +610,25 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_kernel(const float* __res
         lsum = fmaf(lsum, alpha, ps2[0] + ps2[1]);
         m = mn;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int dt = 0; dt < DTN; ++dt) o[dt][r] *= alpha;
         // O^T += V^T P^T: register r of tile t is the B operand of the k-step over keys {row(r), row(r) + 4} of the tile
-        const float* vp = &v_lds[4 * g * ATT32_VSTR + c];
+        const float* vp = &v_lds[4 * g * VSTR + c];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int kr = t * 32 + (r & 3) + 8 * (r >> 2);
-                o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[kr * ATT32_VSTR], s[t][r], o[0], 0, 0, 0);
-                o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[kr * ATT32_VSTR + 32], s[t][r], o[1], 0, 0, 0);
+#pragma unroll
+                for (int dt = 0; dt < DTN; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[kr * VSTR + 32 * dt], s[t][r], o[dt], 0, 0, 0);
             }
         __syncthreads();                               // everybody has read this chunk: the next one may overwrite it
     }
     const float inv = 1.0f / (lsum + __shfl_xor(lsum, 32));
     if (qrow < L) {
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
+        for (int dt = 0; dt < DTN; ++dt)
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr)             // registers 4*rr .. 4*rr + 3 = d columns dt*32 + 8*rr + 4*g + [0,4)
                 *reinterpret_cast<float4*>(obase + (size_t)qrow * hidden + dt * 32 + 8 * rr + 4 * g) =
@@ -597,15 +636,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_f32_kernel(const float* __res
     }
 }
 
+// sc = log2(e) / sqrt(HD): the scores' scale folded into the base-2 exponent
+template <int HD> static constexpr float att_scale() { return HD == 64 ? 1.4426950408889634f * 0.125f : 1.4426950408889634f * 0.17677669529663687f; }
+
+template <int HD>
 static hipError_t launch_attention_f32(const void* qkv, const int* lens, int b, int L, int n_heads, void* out, hipStream_t s) {
-    const int hidden = n_heads * 64;
+    const int hidden = n_heads * HD;
     const int n_qblocks = (L + ATT_QBLOCK - 1) / ATT_QBLOCK;
     const long long total = (long long)n_qblocks * n_heads * b;
     if (total > (1LL << 28)) return hipErrorInvalidValue;
     const long long pairs = (long long)n_heads * b;
     const int per = (int)((pairs + 7) / 8) * n_qblocks;
-    const float sc = 1.4426950408889634f * 0.125f;
-    hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3((unsigned)(per * 8)), dim3(256), 0, s, reinterpret_cast<const float*>(qkv), lens, L, hidden, n_heads, n_qblocks,
+    const float sc = att_scale<HD>();
+    hipLaunchKernelGGL(attn_fwd_f32_kernel<HD>, dim3((unsigned)(per * 8)), dim3(256), 0, s, reinterpret_cast<const float*>(qkv), lens, L, hidden, n_heads, n_qblocks,
                        (int)total, sc, reinterpret_cast<float*>(out));
     return hipGetLastError();
 }
@@ -613,26 +656,37 @@ static hipError_t launch_attention_f32(const void* qkv, const int* lens, int b, 
 #ifndef ATT_WAVES_MODE
 #define ATT_WAVES_MODE 0      // 0: eight waves per workgroup for mini-batches of >= 256 (padded) tokens, four below; 4 / 8: always
 #endif
-template <int DT, int NW>
+template <int DT, int NW, int HD>
 static hipError_t launch_attention(const void* qkv, const int* lens, int b, int L, int n_heads, void* out, hipStream_t s) {
     static_assert(ATT_VTR || NW == 4, "the transposed-store layout of V is a 4-wave mapping");
-    const int hidden = n_heads * 64;
+    const int hidden = n_heads * HD;
     const int n_qblocks = (L + NW * 32 - 1) / (NW * 32);
     const long long total = (long long)n_qblocks * n_heads * b;
     if (total > (1LL << 28)) return hipErrorInvalidValue;
     const long long pairs = (long long)n_heads * b;
     const int per = (int)((pairs + 7) / 8) * n_qblocks;        // workgroups per XCD: its share of the (sequence, head) pairs x their query blocks
-    const float sc = 1.4426950408889634f * 0.125f;
-    hipLaunchKernelGGL((attn_fwd_kernel<DT, NW>), dim3((unsigned)(per * 8)), dim3(NW * 64), 0, s, reinterpret_cast<const unsigned short*>(qkv), lens, L, hidden,
+    const float sc = att_scale<HD>();
+    hipLaunchKernelGGL((attn_fwd_kernel<DT, NW, HD>), dim3((unsigned)(per * 8)), dim3(NW * 64), 0, s, reinterpret_cast<const unsigned short*>(qkv), lens, L, hidden,
                        n_heads, n_qblocks, (int)total, sc, reinterpret_cast<unsigned short*>(out));
     return hipGetLastError();
 }
 
-hipError_t cmr_launch_attention(const void* qkv, int dtype, const int* lens, int b, int L, int n_heads, void* out, hipStream_t s) {
-    if (dtype == CMR_DT_F32) return launch_attention_f32(qkv, lens, b, L, n_heads, out, s);
+// head_dim 64 or 32 (the caller checks).  32-wide heads run on 4 waves for every l (comment at attn_fwd_kernel).
+hipError_t cmr_launch_attention(const void* qkv, int dtype, const int* lens, int b, int L, int n_heads, int head_dim, void* out, hipStream_t s) {
+    if (head_dim == 32) {
+        if (dtype == CMR_DT_F32) return launch_attention_f32<32>(qkv, lens, b, L, n_heads, out, s);
+#if ATT_VTR && !ATT_SWZL && !ATT_DMA
+        if (dtype == CMR_DT_BF16) return launch_attention<CMR_DT_BF16, 4, 32>(qkv, lens, b, L, n_heads, out, s);
+        return launch_attention<CMR_DT_F16, 4, 32>(qkv, lens, b, L, n_heads, out, s);
+#else
+        return hipErrorInvalidValue;                   // a development build of the 64-wide layouts: no 16-bit HD = 32 kernel in it
+#endif
+    }
+    if (head_dim != 64) return hipErrorInvalidValue;
+    if (dtype == CMR_DT_F32) return launch_attention_f32<64>(qkv, lens, b, L, n_heads, out, s);
     const bool eight = ATT_VTR && (ATT_WAVES_MODE == 8 || (ATT_WAVES_MODE == 0 && L >= 256));
-    if (dtype == CMR_DT_BF16) return eight ? launch_attention<CMR_DT_BF16, (ATT_VTR ? 8 : 4)>(qkv, lens, b, L, n_heads, out, s) : launch_attention<CMR_DT_BF16, 4>(qkv, lens, b, L, n_heads, out, s);
-    return eight ? launch_attention<CMR_DT_F16, (ATT_VTR ? 8 : 4)>(qkv, lens, b, L, n_heads, out, s) : launch_attention<CMR_DT_F16, 4>(qkv, lens, b, L, n_heads, out, s);
+    if (dtype == CMR_DT_BF16) return eight ? launch_attention<CMR_DT_BF16, (ATT_VTR ? 8 : 4), 64>(qkv, lens, b, L, n_heads, out, s) : launch_attention<CMR_DT_BF16, 4, 64>(qkv, lens, b, L, n_heads, out, s);
+    return eight ? launch_attention<CMR_DT_F16, (ATT_VTR ? 8 : 4), 64>(qkv, lens, b, L, n_heads, out, s) : launch_attention<CMR_DT_F16, 4, 64>(qkv, lens, b, L, n_heads, out, s);
 }
 
 // ------------------------------------------------------------------------------------------------ bias + residual + LayerNorm
@@ -1111,14 +1165,14 @@ int32_t cmr_encoder_attention(int32_t device_id, const void* qkv_dev, int32_t dt
                               int32_t n_heads, int32_t head_dim, void* out_dev, void* stream) {
     if (!qkv_dev || !lens_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
     if (b <= 0 || l <= 0 || n_heads <= 0) return cmr_fail(CMR_ERR_INVALID, "b, l, n_heads must be > 0");
-    if (head_dim != 64) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: head_dim must be 64 (BERT-base / BERT-large heads)");
+    if (head_dim != 64 && head_dim != 32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: head_dim must be 64 or 32 (BERT-base / -large heads; bge-small / MiniLM heads)");
     if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: dtype must be bf16 or f16 or f32");
     if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & 15) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention: buffers must be 16-byte aligned");
     int rc = cmr_check_device(device_id);
     if (rc) return rc;
     rc = cmr_set_device(device_id);
     if (rc) return rc;
-    HIP_TRY(cmr_launch_attention(qkv_dev, dtype, lens_dev, b, l, n_heads, out_dev, (hipStream_t)stream));
+    HIP_TRY(cmr_launch_attention(qkv_dev, dtype, lens_dev, b, l, n_heads, head_dim, out_dev, (hipStream_t)stream));
     return CMR_OK;
 }
 

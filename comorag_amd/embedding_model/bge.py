@@ -101,7 +101,7 @@ class _EncodeReplica:
             self.model = owner.embedding_model if same else copy.deepcopy(owner.embedding_model).to(device).eval()
             with torch.cuda.device(device):
                 self.fused = fused_bert.FusedBertLayers(self.model, graphs=owner._fused.graphs, gelu="epilogue" if owner._fused.gelu_path.startswith("hipblaslt") else "exact",
-                                                        fp32=owner._fused.dtype == torch.float32)
+                                                        fp32=owner._fused.dtype == torch.float32, head32=owner._fused.head_dim == 32)
         self.stream = torch.cuda.Stream(device)
         self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=f"cmr-enc-{device.index}")
         self.first = first
@@ -148,12 +148,13 @@ class HipBGEEmbeddingModel(BaseEmbeddingModel):
         if bool(cfg_get(self.global_config, "embedding_fused_encoder", True)):
             from . import fused_bert
             fp32 = bool(cfg_get(self.global_config, "embedding_fused_fp32", False))       # opt-in: fp32 models through the fp32 kernels
-            reason = fused_bert.why_not(self.embedding_model, fp32=fp32)
+            head32 = bool(cfg_get(self.global_config, "embedding_fused_head32", False))   # opt-in: 32-wide heads (the 384-hidden small tier)
+            reason = fused_bert.why_not(self.embedding_model, fp32=fp32, head32=head32)
             if reason is None and getattr(tokenizer, "padding_side", "right") != "right":
                 reason = "left-padding tokenizer"
             if reason is None:
                 self._fused = fused_bert.FusedBertLayers(self.embedding_model, graphs=int(cfg_get(self.global_config, "embedding_hip_graphs", 24)),
-                                                         gelu=str(cfg_get(self.global_config, "embedding_gelu", "exact")), fp32=fp32)
+                                                         gelu=str(cfg_get(self.global_config, "embedding_gelu", "exact")), fp32=fp32, head32=head32)
                 self.encoder_path = "hip-fused-layers"
             else:
                 self.encoder_path = f"transformers ({reason})"

@@ -1,11 +1,13 @@
 """The encoder stack behind `self.embedding_model(**inputs)` (embedding_model/BGEEmbedding.py:119) for 16-bit BERT encoders — and,
 opt-in (`fp32=True`, config `embedding_fused_fp32`), for fp32 ones: the same stages with fp32 tensors, fp32 GEMMs and fp32 HIP kernels.
+Heads are 64 wide (bge-base / -large, bge-m3) or, opt-in (`head32=True`, config `embedding_fused_head32`), 32 wide: the 384-hidden / 12-head
+small tier (bge-small, e5-small, gte-small, MiniLM), whose attention runs the HD = 32 instantiation of the same kernels; both opt-ins combine.
 
 transformers' BertLayer is ~20 kernels and as many Python module calls per layer: three projection GEMMs, SDPA with an additive
 mask, the output GEMM, bias / residual adds, LayerNorm, the FFN GEMMs and GELU.  Here a layer is
 
     qkv  = x @ [Wq | Wk | Wv]^T + b          one hipBLASLt GEMM instead of three (PyTorch-ROCm, as north_star prescribes)
-    ctx  = cmr_encoder_attention(qkv, lens)   HIP: masked softmax(QK^T/8)V straight off the packed projection, no head transposes
+    ctx  = cmr_encoder_attention(qkv, lens)   HIP: masked softmax(QK^T/sqrt(head width))V straight off the packed projection, no head transposes
     x    = cmr_encoder_add_layernorm(ctx @ Wo^T, bo, x)       HIP: dense bias + residual + LayerNorm in one pass
     x    = cmr_encoder_add_layernorm(gelu(x @ W1^T + b1) @ W2^T, b2, x)      (bias in the up-projection GEMM's epilogue; GELU: the erf-form kernel)
 
@@ -16,7 +18,7 @@ LayerNorm are one HIP kernel (cmr_encoder_embed_layernorm).  Results equal the t
 three times): tests/test_encoder_fused_gpu.py compares both with the fp32 oracle.
 
 Used when `why_not(model)` is None: BERT / RoBERTa / XLM-R architecture (bge-base / -large, bge-m3), absolute positions, exact GELU,
-64-wide heads, bf16 / fp16 weights; any other model keeps the transformers forward (`HipBGEEmbeddingModel.encoder_path` says which one runs).
+64-wide heads (32-wide with `head32=True`), bf16 / fp16 weights (fp32 with `fp32=True`); any other model keeps the transformers forward (`HipBGEEmbeddingModel.encoder_path` says which one runs).
 """
 from __future__ import annotations
 
@@ -84,9 +86,10 @@ def position_offset(model) -> int:
     return int(pad) + 1
 
 
-def why_not(model, fp32: bool = False) -> Optional[str]:
+def why_not(model, fp32: bool = False, head32: bool = False) -> Optional[str]:
     """None if the fused layer stack can run this model, else the reason it cannot.  fp32 = True also accepts torch.float32 weights
-    (the fp32 kernels, opt-in); every other reason applies unchanged."""
+    (the fp32 kernels, opt-in); head32 = True also accepts 32-wide heads (the HD = 32 attention kernels, opt-in); every other reason
+    applies unchanged."""
     import torch
     cfg = getattr(model, "config", None)
     if cfg is None or getattr(cfg, "model_type", "") not in ENCODER_TYPES:
@@ -100,7 +103,7 @@ def why_not(model, fp32: bool = False) -> Optional[str]:
         return f"activation {cfg.hidden_act!r}"
     if getattr(cfg, "is_decoder", False) or getattr(cfg, "add_cross_attention", False) or getattr(cfg, "chunk_size_feed_forward", 0):
         return "decoder / cross-attention / chunked feed-forward configuration"
-    if cfg.hidden_size % cfg.num_attention_heads or cfg.hidden_size // cfg.num_attention_heads != 64:
+    if cfg.hidden_size % cfg.num_attention_heads or cfg.hidden_size // cfg.num_attention_heads not in ((64, 32) if head32 else (64,)):
         return "head width is not 64"
     if cfg.hidden_size % 4 or cfg.hidden_size > 2048 or cfg.intermediate_size % 4:
         return "hidden size not supported by the LayerNorm kernel"
@@ -159,7 +162,7 @@ def gelu_epilogue_available(device, dtype) -> bool:
 
 
 class FusedBertLayers:
-    def __init__(self, model, graphs: int = 0, gelu: str = "exact", fp32: bool = False):
+    def __init__(self, model, graphs: int = 0, gelu: str = "exact", fp32: bool = False, head32: bool = False):
         """gelu = "exact" (default): FFN-up GEMM + bias in hipBLASLt, then PyTorch's erf-form GELU kernel — the function the model
         was trained with and the reference runs (BGEEmbedding.py:119-120, `hidden_act = "gelu"`).
         gelu = "epilogue" (opt-in, `embedding_gelu`): projection, bias and GELU are ONE hipBLASLt GEMM (`torch._addmm_activation`) —
@@ -171,9 +174,10 @@ class FusedBertLayers:
         "exact" when the build does not fuse it into a single launch (`gelu_path` says which one runs).
         fp32 = True admits an fp32 model: fp32 tensors through every stage (cmr_dtype = CMR_F32: exact f32-input MFMA attention,
         LayerNorm written unrounded), F.linear in fp32 as the transformers forward calls it.  gelu = "epilogue" then runs the exact
-        kernel too: the tanh epilogue was validated against 16-bit rounding steps only."""
+        kernel too: the tanh epilogue was validated against 16-bit rounding steps only.
+        head32 = True admits 32-wide heads (`head_dim` = 32: the attention call names the width, nothing else changes)."""
         import torch
-        reason = why_not(model, fp32=fp32)
+        reason = why_not(model, fp32=fp32, head32=head32)
         if reason is not None:
             raise ValueError("FusedBertLayers: " + reason)
         if gelu not in ("epilogue", "exact"):
@@ -181,6 +185,7 @@ class FusedBertLayers:
         self.model = model
         cfg = model.config
         self.hidden, self.n_heads, self.eps = int(cfg.hidden_size), int(cfg.num_attention_heads), float(cfg.layer_norm_eps)
+        self.head_dim = self.hidden // self.n_heads
         self.dtype = next(model.parameters()).dtype
         self.cmr_dtype = {torch.bfloat16: L.CMR_BF16, torch.float16: L.CMR_F16, torch.float32: L.CMR_F32}[self.dtype]
         if self.dtype == torch.float32:
@@ -213,7 +218,7 @@ class FusedBertLayers:
         if stream is None:
             stream = torch.cuda.current_stream(qkv.device).cuda_stream
         L.check(L.lib().cmr_encoder_attention(qkv.device.index or 0, C.c_void_p(qkv.data_ptr()), self.cmr_dtype, C.c_void_p(lens_dev.data_ptr()),
-                                              b, l, self.n_heads, 64, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+                                              b, l, self.n_heads, self.hidden // self.n_heads, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
     def embed(self, input_ids, token_type_ids=None, stream: Optional[int] = None):

@@ -486,7 +486,8 @@ int32_t cmr_pool_l2norm(int32_t device_id, const void* hidden_dev, int32_t hidde
  * cmr_encoder_attention: out[b*l, hidden] = softmax(Q K^T / sqrt(head_dim), keys >= lens[s] masked) V per sequence and head,
  *   with Q | K | V the three hidden-wide column groups of ONE packed projection qkv_dev[b*l, 3*hidden] (hidden = n_heads *
  *   head_dim, head h = columns h*head_dim.. of its group); lens_dev[b] int32 = real tokens of each right-padded sequence
- *   (transformers' BertSelfAttention + its additive mask).  head_dim must be 64.  Rows >= lens[s] of out are unspecified
+ *   (transformers' BertSelfAttention + its additive mask).  head_dim must be 64 or 32 (BERT-base / -large heads; the 384-hidden
+ *   small tier: bge-small, e5-small, MiniLM), any other width is CMR_ERR_INVALID.  Rows >= lens[s] of out are unspecified
  *   finite values (zeros where a whole 128-row block is padding): the pooling mask drops them.
  * cmr_encoder_embed_layernorm: out[t] = LayerNorm(word[ids[t]] + position[t mod l] + token_type[tt[t]]) for the rows = b*l tokens
  *   of a [b, l] mini-batch (transformers' BertEmbeddings with default position ids; token_type_dev NULL = type 0; ids outside a

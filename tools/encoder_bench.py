@@ -1,7 +1,10 @@
 """Corpus-embed rate and per-stage breakdown of the encoder path (tools/bench_extras.encode_breakdown) for the BERT-base bf16 and
 BERT-large fp16 shapes, fused layer stack against the transformers forward.  `python -m tools.encoder_bench [--quick]`.
 `python -m tools.encoder_bench --fp32 [--out FILE]`: the fp32 rows (`embedding_model_dtype = "auto"`, `embedding_fused_fp32` on and off in the
-same run) — one short query, the corpus forward at 512 tokens, and the fp32 attention kernel next to PyTorch's SDPA on the same tensors."""
+same run) — one short query, the corpus forward at 512 tokens, and the fp32 attention kernel next to PyTorch's SDPA on the same tensors.
+`python -m tools.encoder_bench --head32 [--out FILE]`: the 32-wide-head rows (the bge-small shape, `embedding_fused_head32` on and off in the same
+run, bf16 / f16 / fp32) — one short query, the corpus forward at 512 tokens, and the HD = 32 attention kernel next to SDPA and next to the HD = 64
+kernel on the same tensors zero-padded to 64 columns per head."""
 import json
 import sys
 
@@ -105,9 +108,86 @@ def fp32_report(dev, reps=60):
     return out
 
 
+def _regions(fn, regions=7, reps=10, warm=3):
+    """Microseconds per call over `regions` timed regions of `reps` calls each (a synchronisation on either side of a region):
+    median, min and max of the regions."""
+    import numpy as np
+    _timed(fn, warm, warm=0)
+    ts = [_timed(fn, reps, warm=0) * 1e6 for _ in range(regions)]
+    return {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts)), "regions": regions, "calls_per_region": reps}
+
+
+def head32_report(dev):
+    """The 32-wide-head opt-in (`embedding_fused_head32`) on the bge-small shape (384 hidden, 12 layers, 12 heads, 1536 intermediate) against
+    the transformers forward of the same model, same process, same run, in bf16, f16 and fp32 (the latter with `embedding_fused_fp32` too)."""
+    import types
+    import numpy as np
+    from comorag_amd import _lib as L
+    from comorag_amd.embedding_model.bge import HipBGEEmbeddingModel
+    from comorag_amd.embedding_model.fused_bert import FusedBertLayers
+    from comorag_amd.utils.config_utils import BaseConfig
+    from tools.synthetic import random_bert, synthetic_chunks, synthetic_wordpiece_tokenizer
+    tok, words = synthetic_wordpiece_tokenizer()
+    q = " ".join(words[:12])
+    chunks = synthetic_chunks(words, 32, tokens_per_chunk=560)
+    out = {"what": "32-wide heads (bge-small shape: 384 hidden, 12 layers, 12 heads, 1536 intermediate, random init): fused stack (embedding_fused_head32 = True) "
+                   "vs the transformers forward of the same model; microseconds per call, median / min / max over timed regions",
+           "single_query_encode_us": {}, "corpus_forward_32x512_us": {}, "attention_32x512x12_us": {}}
+    for name, dtype in (("bf16", "bf16"), ("f16", "fp16"), ("fp32", "auto")):
+        qrow, crow = {}, {}
+        for flag in (True, False):
+            cfg = BaseConfig(embedding_model_name="bge-small-random-init", embedding_model_dtype=dtype, device=dev.index or 0,
+                             embedding_fused_head32=flag, embedding_fused_fp32=flag and dtype == "auto", embedding_query_cache=0)      # (every call a forward)
+            em = HipBGEEmbeddingModel(cfg, cfg.embedding_model_name, model=random_bert("small", vocab_size=len(tok)), tokenizer=tok)
+            assert em.encoder_path.startswith("hip-fused-layers" if flag else "transformers ("), em.encoder_path
+            key = "fused" if flag else "transformers"
+            for _ in range(8):
+                em.batch_encode(q)
+            qrow[key] = _regions(lambda: em.batch_encode(q), regions=7, reps=20, warm=2)
+            host = em._tokenize(chunks, 512)
+            inp = {k: v.to(dev) for k, v in host.items()}
+            lens = host["attention_mask"].numpy().sum(1).astype(np.int32)
+            with torch.no_grad():
+                if flag:
+                    crow[key] = _regions(lambda: em._fused(inp["input_ids"], lens, token_type_ids=inp.get("token_type_ids"), pool=True), regions=5, reps=3, warm=2)
+                else:
+                    crow[key] = _regions(lambda: em.embedding_model(**inp).last_hidden_state, regions=5, reps=3, warm=2)
+            crow["tokens_per_chunk"] = int(inp["input_ids"].shape[1])
+            if flag:
+                # the attention call alone at 32 x 512 x 12 heads, every sequence full: the HD = 32 kernel; SDPA on the same tensors already split
+                # and head-major; the HD = 64 kernel on the same tensors with every head zero-padded to 64 columns (a TIMING baseline: its scale
+                # is 1/8, its values differ)
+                fz, b, l, nh = em._fused, 32, 512, 12
+                qkv = (torch.randn((b * l, 3 * fz.hidden), device=dev) * 1.5).to(fz.dtype)
+                lens_dev = torch.full((b,), l, dtype=torch.int32, device=dev)
+                x = qkv.view(b, l, 3, nh, 32)
+                qh, kh, vh = (x[:, :, i].permute(0, 2, 1, 3).contiguous() for i in range(3))
+                padded = torch.zeros((b * l, 3, nh, 64), dtype=fz.dtype, device=dev)
+                padded[..., :32] = qkv.view(b * l, 3, nh, 32)
+                padded = padded.view(b * l, 3 * nh * 64)
+                wide = types.SimpleNamespace(hidden=nh * 64, n_heads=nh, cmr_dtype=fz.cmr_dtype)
+                out["attention_32x512x12_us"][name] = {
+                    "hip_head32": _regions(lambda: fz.attention(qkv, lens_dev, b, l), regions=7, reps=20),
+                    "torch_sdpa_head_major": _regions(lambda: torch.nn.functional.scaled_dot_product_attention(qh, kh, vh), regions=7, reps=20),
+                    "hip_head64_zero_padded": _regions(lambda: FusedBertLayers.attention(wide, padded, lens_dev, b, l), regions=7, reps=20)}
+            em.close()
+        out["single_query_encode_us"][name] = qrow
+        out["corpus_forward_32x512_us"][name] = crow
+    # acceptance, row by row: fused median below the transformers median by more than the two rows' own min-to-max spread; native attention not slower than padded
+    acc = {}
+    for table in ("single_query_encode_us", "corpus_forward_32x512_us"):
+        for name, row in out[table].items():
+            f, t = row["fused"], row["transformers"]
+            acc[f"{table}/{name}"] = bool(t["median"] - f["median"] > (f["max"] - f["min"]) + (t["max"] - t["min"]))
+    for name, row in out["attention_32x512x12_us"].items():
+        acc[f"attention_native_not_slower_than_padded/{name}"] = bool(row["hip_head32"]["median"] <= row["hip_head64_zero_padded"]["median"])
+    out["acceptance"] = acc
+    return out
+
+
 def main():
-    if "--fp32" in sys.argv:
-        rep = fp32_report(torch.device("cuda", 0))
+    if "--head32" in sys.argv or "--fp32" in sys.argv:
+        rep = head32_report(torch.device("cuda", 0)) if "--head32" in sys.argv else fp32_report(torch.device("cuda", 0))
         text = json.dumps(rep, indent=1)
         print(text)
         if "--out" in sys.argv:

@@ -20,9 +20,14 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
     tok, words = synthetic_wordpiece_tokenizer()
     # (the "auto" rows: fp32 weights as stored — the transformers fp32 forward, then the fused fp32 stack, `embedding_fused_fp32`)
-    for kind, dtype, fp32 in (("base", "bf16", False), ("large", "fp16", False), ("base", "auto", False), ("base", "auto", True), ("large", "auto", False), ("large", "auto", True)):
+    # (the "small" rows: 32-wide heads — the transformers forward, then the fused stack, `embedding_fused_head32`; with both flags for fp32 weights)
+    rows = [("base", "bf16", False, False), ("large", "fp16", False, False), ("base", "auto", False, False), ("base", "auto", True, False),
+            ("large", "auto", False, False), ("large", "auto", True, False),
+            ("small", "bf16", False, False), ("small", "bf16", False, True), ("small", "fp16", False, False), ("small", "fp16", False, True),
+            ("small", "auto", False, False), ("small", "auto", True, True)]
+    for kind, dtype, fp32, head32 in rows:
         cfg = BaseConfig(embedding_model_name=f"bge-{kind}-random-init", embedding_model_dtype=dtype, embedding_query_cache=0,      # (every call a forward: the product keeps the last 256 single-string rows)
-                         embedding_fused_fp32=fp32)
+                         embedding_fused_fp32=fp32, embedding_fused_head32=head32)
         em = HipBGEEmbeddingModel(cfg, cfg.embedding_model_name, model=random_bert(kind, vocab_size=len(tok)), tokenizer=tok)
         q = " ".join(words[:12])
         for _ in range(8):

@@ -31,7 +31,8 @@ def synthetic_wordpiece_tokenizer(n_words: int = 30000, seed: int = 1234):
 def random_bert(kind: str = "base", vocab_size: int = 30000, seed: int = 0):
     import torch
     from transformers import BertConfig, BertModel
-    shape = {"base": dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072),
+    shape = {"small": dict(hidden_size=384, num_hidden_layers=12, num_attention_heads=12, intermediate_size=1536),      # bge-small / e5-small / MiniLM-L12: 32-wide heads
+             "base": dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072),
              "large": dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096)}[kind]
     torch.manual_seed(seed)
     return BertModel(BertConfig(vocab_size=vocab_size, max_position_embeddings=512, **shape), add_pooling_layer=False).eval()
