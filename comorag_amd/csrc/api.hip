@@ -105,12 +105,14 @@ const Option kOptions[] = {
     {"prefilter_rescore_wgs", OPT_FIELD(pf_rescore_wgs), Option::clamp, 0, 1024, 0, nullptr, nullptr},
     {"prefilter_tighten", OPT_FIELD(pf_tighten), Option::range, 0, 1, 0, "prefilter_tighten must be 0 or 1", OPT_READ(i->pf_tighten)},
     {"prefilter_pair_cap", OPT_FIELD(pf_pair_cap), Option::clamp, 0, 1 << 20, 0, nullptr, OPT_READ(i->pf_pair_cap)},
+    {"prefilter_wave_cap", OPT_FIELD(pf_wave_cap), Option::clamp, 0, 1 << 20, 0, nullptr, OPT_READ(i->pf_wave_cap)},
     {"prefilter_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->prefilter_active)},
     {"prefilter_rows", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->q8c.q8 ? i->q8c.rows : 0)},
     {"prefilter_bytes", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ((long long)i->q8c.bytes(i->dpad))},
     {"prefilter_candidates", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::candidates))},
     {"prefilter_pairs", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::pairs))},
     {"prefilter_pair_overflow", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::pair_overflow))},
+    {"prefilter_wave_overflow", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::wave_overflow))},
     {"last_route", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->last_route.load(std::memory_order_relaxed))},
     {"pipe_dual_scan_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_active)},
     {"pipe_dual_scan_wide_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_wide_active)},

@@ -203,18 +203,22 @@ struct CmrQ8Args {
     long long nrows;
     int npanels, nq, k;
     int keep_all;              // the filter keeps every row (the re-score path alone)
-    void* pair;                // [nqt * 32][pcap] 16-byte records (row, ub, lb, 0) of the filter's hits
+    void* wrec;                // [grid * 8][wave_cap] 16-byte records (row, ub, lb, query slot) of the filter's hits, one area per wave of its grid
+    unsigned* wcnt;            // [grid * 8] records offered per wave, written by every wave of the filter (past wave_cap: the area filled, the rest went to keep[])
+    int wave_cap;              // records per wave; 0: every hit goes to keep[] directly (keep_all, or pcap == 0)
+    void* pair;                // [nqt * 32][pcap] 16-byte records (row, ub, lb, 0): the wave areas' records sorted by query (bucket step)
     unsigned* pair_cnt;        // [nqt * 32] pairs offered per query, zeroed before the filter (past pcap: the list filled, the rest went to keep[])
-    int pcap;                  // records per query; 0: every hit goes to keep[] directly and there is nothing to tighten
-    unsigned* keep;            // [npanels] one 32-bit row mask per panel: written whole by the filter, OR-ed into by the tightening
+    int pcap;                  // records per query; 0: no records at all and nothing to tighten
+    unsigned* keep;            // [npanels] one 32-bit row mask per panel: written whole by the filter, OR-ed into by the bucket step and the tightening
     float* tau_tight;          // [nq] the thresholds after tightening (diagnostics)
     unsigned* cand_row;        // [nrows]: the rows of keep[]'s bits
     unsigned* n_cand;          // zeroed before the expansion
     u64* lists;
     int* cnt;
 };
-// filter -> (tighten, when pcap > 0) -> expand -> rescore; the last three in stream order behind the filter
+// filter -> (bucket, tighten, when pcap > 0) -> expand -> rescore; all but the first in stream order behind the filter
 hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s);
+hipError_t cmr_launch_q8_bucket(const CmrQ8Args& a, hipStream_t s);
 hipError_t cmr_launch_q8_tighten(const CmrQ8Args& a, hipStream_t s);
 hipError_t cmr_launch_q8_expand(const CmrQ8Args& a, hipStream_t s);
 hipError_t cmr_launch_q8_rescore(const CmrQ8Args& a, hipStream_t s);

@@ -46,15 +46,17 @@ struct Q8Companion {
     void release() { (void)hipFree(q8); (void)hipFree(scales); (void)hipFree(stats); if (ready) (void)hipEventDestroy(ready); *this = Q8Companion{}; }
 };
 // A workspace's buffers of a pre-filtered pass, sized by plan_pass (PassPlan::bytes.q8[]): int8 query parts, queries' constants, candidate
-// rows and their counter, the filter's (row, ub, lb) records per query and their counters, row mask per panel, tightened thresholds.
-enum Q8Buf { Q8_QPACK, Q8_QCONST, Q8_CAND, Q8_NCAND, Q8_PAIR, Q8_PAIRCNT, Q8_KEEP, Q8_TAU, Q8_NBUF };
+// rows and their counter, the filter's (row, ub, lb, query) records per wave of its grid and their counters, the same records per query
+// and their counters, row mask per panel, tightened thresholds.
+enum Q8Buf { Q8_QPACK, Q8_QCONST, Q8_CAND, Q8_NCAND, Q8_WREC, Q8_WCNT, Q8_PAIR, Q8_PAIRCNT, Q8_KEEP, Q8_TAU, Q8_NBUF };
 struct Q8Scratch {
     DevBuf buf[Q8_NBUF];
     bool pf_prev = false;                // the workspace's last pass ran the re-score, which reads qfrag / tau on the merge stream
     hipError_t ensure(const size_t (&bytes)[Q8_NBUF]) { for (int i = 0; i < Q8_NBUF; ++i) if (hipError_t e = buf[i].ensure(bytes[i])) return e; return hipSuccess; }
     void release() { for (DevBuf& b : buf) b.release(); }
 };
-struct Q8LastPass { const unsigned* ncand = nullptr; const unsigned* paircnt = nullptr; int nq = 0, pcap = 0; };      // candidate counter, nq pair counters, their capacity
+// candidate counter, nq pair counters and their capacity, nw wave counters and their capacity
+struct Q8LastPass { const unsigned* ncand = nullptr; const unsigned* paircnt = nullptr; int nq = 0, pcap = 0; const unsigned* wcnt = nullptr; int nw = 0, wave_cap = 0; };
 
 // Scratch of one in-flight search.  One per stream (searches on a stream are serialised by it).
 struct Workspace {
@@ -217,11 +219,14 @@ struct cmr_index {
     // prefilter_tighten: the k-th largest certified lower bound among a query's hits replaces its sampling threshold before the
     // re-score (0: every hit is re-scored — the kept set of the route before the tightening, the A/B arm).  prefilter_pair_cap: hit
     // records per query (16 bytes each: 16 MiB per workspace at 64 queries); a query that offers more keeps the rest directly.
+    // prefilter_wave_cap: records per wave of the filter's grid, which writes them to an area of its own before they are sorted by
+    // query (0: as many as the queries' lists hold, spread over the waves — plan_pass); a wave that offers more keeps the rest directly.
     int pf_tighten = 1;
     int pf_pair_cap = 16384;
+    int pf_wave_cap = 0;
     Q8Companion q8c;
     int prefilter_active = 0;            // read-only: did the last pipelined call run the pre-filter
-    Q8LastPass q8_last;                  // the last pre-filtered pass's counters (the options prefilter_candidates / _pairs / _pair_overflow read them)
+    Q8LastPass q8_last;                  // the last pre-filtered pass's counters (the options prefilter_candidates / _pairs / _pair_overflow / _wave_overflow read them)
     int pipe_slots = 3;      // pipe_slots (2..4): batches in the pipeline.  A third slot lets the pre-phase of batch i+2 start before
                              // scan i has ended: 1 M x 768 bf16, B = 64 step 0.279 -> 0.264 ms; nothing at 10 M rows
     int reserve_cus = -1;    // pipe_reserve_cus: CUs the pipelined main scan leaves free (-1 = by corpus size, see plan_pass)

@@ -55,6 +55,7 @@ int q8_prepare(cmr_index* idx, Workspace* ws, const PassPlan& p, const float* q_
     f.corpus = idx->corpus; f.q8 = c.q8; f.scales = c.scales; f.qfrag = ws->qfrag.p; f.qpack = w[Q8_QPACK].p; f.qconst = (const float4*)w[Q8_QCONST].p;
     f.nrows = idx->n; f.npanels = (int)idx->npanels(); f.nq = p.nqp; f.k = p.k; f.keep_all = p.prefilter == 2 ? 1 : 0;
     f.cand_row = (unsigned*)w[Q8_CAND].p; f.n_cand = (unsigned*)w[Q8_NCAND].p; f.keep = (unsigned*)w[Q8_KEEP].p; f.tau_tight = (float*)w[Q8_TAU].p;
+    f.wrec = w[Q8_WREC].p; f.wcnt = (unsigned*)w[Q8_WCNT].p; f.wave_cap = f.keep_all ? 0 : p.wave_cap;
     f.pair = w[Q8_PAIR].p; f.pair_cnt = (unsigned*)w[Q8_PAIRCNT].p; f.pcap = p.pair_cap;
     return CMR_OK;
 }
@@ -62,13 +63,17 @@ int q8_prepare(cmr_index* idx, Workspace* ws, const PassPlan& p, const float* q_
 int q8_filter(cmr_index* idx, CmrQ8Args& f, const CmrScanArgs& a, hipStream_t sm) {
     f.tau_init = a.tau_init; f.lists = a.lists; f.cnt = a.cnt;
     HIP_TRY(cmr_launch_q8_filter(f, sm));
-    idx->q8_last = Q8LastPass{f.n_cand, f.pair_cnt, f.nq, f.pcap};
+    idx->q8_last = Q8LastPass{f.n_cand, f.pair_cnt, f.nq, f.pcap, f.wcnt, f.grid * CMR_SCAN_WAVES, f.wave_cap};
     idx->prefilter_active = 1;
     return CMR_OK;
 }
-// Step 3, on the merge stream in front of the merge: thresholds tightened into keep[], its bits listed, those rows scored into the merge's lists
+// Step 3, on the merge stream in front of the merge: the waves' records sorted into the queries' lists, thresholds tightened into keep[], its bits
+// listed, those rows scored into the merge's lists
 int q8_rescore(const CmrQ8Args& f, hipStream_t sq) {
-    if (f.pcap > 0) HIP_TRY(cmr_launch_q8_tighten(f, sq));
+    if (f.pcap > 0) {
+        HIP_TRY(cmr_launch_q8_bucket(f, sq));
+        HIP_TRY(cmr_launch_q8_tighten(f, sq));
+    }
     HIP_TRY(hipMemsetAsync(f.n_cand, 0, sizeof(unsigned), sq));
     HIP_TRY(cmr_launch_q8_expand(f, sq));
     HIP_TRY(cmr_launch_q8_rescore(f, sq));
@@ -80,19 +85,21 @@ double prefilter_bytes(const cmr_index* idx, const PassPlan& p) {
 }
 
 // The counters of the last pre-filtered pass, read once the pipeline has drained (0 before any such pass, -1: the read failed).  candidates:
-// rows it handed to the re-score; pairs: the (row, query) records its filter stored, over all queries; pair_overflow: queries that offered more than the capacity.
-enum class Q8Counter { candidates, pairs, pair_overflow };
+// rows it handed to the re-score; pairs: the (row, query) records in the queries' lists, over all queries; pair_overflow: queries that were offered more than
+// the capacity; wave_overflow: waves of the filter's grid that offered more records than their area holds.
+enum class Q8Counter { candidates, pairs, pair_overflow, wave_overflow };
 long long q8_read_counter(const cmr_index* cidx, Q8Counter what) {
     cmr_index* idx = const_cast<cmr_index*>(cidx);
     if (cmr_set_device(idx->device)) return -1;
     std::lock_guard<std::mutex> pl(idx->pipe_mu);
     const Q8LastPass& L = idx->q8_last;
-    const unsigned* const src = what == Q8Counter::candidates ? L.ncand : L.paircnt;
-    std::vector<unsigned> h(what == Q8Counter::candidates ? 1 : (size_t)std::max(L.nq, 0));
+    const unsigned* const src = what == Q8Counter::candidates ? L.ncand : what == Q8Counter::wave_overflow ? L.wcnt : L.paircnt;
+    std::vector<unsigned> h(what == Q8Counter::candidates ? 1 : (size_t)std::max(what == Q8Counter::wave_overflow ? (L.wave_cap > 0 ? L.nw : 0) : L.nq, 0));
     if (!src || h.empty()) return 0;
     for (hipStream_t st : idx->pipe.st) if (st && hipStreamSynchronize(st) != hipSuccess) return -1;
     if (hipMemcpy(h.data(), src, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     if (what == Q8Counter::candidates) return (long long)h[0];
+    if (what == Q8Counter::wave_overflow) return (long long)std::count_if(h.begin(), h.end(), [&](unsigned c) { return c > (unsigned)L.wave_cap; });
     long long stored = 0, overflowed = 0;
     for (unsigned c : h) { stored += std::min(c, (unsigned)L.pcap); overflowed += c > (unsigned)L.pcap ? 1 : 0; }
     return what == Q8Counter::pairs ? stored : overflowed;

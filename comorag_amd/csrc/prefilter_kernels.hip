@@ -169,21 +169,24 @@ struct FilterP {
     const u64* tau_init;       // per-query threshold keys of the sampling passes, or nullptr (nothing to filter by)
     long long nrows;
     int npanels, KB, nq, keep_all;
-    v4u* pair;                 // [nq slots][pcap] records (row, ub, lb, 0)
-    unsigned* pair_cnt;        // [nq slots] pairs offered per query (zeroed before the launch; may run past pcap)
-    unsigned pcap;             // 0: no pairs, every hit is kept directly
+    v4u* wrec;                 // [W][wave_cap] records (row, ub, lb, query slot): wave gw of the grid owns row gw
+    unsigned* wcnt;            // [W] records offered by each wave (written by every wave of the grid; may run past wave_cap)
+    unsigned wave_cap;         // 0: no records, every hit is kept directly
     unsigned* keep;            // [npanels] row masks: every panel's word is written (the rows kept directly, usually none)
 };
 
 // 8 waves per workgroup, each with a contiguous panel range; the two int8 parts of the query tiles in LDS.  Corpus blocks
 // stream through two register buffers of CH blocks (plain non-temporal loads, the compiler counts them): one is in flight
-// while the other feeds the MFMAs — two per block and query tile, hi and lo part.  Panel epilogue: the kept-test on every
-// accumulator element, __any; on a hit every lane takes a slot in its query's pair list for each of its own hits (rows at or
-// beyond nrows excepted: a zero padding row scores 0 and must not reach the threshold selection) and writes (row, ub, lb).  A
-// hit that finds the list full is kept directly: its row bit goes into the panel's word of keep[], which the panel's wave —
-// every panel has exactly one — writes for every panel of its range, so the masks need no clearing between batches.  A lane's
-// query per tile is fixed, so a lane that met a full list stops asking (`full`): a batch without a usable threshold costs
-// each lane one refused atomic per tile, not one per hit.
+// while the other feeds the MFMAs — two per block and query tile, hi and lo part.  The scheduling barrier that ends load()
+// is what makes that true in the ISA: without it the compiler sinks the next buffer's loads behind most of the step's MFMAs
+// (it likes the registers as ds_read temporaries) and the wave drains its one buffer while it computes.
+// Panel epilogue: the kept-test on every accumulator element (the padding rows of the corpus' last panel masked out: a zero row
+// scores 0 and must not reach the threshold selection), __any; on a hit, per accumulator row and tile, a ballot: the hitting
+// lanes take consecutive slots of the WAVE's own record area — a wave-uniform count, no atomic, nothing to wait for, so the
+// corpus loads stay in flight across it — and store (row, ub, lb, query slot); q8_bucket_kernel sorts the records into the
+// queries' lists afterwards.  A hit that finds the wave's area full is kept directly: its row bit goes into the panel's word of
+// keep[], which the panel's wave — every panel has exactly one — writes for every panel of its range, so the masks need no
+// clearing between batches.  Nor do the counts: every wave of the grid stores its own on leaving, a wave without panels a 0.
 template <int NQT, int CH>
 __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -197,7 +200,10 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
     const int W = gridDim.x * CMR_SCAN_WAVES;
     const int gw = blockIdx.x * CMR_SCAN_WAVES + wave;
     const int p0 = (int)(((long long)gw * P.npanels) / W), p1 = (int)(((long long)(gw + 1) * P.npanels) / W);
-    if (p1 <= p0) return;
+    if (p1 <= p0) {
+        if (lane == 0) P.wcnt[gw] = 0u;
+        return;
+    }
 
     float aq[NQT], Bq[NQT], cq[NQT], tau[NQT];
     bool alive[NQT];
@@ -232,7 +238,8 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
     };
     load_scales(p0);
 
-    unsigned full = P.pcap ? 0u : ~0u;      // bit t: the pair list of this lane's query of tile t is full
+    v4u* const wr = P.wrec + (size_t)gw * P.wave_cap;
+    unsigned nrec = 0u;                     // records this wave has offered (wave-uniform)
     const int hrow = 4 * (lane >> 5);
 
     const int CPP = KB / CH;
@@ -244,6 +251,7 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
 #pragma unroll
         for (int u = 0; u < CH; ++u) b[u] = __builtin_nontemporal_load(&src[(size_t)u * 64]);
         src += (size_t)CH * 64;
+        __builtin_amdgcn_sched_barrier(0);      // the loads are issued HERE, in front of the other buffer's MFMAs
     };
     auto step = [&](const v4u (&b)[CH]) {
         const v4u* qg = qf + (size_t)ci * CH * 64 + lane;
@@ -272,31 +280,47 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
             }
         }
         const long long left = P.nrows - (long long)p * CMR_PANEL_ROWS;
-        unsigned rows = 0u;        // the rows of this panel that are kept without a pair
-        if (P.keep_all) rows = ~0u;
+        if (left < CMR_PANEL_ROWS) {            // the corpus' last panel: its padding rows are neither recorded nor kept
+            const int lim = (int)(left > 0 ? left : 0) - hrow;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if ((r & 3) + 8 * (r >> 2) >= lim) hit &= ~(0x10001u << r);
+        }
+        unsigned rows = 0u;        // the rows of this panel that are kept without a record
+        if (P.keep_all) rows = left < CMR_PANEL_ROWS ? (left > 0 ? (1u << left) - 1u : 0u) : ~0u;
         else if (__any(hit != 0u)) {
+            const unsigned row0 = (unsigned)p * CMR_PANEL_ROWS + (unsigned)hrow;
+            // (bits of the lane's accumulator rows WITHOUT the lane half's offset: row i = (r & 3) + 8 (r >> 2) + hrow, shifted once below)
+            if (P.wave_cap == 0u) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = (r & 3) + 8 * (r >> 2) + hrow;
-                const float4 s4 = sc[2 * (r >> 2) + ((r & 3) >> 1)];
-                const float ar = (r & 1) ? s4.z : s4.x, br = (r & 1) ? s4.w : s4.y;
+                for (int r = 0; r < 16; ++r)
+                    if (hit & (0x10001u << r)) rows |= 1u << ((r & 3) + 8 * (r >> 2));
+            } else {
 #pragma unroll
-                for (int t = 0; t < NQT; ++t) {
-                    if (!(hit & (1u << (r + 16 * t))) || i >= left) continue;
-                    if (full & (1u << t)) { rows |= 1u << i; continue; }
-                    const int qi = t * 32 + (lane & 31);
-                    const unsigned slot = atomicAdd(&P.pair_cnt[qi], 1u);
-                    if (slot >= P.pcap) { full |= 1u << t; rows |= 1u << i; continue; }
-                    const float ti = fmaf((float)acc[1][t][r], 1.0f / 254.0f, (float)acc[0][t][r]);
-                    const float e = fmaf(Bq[t], br, cq[t]);
-                    const float ub = fmaf(ar * aq[t], ti, e), lb = fmaf(ar * aq[t], ti, -e);
-                    P.pair[(size_t)qi * P.pcap + slot] = (v4u){(unsigned)p * CMR_PANEL_ROWS + (unsigned)i, __float_as_uint(ub), __float_as_uint(lb), 0u};
+                for (int r = 0; r < 16; ++r) {
+                    const float4 s4 = sc[2 * (r >> 2) + ((r & 3) >> 1)];
+                    const float ar = (r & 1) ? s4.z : s4.x, br = (r & 1) ? s4.w : s4.y;
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t) {
+                        const bool h = (hit & (1u << (r + 16 * t))) != 0u;
+                        const u64 m = __ballot(h);
+                        if (m == 0ull) continue;
+                        const unsigned slot = nrec + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                        nrec += (unsigned)__popcll(m);
+                        if (!h) continue;
+                        if (slot >= P.wave_cap) { rows |= 1u << ((r & 3) + 8 * (r >> 2)); continue; }
+                        const float ti = fmaf((float)acc[1][t][r], 1.0f / 254.0f, (float)acc[0][t][r]);
+                        const float e = fmaf(Bq[t], br, cq[t]);
+                        const float ub = fmaf(ar * aq[t], ti, e), lb = fmaf(ar * aq[t], ti, -e);
+                        wr[slot] = (v4u){row0 + (unsigned)((r & 3) + 8 * (r >> 2)), __float_as_uint(ub), __float_as_uint(lb),
+                                         (unsigned)(t * 32 + (lane & 31))};
+                    }
                 }
             }
+            rows <<= hrow;
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) rows |= (unsigned)__shfl_xor((int)rows, off);
         }
-        if (left < CMR_PANEL_ROWS) rows &= left > 0 ? (1u << left) - 1u : 0u;
         if (lane == 0) P.keep[p] = rows;
         ++p;
         load_scales(p < P.npanels ? p : P.npanels - 1);
@@ -316,6 +340,52 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
             load(bufA);
             step(bufB);
         }
+    }
+    if (lane == 0) P.wcnt[gw] = nrec;
+}
+
+// ------------------------------------------------------------------------------------------ bucket
+struct BucketP {
+    const v4u* wrec;
+    const unsigned* wcnt;
+    unsigned wave_cap;
+    int W;
+    v4u* pair;                 // [nq slots][pcap] records (row, ub, lb, 0)
+    unsigned* pair_cnt;        // [nq slots] pairs offered per query (zeroed before the filter; may run past pcap)
+    unsigned pcap;
+    unsigned* keep;
+};
+
+#define Q8_BUCKET_WAVES 4
+// The filter's records, wave area by wave area, into the queries' lists: one wave per area, min(wcnt, wave_cap) records each.  A
+// workgroup first counts its records per query in LDS, then takes ONE range per query from pair_cnt[] (the queries' counters share
+// two cache lines: a global atomic per record — a quarter of a million a batch — would queue up on them) and hands the range's
+// slots out from LDS again.  A slot at or beyond pcap: the list is full, the row is kept directly — its bit is OR-ed into keep[] as
+// q8_tighten_kernel does it.  Which record gets which slot is arbitrary, as it was when the filter took the slots itself; the
+// tightening is valid for any subset.  No wait on another workgroup; every loop runs to a count read once.
+__global__ __launch_bounds__(Q8_BUCKET_WAVES * 64) void q8_bucket_kernel(BucketP P) {
+    __shared__ unsigned s_cnt[64], s_base[64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = blockIdx.x * Q8_BUCKET_WAVES + (tid >> 6);
+    if (tid < 64) s_cnt[tid] = 0u;
+    __syncthreads();
+    unsigned c = 0u;
+    if (w < P.W) { const unsigned offered = P.wcnt[w]; c = offered < P.wave_cap ? offered : P.wave_cap; }
+    const v4u* rec = P.wrec + (size_t)(w < P.W ? w : 0) * P.wave_cap;
+    for (unsigned i = lane; i < c; i += 64u) atomicAdd(&s_cnt[rec[i].w & 63u], 1u);
+    __syncthreads();
+    if (tid < 64) {
+        const unsigned n = s_cnt[tid];
+        s_base[tid] = n ? atomicAdd(&P.pair_cnt[tid], n) : 0u;
+        s_cnt[tid] = 0u;
+    }
+    __syncthreads();
+    for (unsigned i = lane; i < c; i += 64u) {
+        const v4u v = rec[i];
+        const unsigned q = v.w & 63u;
+        const unsigned slot = s_base[q] + atomicAdd(&s_cnt[q], 1u);
+        if (slot < P.pcap) P.pair[(size_t)q * P.pcap + slot] = (v4u){v.x, v.y, v.z, 0u};
+        else atomicOr(&P.keep[v.x >> 5], 1u << (v.x & 31u));
     }
 }
 
@@ -563,7 +633,7 @@ hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s) {
     p.q8 = reinterpret_cast<const v4u*>(a.q8); p.scales4 = reinterpret_cast<const float4*>(a.scales);
     p.qpack = reinterpret_cast<const v4u*>(a.qpack); p.qconst = a.qconst; p.tau_init = a.tau_init;
     p.nrows = a.nrows; p.npanels = a.npanels; p.KB = a.dpad / 32; p.nq = a.nq; p.keep_all = a.keep_all;
-    p.pair = reinterpret_cast<v4u*>(a.pair); p.pair_cnt = a.pair_cnt; p.pcap = a.keep_all ? 0u : (unsigned)a.pcap; p.keep = a.keep;
+    p.wrec = reinterpret_cast<v4u*>(a.wrec); p.wcnt = a.wcnt; p.wave_cap = (unsigned)a.wave_cap; p.keep = a.keep;
     const size_t lds = cmr_q8_filter_lds(a.dpad, a.nqt);
     auto launch = [&](auto kern) -> hipError_t {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -575,6 +645,14 @@ hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s) {
     if (a.nqt == 2) return ch8 ? launch(q8_filter_kernel<2, 8>) : launch(q8_filter_kernel<2, 4>);
     if (a.nqt == 1) return ch8 ? launch(q8_filter_kernel<1, 8>) : launch(q8_filter_kernel<1, 4>);
     return hipErrorInvalidValue;
+}
+
+hipError_t cmr_launch_q8_bucket(const CmrQ8Args& a, hipStream_t s) {
+    BucketP p;
+    p.wrec = reinterpret_cast<const v4u*>(a.wrec); p.wcnt = a.wcnt; p.wave_cap = (unsigned)a.wave_cap; p.W = a.grid * CMR_SCAN_WAVES;
+    p.pair = reinterpret_cast<v4u*>(a.pair); p.pair_cnt = a.pair_cnt; p.pcap = (unsigned)a.pcap; p.keep = a.keep;
+    hipLaunchKernelGGL(q8_bucket_kernel, dim3((p.W + Q8_BUCKET_WAVES - 1) / Q8_BUCKET_WAVES), dim3(Q8_BUCKET_WAVES * 64), 0, s, p);
+    return hipGetLastError();
 }
 
 hipError_t cmr_launch_q8_tighten(const CmrQ8Args& a, hipStream_t s) {

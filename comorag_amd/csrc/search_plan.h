@@ -82,6 +82,7 @@ struct PassPlan {
     int prefilter = 0;               // 1 | 2: the int8 filter in the place of the main scan, the re-score in front of the merge (W: the re-score's lists)
     int rescore_grid = 0;
     int pair_cap = 0;                // pre-filter: hit records per query for the threshold tightening (0: none, every hit is re-scored)
+    int wave_cap = 0;                // pre-filter: hit records per wave of the filter's grid (0 exactly when pair_cap is)
     int G = 1;                       // query groups of the query-split grid
     int n_levels = 0;                // sampling passes in front of the main scan
     struct Level { long long panels; int grid, Wl, clog, stride; } level[2] = {};      // grid: launch grid (all groups); Wl: candidate lists per query
@@ -238,6 +239,11 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
         p.bytes.q8[Q8_QCONST] = (size_t)NQ * sizeof(float4);
         p.bytes.q8[Q8_CAND] = (size_t)idx->cap_panels * CMR_PANEL_ROWS * sizeof(unsigned);      // (cap_panels: candidate rows and keep masks follow the corpus buffer)
         p.bytes.q8[Q8_NCAND] = sizeof(unsigned);
+        // the waves' record areas: by default they hold together what the queries' lists hold, in multiples of a wave's 64 lanes
+        const long long fw = (long long)g.grid * CMR_SCAN_WAVES;
+        p.wave_cap = !p.pair_cap ? 0 : idx->pf_wave_cap > 0 ? idx->pf_wave_cap : (int)std::min<long long>(1 << 20, (((long long)NQ * p.pair_cap + fw - 1) / fw + 63) / 64 * 64);
+        p.bytes.q8[Q8_WREC] = std::max<size_t>((size_t)fw * p.wave_cap * 16, 16);
+        p.bytes.q8[Q8_WCNT] = (size_t)fw * sizeof(unsigned);
         p.bytes.q8[Q8_PAIR] = std::max<size_t>((size_t)NQ * p.pair_cap * 16, 16);
         p.bytes.q8[Q8_PAIRCNT] = (size_t)NQ * sizeof(unsigned);
         p.bytes.q8[Q8_KEEP] = (size_t)idx->cap_panels * sizeof(unsigned);

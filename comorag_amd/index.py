@@ -212,7 +212,7 @@ class DenseIndex(HostArrayIndex):
         include/comorag_hip.h), "pipe_dual_scan_active", "pipe_cu_mask_active", "pipe_scan_cus", "exact_cand", "combine",
         "combine_wait_us", the combiner's counters (`combine_stats`), "prefilter" and, of the last pipelined call, "prefilter_active",
         "prefilter_rows", "prefilter_bytes" and — these wait for the pipeline — "prefilter_candidates", "prefilter_pairs",
-        "prefilter_pair_overflow"; "prefilter_tighten", "prefilter_pair_cap"."""
+        "prefilter_pair_overflow", "prefilter_wave_overflow"; "prefilter_tighten", "prefilter_pair_cap", "prefilter_wave_cap"."""
         v = C.c_int64(0)
         L.check(L.lib().cmr_index_get_option(self._h, name.encode(), C.byref(v)))
         return v.value

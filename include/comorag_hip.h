@@ -183,9 +183,12 @@ int32_t cmr_index_set_id_blocks(cmr_index_t* idx, int32_t n_blocks, const int64_
  * row), prefilter_rescore_wgs, prefilter_tighten (1, the default: the k-th largest certified lower bound among a query's hits replaces
  * its sampling threshold in front of the re-score | 0: every hit is re-scored) and prefilter_pair_cap (hit records per query the
  * tightening selects from, 16 bytes each, clamped to [0, 2^20], default 16384; a query with more hits keeps the rest directly; 0:
- * as prefilter_tighten = 0).  cmr_index_get_option reads, of the last pre-filtered pass and waiting for the pipeline:
- * prefilter_candidates (rows handed to the re-score), prefilter_pairs (hit records stored, summed over the queries) and
- * prefilter_pair_overflow (queries that had more hits than records).
+ * as prefilter_tighten = 0) and prefilter_wave_cap (hit records per wave of the filter's grid, which writes them to an area of its own
+ * before they are sorted into the queries' lists, 16 bytes each, clamped to [0, 2^20]; 0, the default: as many as the queries' lists
+ * hold, spread over the waves and rounded up to a multiple of 64; a wave with more hits keeps the rest directly).
+ * cmr_index_get_option reads, of the last pre-filtered pass and waiting for the pipeline:
+ * prefilter_candidates (rows handed to the re-score), prefilter_pairs (hit records stored, summed over the queries),
+ * prefilter_pair_overflow (queries that had more hits than records) and prefilter_wave_overflow (waves that had more hits than records).
  * Unknown names: CMR_ERR_INVALID.
  * The wide-batch kernel exists for padded dims 768 (256 queries per pass) and 1024 (128 per pass) in bf16 / f16; any other
  * dim and every fp32 index run a batch of B > 64 queries on the query-split grid of the narrow kernel (up to four query tiles
