@@ -129,6 +129,34 @@ def test_add_layernorm_fp32_vs_fp64(d, rows, parts):
     _within_protocol(got, ref, want, f"add_layernorm d={d} rows={rows} {parts}")
 
 
+# Every vectors-per-lane bucket of both LayerNorm forms, every element type.  rows = 300: sixteen lanes per row, (d / 8 + 15) / 16 = 3, 4, 5, 7, 10,
+# 14 -> buckets 4, 4, 6, 8, 12, 16.  rows = 7 (<= ENC_LN_FEW_ROWS): a wave per row, (d / 4 + 63) / 64 = 2, 2, 3, 4, 5, 7 -> buckets 2, 2, 3, 4, 6, 8.
+# 16-bit: test_add_layernorm_kernel's fp32 reference and tolerances (tests/test_encoder_fused_gpu.py); fp32: the protocol above.
+@pytest.mark.parametrize("dtype", ["bfloat16", "float16", "float32"])
+@pytest.mark.parametrize("rows", [7, 300])
+@pytest.mark.parametrize("d", [384, 512, 640, 896, 1280, 1792])
+def test_add_layernorm_every_vectors_per_lane_bucket(d, rows, dtype):
+    import torch
+    import torch.nn.functional as F
+    from comorag_amd import _lib as L
+    from tests.test_encoder_fused_gpu import TOL
+    tdt = getattr(torch, dtype)
+    g = torch.Generator(device="cuda").manual_seed(d + rows)
+    rnd = lambda *s: torch.randn(s, generator=g, device="cuda")
+    y, res = (rnd(rows, d) * 2 + 0.3).to(tdt), rnd(rows, d).to(tdt)
+    bias, gamma, beta = rnd(d).to(tdt), (1 + 0.2 * rnd(d)).to(tdt), (0.1 * rnd(d)).to(tdt)
+    fz = _Stages(d, 1)
+    fz.cmr_dtype = {"bfloat16": L.CMR_BF16, "float16": L.CMR_F16, "float32": L.CMR_F32}[dtype]
+    got = fz.add_layernorm(y, bias, res, gamma, beta)
+    assert got.dtype == tdt and got.shape == (rows, d)
+    ref = F.layer_norm(y.float() + bias.float() + res.float(), (d,), gamma.float(), beta.float(), 1e-12)
+    if dtype == "float32":
+        want = F.layer_norm(y.double() + bias.double() + res.double(), (d,), gamma.double(), beta.double(), 1e-12)
+        _within_protocol(got, ref, want, f"add_layernorm d={d} rows={rows}")
+    else:
+        np.testing.assert_allclose(got.float().cpu().numpy(), ref.cpu().numpy(), atol=TOL[dtype], rtol=TOL[dtype])
+
+
 @pytest.mark.parametrize("b,l,d", [(2, 16, 256), (5, 64, 768), (1, 32, 72), (4, 48, 2048)])
 @pytest.mark.parametrize("normalize", [True, False])
 def test_add_layernorm_pool_fp32_vs_fp64(b, l, d, normalize):
