@@ -169,6 +169,13 @@ hipError_t cmr_launch_add_layernorm_pool(const void* y, const void* bias, const 
 hipError_t cmr_launch_embed_layernorm_ragged(const int* ids32, const int* off, const void* word, const void* pos, const void* type, const void* gamma,
                                              const void* beta, float eps, long long rows, int L, int d, int vocab, int n_pos, int pos_off, int dtype,
                                              void* out, hipStream_t s);
+// small-M linear (one short query's token rows): mode 0 y = x w^T + bias, 1 gelu of it, 2 fp32 partial slabs [split, m, n]; and the slabs' consumer
+int cmr_small_linear_split(int n, int k);
+hipError_t cmr_launch_small_linear(const void* x, const void* w, const void* bias, int m, int n, int k, int dtype, int mode, void* out, hipStream_t s);
+hipError_t cmr_launch_add_layernorm_partials(const float* part, int n_split, const void* bias, const void* res, const void* gamma, const void* beta, float eps,
+                                             long long rows, int d, int dtype, void* out, hipStream_t s);
+hipError_t cmr_launch_add_layernorm_partials_pool(const float* slabs, int n_split, const void* bias, const void* res, const void* gamma, const void* beta, float eps, int b,
+                                                  int l, int d, int dtype, const int* lens, int normalize, float* partial, float* out, hipStream_t s);
 // exact top-k of a 16-bit index (cmr_index_search_exact): rows fp32 [n, dim] (device) -> atomicMax of (max ||round(x)||, max ||round(x) - x||)
 // into stats[2] (fp32, device), skipped when *flag (the append's non-finite flag, may be NULL) is set; no-op for fp32 indexes
 hipError_t cmr_launch_round_stats(int dtype, const float* rows, long long n, int dim, const int* flag, float* stats, hipStream_t s);

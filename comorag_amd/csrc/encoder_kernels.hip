@@ -820,10 +820,13 @@ __global__ __launch_bounds__(256) void add_ln16_kernel(const typename EncVec<DT>
 // LDS): one fp32 partial row [d] per block, 1/16 of the bytes of the hidden state at 4 bytes instead of 2 -> an eighth of the
 // write, and nothing is read back but these partials.  Blocks that hold only padding leave at once (no loads, no partial).
 // pool_finish_kernel then adds a sequence's partials in block order, divides by the token count and L2-normalises (eps 1e-12).
-template <int DT, int VPL>
+// SLABS = true (the short-row route's last layer): y is not a 16-bit tensor but the n_split fp32 slabs [n_split, b*l, d] of small_linear_kernel's
+// partials form, added in slab order as add_ln_partials_kernel adds them (slabs: float4 pairs, slab_stride = b*l*d / 4 of them apart).
+template <int DT, int VPL, bool SLABS = false>
 __global__ __launch_bounds__(256) void add_ln16_pool_kernel(const typename EncVec<DT>::V8* __restrict__ y, const typename EncVec<DT>::V8* __restrict__ bias, const typename EncVec<DT>::V8* __restrict__ res,
                                                             const typename EncVec<DT>::V8* __restrict__ gamma, const typename EncVec<DT>::V8* __restrict__ beta, float eps, int l, int d8,
-                                                            const int* __restrict__ lens, float* __restrict__ partial) {
+                                                            const int* __restrict__ lens, float* __restrict__ partial, const float4* __restrict__ slabs = nullptr, int n_split = 0,
+                                                            long long slab_stride = 0) {
     __shared__ float red[4][16 * VPL * 8];
     const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4, wave = threadIdx.x >> 6;
     const int seq = blockIdx.y, t0 = blockIdx.x * 16;
@@ -838,7 +841,16 @@ __global__ __launch_bounds__(256) void add_ln16_pool_kernel(const typename EncVe
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[j][e] = 0.0f;
         if (i < d8) {
-            enc_acc8<DT>(v[j], y[row * d8 + i]);
+            if constexpr (SLABS) {
+                const float4* p = slabs + (row * d8 + i) * 2;
+                for (int sp = 0; sp < n_split; ++sp) {
+                    const float4 lo = p[sp * slab_stride], hi = p[sp * slab_stride + 1];
+                    v[j][0] += lo.x; v[j][1] += lo.y; v[j][2] += lo.z; v[j][3] += lo.w;
+                    v[j][4] += hi.x; v[j][5] += hi.y; v[j][6] += hi.z; v[j][7] += hi.w;
+                }
+            } else {
+                enc_acc8<DT>(v[j], y[row * d8 + i]);
+            }
             if (bias) enc_acc8<DT>(v[j], bias[i]);
             if (res) enc_acc8<DT>(v[j], res[row * d8 + i]);
             sum += ((v[j][0] + v[j][1]) + (v[j][2] + v[j][3])) + ((v[j][4] + v[j][5]) + (v[j][6] + v[j][7]));
@@ -1107,15 +1119,16 @@ static hipError_t launch_embed_ln(const long long* ids, const long long* tt, con
     return hipGetLastError();
 }
 
-template <int DT>
+template <int DT, bool SLABS = false>
 static hipError_t launch_add_ln_pool(const void* y, const void* bias, const void* res, const void* gamma, const void* beta, float eps, int b, int l,
-                                     int d, const int* lens, int normalize, float* partial, float* out, hipStream_t s) {
+                                     int d, const int* lens, int normalize, float* partial, float* out, hipStream_t s, int n_split = 0) {
     const int d8 = d / 8, vpl16 = (d8 + 15) / 16;
     const dim3 grid((unsigned)(l / 16), (unsigned)b), block(256);
+    // (SLABS: y is the fp32 slab array, not a 16-bit tensor)
 #define ENC_LNP(V)                                                                                                                        \
-    hipLaunchKernelGGL((add_ln16_pool_kernel<DT, V>), grid, block, 0, s, reinterpret_cast<const typename EncVec<DT>::V8*>(y), reinterpret_cast<const typename EncVec<DT>::V8*>(bias), \
+    hipLaunchKernelGGL((add_ln16_pool_kernel<DT, V, SLABS>), grid, block, 0, s, reinterpret_cast<const typename EncVec<DT>::V8*>(SLABS ? nullptr : y), reinterpret_cast<const typename EncVec<DT>::V8*>(bias), \
                        reinterpret_cast<const typename EncVec<DT>::V8*>(res), reinterpret_cast<const typename EncVec<DT>::V8*>(gamma), reinterpret_cast<const typename EncVec<DT>::V8*>(beta), eps, l, \
-                       d8, lens, partial)
+                       d8, lens, partial, reinterpret_cast<const float4*>(SLABS ? y : nullptr), n_split, (long long)b * l * d8 * 2)
     switch (vpl16) {
         case 1: ENC_LNP(1); break;
         case 2: ENC_LNP(2); break;
@@ -1142,6 +1155,13 @@ hipError_t cmr_launch_add_layernorm_pool(const void* y, const void* bias, const 
     return launch_add_ln_pool<CMR_DT_F16>(y, bias, res, gamma, beta, eps, b, l, d, lens, normalize, partial, out, s);
 }
 
+// the same with y given as the n_split fp32 slabs [n_split, b*l, d] of the small-M linear's partials form (16-bit dtypes)
+hipError_t cmr_launch_add_layernorm_partials_pool(const float* slabs, int n_split, const void* bias, const void* res, const void* gamma, const void* beta, float eps, int b,
+                                                  int l, int d, int dtype, const int* lens, int normalize, float* partial, float* out, hipStream_t s) {
+    if (dtype == CMR_DT_BF16) return launch_add_ln_pool<CMR_DT_BF16, true>(slabs, bias, res, gamma, beta, eps, b, l, d, lens, normalize, partial, out, s, n_split);
+    return launch_add_ln_pool<CMR_DT_F16, true>(slabs, bias, res, gamma, beta, eps, b, l, d, lens, normalize, partial, out, s, n_split);
+}
+
 hipError_t cmr_launch_embed_layernorm(const long long* ids, const long long* tt, const void* word, const void* pos, const void* type,
                                       const void* gamma, const void* beta, float eps, long long rows, int L, int d, int vocab, int n_pos,
                                       int n_types, int pos_off, int dtype, void* out, hipStream_t s) {
@@ -1155,6 +1175,252 @@ hipError_t cmr_launch_add_layernorm(const void* y, const void* bias, const void*
     if (dtype == CMR_DT_BF16) return launch_add_ln<CMR_DT_BF16>(y, bias, res, gamma, beta, eps, rows, d, out, s);
     if (dtype == CMR_DT_F32) return launch_add_ln<CMR_DT_F32>(y, bias, res, gamma, beta, eps, rows, d, out, s);
     return launch_add_ln<CMR_DT_F16>(y, bias, res, gamma, beta, eps, rows, d, out, s);
+}
+
+// ------------------------------------------------------------------------------------------------ small-M linear
+// y[M, N] = act(x[M, K] w[N, K]^T + bias) for the 1 .. 128 token rows of one short query (`self.embedding_model(**inputs)`,
+// embedding_model/BGEEmbedding.py:119, the four nn.Linear of a BertLayer): all latency, and the weight is the only large operand, so the
+// kernel is a weight stream.  A workgroup owns ONE 16-row tile of w (the A operand of v_mfma_f32_16x16x32: lane l = weight row l & 15,
+// k = 8 (l >> 4) + [0, 8) of a k-step — a 16-byte load straight from nn.Linear's row-major tensor) and one K slice; the token rows are
+// the MFMA's N dimension, 16 per tile, up to eight accumulator tiles per wave.  The grid is N / 16 tiles x S slices: every weight byte
+// is read by exactly one lane of the grid, once.  Inside a workgroup the slice's k-steps go round the four waves (step j of an
+// eight-step chunk -> wave j & 3) and each wave issues ALL the weight loads of a 32-step batch — up to eight 16-byte non-temporal loads
+// per lane — before its first MFMA.  The slice's token tile goes through LDS in chunks of SML_KC columns: every thread brings 16-byte
+// pieces of whole rows (coalesced, once per workgroup), the next chunk's pieces are in flight in registers while this one is multiplied,
+// and the waves read their B fragments from LDS (rows SML_XSTR apart: the sixteen rows of a ds_read_b128 start in sixteen different
+// 16-byte slots).  The four waves' partial tiles are added in wave order through LDS (the token buffer, reused).
+//   MODE 0 / 1 (direct, S = 1): + bias in fp32, rounded to the 16-bit type as the GEMM's output would have been; MODE 1 then applies the
+//     exact erf GELU to the ROUNDED value and rounds again — F.gelu(F.linear(x, w, b)) in one launch.
+//   MODE 2 (partials): the slice's fp32 sums go to slab blockIdx.y of out[S, M, N] with plain 16-byte vector stores, no bias, no
+//     rounding; the consumer launch (add_ln_partials_kernel) adds the slabs in slab order.  No workgroup waits on another one.
+// S, the tile and the order of every sum depend on (N, K) only: a token row's bits do not depend on M or on the other rows.
+#define SML_ROWS 16           // weight rows per workgroup
+#define SML_MAXM 128          // token rows
+#define SML_KC 256            // columns of the token tile per LDS chunk: eight k-steps of 32, two per wave
+#define SML_XSTR (SML_KC + 8) // LDS row stride, elements (528 B = 33 slots of 16 B)
+#define SML_TARGET_WG 192     // workgroups the split aims at (256 CUs; the round-6 kernel's 24 .. 96 were too few requests in flight)
+typedef __attribute__((ext_vector_type(4))) float enc_f32x4;
+
+template <int DT> __device__ __forceinline__ enc_f32x4 sml_mma(v4u a, v4u b, enc_f32x4 c) {
+    if constexpr (DT == CMR_DT_BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+// K slices of the partials form: the smallest divisor s of the K / 32 k-steps that puts N / 16 * s >= SML_TARGET_WG workgroups on the
+// chip while a slice keeps at least four k-steps (one per wave); the largest such divisor if none reaches the target.
+static int sml_split(int n, int k) {
+    const int tiles = n / SML_ROWS, steps = k / 32;
+    int best = 1;
+    for (int s = 1; s <= steps / 4; ++s) {
+        if (steps % s) continue;
+        best = s;
+        if (tiles * s >= SML_TARGET_WG) break;
+    }
+    return best;
+}
+
+// MT = token tiles of 16 rows the instantiation carries (2, 4, 6, 8: M <= 32, 64, 96, 128): it sizes the accumulators, the staging registers and
+// the LDS buffer, never the order of a sum.  No branch in the loads or the MFMA loops: token rows >= M re-read row M - 1 (their columns of
+// the product are never stored), k-steps behind the slice's end load the slice's last step and multiply a ZERO weight fragment (+ 0.0f).
+template <int DT, int MODE, int MT>
+__global__ __launch_bounds__(256) void small_linear_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ w, const unsigned short* __restrict__ bias,
+                                                           int M, int N, int K, int kslice, void* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) unsigned short xs[MT * 16 * SML_XSTR];      // 8.25 KiB per token tile; the wave-order reduction reuses it (4 KiB per tile)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int n0 = blockIdx.x * SML_ROWS, k0 = blockIdx.y * kslice;
+    const int nsteps = kslice / 32, nchunks = (nsteps + 7) / 8;
+    const unsigned short* wrow = w + (size_t)(n0 + r) * K + k0 + 8 * q;
+
+    // token-tile staging: thread -> 16-byte piece xseg of rows xrow + 8 i
+    const int xseg = tid & 31, xrow = tid >> 5;
+    const unsigned short* xp[2 * MT];
+#pragma unroll
+    for (int i = 0; i < 2 * MT; ++i) {
+        const int row = xrow + 8 * i;
+        xp[i] = x + (size_t)(row < M ? row : M - 1) * K + k0;
+    }
+    v4u xr[2 * MT];
+    auto load_x = [&](int c) {
+        int kk = c * SML_KC + 8 * xseg;
+        kk = kk < kslice ? kk : kslice - 8;
+#pragma unroll
+        for (int i = 0; i < 2 * MT; ++i) xr[i] = *reinterpret_cast<const v4u*>(xp[i] + kk);
+    };
+    auto store_x = [&]() {
+#pragma unroll
+        for (int i = 0; i < 2 * MT; ++i) *reinterpret_cast<v4u*>(&xs[(xrow + 8 * i) * SML_XSTR + 8 * xseg]) = xr[i];
+    };
+
+    enc_f32x4 acc[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = enc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    load_x(0);
+    for (int sb = 0; sb < nchunks; sb += 4) {          // a batch: four chunks = 32 k-steps, eight per wave
+        v4u wr[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {                  // the wave's k-steps of the batch, all in flight before the first MFMA
+            const int step = (sb + (i >> 1)) * 8 + 4 * (i & 1) + wave;
+            const v4u t = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(wrow + (step < nsteps ? step : nsteps - 1) * 32));
+            wr[i] = step < nsteps ? t : v4u{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+            const int c = sb + cc;
+            if (c < nchunks) {                         // (workgroup-uniform: every thread meets the same barriers)
+                store_x();
+                __syncthreads();
+                if (c + 1 < nchunks) load_x(c + 1);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const unsigned short* xb = &xs[r * SML_XSTR + (4 * j + wave) * 32 + 8 * q];
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+                        acc[mt] = sml_mma<DT>(wr[2 * cc + j], *reinterpret_cast<const v4u*>(xb + mt * 16 * SML_XSTR), acc[mt]);
+                }
+                __syncthreads();                       // everybody has read this chunk: the next one (or the reduction) may overwrite it
+            }
+        }
+    }
+
+    // the four waves' tiles added in wave order; C/D layout of the 16x16 MFMA: lane -> token l & 15, weight rows 4 (l >> 4) + [0, 4)
+    float* red = reinterpret_cast<float*>(xs);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) *reinterpret_cast<enc_f32x4*>(&red[((wave * MT + mt) * 64 + lane) * 4]) = acc[mt];
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < MT / 4 + (MT % 4 ? 1 : 0); ++it) {
+        const int item = tid + 256 * it, mt = item >> 6, ln = item & 63;
+        const int m = mt * 16 + (ln & 15), n = n0 + 4 * (ln >> 4);
+        if (mt >= MT || m >= M) continue;
+        enc_f32x4 s = *reinterpret_cast<const enc_f32x4*>(&red[(mt * 64 + ln) * 4]);
+#pragma unroll
+        for (int wv = 1; wv < 4; ++wv) s += *reinterpret_cast<const enc_f32x4*>(&red[((wv * MT + mt) * 64 + ln) * 4]);
+        if constexpr (MODE == 2) {
+            *reinterpret_cast<enc_f32x4*>(reinterpret_cast<float*>(out) + ((size_t)blockIdx.y * M + m) * N + n) = s;
+        } else {
+            float v[4] = {s[0], s[1], s[2], s[3]};
+            if (bias) enc_acc4<DT>(v, *reinterpret_cast<const uint2*>(bias + n));
+            uint2 o = enc_put4<DT>(v[0], v[1], v[2], v[3]);
+            if constexpr (MODE == 1) {                 // the model's erf GELU on the rounded pre-activation, as F.gelu sees it
+                enc_get4<DT>(v, o);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = 0.5f * v[e] * (1.0f + erff(v[e] * 0.70710678118654752440f));
+                o = enc_put4<DT>(v[0], v[1], v[2], v[3]);
+            }
+            *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(out) + (size_t)m * N + n) = o;
+        }
+    }
+}
+
+template <int DT, int MODE>
+static hipError_t launch_small_linear(const void* x, const void* w, const void* bias, int m, int n, int k, int split, void* out, hipStream_t s) {
+    const dim3 grid((unsigned)(n / SML_ROWS), (unsigned)split), block(256);
+#define ENC_SML(T)                                                                                                                     \
+    hipLaunchKernelGGL((small_linear_kernel<DT, MODE, T>), grid, block, 0, s, reinterpret_cast<const unsigned short*>(x), reinterpret_cast<const unsigned short*>(w), \
+                       reinterpret_cast<const unsigned short*>(bias), m, n, k, k / split, out)
+    if (m <= 32) ENC_SML(2);
+    else if (m <= 64) ENC_SML(4);
+    else if (m <= 96) ENC_SML(6);
+    else ENC_SML(8);
+#undef ENC_SML
+    return hipGetLastError();
+}
+
+int cmr_small_linear_split(int n, int k) { return sml_split(n, k); }
+
+// mode 0: F.linear; 1: F.gelu(F.linear); 2: fp32 partial slabs [cmr_small_linear_split(n, k), m, n] (bias unused).  16-bit dtypes, 1 <= m <= 128,
+// n % 16 == 0, k % 32 == 0, 16-byte aligned buffers (the caller checks)
+hipError_t cmr_launch_small_linear(const void* x, const void* w, const void* bias, int m, int n, int k, int dtype, int mode, void* out, hipStream_t s) {
+    const int split = mode == 2 ? sml_split(n, k) : 1;
+    if (dtype == CMR_DT_BF16) {
+        if (mode == 0) return launch_small_linear<CMR_DT_BF16, 0>(x, w, bias, m, n, k, split, out, s);
+        if (mode == 1) return launch_small_linear<CMR_DT_BF16, 1>(x, w, bias, m, n, k, split, out, s);
+        return launch_small_linear<CMR_DT_BF16, 2>(x, w, bias, m, n, k, split, out, s);
+    }
+    if (mode == 0) return launch_small_linear<CMR_DT_F16, 0>(x, w, bias, m, n, k, split, out, s);
+    if (mode == 1) return launch_small_linear<CMR_DT_F16, 1>(x, w, bias, m, n, k, split, out, s);
+    return launch_small_linear<CMR_DT_F16, 2>(x, w, bias, m, n, k, split, out, s);
+}
+
+// LayerNorm(sum over the S slabs of partial[s] + bias + residual): the consumer of small_linear_kernel's partials form.  The slabs
+// [S, rows, d] fp32 are added in slab order; from there on it is add_ln_kernel (a wave per row, the shared body enc_ln_store).
+template <int DT, int VPL>
+__global__ __launch_bounds__(256) void add_ln_partials_kernel(const float4* __restrict__ part, int n_split, const typename EncVec<DT>::V4* __restrict__ bias,
+                                                              const typename EncVec<DT>::V4* __restrict__ res, const typename EncVec<DT>::V4* __restrict__ gamma,
+                                                              const typename EncVec<DT>::V4* __restrict__ beta, float eps, long long rows, int d4, typename EncVec<DT>::V4* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long row = (long long)blockIdx.x * 4 + wave;
+    if (row >= rows) return;
+    const long long slab = rows * d4;
+    float v[VPL][4];
+    float sum = 0.0f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) v[j][0] = v[j][1] = v[j][2] = v[j][3] = 0.0f;
+    // slab order.  Four slabs at a time: their 4 VPL loads per lane are in flight together (80 rows are 80 waves: all latency), then added in order
+    int sp = 0;
+    for (; sp + 4 <= n_split; sp += 4) {
+        const float4* p = part + sp * slab + row * d4;
+        float4 t[4][VPL];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) {
+                const int i = j * 64 + lane;
+                t[u][j] = p[u * slab + (i < d4 ? i : 0)];
+            }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) { v[j][0] += t[u][j].x; v[j][1] += t[u][j].y; v[j][2] += t[u][j].z; v[j][3] += t[u][j].w; }
+    }
+    for (; sp < n_split; ++sp) {
+        const float4* p = part + sp * slab + row * d4;
+#pragma unroll
+        for (int j = 0; j < VPL; ++j) {
+            const int i = j * 64 + lane;
+            const float4 t = p[i < d4 ? i : 0];
+            v[j][0] += t.x; v[j][1] += t.y; v[j][2] += t.z; v[j][3] += t.w;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int i = j * 64 + lane;
+        if (i < d4) {
+            if (bias) enc_acc4<DT>(v[j], bias[i]);
+            if (res) enc_acc4<DT>(v[j], res[row * d4 + i]);
+            sum += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
+        }
+    }
+    enc_ln_store<DT, VPL>(v, sum, lane, d4, gamma, beta, eps, out + row * d4);
+}
+
+template <int DT>
+static hipError_t launch_add_ln_partials(const float* part, int n_split, const void* bias, const void* res, const void* gamma, const void* beta, float eps,
+                                         long long rows, int d, void* out, hipStream_t s) {
+    const int d4 = d / 4, vpl = (d4 + 63) / 64;
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+#define ENC_LNS(V)                                                                                                                    \
+    hipLaunchKernelGGL((add_ln_partials_kernel<DT, V>), grid, block, 0, s, reinterpret_cast<const float4*>(part), n_split, reinterpret_cast<const typename EncVec<DT>::V4*>(bias), \
+                       reinterpret_cast<const typename EncVec<DT>::V4*>(res), reinterpret_cast<const typename EncVec<DT>::V4*>(gamma), reinterpret_cast<const typename EncVec<DT>::V4*>(beta), eps, \
+                       rows, d4, reinterpret_cast<typename EncVec<DT>::V4*>(out))
+    switch (vpl) {
+        case 1: ENC_LNS(1); break;
+        case 2: ENC_LNS(2); break;
+        case 3: ENC_LNS(3); break;
+        case 4: ENC_LNS(4); break;
+        case 5: case 6: ENC_LNS(6); break;
+        case 7: case 8: ENC_LNS(8); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef ENC_LNS
+    return hipGetLastError();
+}
+
+hipError_t cmr_launch_add_layernorm_partials(const float* part, int n_split, const void* bias, const void* res, const void* gamma, const void* beta, float eps,
+                                             long long rows, int d, int dtype, void* out, hipStream_t s) {
+    if (dtype == CMR_DT_BF16) return launch_add_ln_partials<CMR_DT_BF16>(part, n_split, bias, res, gamma, beta, eps, rows, d, out, s);
+    return launch_add_ln_partials<CMR_DT_F16>(part, n_split, bias, res, gamma, beta, eps, rows, d, out, s);
 }
 
 // ------------------------------------------------------------------------------------------ C-ABI (include/comorag_hip.h)
@@ -1206,6 +1472,92 @@ int32_t cmr_encoder_add_layernorm_pool(int32_t device_id, const void* y_dev, con
     if (rc) return rc;
     HIP_TRY(cmr_launch_add_layernorm_pool(y_dev, bias_dev, residual_dev, gamma_dev, beta_dev, eps, b, l, d, dtype, (const int*)lens_dev, normalize, partial_dev,
                                           out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+// shape / type checks shared by the small-M entry points (no device call)
+static int sml_check(const char* who, int32_t m, int32_t n, int32_t k, int32_t dtype) {
+    if (m <= 0 || n <= 0 || k <= 0) return cmr_fail(CMR_ERR_INVALID, "%s: m, n, k must be > 0", who);
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "%s: dtype must be bf16 or f16", who);
+    if (dtype == CMR_F32) return cmr_fail(CMR_ERR_UNSUPPORTED, "%s: 16-bit tensors only (bf16 or f16)", who);
+    if (m > SML_MAXM) return cmr_fail(CMR_ERR_UNSUPPORTED, "%s: at most %d token rows", who, SML_MAXM);
+    if (n % SML_ROWS || k % 32) return cmr_fail(CMR_ERR_UNSUPPORTED, "%s: n must be a multiple of 16 and k a multiple of 32", who);
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_linear_small_split(int32_t m, int32_t n, int32_t k, int32_t dtype, int32_t* n_split, int64_t* slab_bytes) {
+    if (!n_split || !slab_bytes) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = sml_check("cmr_encoder_linear_small_split", m, n, k, dtype);
+    if (rc) return rc;
+    *n_split = cmr_small_linear_split(n, k);
+    *slab_bytes = (int64_t)*n_split * m * n * (int64_t)sizeof(float);
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_linear_small(int32_t device_id, const void* x_dev, const void* w_dev, const void* bias_dev, int32_t m, int32_t n, int32_t k, int32_t dtype,
+                                 int32_t act, void* out_dev, void* stream) {
+    if (!x_dev || !w_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (act != 0 && act != 1) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_linear_small: act must be 0 (none) or 1 (erf GELU)");
+    int rc = sml_check("cmr_encoder_linear_small", m, n, k, dtype);
+    if (rc) return rc;
+    if (((uintptr_t)x_dev | (uintptr_t)w_dev | (uintptr_t)bias_dev | (uintptr_t)out_dev) & 15)
+        return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_linear_small: buffers must be 16-byte aligned");
+    rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_small_linear(x_dev, w_dev, bias_dev, m, n, k, dtype, act, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_linear_small_partials(int32_t device_id, const void* x_dev, const void* w_dev, int32_t m, int32_t n, int32_t k, int32_t dtype,
+                                          float* partials_dev, void* stream) {
+    if (!x_dev || !w_dev || !partials_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = sml_check("cmr_encoder_linear_small_partials", m, n, k, dtype);
+    if (rc) return rc;
+    if (((uintptr_t)x_dev | (uintptr_t)w_dev | (uintptr_t)partials_dev) & 15)
+        return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_linear_small_partials: buffers must be 16-byte aligned");
+    rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_small_linear(x_dev, w_dev, nullptr, m, n, k, dtype, 2, partials_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_add_layernorm_partials(int32_t device_id, const float* partials_dev, int32_t n_split, const void* bias_dev, const void* residual_dev,
+                                           const void* gamma_dev, const void* beta_dev, float eps, int64_t rows, int32_t d, int32_t dtype, void* out_dev, void* stream) {
+    if (!partials_dev || !gamma_dev || !beta_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (rows <= 0 || n_split <= 0 || d <= 0 || d % 4 || d > 2048)
+        return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm_partials: rows, n_split > 0, d a multiple of 4, d <= 2048");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm_partials: dtype must be bf16 or f16");
+    if (dtype == CMR_F32) return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_partials: 16-bit tensors only (bf16 or f16)");
+    if (((uintptr_t)partials_dev & 15) || (((uintptr_t)bias_dev | (uintptr_t)residual_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)out_dev) & 7))
+        return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_partials: the slabs must be 16-byte aligned, the 16-bit buffers 8-byte aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_add_layernorm_partials(partials_dev, n_split, bias_dev, residual_dev, gamma_dev, beta_dev, eps, rows, d, dtype, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_add_layernorm_partials_pool(int32_t device_id, const float* partials_dev, int32_t n_split, const void* bias_dev, const void* residual_dev,
+                                                const void* gamma_dev, const void* beta_dev, float eps, int32_t b, int32_t l, int32_t d, int32_t dtype,
+                                                const int32_t* lens_dev, int32_t normalize, float* pool_partial_dev, float* out_dev, void* stream) {
+    if (!partials_dev || !gamma_dev || !beta_dev || !lens_dev || !pool_partial_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (b <= 0 || l <= 0 || d <= 0 || n_split <= 0) return cmr_fail(CMR_ERR_INVALID, "b, l, d, n_split must be > 0");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_add_layernorm_partials_pool: dtype must be bf16 or f16");
+    if (dtype == CMR_F32) return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_partials_pool: 16-bit tensors only (bf16 or f16)");
+    if (l % 16 || d % 8 || d > 2048) return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_partials_pool: l must be a multiple of 16, d a multiple of 8 and <= 2048");
+    if (((uintptr_t)partials_dev | (uintptr_t)bias_dev | (uintptr_t)residual_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)pool_partial_dev | (uintptr_t)out_dev) & 15)
+        return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_add_layernorm_partials_pool: buffers must be 16-byte aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_add_layernorm_partials_pool(partials_dev, n_split, bias_dev, residual_dev, gamma_dev, beta_dev, eps, b, l, d, dtype, (const int*)lens_dev, normalize,
+                                                   pool_partial_dev, out_dev, (hipStream_t)stream));
     return CMR_OK;
 }
 

@@ -101,7 +101,8 @@ class _EncodeReplica:
             self.model = owner.embedding_model if same else copy.deepcopy(owner.embedding_model).to(device).eval()
             with torch.cuda.device(device):
                 self.fused = fused_bert.FusedBertLayers(self.model, graphs=owner._fused.graphs, gelu="epilogue" if owner._fused.gelu_path.startswith("hipblaslt") else "exact",
-                                                        fp32=owner._fused.dtype == torch.float32, head32=owner._fused.head_dim == 32)
+                                                        fp32=owner._fused.dtype == torch.float32, head32=owner._fused.head_dim == 32,
+                                                        small_m=owner._fused.small_m_rows > 0, small_m_rows=owner._fused.small_m_rows)
         self.stream = torch.cuda.Stream(device)
         self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=f"cmr-enc-{device.index}")
         self.first = first
@@ -145,17 +146,22 @@ class HipBGEEmbeddingModel(BaseEmbeddingModel):
         # 16-bit BERT encoders run their layers through fused_bert.FusedBertLayers (HIP attention and bias + residual +
         # LayerNorm stages around PyTorch's GEMMs); anything else keeps the transformers forward.  `encoder_path` names it.
         self._fused, self.encoder_path = None, "transformers"
+        self.small_m_rows = 0      # token rows up to which the short-row route (embedding_fused_small_m) is armed; 0: not armed
         if bool(cfg_get(self.global_config, "embedding_fused_encoder", True)):
             from . import fused_bert
             fp32 = bool(cfg_get(self.global_config, "embedding_fused_fp32", False))       # opt-in: fp32 models through the fp32 kernels
             head32 = bool(cfg_get(self.global_config, "embedding_fused_head32", False))   # opt-in: 32-wide heads (the 384-hidden small tier)
+            small_m = bool(cfg_get(self.global_config, "embedding_fused_small_m", False))  # opt-in: one short query's linear layers on the small-M kernels
+            small_m_rows = int(cfg_get(self.global_config, "embedding_small_m_rows", fused_bert.SMALL_M_ROWS))
             reason = fused_bert.why_not(self.embedding_model, fp32=fp32, head32=head32)
             if reason is None and getattr(tokenizer, "padding_side", "right") != "right":
                 reason = "left-padding tokenizer"
             if reason is None:
                 self._fused = fused_bert.FusedBertLayers(self.embedding_model, graphs=int(cfg_get(self.global_config, "embedding_hip_graphs", 24)),
-                                                         gelu=str(cfg_get(self.global_config, "embedding_gelu", "exact")), fp32=fp32, head32=head32)
+                                                         gelu=str(cfg_get(self.global_config, "embedding_gelu", "exact")), fp32=fp32, head32=head32,
+                                                         small_m=small_m, small_m_rows=small_m_rows)
                 self.encoder_path = "hip-fused-layers"
+                self.small_m_rows = self._fused.small_m_rows
             else:
                 self.encoder_path = f"transformers ({reason})"
         self.max_positions = int(getattr(self.embedding_model.config, "max_position_embeddings", 1 << 30))

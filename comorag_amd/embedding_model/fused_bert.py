@@ -161,8 +161,21 @@ def gelu_epilogue_available(device, dtype) -> bool:
         return False
 
 
+# The short-row route (small_m = True): token rows b*l up to which it is taken.  SMALL_M_MAX_ROWS is the kernels' limit; SMALL_M_ROWS the
+# default, the measured crossover of tools/encoder_bench.py --small-m (profiles/encoder_small_m.json).
+# Measured (profiles/encoder_small_m.json; us per layer, small-M / hipBLASLt stages, medians, one weight set per layer taken in turn):
+#   BGE-base bf16   M = 16: 34.5 / 40.5   80: 41.0 / 48.9   96: 41.5 / 46.6   128: 45.4 / 48.2 (inside the spreads: fails the rule)
+#   BGE-large fp16  M = 16: 40.5 / 48.8   80: 49.0 / 61.0   96: 49.9 / 61.6   128: 55.4 / 63.8
+# The whole route passes the rule at both shapes up to 96 rows, so every stage is routed — also the O-projection + LayerNorm stage, which
+# alone loses at the base shape (12.1 against 11.1 us at 80 rows).
+SMALL_M_MAX_ROWS = 128
+SMALL_M_ROWS = 96
+_SPLITS = {}      # (n, k, cmr dtype) -> K slices of the partials form (cmr_encoder_linear_small_split)
+
+
 class FusedBertLayers:
-    def __init__(self, model, graphs: int = 0, gelu: str = "exact", fp32: bool = False, head32: bool = False):
+    def __init__(self, model, graphs: int = 0, gelu: str = "exact", fp32: bool = False, head32: bool = False, small_m: bool = False,
+                 small_m_rows: Optional[int] = None):
         """gelu = "exact" (default): FFN-up GEMM + bias in hipBLASLt, then PyTorch's erf-form GELU kernel — the function the model
         was trained with and the reference runs (BGEEmbedding.py:119-120, `hidden_act = "gelu"`).
         gelu = "epilogue" (opt-in, `embedding_gelu`): projection, bias and GELU are ONE hipBLASLt GEMM (`torch._addmm_activation`) —
@@ -175,7 +188,12 @@ class FusedBertLayers:
         fp32 = True admits an fp32 model: fp32 tensors through every stage (cmr_dtype = CMR_F32: exact f32-input MFMA attention,
         LayerNorm written unrounded), F.linear in fp32 as the transformers forward calls it.  gelu = "epilogue" then runs the exact
         kernel too: the tanh epilogue was validated against 16-bit rounding steps only.
-        head32 = True admits 32-wide heads (`head_dim` = 32: the attention call names the width, nothing else changes)."""
+        head32 = True admits 32-wide heads (`head_dim` = 32: the attention call names the width, nothing else changes).
+        small_m = True (opt-in, `embedding_fused_small_m`; 16-bit models, fp32 ones ignore it) arms the short-row route: a mini-batch of
+        b*l <= small_m_rows token rows (default SMALL_M_ROWS = 96, at most 128 — one short query) runs its four linear layers on the library's
+        weight-streaming small-M kernels instead of hipBLASLt (`_layers_small_m`); larger mini-batches keep the route above, bit for bit.
+        `small_m_rows` is the armed limit (0: not armed).  The route computes the exact erf GELU: where gelu = "epilogue" is in effect
+        (`gelu_path` says so) it is NOT armed, so that every mini-batch size gets the same function."""
         import torch
         reason = why_not(model, fp32=fp32, head32=head32)
         if reason is not None:
@@ -198,6 +216,11 @@ class FusedBertLayers:
         self.gelu_path = "hipblaslt-epilogue-tanh" if (gelu == "epilogue" and gelu_epilogue_available(self.device, self.dtype)) else "exact-erf-kernel"
         import threading
         self.fold_pool = True                        # the encoder tail (mean-pool + L2-norm) rides the last layer's LayerNorm kernel
+        # (not with the tanh epilogue: the route's GELU is the erf form, and one model must not compute two functions depending on the batch size)
+        armed = (bool(small_m) and self.dtype != torch.float32 and self.hidden % 32 == 0 and int(cfg.intermediate_size) % 32 == 0
+                 and self.gelu_path == "exact-erf-kernel")
+        rows = SMALL_M_ROWS if small_m_rows is None else int(small_m_rows)
+        self.small_m_rows = max(0, min(rows, SMALL_M_MAX_ROWS)) if armed else 0
         self.graphs = int(graphs)                    # mini-batch shapes kept as captured hipGraphs (0: every forward is launched eagerly)
         self._graphs, self._seen, self._glock = {}, {}, threading.Lock()
         self.layers = []
@@ -278,6 +301,65 @@ class FusedBertLayers:
                                                        1 if normalize else 0, C.c_void_p(partial.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
+    def linear_small(self, x, w, bias=None, gelu: bool = False, stream: Optional[int] = None):
+        """F.linear(x, w, bias) — or F.gelu of it — for 1 .. 128 token rows in one launch (cmr_encoder_linear_small)."""
+        import torch
+        m, k = x.shape
+        n = w.shape[0]
+        assert x.is_contiguous() and w.is_contiguous() and w.shape[1] == k, "linear_small reads row-major [m, k] and [n, k] tensors"
+        out = torch.empty((m, n), dtype=x.dtype, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        L.check(L.lib().cmr_encoder_linear_small(x.device.index or 0, C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()),
+                                                 C.c_void_p(bias.data_ptr() if bias is not None else 0), m, n, k, self.cmr_dtype, 1 if gelu else 0,
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
+    def linear_small_partials(self, x, w, stream: Optional[int] = None):
+        """x @ w.T for 1 .. 128 token rows as fp32 slabs [n_split, m, n] (cmr_encoder_linear_small_partials): K is split over the grid,
+        the slabs are summed by `add_layernorm_partials`.  The slab tensor is allocated here, so a graph capture owns it."""
+        import torch
+        m, k = x.shape
+        n = w.shape[0]
+        assert x.is_contiguous() and w.is_contiguous() and w.shape[1] == k, "linear_small_partials reads row-major [m, k] and [n, k] tensors"
+        n_split = _SPLITS.get((n, k, self.cmr_dtype))
+        if n_split is None:                                         # a function of (n, k, dtype): asked once
+            ns, nbytes = C.c_int32(0), C.c_int64(0)
+            L.check(L.lib().cmr_encoder_linear_small_split(m, n, k, self.cmr_dtype, C.byref(ns), C.byref(nbytes)))
+            n_split = _SPLITS[(n, k, self.cmr_dtype)] = int(ns.value)
+        part = torch.empty((n_split, m, n), dtype=torch.float32, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        L.check(L.lib().cmr_encoder_linear_small_partials(x.device.index or 0, C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), m, n, k, self.cmr_dtype,
+                                                          C.c_void_p(part.data_ptr()), C.c_void_p(stream)))
+        return part
+
+    def add_layernorm_partials(self, part, bias, residual, gamma, beta, stream: Optional[int] = None):
+        """LayerNorm(sum of the slabs + bias + residual) (cmr_encoder_add_layernorm_partials) -> [m, n] of the model's dtype."""
+        import torch
+        n_split, m, n = part.shape
+        out = torch.empty((m, n), dtype=self.dtype, device=part.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(part.device).cuda_stream
+        L.check(L.lib().cmr_encoder_add_layernorm_partials(part.device.index or 0, C.c_void_p(part.data_ptr()), n_split, C.c_void_p(bias.data_ptr() if bias is not None else 0),
+                                                           C.c_void_p(residual.data_ptr() if residual is not None else 0), C.c_void_p(gamma.data_ptr()),
+                                                           C.c_void_p(beta.data_ptr()), self.eps, m, n, self.cmr_dtype, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
+    def add_layernorm_partials_pool(self, part, bias, residual, gamma, beta, lens_dev, b: int, l: int, normalize: bool = True, stream: Optional[int] = None):
+        """The last layer's add_layernorm_partials with mean_pooling + F.normalize folded in (cmr_encoder_add_layernorm_partials_pool: the
+        add_layernorm_pool kernel reading the slabs): [b, hidden] fp32."""
+        import torch
+        out = torch.empty((b, self.hidden), dtype=torch.float32, device=part.device)
+        scratch = torch.empty((b * (l // 16), self.hidden), dtype=torch.float32, device=part.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(part.device).cuda_stream
+        L.check(L.lib().cmr_encoder_add_layernorm_partials_pool(part.device.index or 0, C.c_void_p(part.data_ptr()), part.shape[0], C.c_void_p(bias.data_ptr() if bias is not None else 0),
+                                                                C.c_void_p(residual.data_ptr() if residual is not None else 0), C.c_void_p(gamma.data_ptr()),
+                                                                C.c_void_p(beta.data_ptr()), self.eps, b, l, self.hidden, self.cmr_dtype, C.c_void_p(lens_dev.data_ptr()),
+                                                                1 if normalize else 0, C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
     def can_pool(self, l: int) -> bool:
         """Can the encoder tail be folded into the last layer's LayerNorm for mini-batches of l (padded) tokens?"""
         return self.fold_pool and l % 16 == 0 and self.hidden % 8 == 0
@@ -303,6 +385,8 @@ class FusedBertLayers:
     def _layers(self, x, lens_dev, b: int, l: int, pool, stream):
         import torch
         import torch.nn.functional as F
+        if 0 < b * l <= self.small_m_rows:
+            return self._layers_small_m(x, lens_dev, b, l, pool, stream)
         last = len(self.layers) - 1
         for n, (wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2) in enumerate(self.layers):
             qkv = F.linear(x, wqkv, bqkv)
@@ -315,6 +399,21 @@ class FusedBertLayers:
             if n == last and pool is not None:
                 return self.add_layernorm_pool(F.linear(h, w2), b2, x, g2, be2, lens_dev, b, l, bool(pool), stream)
             x = self.add_layernorm(F.linear(h, w2), b2, x, g2, be2, stream)
+        return x.view(b, l, self.hidden)
+
+    def _layers_small_m(self, x, lens_dev, b: int, l: int, pool, stream):
+        """The short-row route: seven launches per layer, none of them a PyTorch GEMM or GELU kernel.  The two K-split projections hand
+        fp32 slabs to the LayerNorm launch that follows them; nothing waits inside a launch.  The GELU is the exact erf form."""
+        last = len(self.layers) - 1
+        for n, (wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2) in enumerate(self.layers):
+            qkv = self.linear_small(x, wqkv, bqkv, False, stream)
+            ctx = self.attention(qkv, lens_dev, b, l, stream)
+            x = self.add_layernorm_partials(self.linear_small_partials(ctx, wo, stream), bo, x, g1, be1, stream)
+            h = self.linear_small(x, w1, b1, True, stream)
+            part = self.linear_small_partials(h, w2, stream)
+            if n == last and pool is not None:
+                return self.add_layernorm_partials_pool(part, b2, x, g2, be2, lens_dev, b, l, bool(pool), stream)
+            x = self.add_layernorm_partials(part, b2, x, g2, be2, stream)
         return x.view(b, l, self.hidden)
 
     def __call__(self, input_ids, lens: np.ndarray, token_type_ids=None, consume=None, pool=None):

@@ -42,6 +42,8 @@ class BaseConfig:
     embedding_fused_encoder: bool = True          # 16-bit BERT encoders: HIP attention + bias/residual/LayerNorm stages, one QKV GEMM (embedding_model/fused_bert.py)
     embedding_fused_fp32: bool = False            # opt-in: fp32 BERT encoders (embedding_model_dtype "auto" / fp32 checkpoints) run the fused stack too, fp32 end to end (f32-input MFMA attention, fp32 LayerNorm kernels)
     embedding_fused_head32: bool = False          # opt-in: 32-wide heads (384 hidden / 12 heads: bge-small, e5-small, MiniLM) run the fused stack too (HD = 32 attention kernels); combinable with embedding_fused_fp32.  Off ONLY because three existing tests pin the default refusal "head width is not 64" (tests/test_encoder_fused_gpu.py, test_store_host.py, test_encoder_fp32_host.py): flip the default together with those tests
+    embedding_fused_small_m: bool = False         # opt-in: a mini-batch of at most embedding_small_m_rows token rows (one short query) runs its linear layers on the library's weight-streaming small-M kernels instead of hipBLASLt (16-bit models; fp32 ones ignore it; not armed with embedding_gelu = "epilogue" in effect: the route's GELU is the exact erf form)
+    embedding_small_m_rows: int = 96              # token rows b*l up to which that route is taken (at most 128): the measured crossover, profiles/encoder_small_m.json
     embedding_devices: Optional[list] = None      # GPUs of the corpus-encode replicas (BGEEmbedding.py:77 `device_map="auto"`): one copy of the layer stack each, bucketing windows dealt round them; None = `device` only
     embedding_encode_replicas: int = 0            # > the device count: logical replicas going round `embedding_devices` (rehearsal on a one-GPU box); 0 = one per device
     embedding_query_cache: int = 256              # single-string batch_encode results kept (by prompt, max_length, normalisation): a question is encoded three times per tri_retrieve — the same prompt each time; 0 = off

@@ -529,6 +529,41 @@ int32_t cmr_encoder_add_layernorm(int32_t device_id, const void* y_dev, const vo
                                   const void* residual_dev, const void* gamma_dev, const void* beta_dev,
                                   float eps, int64_t rows, int32_t d, int32_t dtype, void* out_dev, void* stream);
 
+/* ---- encoder: the linear layers of ONE SHORT QUERY (1 .. 128 token rows) -----------------------------------------------------
+ * The four nn.Linear of the model's BertLayer inside `self.embedding_model(**inputs)` (embedding_model/BGEEmbedding.py:119) for a
+ * mini-batch of m = b*l <= 128 token rows, where a library GEMM is all launch and latency: weight-streaming kernels over nn.Linear's
+ * own row-major weight w_dev [n, k] (no packed copy), fp32 accumulation.  dtype = CMR_BF16 or CMR_F16 (every 16-bit tensor of a call has
+ * that type); n % 16 == 0, k % 32 == 0, 16-byte aligned buffers.  Checked before any device call: NULL pointers, m / n / k <= 0 and an
+ * unknown dtype are CMR_ERR_INVALID; m > 128, other n / k, CMR_F32 and misaligned buffers are CMR_ERR_UNSUPPORTED.  A token row's result
+ * does not depend on m or on the other rows (the split and the order of every sum are functions of n and k).
+ *
+ * cmr_encoder_linear_small: out16_dev [m, n] = x_dev [m, k] w^T + bias (bias_dev [n] or NULL) summed in fp32 and rounded to the 16-bit
+ *   type — BertSelfAttention's packed query | key | value projection (act = 0) — and, with act = 1, the model's exact erf GELU of that
+ *   ROUNDED value, rounded again: BertIntermediate, F.gelu(F.linear(x, w, b)) in one launch.
+ * cmr_encoder_linear_small_partials: the same product with K split over n_split workgroup slices (BertSelfOutput.dense, BertOutput.dense:
+ *   k = hidden or intermediate): partials_dev [n_split, m, n] fp32, slice s of the sum in slab s, no bias, nothing rounded.  The slabs
+ *   are combined by the NEXT launch, cmr_encoder_add_layernorm_partials — no workgroup waits on another one.
+ * cmr_encoder_linear_small_split: n_split and the bytes of the slabs for (m, n, k, dtype), so that the caller can allocate.
+ * cmr_encoder_add_layernorm_partials: out = LayerNorm(sum_s partials[s] + bias + residual) * gamma + beta over rows of d elements (the
+ *   slabs added in slab order in fp32, then cmr_encoder_add_layernorm's body: BertSelfOutput / BertOutput after their dense GEMM);
+ *   bias_dev / residual_dev may be NULL; d % 4 == 0, d <= 2048, slabs 16-byte and 16-bit buffers 8-byte aligned.
+ * cmr_encoder_add_layernorm_partials_pool: the LAST layer's cmr_encoder_add_layernorm_partials with the encoder tail folded in — what
+ *   cmr_encoder_add_layernorm_pool is to cmr_encoder_add_layernorm (mean_pooling, embedding_model/BGEEmbedding.py:15-28, and F.normalize,
+ *   :126-127): the same kernel with the slabs as its input; out_dev [b, d] fp32, pool_partial_dev b * (l / 16) * d floats of scratch;
+ *   l % 16 == 0, d % 8 == 0, d <= 2048, 16-byte aligned buffers, CMR_ERR_UNSUPPORTED otherwise.                                    */
+int32_t cmr_encoder_linear_small(int32_t device_id, const void* x_dev, const void* w_dev, const void* bias_dev, int32_t m, int32_t n,
+                                 int32_t k, int32_t dtype, int32_t act, void* out16_dev, void* stream);
+int32_t cmr_encoder_linear_small_partials(int32_t device_id, const void* x_dev, const void* w_dev, int32_t m, int32_t n, int32_t k,
+                                          int32_t dtype, float* partials_dev, void* stream);
+int32_t cmr_encoder_linear_small_split(int32_t m, int32_t n, int32_t k, int32_t dtype, int32_t* n_split, int64_t* slab_bytes);
+int32_t cmr_encoder_add_layernorm_partials(int32_t device_id, const float* partials_dev, int32_t n_split, const void* bias_dev,
+                                           const void* residual_dev, const void* gamma_dev, const void* beta_dev, float eps,
+                                           int64_t rows, int32_t d, int32_t dtype, void* out_dev, void* stream);
+int32_t cmr_encoder_add_layernorm_partials_pool(int32_t device_id, const float* partials_dev, int32_t n_split, const void* bias_dev,
+                                                const void* residual_dev, const void* gamma_dev, const void* beta_dev, float eps,
+                                                int32_t b, int32_t l, int32_t d, int32_t dtype, const int32_t* lens_dev, int32_t normalize,
+                                                float* pool_partial_dev, float* out_dev, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------
  * HIP-event timing of the dominant kernel (the corpus scan) on the stream it is launched on.
  * enable → run searches → collect returns launches, summed kernel ms and the algorithmic bytes

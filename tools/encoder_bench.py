@@ -4,7 +4,10 @@ BERT-large fp16 shapes, fused layer stack against the transformers forward.  `py
 same run) — one short query, the corpus forward at 512 tokens, and the fp32 attention kernel next to PyTorch's SDPA on the same tensors.
 `python -m tools.encoder_bench --head32 [--out FILE]`: the 32-wide-head rows (the bge-small shape, `embedding_fused_head32` on and off in the same
 run, bf16 / f16 / fp32) — one short query, the corpus forward at 512 tokens, and the HD = 32 attention kernel next to SDPA and next to the HD = 64
-kernel on the same tensors zero-padded to 64 columns per head."""
+kernel on the same tensors zero-padded to 64 columns per head.
+`python -m tools.encoder_bench --small-m [--out profiles/encoder_small_m.json]`: the short-row route (`embedding_fused_small_m`) — every small-M stage
+next to what it replaces for 16 .. 128 token rows at the base / large / small layer shapes, and the one-query call with the flag on and off; both arms
+in one process, alternating region by region."""
 import json
 import sys
 
@@ -185,7 +188,145 @@ def head32_report(dev):
     return out
 
 
+def _alternating(arms, regions=7, reps=20, graph=False):
+    """{name: callable} -> {name: median / min / max microseconds per call}: `regions` rounds, each timing every arm once (`reps` calls
+    between two synchronisations), so the arms see the same clocks and neighbours.  graph = True: an arm's `reps` calls are captured
+    as ONE hipGraph and a region is one replay timed with device events — the device time of the stage, free of the interpreter."""
+    import time
+    import numpy as np
+    runs = {}
+    for name, fn in arms.items():
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        if graph:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for _ in range(reps):
+                    fn()
+            g.replay()
+            runs[name] = g
+        else:
+            runs[name] = fn
+    torch.cuda.synchronize()
+    ts = {name: [] for name in arms}
+    for _ in range(regions):
+        for name, run in runs.items():
+            if graph:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); run.replay(); e1.record(); e1.synchronize()
+                ts[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+            else:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    run()
+                torch.cuda.synchronize()
+                ts[name].append((time.perf_counter() - t0) * 1e6 / reps)
+    return {name: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v)), "regions": regions, "calls_per_region": reps} for name, v in ts.items()}
+
+
+def _passes(new, old):
+    """The rule of DESIGN 4.10: the new median below the old one by more than the two rows' min-to-max spreads added together."""
+    return bool(old["median"] - new["median"] > (new["max"] - new["min"]) + (old["max"] - old["min"]))
+
+
+SMALL_M_SWEEP = (16, 32, 48, 64, 80, 96, 128)
+SMALL_M_SHAPES = {"base": ("bf16", 768, 3072), "large": ("fp16", 1024, 4096), "small": ("bf16", 384, 1536)}
+SMALL_M_LAYERS = {"base": 12, "large": 24, "small": 12}
+
+
+def small_m_report(dev):
+    """The short-row route (`embedding_fused_small_m`): device time of each small-M stage against the PyTorch stage it replaces (hipGraph replays of
+    20 calls, device events), per layer shape and token-row count; then batch_encode(one 12-word query) with the flag on and off."""
+    import types
+    import torch.nn.functional as F
+    from comorag_amd import _lib as L
+    from comorag_amd.embedding_model.bge import HipBGEEmbeddingModel
+    from comorag_amd.embedding_model.fused_bert import FusedBertLayers
+    from comorag_amd.utils.config_utils import BaseConfig
+    from tools.synthetic import random_bert, synthetic_wordpiece_tokenizer
+    out = {"what": "short-row route of the fused encoder stack: small-M HIP stages vs the PyTorch / hipBLASLt stages they replace; microseconds per call, "
+                   "median / min / max of 7 regions x 20 calls, both arms in one process, alternating",
+           "rule": "pass = new median below the old median by more than the two rows' (max - min) added together",
+           "stages_us": {}, "per_layer_sum_us": {}, "single_query_encode_us": {}}
+    for kind, (dname, hidden, inter) in SMALL_M_SHAPES.items():
+        tdt = torch.bfloat16 if dname == "bf16" else torch.float16
+        fz = types.SimpleNamespace(dtype=tdt, eps=1e-12, cmr_dtype=L.CMR_BF16 if dname == "bf16" else L.CMR_F16)
+        for name in ("linear_small", "linear_small_partials", "add_layernorm_partials", "add_layernorm"):
+            setattr(fz, name, getattr(FusedBertLayers, name).__get__(fz))
+        rnd = lambda *sh: torch.randn(sh, device=dev)
+        # one weight set per LAYER of the model, taken in turn by consecutive calls: a forward streams every layer's own weights once, so a stage
+        # timed on ONE weight tensor over and over would be timed out of the caches instead
+        nl = SMALL_M_LAYERS[kind]
+        wqkv, wo, w1, w2 = ([(rnd(n, k) / k ** 0.5).to(tdt) for _ in range(nl)] for n, k in ((3 * hidden, hidden), (hidden, hidden), (inter, hidden), (hidden, inter)))
+        bqkv, b1, bh, gamma, beta = rnd(3 * hidden).to(tdt), rnd(inter).to(tdt), rnd(hidden).to(tdt), rnd(hidden).to(tdt), rnd(hidden).to(tdt)
+        out["stages_us"][kind], out["per_layer_sum_us"][kind] = {}, {}
+
+        def turn(fn):
+            state = [0]
+            def call():
+                i = state[0]
+                state[0] = (i + 1) % nl
+                return fn(i)
+            return call
+
+        for m in SMALL_M_SWEEP:
+            x, h = rnd(m, hidden).to(tdt), rnd(m, inter).to(tdt)
+            stages = {
+                "qkv": {"small_m": lambda i: fz.linear_small(x, wqkv[i], bqkv), "torch": lambda i: F.linear(x, wqkv[i], bqkv)},
+                "ffn_up_gelu": {"small_m": lambda i: fz.linear_small(x, w1[i], b1, True), "torch": lambda i: F.gelu(F.linear(x, w1[i], b1))},
+                "o_proj_ln": {"small_m": lambda i: fz.add_layernorm_partials(fz.linear_small_partials(x, wo[i]), bh, x, gamma, beta),
+                              "torch": lambda i: fz.add_layernorm(F.linear(x, wo[i]), bh, x, gamma, beta)},
+                "ffn_down_ln": {"small_m": lambda i: fz.add_layernorm_partials(fz.linear_small_partials(h, w2[i]), bh, x, gamma, beta),
+                                "torch": lambda i: fz.add_layernorm(F.linear(h, w2[i]), bh, x, gamma, beta)}}
+            row = {name: _alternating({arm: turn(fn) for arm, fn in arms.items()}, graph=True) for name, arms in stages.items()}
+            for name in row:
+                row[name]["pass"] = _passes(row[name]["small_m"], row[name]["torch"])
+            # a layer's four stages together, one graph per arm (the sum the crossover is read from)
+            layer = _alternating({arm: turn(lambda i, arm=arm: [stages[name][arm](i) for name in stages]) for arm in ("small_m", "torch")}, graph=True)
+            layer["pass"] = _passes(layer["small_m"], layer["torch"])
+            out["stages_us"][kind][str(m)] = row
+            out["per_layer_sum_us"][kind][str(m)] = layer
+            print(kind, m, {k: (round(v["small_m"]["median"], 2), round(v["torch"]["median"], 2), v["pass"]) for k, v in {**row, "layer": layer}.items()}, flush=True)
+    ok = [m for m in SMALL_M_SWEEP if all(out["per_layer_sum_us"][kind][str(m)]["pass"] for kind in ("base", "large"))]
+    upto = 0
+    for m in SMALL_M_SWEEP:                                 # the largest M up to which every row of the sweep passes at both gating shapes
+        if m not in ok:
+            break
+        upto = m
+    out["crossover_rows"] = upto
+    tok, words = synthetic_wordpiece_tokenizer()
+    q = " ".join(words[:12])
+    for kind, dtype, head32 in (("base", "bf16", False), ("large", "fp16", False), ("small", "bf16", True), ("small", "fp16", True)):
+        ems = {}
+        for flag in (True, False):
+            cfg = BaseConfig(embedding_model_name=f"bge-{kind}-random-init", embedding_model_dtype=dtype, device=dev.index or 0, embedding_fused_head32=head32,
+                             embedding_fused_small_m=flag, embedding_query_cache=0)      # (every call a forward)
+            em = ems["small_m" if flag else "flag_off"] = HipBGEEmbeddingModel(cfg, cfg.embedding_model_name, model=random_bert(kind, vocab_size=len(tok)), tokenizer=tok)
+            assert em.encoder_path == "hip-fused-layers" and (em.small_m_rows > 0) == flag
+            for _ in range(8):
+                em.batch_encode(q)
+        row = _alternating({name: (lambda em=em: em.batch_encode(q)) for name, em in ems.items()})
+        row["pass"] = _passes(row["small_m"], row["flag_off"])
+        row["token_rows"] = int(sum(k[0] * k[1] for k in list(ems["small_m"]._fused._graphs)[:1]))
+        out["single_query_encode_us"][f"{kind}_{dtype}"] = row
+        print(kind, dtype, row, flush=True)
+        for em in ems.values():
+            em.close()
+    out["gating_rows_pass"] = bool(out["single_query_encode_us"]["base_bf16"]["pass"] and out["single_query_encode_us"]["large_fp16"]["pass"])
+    return out
+
+
 def main():
+    if "--small-m" in sys.argv:
+        rep = small_m_report(torch.device("cuda", 0))
+        text = json.dumps(rep, indent=1)
+        print(text)
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else "profiles/encoder_small_m.json"
+        with open(out, "w") as f:
+            f.write(text + "\n")
+        return
     if "--head32" in sys.argv or "--fp32" in sys.argv:
         rep = head32_report(torch.device("cuda", 0)) if "--head32" in sys.argv else fp32_report(torch.device("cuda", 0))
         text = json.dumps(rep, indent=1)

@@ -21,13 +21,16 @@ def main():
     tok, words = synthetic_wordpiece_tokenizer()
     # (the "auto" rows: fp32 weights as stored — the transformers fp32 forward, then the fused fp32 stack, `embedding_fused_fp32`)
     # (the "small" rows: 32-wide heads — the transformers forward, then the fused stack, `embedding_fused_head32`; with both flags for fp32 weights)
-    rows = [("base", "bf16", False, False), ("large", "fp16", False, False), ("base", "auto", False, False), ("base", "auto", True, False),
-            ("large", "auto", False, False), ("large", "auto", True, False),
-            ("small", "bf16", False, False), ("small", "bf16", False, True), ("small", "fp16", False, False), ("small", "fp16", False, True),
-            ("small", "auto", False, False), ("small", "auto", True, True)]
-    for kind, dtype, fp32, head32 in rows:
+    # (the "small-M" rows: the short-row route, `embedding_fused_small_m`, next to the same model without it)
+    rows = [("base", "bf16", False, False, False), ("base", "bf16", False, False, True), ("large", "fp16", False, False, False), ("large", "fp16", False, False, True),
+            ("base", "auto", False, False, False), ("base", "auto", True, False, False),
+            ("large", "auto", False, False, False), ("large", "auto", True, False, False),
+            ("small", "bf16", False, False, False), ("small", "bf16", False, True, False), ("small", "bf16", False, True, True),
+            ("small", "fp16", False, False, False), ("small", "fp16", False, True, False), ("small", "fp16", False, True, True),
+            ("small", "auto", False, False, False), ("small", "auto", True, True, False)]
+    for kind, dtype, fp32, head32, small_m in rows:
         cfg = BaseConfig(embedding_model_name=f"bge-{kind}-random-init", embedding_model_dtype=dtype, embedding_query_cache=0,      # (every call a forward: the product keeps the last 256 single-string rows)
-                         embedding_fused_fp32=fp32, embedding_fused_head32=head32)
+                         embedding_fused_fp32=fp32, embedding_fused_head32=head32, embedding_fused_small_m=small_m)
         em = HipBGEEmbeddingModel(cfg, cfg.embedding_model_name, model=random_bert(kind, vocab_size=len(tok)), tokenizer=tok)
         q = " ".join(words[:12])
         for _ in range(8):
@@ -38,7 +41,7 @@ def main():
         prompt = [em.embedding_config.encode_params.get("passage_instruction", "") + q]
         tk = med(lambda: em._ragged(prompt, 512), n)
         print(f"bge-{kind} {dtype}: batch_encode(one 12-word query) median {call[0]:.1f} us (min {call[1]:.1f}); rows left on the device {dev[0]:.1f}; "
-              f"tokenizer alone {tk[0]:.1f}; encoder path {em.encoder_path}", flush=True)
+              f"tokenizer alone {tk[0]:.1f}; encoder path {em.encoder_path}" + (f", small-M route up to {em.small_m_rows} rows" if em.small_m_rows else ""), flush=True)
         em.close()
 
 
