@@ -106,6 +106,14 @@ const Option kOptions[] = {
     {"prefilter_tighten", OPT_FIELD(pf_tighten), Option::range, 0, 1, 0, "prefilter_tighten must be 0 or 1", OPT_READ(i->pf_tighten)},
     {"prefilter_pair_cap", OPT_FIELD(pf_pair_cap), Option::clamp, 0, 1 << 20, 0, nullptr, OPT_READ(i->pf_pair_cap)},
     {"prefilter_wave_cap", OPT_FIELD(pf_wave_cap), Option::clamp, 0, 1 << 20, 0, nullptr, OPT_READ(i->pf_wave_cap)},
+    {"prefilter_sample", OPT_FIELD(pf_sample), Option::range, -1, 1, 0, "prefilter_sample must be -1 (auto), 0 (bf16 sampling) or 1 (int8 sample)", OPT_READ(i->pf_sample)},
+    {"prefilter_sample_panels", OPT_FIELD(pf_sample_panels), Option::clamp, 0, INT_MAX, 0, nullptr, OPT_READ(i->pf_sample_panels)},
+    {"prefilter_sample_run", OPT_FIELD(pf_sample_run), Option::clamp, 0, 1 << 16, 0, nullptr, OPT_READ(i->pf_sample_run)},
+    {"prefilter_sample_wave_cap", OPT_FIELD(pf_sample_wave_cap), Option::clamp, 0, 1 << 20, 0, nullptr, OPT_READ(i->pf_sample_wave_cap)},
+    {"prefilter_sample_level0", OPT_FIELD(pf_sample_level0), Option::clamp, 0, 128, 0, nullptr, OPT_READ(i->pf_sample_level0)},
+    {"prefilter_sample_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->prefilter_sample_active)},
+    {"prefilter_sample_pairs", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::sample_pairs))},
+    {"prefilter_sample_overflow", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::sample_overflow))},
     {"prefilter_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->prefilter_active)},
     {"prefilter_rows", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->q8c.q8 ? i->q8c.rows : 0)},
     {"prefilter_bytes", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ((long long)i->q8c.bytes(i->dpad))},
@@ -306,6 +314,11 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
         as.lists = (u64*)ws->s_lists.p; as.cnt = (int*)ws->s_cnt.p; as.mm = (float2*)ws->s_mm.p;
         as.sample_waves = (int)L.panels; as.sample_chunk_log2 = L.clog; as.sample_stride = L.stride;
         u64* tau_out = (u64*)ws->tau.p + (size_t)(lv & 1) * p.NQA;
+        if (lv == 1 && p.sample_q8) {      // level 1 from the int8 companion: filter in sample mode, bucket, select (prefilter_host.h)
+            if ((rc = q8_sample(idx, f, a.tau_init, tau_out, p.bytes.q8[Q8_SPAIRCNT], sp))) return rc;
+            a.tau_init = tau_out;
+            continue;
+        }
         HIP_TRY(p.wide ? cmr_launch_scan_wide(gs, as, sp) : cmr_launch_scan_topk(gs, as, sp));
         if (p.tau_in_scan) {      // the main scan's workgroups derive the thresholds from these lists themselves
             a.sample_lists = (const u64*)ws->s_lists.p; a.sample_cnt = (const int*)ws->s_cnt.p; a.sample_W = L.Wl;
@@ -527,6 +540,7 @@ int search_pipelined_enqueue_locked(cmr_index* idx, const float* q_dev, int nq, 
     int prefilter = prefilter_eligible(idx, min_score != nullptr, min_dev || max_dev, nq, may_prefilter);
     if (prefilter && !q8_ensure_companion(idx, nsp)) prefilter = 0;
     idx->prefilter_active = 0;
+    idx->prefilter_sample_active = 0;
     PipeSlot* last = nullptr;
     while (ps.next()) {
         const bool wide = ps.wide_streams();

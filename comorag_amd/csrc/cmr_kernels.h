@@ -222,10 +222,23 @@ struct CmrQ8Args {
     unsigned* n_cand;          // zeroed before the expansion
     u64* lists;
     int* cnt;
+    // the int8 sample in front of the main pass (s_grid > 0): the filter body over s_nruns runs of s_run consecutive panels, run g at panel
+    // g * s_stride (s_stride >= s_run), one run per wave of a grid of s_grid workgroups, against the level-0 threshold keys s_tau0
+    int s_grid, s_run, s_stride, s_nruns;
+    void* s_wrec;              // [s_grid * 8][s_wave_cap] the sample's records (a hit beyond the area is dropped)
+    unsigned* s_wcnt;          // [s_grid * 8]
+    int s_wave_cap;
+    void* s_pair;              // [nqt * 32][s_pcap] the sample's records by query (a record beyond the list is dropped)
+    unsigned* s_pair_cnt;      // [nqt * 32] zeroed before the sample
+    int s_pcap;
+    const u64* s_tau0;         // [nqt * 32] level-0 threshold keys
+    u64* s_tau_out;            // [nq] threshold keys for the main pass: max(key of the k-th largest sampled lb, level-0 key)
 };
 // filter -> (bucket, tighten, when pcap > 0) -> expand -> rescore; all but the first in stream order behind the filter
-hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s);
-hipError_t cmr_launch_q8_bucket(const CmrQ8Args& a, hipStream_t s);
+// in front of them, with the int8 sample: filter (sample) -> bucket (sample) -> select, in stream order
+hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s, bool sample = false);
+hipError_t cmr_launch_q8_bucket(const CmrQ8Args& a, hipStream_t s, bool sample = false);
+hipError_t cmr_launch_q8_select(const CmrQ8Args& a, hipStream_t s);
 hipError_t cmr_launch_q8_tighten(const CmrQ8Args& a, hipStream_t s);
 hipError_t cmr_launch_q8_expand(const CmrQ8Args& a, hipStream_t s);
 hipError_t cmr_launch_q8_rescore(const CmrQ8Args& a, hipStream_t s);

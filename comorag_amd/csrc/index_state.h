@@ -47,16 +47,21 @@ struct Q8Companion {
 };
 // A workspace's buffers of a pre-filtered pass, sized by plan_pass (PassPlan::bytes.q8[]): int8 query parts, queries' constants, candidate
 // rows and their counter, the filter's (row, ub, lb, query) records per wave of its grid and their counters, the same records per query
-// and their counters, row mask per panel, tightened thresholds.
-enum Q8Buf { Q8_QPACK, Q8_QCONST, Q8_CAND, Q8_NCAND, Q8_WREC, Q8_WCNT, Q8_PAIR, Q8_PAIRCNT, Q8_KEEP, Q8_TAU, Q8_NBUF };
+// and their counters, row mask per panel, tightened thresholds; the int8 sample's records per wave of ITS grid and per query, with
+// their counters (areas of their own: the slot's wrec / pair may still be read by the previous batch's bucket step and tightening on
+// the merge stream while the pre-phase stream samples for the next one).
+enum Q8Buf { Q8_QPACK, Q8_QCONST, Q8_CAND, Q8_NCAND, Q8_WREC, Q8_WCNT, Q8_PAIR, Q8_PAIRCNT, Q8_KEEP, Q8_TAU, Q8_SWREC, Q8_SWCNT, Q8_SPAIR, Q8_SPAIRCNT, Q8_NBUF };
 struct Q8Scratch {
     DevBuf buf[Q8_NBUF];
     bool pf_prev = false;                // the workspace's last pass ran the re-score, which reads qfrag / tau on the merge stream
     hipError_t ensure(const size_t (&bytes)[Q8_NBUF]) { for (int i = 0; i < Q8_NBUF; ++i) if (hipError_t e = buf[i].ensure(bytes[i])) return e; return hipSuccess; }
     void release() { for (DevBuf& b : buf) b.release(); }
 };
-// candidate counter, nq pair counters and their capacity, nw wave counters and their capacity
-struct Q8LastPass { const unsigned* ncand = nullptr; const unsigned* paircnt = nullptr; int nq = 0, pcap = 0; const unsigned* wcnt = nullptr; int nw = 0, wave_cap = 0; };
+// candidate counter, nq pair counters and their capacity, nw wave counters and their capacity; the int8 sample's pair counters and capacity
+struct Q8LastPass {
+    const unsigned* ncand = nullptr; const unsigned* paircnt = nullptr; int nq = 0, pcap = 0; const unsigned* wcnt = nullptr; int nw = 0, wave_cap = 0;
+    const unsigned* s_paircnt = nullptr; int s_pcap = 0;
+};
 
 // Scratch of one in-flight search.  One per stream (searches on a stream are serialised by it).
 struct Workspace {
@@ -224,6 +229,17 @@ struct cmr_index {
     int pf_tighten = 1;
     int pf_pair_cap = 16384;
     int pf_wave_cap = 0;
+    // prefilter_sample: where the level-1 sampling threshold of a pre-filtered pass with record lists comes from — 1: from the int8 companion
+    // (the filter body over strided runs of panels, bucket, select: DESIGN 4.14) | 0: from the bf16 panels (scan_kernel + merge, launch for
+    // launch what every other route does) | -1 auto (kPrefilterSampleAuto, search_plan.h).  prefilter_sample_panels (0 = auto; a forced value
+    // is taken as it is, up to every panel), prefilter_sample_run (panels per wave, 0 = auto), prefilter_sample_wave_cap (records per wave of
+    // the sample's grid, 0 = auto), prefilter_sample_level0 (panels of the bf16 level 0 on this route, 0 = auto; at least k).
+    int pf_sample = -1;
+    int pf_sample_panels = 0;
+    int pf_sample_run = 0;
+    int pf_sample_wave_cap = 0;
+    int pf_sample_level0 = 0;
+    int prefilter_sample_active = 0;     // read-only: did the last pre-filtered pass draw its sampling threshold from the companion
     Q8Companion q8c;
     int prefilter_active = 0;            // read-only: did the last pipelined call run the pre-filter
     Q8LastPass q8_last;                  // the last pre-filtered pass's counters (the options prefilter_candidates / _pairs / _pair_overflow / _wave_overflow read them)

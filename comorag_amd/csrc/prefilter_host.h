@@ -57,13 +57,31 @@ int q8_prepare(cmr_index* idx, Workspace* ws, const PassPlan& p, const float* q_
     f.cand_row = (unsigned*)w[Q8_CAND].p; f.n_cand = (unsigned*)w[Q8_NCAND].p; f.keep = (unsigned*)w[Q8_KEEP].p; f.tau_tight = (float*)w[Q8_TAU].p;
     f.wrec = w[Q8_WREC].p; f.wcnt = (unsigned*)w[Q8_WCNT].p; f.wave_cap = f.keep_all ? 0 : p.wave_cap;
     f.pair = w[Q8_PAIR].p; f.pair_cnt = (unsigned*)w[Q8_PAIRCNT].p; f.pcap = p.pair_cap;
+    if (p.sample_q8) {
+        f.s_grid = p.level[1].grid; f.s_run = p.s_run; f.s_stride = p.s_stride; f.s_nruns = p.s_nruns;
+        f.s_wrec = w[Q8_SWREC].p; f.s_wcnt = (unsigned*)w[Q8_SWCNT].p; f.s_wave_cap = p.s_wave_cap;
+        f.s_pair = w[Q8_SPAIR].p; f.s_pair_cnt = (unsigned*)w[Q8_SPAIRCNT].p; f.s_pcap = p.s_pair_cap;
+    }
+    return CMR_OK;
+}
+// Level 1 of a pre-filtered pass with record lists, on the pre-phase stream where the bf16 level-1 scan and its merge stand otherwise: the
+// filter body over the sample's runs against the level-0 keys `tau0`, its records sorted by query, and per query the key of the k-th largest
+// lower bound (or the level-0 key, whichever is larger) into `tau_out` — what the main filter, the tightening, the re-score and the merge
+// then take as tau_init.  The sample's buffers are touched on this stream only, so stream order is all they need.
+int q8_sample(cmr_index* idx, CmrQ8Args& f, const u64* tau0, u64* tau_out, size_t cnt_bytes, hipStream_t sp) {
+    f.s_tau0 = tau0; f.s_tau_out = tau_out;
+    HIP_TRY(hipMemsetAsync(f.s_pair_cnt, 0, cnt_bytes, sp));
+    HIP_TRY(cmr_launch_q8_filter(f, sp, true));
+    HIP_TRY(cmr_launch_q8_bucket(f, sp, true));
+    HIP_TRY(cmr_launch_q8_select(f, sp));
+    idx->prefilter_sample_active = 1;
     return CMR_OK;
 }
 // Step 2, on the scan stream in the place of the main scan: the filter, with that scan's thresholds and lists; the diagnostics now read this pass
 int q8_filter(cmr_index* idx, CmrQ8Args& f, const CmrScanArgs& a, hipStream_t sm) {
     f.tau_init = a.tau_init; f.lists = a.lists; f.cnt = a.cnt;
     HIP_TRY(cmr_launch_q8_filter(f, sm));
-    idx->q8_last = Q8LastPass{f.n_cand, f.pair_cnt, f.nq, f.pcap, f.wcnt, f.grid * CMR_SCAN_WAVES, f.wave_cap};
+    idx->q8_last = Q8LastPass{f.n_cand, f.pair_cnt, f.nq, f.pcap, f.wcnt, f.grid * CMR_SCAN_WAVES, f.wave_cap, f.s_grid > 0 ? f.s_pair_cnt : nullptr, f.s_pcap};
     idx->prefilter_active = 1;
     return CMR_OK;
 }
@@ -86,14 +104,17 @@ double prefilter_bytes(const cmr_index* idx, const PassPlan& p) {
 
 // The counters of the last pre-filtered pass, read once the pipeline has drained (0 before any such pass, -1: the read failed).  candidates:
 // rows it handed to the re-score; pairs: the (row, query) records in the queries' lists, over all queries; pair_overflow: queries that were offered more than
-// the capacity; wave_overflow: waves of the filter's grid that offered more records than their area holds.
-enum class Q8Counter { candidates, pairs, pair_overflow, wave_overflow };
+// the capacity; wave_overflow: waves of the filter's grid that offered more records than their area holds; sample_pairs / sample_overflow: pairs and
+// pair_overflow of the int8 sample's lists (0 where the pass had no int8 sample).
+enum class Q8Counter { candidates, pairs, pair_overflow, wave_overflow, sample_pairs, sample_overflow };
 long long q8_read_counter(const cmr_index* cidx, Q8Counter what) {
     cmr_index* idx = const_cast<cmr_index*>(cidx);
     if (cmr_set_device(idx->device)) return -1;
     std::lock_guard<std::mutex> pl(idx->pipe_mu);
     const Q8LastPass& L = idx->q8_last;
-    const unsigned* const src = what == Q8Counter::candidates ? L.ncand : what == Q8Counter::wave_overflow ? L.wcnt : L.paircnt;
+    const bool sample = what == Q8Counter::sample_pairs || what == Q8Counter::sample_overflow;
+    const unsigned* const src = what == Q8Counter::candidates ? L.ncand : what == Q8Counter::wave_overflow ? L.wcnt : sample ? L.s_paircnt : L.paircnt;
+    const unsigned pcap = (unsigned)(sample ? L.s_pcap : L.pcap);
     std::vector<unsigned> h(what == Q8Counter::candidates ? 1 : (size_t)std::max(what == Q8Counter::wave_overflow ? (L.wave_cap > 0 ? L.nw : 0) : L.nq, 0));
     if (!src || h.empty()) return 0;
     for (hipStream_t st : idx->pipe.st) if (st && hipStreamSynchronize(st) != hipSuccess) return -1;
@@ -101,8 +122,8 @@ long long q8_read_counter(const cmr_index* cidx, Q8Counter what) {
     if (what == Q8Counter::candidates) return (long long)h[0];
     if (what == Q8Counter::wave_overflow) return (long long)std::count_if(h.begin(), h.end(), [&](unsigned c) { return c > (unsigned)L.wave_cap; });
     long long stored = 0, overflowed = 0;
-    for (unsigned c : h) { stored += std::min(c, (unsigned)L.pcap); overflowed += c > (unsigned)L.pcap ? 1 : 0; }
-    return what == Q8Counter::pairs ? stored : overflowed;
+    for (unsigned c : h) { stored += std::min(c, pcap); overflowed += c > pcap ? 1 : 0; }
+    return what == Q8Counter::pairs || what == Q8Counter::sample_pairs ? stored : overflowed;
 }
 
 }  // namespace

@@ -173,6 +173,7 @@ struct FilterP {
     unsigned* wcnt;            // [W] records offered by each wave (written by every wave of the grid; may run past wave_cap)
     unsigned wave_cap;         // 0: no records, every hit is kept directly
     unsigned* keep;            // [npanels] row masks: every panel's word is written (the rows kept directly, usually none)
+    int s_run, s_stride, s_nruns;      // sample mode: wave gw < s_nruns takes the s_run panels from gw * s_stride (s_stride >= s_run)
 };
 
 // 8 waves per workgroup, each with a contiguous panel range; the two int8 parts of the query tiles in LDS.  Corpus blocks
@@ -187,7 +188,11 @@ struct FilterP {
 // queries' lists afterwards.  A hit that finds the wave's area full is kept directly: its row bit goes into the panel's word of
 // keep[], which the panel's wave — every panel has exactly one — writes for every panel of its range, so the masks need no
 // clearing between batches.  Nor do the counts: every wave of the grid stores its own on leaving, a wave without panels a 0.
-template <int NQT, int CH>
+// SAMPLE (the level-1 sampling pass of a pre-filtered batch, in front of the main pass): the same loop, kept-test and records over ONE
+// run of s_run consecutive panels per wave, run gw starting at panel gw * s_stride — s_stride >= s_run, so no (row, query) pair is
+// evaluated twice — against the level-0 sampling threshold.  It writes no keep[] word, and a hit that finds the wave's area full is
+// dropped: q8_select_kernel takes the k-th largest lb of whatever was recorded, and any k distinct real rows certify it.
+template <int NQT, int CH, bool SAMPLE>
 __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -199,7 +204,15 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
 
     const int W = gridDim.x * CMR_SCAN_WAVES;
     const int gw = blockIdx.x * CMR_SCAN_WAVES + wave;
-    const int p0 = (int)(((long long)gw * P.npanels) / W), p1 = (int)(((long long)(gw + 1) * P.npanels) / W);
+    int p0, p1;
+    if (SAMPLE) {      // (a run that the corpus' end cuts is shorter; a wave beyond the runs, or whose run would start behind the end, has none)
+        const long long s0 = (long long)gw * P.s_stride;
+        p0 = (int)(s0 < P.npanels ? s0 : P.npanels);
+        p1 = gw < P.s_nruns ? (P.npanels - p0 < P.s_run ? P.npanels : p0 + P.s_run) : p0;
+    } else {
+        p0 = (int)(((long long)gw * P.npanels) / W);
+        p1 = (int)(((long long)(gw + 1) * P.npanels) / W);
+    }
     if (p1 <= p0) {
         if (lane == 0) P.wcnt[gw] = 0u;
         return;
@@ -287,11 +300,11 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
                 if ((r & 3) + 8 * (r >> 2) >= lim) hit &= ~(0x10001u << r);
         }
         unsigned rows = 0u;        // the rows of this panel that are kept without a record
-        if (P.keep_all) rows = left < CMR_PANEL_ROWS ? (left > 0 ? (1u << left) - 1u : 0u) : ~0u;
+        if (!SAMPLE && P.keep_all) rows = left < CMR_PANEL_ROWS ? (left > 0 ? (1u << left) - 1u : 0u) : ~0u;
         else if (__any(hit != 0u)) {
             const unsigned row0 = (unsigned)p * CMR_PANEL_ROWS + (unsigned)hrow;
             // (bits of the lane's accumulator rows WITHOUT the lane half's offset: row i = (r & 3) + 8 (r >> 2) + hrow, shifted once below)
-            if (P.wave_cap == 0u) {
+            if (!SAMPLE && P.wave_cap == 0u) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     if (hit & (0x10001u << r)) rows |= 1u << ((r & 3) + 8 * (r >> 2));
@@ -308,7 +321,10 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
                         const unsigned slot = nrec + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
                         nrec += (unsigned)__popcll(m);
                         if (!h) continue;
-                        if (slot >= P.wave_cap) { rows |= 1u << ((r & 3) + 8 * (r >> 2)); continue; }
+                        if (slot >= P.wave_cap) {
+                            if (!SAMPLE) rows |= 1u << ((r & 3) + 8 * (r >> 2));
+                            continue;
+                        }
                         const float ti = fmaf((float)acc[1][t][r], 1.0f / 254.0f, (float)acc[0][t][r]);
                         const float e = fmaf(Bq[t], br, cq[t]);
                         const float ub = fmaf(ar * aq[t], ti, e), lb = fmaf(ar * aq[t], ti, -e);
@@ -317,11 +333,13 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 1) void q8_filter_kernel(FilterP 
                     }
                 }
             }
-            rows <<= hrow;
+            if (!SAMPLE) {
+                rows <<= hrow;
 #pragma unroll
-            for (int off = 1; off < 64; off <<= 1) rows |= (unsigned)__shfl_xor((int)rows, off);
+                for (int off = 1; off < 64; off <<= 1) rows |= (unsigned)__shfl_xor((int)rows, off);
+            }
         }
-        if (lane == 0) P.keep[p] = rows;
+        if (!SAMPLE && lane == 0) P.keep[p] = rows;
         ++p;
         load_scales(p < P.npanels ? p : P.npanels - 1);
 #pragma unroll
@@ -353,7 +371,7 @@ struct BucketP {
     v4u* pair;                 // [nq slots][pcap] records (row, ub, lb, 0)
     unsigned* pair_cnt;        // [nq slots] pairs offered per query (zeroed before the filter; may run past pcap)
     unsigned pcap;
-    unsigned* keep;
+    unsigned* keep;            // nullptr: a record beyond pcap is dropped
 };
 
 #define Q8_BUCKET_WAVES 4
@@ -385,7 +403,7 @@ __global__ __launch_bounds__(Q8_BUCKET_WAVES * 64) void q8_bucket_kernel(BucketP
         const unsigned q = v.w & 63u;
         const unsigned slot = s_base[q] + atomicAdd(&s_cnt[q], 1u);
         if (slot < P.pcap) P.pair[(size_t)q * P.pcap + slot] = (v4u){v.x, v.y, v.z, 0u};
-        else atomicOr(&P.keep[v.x >> 5], 1u << (v.x & 31u));
+        else if (P.keep) atomicOr(&P.keep[v.x >> 5], 1u << (v.x & 31u));      // (no keep[]: the sample's records — one beyond the list is dropped)
     }
 }
 
@@ -398,6 +416,7 @@ struct TightenP {
     int k;
     unsigned* keep;
     float* tau_out;            // [nq] the threshold each query ended with (diagnostics)
+    u64* key_out;              // select form: [nq] the threshold key the main pass takes as its tau_init
 };
 
 // the order-preserving 32-bit image of a non-NaN float, and back
@@ -410,7 +429,12 @@ __device__ __forceinline__ float q8_ord2f(unsigned u) { return __uint_as_float((
 // gives a smaller k-th largest, which is as valid).  Radix select, four passes of 8 bits over the image of lb with a 256-bin
 // histogram in LDS; then every stored pair that still stands sets its row's bit in keep[] (the OR also folds the queries that hit one
 // row into one candidate).  Every loop runs to a count read once.
-__global__ __launch_bounds__(256) void q8_tighten_kernel(TightenP P) {
+// SELECT (behind the int8 sample, in front of the main pass): the same selection over the sample's records and nothing else — no loop over
+// the pairs, no keep[].  The k-th largest lb, tau_s, is written as a threshold KEY: the smallest key with score tau_s, minus 1
+// (cmr_launch_fill_threshold's construction), so that key > tau <=> score >= tau_s and a row tied with tau_s stays; the key written is
+// the larger of that and the level-0 key in tau_init[q], and the level-0 key alone with fewer than k usable records.
+template <bool SELECT>
+__device__ __forceinline__ void q8_tighten_body(const TightenP& P) {
     __shared__ unsigned hist[256];
     __shared__ unsigned s_bin, s_need;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -461,7 +485,22 @@ __global__ __launch_bounds__(256) void q8_tighten_kernel(TightenP P) {
             prefix |= bin << shift;
             mask |= 255u << shift;
         }
+        if (SELECT) {
+            if (tid == 0) {
+                u64 key = P.tau_init ? P.tau_init[q] : 0ull;
+                if (found) {
+                    const u64 ks = cmr_make_key(q8_ord2f(prefix), 0xFFFFFFFFu) - 1ull;
+                    key = ks > key ? ks : key;
+                }
+                P.key_out[q] = key;
+            }
+            return;
+        }
         if (found) tau = fmaxf(tau, q8_ord2f(prefix));
+    }
+    if (SELECT) {
+        if (tid == 0) P.key_out[q] = P.tau_init ? P.tau_init[q] : 0ull;
+        return;
     }
     for (unsigned i = tid; i < c; i += 256u) {
         const v4u v = pr[i];
@@ -469,6 +508,8 @@ __global__ __launch_bounds__(256) void q8_tighten_kernel(TightenP P) {
     }
     if (tid == 0) P.tau_out[q] = tau;
 }
+__global__ __launch_bounds__(256) void q8_tighten_kernel(TightenP P) { q8_tighten_body<false>(P); }
+__global__ __launch_bounds__(256) void q8_select_kernel(TightenP P) { q8_tighten_body<true>(P); }
 
 // ------------------------------------------------------------------------------------------ expand
 // keep[0 .. npanels) -> the rows of the set bits in cand_row[], counted in *n_cand (zeroed in front of the launch) with one
@@ -628,29 +669,45 @@ hipError_t cmr_launch_q8_pack_queries(int dtype, const float* q, int nq, int dim
 
 size_t cmr_q8_filter_lds(int dpad, int nqt) { return (size_t)2 * nqt * (dpad / 32) * 1024; }
 
-hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s) {
+// sample = true: the level-1 sampling pass (the a.s_* fields: grid, runs, record areas, the level-0 keys as thresholds)
+hipError_t cmr_launch_q8_filter(const CmrQ8Args& a, hipStream_t s, bool sample) {
     FilterP p;
     p.q8 = reinterpret_cast<const v4u*>(a.q8); p.scales4 = reinterpret_cast<const float4*>(a.scales);
-    p.qpack = reinterpret_cast<const v4u*>(a.qpack); p.qconst = a.qconst; p.tau_init = a.tau_init;
-    p.nrows = a.nrows; p.npanels = a.npanels; p.KB = a.dpad / 32; p.nq = a.nq; p.keep_all = a.keep_all;
-    p.wrec = reinterpret_cast<v4u*>(a.wrec); p.wcnt = a.wcnt; p.wave_cap = (unsigned)a.wave_cap; p.keep = a.keep;
+    p.qpack = reinterpret_cast<const v4u*>(a.qpack); p.qconst = a.qconst; p.tau_init = sample ? a.s_tau0 : a.tau_init;
+    p.nrows = a.nrows; p.npanels = a.npanels; p.KB = a.dpad / 32; p.nq = a.nq; p.keep_all = sample ? 0 : a.keep_all;
+    p.wrec = reinterpret_cast<v4u*>(sample ? a.s_wrec : a.wrec); p.wcnt = sample ? a.s_wcnt : a.wcnt;
+    p.wave_cap = (unsigned)(sample ? a.s_wave_cap : a.wave_cap); p.keep = sample ? nullptr : a.keep;
+    p.s_run = a.s_run; p.s_stride = a.s_stride; p.s_nruns = a.s_nruns;
+    if (sample && (a.s_run < 1 || a.s_stride < a.s_run || a.s_nruns > a.s_grid * CMR_SCAN_WAVES || a.s_wave_cap < 1 || a.s_grid < 1)) return hipErrorInvalidValue;
+    const int grid = sample ? a.s_grid : a.grid;
     const size_t lds = cmr_q8_filter_lds(a.dpad, a.nqt);
     auto launch = [&](auto kern) -> hipError_t {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(a.grid), dim3(CMR_SCAN_THREADS), lds, s, p);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(CMR_SCAN_THREADS), lds, s, p);
         return hipGetLastError();
     };
     const bool ch8 = p.KB % 8 == 0;
-    if (a.nqt == 2) return ch8 ? launch(q8_filter_kernel<2, 8>) : launch(q8_filter_kernel<2, 4>);
-    if (a.nqt == 1) return ch8 ? launch(q8_filter_kernel<1, 8>) : launch(q8_filter_kernel<1, 4>);
+    if (sample) {
+        if (a.nqt == 2) return ch8 ? launch(q8_filter_kernel<2, 8, true>) : launch(q8_filter_kernel<2, 4, true>);
+        if (a.nqt == 1) return ch8 ? launch(q8_filter_kernel<1, 8, true>) : launch(q8_filter_kernel<1, 4, true>);
+        return hipErrorInvalidValue;
+    }
+    if (a.nqt == 2) return ch8 ? launch(q8_filter_kernel<2, 8, false>) : launch(q8_filter_kernel<2, 4, false>);
+    if (a.nqt == 1) return ch8 ? launch(q8_filter_kernel<1, 8, false>) : launch(q8_filter_kernel<1, 4, false>);
     return hipErrorInvalidValue;
 }
 
-hipError_t cmr_launch_q8_bucket(const CmrQ8Args& a, hipStream_t s) {
+// sample = true: the sample's wave areas into the sample's lists, nothing kept directly
+hipError_t cmr_launch_q8_bucket(const CmrQ8Args& a, hipStream_t s, bool sample) {
     BucketP p;
-    p.wrec = reinterpret_cast<const v4u*>(a.wrec); p.wcnt = a.wcnt; p.wave_cap = (unsigned)a.wave_cap; p.W = a.grid * CMR_SCAN_WAVES;
-    p.pair = reinterpret_cast<v4u*>(a.pair); p.pair_cnt = a.pair_cnt; p.pcap = (unsigned)a.pcap; p.keep = a.keep;
+    if (sample) {
+        p.wrec = reinterpret_cast<const v4u*>(a.s_wrec); p.wcnt = a.s_wcnt; p.wave_cap = (unsigned)a.s_wave_cap; p.W = a.s_grid * CMR_SCAN_WAVES;
+        p.pair = reinterpret_cast<v4u*>(a.s_pair); p.pair_cnt = a.s_pair_cnt; p.pcap = (unsigned)a.s_pcap; p.keep = nullptr;
+    } else {
+        p.wrec = reinterpret_cast<const v4u*>(a.wrec); p.wcnt = a.wcnt; p.wave_cap = (unsigned)a.wave_cap; p.W = a.grid * CMR_SCAN_WAVES;
+        p.pair = reinterpret_cast<v4u*>(a.pair); p.pair_cnt = a.pair_cnt; p.pcap = (unsigned)a.pcap; p.keep = a.keep;
+    }
     hipLaunchKernelGGL(q8_bucket_kernel, dim3((p.W + Q8_BUCKET_WAVES - 1) / Q8_BUCKET_WAVES), dim3(Q8_BUCKET_WAVES * 64), 0, s, p);
     return hipGetLastError();
 }
@@ -658,8 +715,17 @@ hipError_t cmr_launch_q8_bucket(const CmrQ8Args& a, hipStream_t s) {
 hipError_t cmr_launch_q8_tighten(const CmrQ8Args& a, hipStream_t s) {
     TightenP p;
     p.pair = reinterpret_cast<const v4u*>(a.pair); p.pair_cnt = a.pair_cnt; p.pcap = (unsigned)a.pcap; p.tau_init = a.tau_init; p.k = a.k;
-    p.keep = a.keep; p.tau_out = a.tau_tight;
+    p.keep = a.keep; p.tau_out = a.tau_tight; p.key_out = nullptr;
     hipLaunchKernelGGL(q8_tighten_kernel, dim3(a.nq), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// the sample's lists -> per query max(key of the k-th largest lb, level-0 key a.s_tau0[q]) in a.s_tau_out[q]
+hipError_t cmr_launch_q8_select(const CmrQ8Args& a, hipStream_t s) {
+    TightenP p;
+    p.pair = reinterpret_cast<const v4u*>(a.s_pair); p.pair_cnt = a.s_pair_cnt; p.pcap = (unsigned)a.s_pcap; p.tau_init = a.s_tau0; p.k = a.k;
+    p.keep = nullptr; p.tau_out = nullptr; p.key_out = a.s_tau_out;
+    hipLaunchKernelGGL(q8_select_kernel, dim3(a.nq), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

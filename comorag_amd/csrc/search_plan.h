@@ -8,6 +8,12 @@
 
 bool cmr_ring_audit_ok(int dtype, int nqt, int cap, int ring, int mode);  // ring_audit.cpp (generated at build); mode: 0 top-k, 1 scores, 2 top-k with the finishing stage
 static const long long kMaxMergeLists = 4096;                    // merge_query_kernel: W <= 16 * MERGE_THREADS
+// The int8 sample of a pre-filtered pass (prefilter_sample; DESIGN 4.14 has the sweeps): auto on / off, and its auto shape — level-1 panels
+// (no merge behind it, so no list cap), panels per wave, panels of the bf16 level 0 whose threshold the sample tests against
+constexpr bool kPrefilterSampleAuto = false;     // off: at equal reserve it never beat the bf16 sampling by the project's rule
+static const long long kQ8SamplePanels = 8192;
+static const int kQ8SampleRun = 16;
+static const int kQ8SampleLevel0 = 64;
 
 namespace {
 
@@ -83,6 +89,10 @@ struct PassPlan {
     int rescore_grid = 0;
     int pair_cap = 0;                // pre-filter: hit records per query for the threshold tightening (0: none, every hit is re-scored)
     int wave_cap = 0;                // pre-filter: hit records per wave of the filter's grid (0 exactly when pair_cap is)
+    // pre-filter with record lists: level 1 is the int8 sample — the filter body over s_nruns runs of s_run panels, run g at panel g * s_stride
+    // (>= s_run), one per wave of level[1].grid workgroups, then bucket and select; level[1] holds its panels and grid, no lists (Wl = 0)
+    bool sample_q8 = false;
+    int s_run = 0, s_stride = 0, s_nruns = 0, s_wave_cap = 0, s_pair_cap = 0;
     int G = 1;                       // query groups of the query-split grid
     int n_levels = 0;                // sampling passes in front of the main scan
     struct Level { long long panels; int grid, Wl, clog, stride; } level[2] = {};      // grid: launch grid (all groups); Wl: candidate lists per query
@@ -141,13 +151,18 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     // Wide kernel: the sampling workgroups split the sampled panels among them (one list per workgroup and query).
     // Certified int8 pre-filter: a narrow pass with thresholds from tau_init (16-bit index, no threshold search: tested by prefilter_eligible)
     const bool prefilter = rq.prefilter && !wide && G == 1 && !fin;
+    // ... whose level-1 threshold is drawn from the int8 companion: only where the pass keeps record lists (the select step reads them)
+    const bool sample_q8 = prefilter && rq.prefilter == 1 && idx->pf_tighten && idx->pf_pair_cap > 0 && npanels >= 4096 &&
+                           (idx->pf_sample < 0 ? kPrefilterSampleAuto : idx->pf_sample == 1);
     long long level_panels[2] = {0, 0};
+    long long bf16_level1 = 0;       // the bf16 level 1 this shape would sample (what the reserve rule was measured with)
     int n_levels = 0;
     bool single_level = false;
     // threshold search (min_score): the caller's bound is the initial threshold of every query — already selective, so no
     // sampling passes
     if (!idx->no_sample && npanels >= 256 && !rq.has_min_score && !fin) {
-        const long long s0 = std::max<long long>(16, k);                       // panels
+        // (int8 sample: a larger level 0 — its threshold decides how many of the sample's pairs become records; k panels at least, as everywhere)
+        const long long s0 = sample_q8 ? std::max<long long>(idx->pf_sample_level0 > 0 ? idx->pf_sample_level0 : kQ8SampleLevel0, k) : std::max<long long>(16, k);      // panels
         // A handful of queries on a mid-size corpus (what a synchronous caller issues) is a chain of dependent launches
         // around a short scan: ONE sampling level of 128 panels instead of two saves a scan + merge pair (~45 us of a
         // 0.4 ms call at 1 M rows).  Its threshold lets ~k * npanels / 128 scores per query through — a few slow-path
@@ -162,14 +177,23 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
             // pre-filter: every row the threshold lets through costs a gather of 96 cache lines, so the sample is as large as the
             // merge allows (10 M rows, 2560 -> 4096 panels: 330 K -> 216 K kept rows per batch, step 2.00 -> 1.90 ms)
             const long long maxmul = idx->sample_maxmul > 0 ? idx->sample_maxmul : (wide ? 512 : prefilter ? kMaxMergeLists : 128);
-            long long s1 = std::min<long long>(std::max<long long>(npanels / idx->sample_div, 8 * s0), maxmul * s0);
+            const long long b0 = std::max<long long>(16, k);
+            long long s1 = std::min<long long>(std::max<long long>(npanels / idx->sample_div, 8 * b0), maxmul * b0);
             if (!wide) s1 = std::min<long long>(s1, kMaxMergeLists);
-            if (s1 < npanels / 2) level_panels[n_levels++] = s1;
+            if (s1 < npanels / 2) bf16_level1 = s1;
+            if (sample_q8) {
+                // int8 sample: half the bytes per row and no merge behind it, so the merge's list cap does not bind; a forced size is taken as
+                // it is, up to every panel (8 * s0 <= 1024 < npanels / 2 here: auto always has its level 1)
+                level_panels[n_levels++] = idx->pf_sample_panels > 0 ? std::min<long long>(idx->pf_sample_panels, npanels)
+                                                                     : std::min<long long>(std::max<long long>(npanels / idx->sample_div, 8 * s0), kQ8SamplePanels);
+            } else if (bf16_level1) level_panels[n_levels++] = bf16_level1;
         }
     }
     p.n_levels = n_levels;
     p.single_level = single_level;
-    const long long max_sample = std::max(level_panels[0], level_panels[1]);
+    p.sample_q8 = sample_q8 && n_levels == 2;
+    // (the largest bf16 sampling pass: the int8 sample has no candidate lists and runs one workgroup per 8 runs)
+    const long long max_sample = std::max(level_panels[0], p.sample_q8 ? 0 : level_panels[1]);
     int reserve_cus = rq.reserve_cus;
     if (reserve_cus < 0) {
         if (!max_sample) reserve_cus = 0;
@@ -180,6 +204,16 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
             // waited 4.4 ms for the main scan to end (kernel trace), while 224 + 32 — one free CU in every one of the 32
             // engines — flows.  So the reserve is one CU per shader engine; the main pass is matrix-pipe-bound and pays for
             // them in proportion (4.2 -> 4.6 ms at 10 M rows), about what a serialised pre-phase would cost.
+            reserve_cus = 32;
+        } else if (prefilter && idx->scan_us() >= 1250.0) {
+            // Pipelined mode, int8 pre-filter over a corpus of ~4.9 M x 768 16-bit rows and more: the filter is limited by the CUs it gets,
+            // not by HBM (10 M rows: 1.31 ms alone on 256 CUs, 1.35 / 1.45 / 1.51 ms in the pipeline on 240 / 222 / 192), and the free
+            // CUs carry BOTH the next batch's pre-phase and the previous batch's merge-stream chain — neither a sampling workgroup nor
+            // a re-score workgroup finds registers beside a filter workgroup.  Kernel traces at 10 M rows: on 32 free CUs
+            // the level-1 sampling scan takes 436 us and still ends 146 us (46 at worst) before the filter it runs under; on 16 it no
+            // longer does, and an int8 sample there starves the re-score (0.2 -> 1 ms).  The pre-phase on 32 CUs is ~650 us in a row, so it
+            // needs a filter of that length: 32 against 64 CUs, median ms per step — 10 M rows 1.50 / 1.57 (B = 33: 1.41 / 1.44, B = 8:
+            // 1.30 / 1.30, B = 1: 1.26 / 1.26), 5 M rows 0.823 / 0.829, but 4 M rows 0.694 / 0.686: there, and below, the rule by size stays.
             reserve_cus = 32;
         } else {
             // Pipelined mode, reserve chosen by size: the next batch's pre-phase has to fit under this scan (~6 TB/s).
@@ -203,7 +237,7 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
         const int cap_wgs = rq.pipelined && reserve_cus > 0 ? reserve_cus : idx->n_cu;
         return (int)std::min<long long>(spn, std::max<long long>(cap_wgs, (spn + 47) / 48));
     };
-    const int Ws = max_sample ? std::max(sample_grid(level_panels[0]), n_levels > 1 ? sample_grid(level_panels[1]) : 0) * lists_per_wg : 0;
+    const int Ws = max_sample ? std::max(sample_grid(level_panels[0]), n_levels > 1 && !p.sample_q8 ? sample_grid(level_panels[1]) : 0) * lists_per_wg : 0;
     int NQ, W, tiles;
     if (wide) {
         // register-resident queries: 4 waves x 2 (768-d) or 1 (1024-d) tiles of 32, one list row per
@@ -248,6 +282,23 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
         p.bytes.q8[Q8_PAIRCNT] = (size_t)NQ * sizeof(unsigned);
         p.bytes.q8[Q8_KEEP] = (size_t)idx->cap_panels * sizeof(unsigned);
         p.bytes.q8[Q8_TAU] = (size_t)NQ * sizeof(float);
+        if (p.sample_q8) {
+            // runs of s_run panels spread evenly; a sample that does not fit with gaps (forced: beyond npanels / 2) is laid end to end — full
+            // coverage, the last run cut by the corpus' end.  One wave per run; the area of a wave holds 1 / 16 of its run's (row, query)
+            // pairs by default (the level-0 threshold of 64 panels lets ~2 % through), a hit beyond it is dropped
+            const long long s1 = level_panels[1];
+            const long long run = std::min<long long>(idx->pf_sample_run > 0 ? idx->pf_sample_run : kQ8SampleRun, s1);
+            long long nruns = (s1 + run - 1) / run, stride = npanels / nruns;
+            if (stride < run) { stride = run; nruns = std::min(nruns, (npanels + run - 1) / run); }
+            p.s_run = (int)run; p.s_stride = (int)stride; p.s_nruns = (int)nruns;
+            p.s_wave_cap = idx->pf_sample_wave_cap > 0 ? idx->pf_sample_wave_cap : (int)std::min<long long>(1 << 20, (run * CMR_PANEL_ROWS * NQ / 16 + 63) / 64 * 64);
+            p.s_pair_cap = p.pair_cap;
+            const long long sw = (nruns + CMR_SCAN_WAVES - 1) / CMR_SCAN_WAVES * CMR_SCAN_WAVES;
+            p.bytes.q8[Q8_SWREC] = (size_t)sw * p.s_wave_cap * 16;
+            p.bytes.q8[Q8_SWCNT] = (size_t)sw * sizeof(unsigned);
+            p.bytes.q8[Q8_SPAIR] = (size_t)NQ * p.s_pair_cap * 16;
+            p.bytes.q8[Q8_SPAIRCNT] = (size_t)NQ * sizeof(unsigned);
+        }
     }
     const int NQA = G * NQ;          // query slots of the pass over all groups
     p.NQ = NQ; p.W = W; p.Ws = Ws; p.tiles = tiles; p.NQA = NQA;
@@ -265,6 +316,10 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
         PassPlan::Level& L = p.level[lv];
         const long long spn = level_panels[lv];
         L.panels = spn;
+        if (lv == 1 && p.sample_q8) {      // (no candidate lists; the runs are in s_run / s_stride / s_nruns)
+            L.grid = (p.s_nruns + CMR_SCAN_WAVES - 1) / CMR_SCAN_WAVES; L.Wl = 0; L.clog = 0; L.stride = p.s_stride;
+            continue;
+        }
         L.grid = sample_grid(spn);
         L.Wl = L.grid * lists_per_wg;
         L.grid *= G;                               // (query-split grid: every group samples the same panels)

@@ -212,7 +212,10 @@ class DenseIndex(HostArrayIndex):
         include/comorag_hip.h), "pipe_dual_scan_active", "pipe_cu_mask_active", "pipe_scan_cus", "exact_cand", "combine",
         "combine_wait_us", the combiner's counters (`combine_stats`), "prefilter" and, of the last pipelined call, "prefilter_active",
         "prefilter_rows", "prefilter_bytes" and — these wait for the pipeline — "prefilter_candidates", "prefilter_pairs",
-        "prefilter_pair_overflow", "prefilter_wave_overflow"; "prefilter_tighten", "prefilter_pair_cap", "prefilter_wave_cap"."""
+        "prefilter_pair_overflow", "prefilter_wave_overflow"; "prefilter_tighten", "prefilter_pair_cap", "prefilter_wave_cap"; the int8
+        sample's "prefilter_sample", "prefilter_sample_panels", "prefilter_sample_run", "prefilter_sample_wave_cap",
+        "prefilter_sample_level0", "prefilter_sample_active" and — waiting for the pipeline — "prefilter_sample_pairs",
+        "prefilter_sample_overflow"."""
         v = C.c_int64(0)
         L.check(L.lib().cmr_index_get_option(self._h, name.encode(), C.byref(v)))
         return v.value

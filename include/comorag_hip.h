@@ -186,9 +186,18 @@ int32_t cmr_index_set_id_blocks(cmr_index_t* idx, int32_t n_blocks, const int64_
  * as prefilter_tighten = 0) and prefilter_wave_cap (hit records per wave of the filter's grid, which writes them to an area of its own
  * before they are sorted into the queries' lists, 16 bytes each, clamped to [0, 2^20]; 0, the default: as many as the queries' lists
  * hold, spread over the waves and rounded up to a multiple of 64; a wave with more hits keeps the rest directly).
+ * prefilter_sample (-1 auto, currently off | 0: the level-1 sampling threshold of a pre-filtered pass comes from the 16-bit panels, scan
+ * + merge as on every other route | 1: from the int8 companion — the filter's loop over strided runs of panels, its records sorted by
+ * query, the k-th largest certified lower bound as the threshold; only where the pass keeps record lists: prefilter = 1,
+ * prefilter_tighten = 1, prefilter_pair_cap > 0, 4096 panels or more), with prefilter_sample_panels (0 auto: 8192; a forced value is
+ * taken as it is, up to every panel), prefilter_sample_run (panels per wave, 0 auto: 16), prefilter_sample_wave_cap (records per wave
+ * of the sample's grid, 0 auto; a hit beyond it is dropped) and prefilter_sample_level0 (panels of the 16-bit level 0 in front of it,
+ * 0 auto: 64; at least k, at most 128).
  * cmr_index_get_option reads, of the last pre-filtered pass and waiting for the pipeline:
  * prefilter_candidates (rows handed to the re-score), prefilter_pairs (hit records stored, summed over the queries),
- * prefilter_pair_overflow (queries that had more hits than records) and prefilter_wave_overflow (waves that had more hits than records).
+ * prefilter_pair_overflow (queries that had more hits than records) and prefilter_wave_overflow (waves that had more hits than records);
+ * prefilter_sample_active (did the pass sample from the companion; does not wait), prefilter_sample_pairs and prefilter_sample_overflow
+ * (records the sample stored, and queries whose sample list filled).
  * Unknown names: CMR_ERR_INVALID.
  * The wide-batch kernel exists for padded dims 768 (256 queries per pass) and 1024 (128 per pass) in bf16 / f16; any other
  * dim and every fp32 index run a batch of B > 64 queries on the query-split grid of the narrow kernel (up to four query tiles
