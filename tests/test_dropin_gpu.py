@@ -180,8 +180,24 @@ def test_memory_pool_numeric(golden_dir, fake_embedder):
     idx.close()
 
 
+def holed_mask(b, l, seed):
+    """A full HF attention mask, not a right-padded one: random 0 / 1 per token with at least one live token per row; row 0's first token is
+    masked, the last row (of two or more) has a single live token, the last one."""
+    rng = np.random.default_rng(seed)
+    mask = rng.integers(0, 2, size=(b, l)).astype(np.int64)
+    mask[np.arange(b), rng.integers(0, l, size=b)] = 1
+    if l > 1:
+        mask[0, 0], mask[0, 1 + int(rng.integers(0, l - 1))] = 0, 1
+    if b > 1:
+        mask[-1] = 0
+        mask[-1, -1] = 1
+    return mask
+
+
+# the last three: d = 36 and 30 are no multiple of the 16-byte vector of the 16-bit / the fp32 kernel (its scalar path); 16 640 tokens make
+# each of the 64 splits longer than 256 tokens (the per-token loads instead of the bit sets)
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16", "float16"])
-@pytest.mark.parametrize("shape", [(5, 19, 40), (32, 512, 768), (3, 7, 1024), (1, 1, 8), (64, 128, 1000)])
+@pytest.mark.parametrize("shape", [(5, 19, 40), (32, 512, 768), (3, 7, 1024), (1, 1, 8), (64, 128, 1000), (3, 50, 36), (2, 70, 30), (1, 16640, 8)])
 def test_pool_kernel(golden_dir, dtype, shape):
     import torch
     from comorag_amd.embedding_model.bge import pool_l2norm
@@ -200,6 +216,16 @@ def test_pool_kernel(golden_dir, dtype, shape):
     want = orc.mean_pool_l2norm(ht.float().cpu().numpy(), mask)     # oracle on the same (rounded) inputs
     np.testing.assert_allclose(got, want, atol=2e-6, rtol=1e-5)
     np.testing.assert_allclose((got ** 2).sum(1), 1.0, atol=1e-5)
+    if b * l * d > 1_000_000:
+        return
+    # the same rows under a mask with holes: same oracle, same tolerances, with and without the normalisation
+    mask = holed_mask(b, l, b * l + d)
+    assert mask.sum(1).min() >= 1 and (l == 1 or mask[0, 0] == 0) and (b == 1 or (mask[-1].sum() == 1 and mask[-1, -1] == 1))
+    assert l < 8 or not np.array_equal(mask, (np.arange(l)[None, :] < mask.sum(1)[:, None]).astype(np.int64))      # not a right-padded one
+    for normalize in (True, False):
+        got = pool_l2norm(ht, torch.from_numpy(mask).cuda(), normalize=normalize).cpu().numpy()
+        want = orc.mean_pool_l2norm(ht.float().cpu().numpy(), mask, normalize=normalize)
+        np.testing.assert_allclose(got, want, atol=2e-6, rtol=1e-5)
 
 
 def test_encoder_end_to_end_vs_oracle():
