@@ -23,6 +23,7 @@ CMR_MAX_K_2PASS = 4096
 CMR_MAX_K_EXACT = 64      # cmr_index_search_exact
 CMR_PPR_MAX_BATCH = 16    # cmr_graph_ppr_batch / cmr_index_ppr_batch: queries per power iteration
 CMR_PPR_RANK_TILE = 2048  # keys per workgroup of the ranked calls' radix sort
+CMR_ENCODER_ROWS_MAX = 2048  # cmr_encoder_linear_rows*: 16 questions x 128 token rows
 DTYPES = {"f32": CMR_F32, "fp32": CMR_F32, "float32": CMR_F32, "bf16": CMR_BF16, "bfloat16": CMR_BF16,
           "f16": CMR_F16, "fp16": CMR_F16, "float16": CMR_F16}
 
@@ -119,6 +120,8 @@ SIGNATURES = {
     "cmr_encoder_linear_small": (_i32, [_i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "cmr_encoder_linear_small_partials": (_i32, [_i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "cmr_encoder_linear_small_split": (_i32, [_i32, _i32, _i32, _i32, _P(_i32), _P(_i64)]),
+    "cmr_encoder_linear_rows": (_i32, [_i32, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "cmr_encoder_linear_rows_partials": (_i32, [_i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "cmr_encoder_add_layernorm_partials": (_i32, [_i32, _p, _i32, _p, _p, _p, _p, _f32, _i64, _i32, _i32, _p, _p]),
     "cmr_encoder_add_layernorm_partials_pool": (_i32, [_i32, _p, _i32, _p, _p, _p, _p, _f32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
     "cmr_profile_enable": (_i32, [_p, _i32]),

@@ -169,7 +169,8 @@ hipError_t cmr_launch_add_layernorm_pool(const void* y, const void* bias, const 
 hipError_t cmr_launch_embed_layernorm_ragged(const int* ids32, const int* off, const void* word, const void* pos, const void* type, const void* gamma,
                                              const void* beta, float eps, long long rows, int L, int d, int vocab, int n_pos, int pos_off, int dtype,
                                              void* out, hipStream_t s);
-// small-M linear (one short query's token rows): mode 0 y = x w^T + bias, 1 gelu of it, 2 fp32 partial slabs [split, m, n]; and the slabs' consumer
+// small-M linear (one short query's token rows): mode 0 y = x w^T + bias, 1 gelu of it, 2 fp32 partial slabs [split, m, n]; and the slabs' consumer.
+// m > 128 (up to CMR_ENCODER_ROWS_MAX, the many-row entry points): row tiles of 128 over grid.z, every row with the bits of the m <= 128 launch
 int cmr_small_linear_split(int n, int k);
 hipError_t cmr_launch_small_linear(const void* x, const void* w, const void* bias, int m, int n, int k, int dtype, int mode, void* out, hipStream_t s);
 hipError_t cmr_launch_add_layernorm_partials(const float* part, int n_split, const void* bias, const void* res, const void* gamma, const void* beta, float eps,

@@ -23,8 +23,9 @@
 // each participant publishes them in its own thread after submit() returns.
 //
 // Not combined (the owner never queues them): cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact,
-// cmr_graph_ppr, every _dev / pipelined call, cmr_mindex_* (searches through a multi-device handle do not pass here), and the
-// encoder (a combined forward is not bit-equal to a solo one).
+// cmr_graph_ppr, every _dev / pipelined call, cmr_mindex_* (searches through a multi-device handle do not pass here).  The encoder
+// does not pass here either: concurrent one-question encodes are combined one level up, by the Python restatement of this protocol
+// (embedding_model/combine.py, config `embedding_combine`), over the many-row linear kernels (cmr_encoder_linear_rows*).
 #pragma once
 #include <chrono>
 #include <condition_variable>

@@ -1222,12 +1222,15 @@ static int sml_split(int n, int k) {
 // MT = token tiles of 16 rows the instantiation carries (2, 4, 6, 8: M <= 32, 64, 96, 128): it sizes the accumulators, the staging registers and
 // the LDS buffer, never the order of a sum.  No branch in the loads or the MFMA loops: token rows >= M re-read row M - 1 (their columns of
 // the product are never stored), k-steps behind the slice's end load the slice's last step and multiply a ZERO weight fragment (+ 0.0f).
-template <int DT, int MODE, int MT>
+// TILED (the many-row form, cmr_encoder_linear_rows*): the workgroup's token rows are the 128 from blockIdx.z * 128 on (MT = 8); the row clamp
+// and the slab index take the global row and the total M, everything else is the same code: the same sums in the same order for every row.
+template <int DT, int MODE, int MT, bool TILED = false>
 __global__ __launch_bounds__(256) void small_linear_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ w, const unsigned short* __restrict__ bias,
                                                            int M, int N, int K, int kslice, void* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) unsigned short xs[MT * 16 * SML_XSTR];      // 8.25 KiB per token tile; the wave-order reduction reuses it (4 KiB per tile)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
     const int n0 = blockIdx.x * SML_ROWS, k0 = blockIdx.y * kslice;
+    const int m0 = TILED ? (int)blockIdx.z * SML_MAXM : 0;     // first token row of this workgroup
     const int nsteps = kslice / 32, nchunks = (nsteps + 7) / 8;
     const unsigned short* wrow = w + (size_t)(n0 + r) * K + k0 + 8 * q;
 
@@ -1236,7 +1239,7 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const unsigned short*
     const unsigned short* xp[2 * MT];
 #pragma unroll
     for (int i = 0; i < 2 * MT; ++i) {
-        const int row = xrow + 8 * i;
+        const int row = m0 + xrow + 8 * i;
         xp[i] = x + (size_t)(row < M ? row : M - 1) * K + k0;
     }
     v4u xr[2 * MT];
@@ -1291,7 +1294,7 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const unsigned short*
 #pragma unroll
     for (int it = 0; it < MT / 4 + (MT % 4 ? 1 : 0); ++it) {
         const int item = tid + 256 * it, mt = item >> 6, ln = item & 63;
-        const int m = mt * 16 + (ln & 15), n = n0 + 4 * (ln >> 4);
+        const int m = m0 + mt * 16 + (ln & 15), n = n0 + 4 * (ln >> 4);
         if (mt >= MT || m >= M) continue;
         enc_f32x4 s = *reinterpret_cast<const enc_f32x4*>(&red[(mt * 64 + ln) * 4]);
 #pragma unroll
@@ -1322,14 +1325,20 @@ static hipError_t launch_small_linear(const void* x, const void* w, const void* 
     if (m <= 32) ENC_SML(2);
     else if (m <= 64) ENC_SML(4);
     else if (m <= 96) ENC_SML(6);
-    else ENC_SML(8);
+    else if (m <= SML_MAXM) ENC_SML(8);
+    else {                                             // the many-row form: ceil(m / 128) row tiles over the grid's third dimension
+        const dim3 tiled((unsigned)(n / SML_ROWS), (unsigned)split, (unsigned)((m + SML_MAXM - 1) / SML_MAXM));
+        hipLaunchKernelGGL((small_linear_kernel<DT, MODE, 8, true>), tiled, block, 0, s, reinterpret_cast<const unsigned short*>(x), reinterpret_cast<const unsigned short*>(w),
+                           reinterpret_cast<const unsigned short*>(bias), m, n, k, k / split, out);
+    }
 #undef ENC_SML
     return hipGetLastError();
 }
 
 int cmr_small_linear_split(int n, int k) { return sml_split(n, k); }
 
-// mode 0: F.linear; 1: F.gelu(F.linear); 2: fp32 partial slabs [cmr_small_linear_split(n, k), m, n] (bias unused).  16-bit dtypes, 1 <= m <= 128,
+// mode 0: F.linear; 1: F.gelu(F.linear); 2: fp32 partial slabs [cmr_small_linear_split(n, k), m, n] (bias unused).  16-bit dtypes, 1 <= m <= 128
+// for cmr_encoder_linear_small*, <= CMR_ENCODER_ROWS_MAX for cmr_encoder_linear_rows* (m > 128: row tiles of 128 over grid.z),
 // n % 16 == 0, k % 32 == 0, 16-byte aligned buffers (the caller checks)
 hipError_t cmr_launch_small_linear(const void* x, const void* w, const void* bias, int m, int n, int k, int dtype, int mode, void* out, hipStream_t s) {
     const int split = mode == 2 ? sml_split(n, k) : 1;
@@ -1476,11 +1485,11 @@ int32_t cmr_encoder_add_layernorm_pool(int32_t device_id, const void* y_dev, con
 }
 
 // shape / type checks shared by the small-M entry points (no device call)
-static int sml_check(const char* who, int32_t m, int32_t n, int32_t k, int32_t dtype) {
+static int sml_check(const char* who, int32_t m, int32_t n, int32_t k, int32_t dtype, int32_t max_m = SML_MAXM) {
     if (m <= 0 || n <= 0 || k <= 0) return cmr_fail(CMR_ERR_INVALID, "%s: m, n, k must be > 0", who);
     if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "%s: dtype must be bf16 or f16", who);
     if (dtype == CMR_F32) return cmr_fail(CMR_ERR_UNSUPPORTED, "%s: 16-bit tensors only (bf16 or f16)", who);
-    if (m > SML_MAXM) return cmr_fail(CMR_ERR_UNSUPPORTED, "%s: at most %d token rows", who, SML_MAXM);
+    if (m > max_m) return cmr_fail(CMR_ERR_UNSUPPORTED, "%s: at most %d token rows", who, max_m);
     if (n % SML_ROWS || k % 32) return cmr_fail(CMR_ERR_UNSUPPORTED, "%s: n must be a multiple of 16 and k a multiple of 32", who);
     return CMR_OK;
 }
@@ -1517,6 +1526,38 @@ int32_t cmr_encoder_linear_small_partials(int32_t device_id, const void* x_dev, 
     if (rc) return rc;
     if (((uintptr_t)x_dev | (uintptr_t)w_dev | (uintptr_t)partials_dev) & 15)
         return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_linear_small_partials: buffers must be 16-byte aligned");
+    rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_small_linear(x_dev, w_dev, nullptr, m, n, k, dtype, 2, partials_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+// the many-row forms: the same launcher; m > 128 takes the row-tiled instantiation (a row's bits are those of cmr_encoder_linear_small*)
+int32_t cmr_encoder_linear_rows(int32_t device_id, const void* x_dev, const void* w_dev, const void* bias_dev, int32_t m, int32_t n, int32_t k, int32_t dtype,
+                                int32_t act, void* out_dev, void* stream) {
+    if (!x_dev || !w_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (act != 0 && act != 1) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_linear_rows: act must be 0 (none) or 1 (erf GELU)");
+    int rc = sml_check("cmr_encoder_linear_rows", m, n, k, dtype, CMR_ENCODER_ROWS_MAX);
+    if (rc) return rc;
+    if (((uintptr_t)x_dev | (uintptr_t)w_dev | (uintptr_t)bias_dev | (uintptr_t)out_dev) & 15)
+        return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_linear_rows: buffers must be 16-byte aligned");
+    rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_small_linear(x_dev, w_dev, bias_dev, m, n, k, dtype, act, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_linear_rows_partials(int32_t device_id, const void* x_dev, const void* w_dev, int32_t m, int32_t n, int32_t k, int32_t dtype,
+                                         float* partials_dev, void* stream) {
+    if (!x_dev || !w_dev || !partials_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = sml_check("cmr_encoder_linear_rows_partials", m, n, k, dtype, CMR_ENCODER_ROWS_MAX);
+    if (rc) return rc;
+    if (((uintptr_t)x_dev | (uintptr_t)w_dev | (uintptr_t)partials_dev) & 15)
+        return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_linear_rows_partials: buffers must be 16-byte aligned");
     rc = cmr_check_device(device_id);
     if (rc) return rc;
     rc = cmr_set_device(device_id);

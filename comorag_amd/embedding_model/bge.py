@@ -164,6 +164,17 @@ class HipBGEEmbeddingModel(BaseEmbeddingModel):
                 self.small_m_rows = self._fused.small_m_rows
             else:
                 self.encoder_path = f"transformers ({reason})"
+        # Concurrent one-question encodes share ONE forward (embedding_combine = W in 2..16; 0, the default, is one branch in front of
+        # today's code): ComoRAG answers up to 16 questions from one thread pool and every thread encodes one short string.  Armed only
+        # where a combined caller gets the BITS of its solo call: the ragged fused path with the short-row route on (combine.py).
+        self._combiner = None
+        width = int(cfg_get(self.global_config, "embedding_combine", 0) or 0)
+        if width:
+            from .combine import MAX_WIDTH, EncodeCombiner
+            if not 2 <= width <= MAX_WIDTH:
+                raise ValueError(f"embedding_combine must be 0 (off) or in 2..{MAX_WIDTH}")
+            if self._fused is not None and self._fused.small_m_rows > 0 and self._ragged_ok():
+                self._combiner = EncodeCombiner(width, int(cfg_get(self.global_config, "embedding_combine_wait_us", 0) or 0))
         self.max_positions = int(getattr(self.embedding_model.config, "max_position_embeddings", 1 << 30))
         if getattr(self.embedding_model.config, "model_type", "") in ("roberta", "xlm-roberta", "camembert"):
             # RoBERTa-family position ids start at padding_idx + 1: a table of 8194 rows serves sequences of 8192 tokens
@@ -310,6 +321,35 @@ class HipBGEEmbeddingModel(BaseEmbeddingModel):
         width = -(-int(lens.max()) // 16) * 16        # rows are padded (on the device) to the longest one, rounded up to 16 tokens
         return (fused or self._fused).forward_ragged(np.concatenate([head, *id_arrays]), b, width, normalize)
 
+    def _forward_combined(self, key, id_arrays):
+        """The combiner's batch call: 2 .. 16 one-prompt calls of one padded width l as ONE forward on the many-row route
+        (`forward_ragged(..., rows_route=True)`): every sequence runs the attention instantiation and the pooling blocks of its solo
+        [1, l] call and the linear kernels give a row the bits of that call.  b is rounded up to 2, 4, 8 or 16 with one-token filler
+        sequences (a width then has at most four graph shapes); their rows are dropped.  Returns one [1, D] row per caller, COMPLETE on
+        the device: the leader waits for an event behind the forward before the members are woken."""
+        import torch
+        l, normalize = key
+        n = len(id_arrays)
+        b = next(p for p in (2, 4, 8, 16) if p >= n)
+        arrays = list(id_arrays) + [id_arrays[0][:1]] * (b - n)
+        head = np.empty(2 * b + 1, dtype=np.int32)
+        lens = head[:b]
+        lens[:] = [len(x) for x in arrays]
+        head[b] = 0
+        np.cumsum(lens, out=head[b + 1:])
+        rows = self._fused.forward_ragged(np.concatenate([head, *arrays]), b, int(l), bool(normalize), rows_route=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(self.device))
+        done.synchronize()
+        return [rows[i:i + 1] for i in range(n)]
+
+    def combine_stats(self) -> dict:
+        """Counters of the encode combiner (`embedding_combine`): forwards run for queued calls (batches of one included), calls they
+        served, the widest batch so far.  All 0 where the option is off or not armed."""
+        if self._combiner is None:
+            return {"batches": 0, "queries": 0, "max_width": 0}
+        return self._combiner.stats()
+
     @staticmethod
     def _window_groups(lens, batch_size: int, budget: int):
         """Mini-batches of one bucketing window: stable sort by token count, then as many rows as fit the token budget of a full-length
@@ -387,7 +427,12 @@ class HipBGEEmbeddingModel(BaseEmbeddingModel):
         if self._ragged_ok():
             ids = self._ragged(prompts, min(int(max_length), self.max_positions))
             if all(len(x) for x in ids):
-                return self._forward_ragged(ids, kwargs.get("normalize", True))
+                normalize = kwargs.get("normalize", True)
+                if self._combiner is not None and len(ids) == 1 and not kwargs.get("_solo", False):
+                    l = -(-len(ids[0]) // 16) * 16
+                    if l <= self._fused.small_m_rows:          # its solo call runs the short-row route: the combined one returns the same bits
+                        return self._combiner.submit((l, bool(normalize)), ids[0], lambda: self._forward_ragged(ids, normalize), self._forward_combined)
+                return self._forward_ragged(ids, normalize)
         return self._forward_pool(self._tokenize(prompts, max_length), kwargs.get("normalize", True))
 
     # ------------------------------------------------------------------ public
@@ -405,6 +450,8 @@ class HipBGEEmbeddingModel(BaseEmbeddingModel):
         else:
             params["instruction"] = params.get("passage_instruction", BGE_PREFIX)
         batch_size = params.pop("batch_size", 16)
+        if return_device:
+            params["_solo"] = True                        # rows that stay on the device never join the combining queue
         # One string — a question: ComoRAG encodes the same question three times per tri_retrieve (once per query instruction, ComoRAG.py:921-935,
         # and once more for the episodic layer, utils/embed_utils.py get_similar_summaries), and every one of those is the same prompt through the
         # same deterministic forward (0.75 ms at BGE-base).  The last `embedding_query_cache` single-string results are kept by (prompt, max_length,

@@ -170,6 +170,9 @@ def gelu_epilogue_available(device, dtype) -> bool:
 # alone loses at the base shape (12.1 against 11.1 us at 80 rows).
 SMALL_M_MAX_ROWS = 128
 SMALL_M_ROWS = 96
+# The many-row route (`forward_ragged(..., rows_route=True)`, taken only when the caller asks: bge's combining queue): the same kernels
+# over up to ROWS_MAX token rows — 16 one-question forwards of at most 128 rows each (cmr_encoder_linear_rows*, CMR_ENCODER_ROWS_MAX).
+ROWS_MAX = L.CMR_ENCODER_ROWS_MAX
 _SPLITS = {}      # (n, k, cmr dtype) -> K slices of the partials form (cmr_encoder_linear_small_split)
 
 
@@ -334,6 +337,39 @@ class FusedBertLayers:
                                                           C.c_void_p(part.data_ptr()), C.c_void_p(stream)))
         return part
 
+    def linear_rows(self, x, w, bias=None, gelu: bool = False, stream: Optional[int] = None):
+        """`linear_small` for 1 .. 2048 token rows (cmr_encoder_linear_rows): every row gets the bits `linear_small` gives it."""
+        import torch
+        m, k = x.shape
+        n = w.shape[0]
+        assert x.is_contiguous() and w.is_contiguous() and w.shape[1] == k, "linear_rows reads row-major [m, k] and [n, k] tensors"
+        out = torch.empty((m, n), dtype=x.dtype, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        L.check(L.lib().cmr_encoder_linear_rows(x.device.index or 0, C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()),
+                                                C.c_void_p(bias.data_ptr() if bias is not None else 0), m, n, k, self.cmr_dtype, 1 if gelu else 0,
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
+    def linear_rows_partials(self, x, w, stream: Optional[int] = None):
+        """`linear_small_partials` for 1 .. 2048 token rows (cmr_encoder_linear_rows_partials): fp32 slabs [n_split, m, n], n_split that of
+        cmr_encoder_linear_small_split for (n, k, dtype) — it does not depend on m, so it is asked with one row."""
+        import torch
+        m, k = x.shape
+        n = w.shape[0]
+        assert x.is_contiguous() and w.is_contiguous() and w.shape[1] == k, "linear_rows_partials reads row-major [m, k] and [n, k] tensors"
+        n_split = _SPLITS.get((n, k, self.cmr_dtype))
+        if n_split is None:
+            ns, nbytes = C.c_int32(0), C.c_int64(0)
+            L.check(L.lib().cmr_encoder_linear_small_split(1, n, k, self.cmr_dtype, C.byref(ns), C.byref(nbytes)))
+            n_split = _SPLITS[(n, k, self.cmr_dtype)] = int(ns.value)
+        part = torch.empty((n_split, m, n), dtype=torch.float32, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        L.check(L.lib().cmr_encoder_linear_rows_partials(x.device.index or 0, C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), m, n, k, self.cmr_dtype,
+                                                         C.c_void_p(part.data_ptr()), C.c_void_p(stream)))
+        return part
+
     def add_layernorm_partials(self, part, bias, residual, gamma, beta, stream: Optional[int] = None):
         """LayerNorm(sum of the slabs + bias + residual) (cmr_encoder_add_layernorm_partials) -> [m, n] of the model's dtype."""
         import torch
@@ -375,16 +411,18 @@ class FusedBertLayers:
         stream = torch.cuda.current_stream(input_ids.device).cuda_stream
         return self._layers(self.embed(input_ids, token_type_ids, stream), lens_dev, b, l, pool, stream)
 
-    def _stack_ragged(self, packed, b: int, l: int, pool):
+    def _stack_ragged(self, packed, b: int, l: int, pool, rows_route: bool = False):
         """The same from ONE int32 tensor lens[b] | offsets[b + 1] | token ids (ragged, back to back)."""
         import torch
         stream = torch.cuda.current_stream(packed.device).cuda_stream
         x = self.embed_ragged(packed[2 * b + 1:], packed[b:2 * b + 1], b, l, stream)
-        return self._layers(x, packed[:b], b, l, pool, stream)
+        return self._layers(x, packed[:b], b, l, pool, stream, rows_route)
 
-    def _layers(self, x, lens_dev, b: int, l: int, pool, stream):
+    def _layers(self, x, lens_dev, b: int, l: int, pool, stream, rows_route: bool = False):
         import torch
         import torch.nn.functional as F
+        if rows_route:                                 # asked for by the caller, never chosen by size: an ordinary mini-batch keeps hipBLASLt
+            return self._layers_rows(x, lens_dev, b, l, pool, stream)
         if 0 < b * l <= self.small_m_rows:
             return self._layers_small_m(x, lens_dev, b, l, pool, stream)
         last = len(self.layers) - 1
@@ -411,6 +449,22 @@ class FusedBertLayers:
             x = self.add_layernorm_partials(self.linear_small_partials(ctx, wo, stream), bo, x, g1, be1, stream)
             h = self.linear_small(x, w1, b1, True, stream)
             part = self.linear_small_partials(h, w2, stream)
+            if n == last and pool is not None:
+                return self.add_layernorm_partials_pool(part, b2, x, g2, be2, lens_dev, b, l, bool(pool), stream)
+            x = self.add_layernorm_partials(part, b2, x, g2, be2, stream)
+        return x.view(b, l, self.hidden)
+
+    def _layers_rows(self, x, lens_dev, b: int, l: int, pool, stream):
+        """The many-row route: `_layers_small_m` with the linear layers' many-row entry points — the same seven launches per layer, the same
+        attention and partials-LayerNorm calls, the pooled last layer.  A sequence of b*l <= 2048 token rows gets, row for row, the bits of its
+        own [1, l] forward on the short-row route: the linear kernels' contract, and every other stage works per sequence or per row."""
+        last = len(self.layers) - 1
+        for n, (wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2) in enumerate(self.layers):
+            qkv = self.linear_rows(x, wqkv, bqkv, False, stream)
+            ctx = self.attention(qkv, lens_dev, b, l, stream)
+            x = self.add_layernorm_partials(self.linear_rows_partials(ctx, wo, stream), bo, x, g1, be1, stream)
+            h = self.linear_rows(x, w1, b1, True, stream)
+            part = self.linear_rows_partials(h, w2, stream)
             if n == last and pool is not None:
                 return self.add_layernorm_partials_pool(part, b2, x, g2, be2, lens_dev, b, l, bool(pool), stream)
             x = self.add_layernorm_partials(part, b2, x, g2, be2, stream)
@@ -469,18 +523,23 @@ class FusedBertLayers:
                 hidden = self._stack(input_ids, lens_src.to(input_ids.device, non_blocking=True), token_type_ids, pool)
                 return hidden if pool is not None else (consume(hidden) if consume is not None else hidden)
 
-    def forward_ragged(self, packed_host: np.ndarray, b: int, l: int, normalize: bool = True):
+    def forward_ragged(self, packed_host: np.ndarray, b: int, l: int, normalize: bool = True, rows_route: bool = False):
         """One mini-batch from the tokenizer's ragged output: packed_host = int32 [lens (b) | offsets (b + 1) | token ids back to
         back], l = the padded width (a multiple of 16, >= the longest sequence).  Returns the pooled rows [b, hidden] fp32
         (masked mean, L2-normalised unless normalize = False).  The host ships ONE pinned array per mini-batch — no padded id /
-        mask / token-type tensors are built on either side of the link; a shape seen before replays its captured hipGraph."""
+        mask / token-type tensors are built on either side of the link; a shape seen before replays its captured hipGraph.
+        rows_route = True (the short-row route must be armed; b*l <= ROWS_MAX): the linear layers run on the many-row small-M kernels
+        (`_layers_rows`) whatever b*l is — several one-question forwards in one, each sequence with the bits of its own [1, l] forward.
+        The route is part of the captured graph's key."""
         import torch
         if l % 16 or not self.can_pool(l):
             raise ValueError("forward_ragged needs a padded width that is a multiple of 16")
+        if rows_route and not (self.small_m_rows > 0 and 0 < b * l <= ROWS_MAX):
+            raise ValueError(f"forward_ragged: rows_route needs the short-row route armed (small_m) and at most {ROWS_MAX} token rows")
         n = int(packed_host.shape[0])
         with torch.no_grad():
             src = torch.from_numpy(packed_host).pin_memory()        # pinned: a pageable source makes the host wait for the stream
-            key = (b, l, "ragged", bool(normalize))
+            key = (b, l, "ragged-rows" if rows_route else "ragged", bool(normalize))
             if self.graphs > 0:
                 with self._glock:
                     ent = self._graphs.get(key)
@@ -490,7 +549,7 @@ class FusedBertLayers:
                         seen = self._seen[key] = self._seen.get(key, 0) + 1
                         if seen >= 2 and self._room_for_a_graph():
                             with _GATE.exclusive():
-                                ent = self._graphs[key] = self._capture_ragged(b, l, bool(normalize))
+                                ent = self._graphs[key] = self._capture_ragged(b, l, bool(normalize), bool(rows_route))
                     if ent is not None:
                         with _GATE.shared():
                             cur = torch.cuda.current_stream(self.device)
@@ -502,9 +561,9 @@ class FusedBertLayers:
                             ent["graph"].replay()
                             return ent["hidden"].clone()
             with _GATE.shared():
-                return self._stack_ragged(src.to(self.device, non_blocking=True), b, l, bool(normalize))
+                return self._stack_ragged(src.to(self.device, non_blocking=True), b, l, bool(normalize), bool(rows_route))
 
-    def _capture_ragged(self, b: int, l: int, normalize: bool):
+    def _capture_ragged(self, b: int, l: int, normalize: bool, rows_route: bool = False):
         import torch
         dev = self.device
         packed = torch.zeros((2 * b + 1 + b * l,), dtype=torch.int32, device=dev)
@@ -515,11 +574,11 @@ class FusedBertLayers:
         side = torch.cuda.Stream(dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            self._stack_ragged(packed, b, l, normalize)
+            self._stack_ragged(packed, b, l, normalize, rows_route)
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=self._capture_stream(), capture_error_mode="thread_local"):
-            ent["hidden"] = self._stack_ragged(packed, b, l, normalize)
+            ent["hidden"] = self._stack_ragged(packed, b, l, normalize, rows_route)
         ent["graph"] = graph
         return ent
 

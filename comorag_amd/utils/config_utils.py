@@ -44,7 +44,9 @@ class BaseConfig:
     embedding_fused_head32: bool = False          # opt-in: 32-wide heads (384 hidden / 12 heads: bge-small, e5-small, MiniLM) run the fused stack too (HD = 32 attention kernels); combinable with embedding_fused_fp32.  Off ONLY because three existing tests pin the default refusal "head width is not 64" (tests/test_encoder_fused_gpu.py, test_store_host.py, test_encoder_fp32_host.py): flip the default together with those tests
     embedding_fused_small_m: bool = False         # opt-in: a mini-batch of at most embedding_small_m_rows token rows (one short query) runs its linear layers on the library's weight-streaming small-M kernels instead of hipBLASLt (16-bit models; fp32 ones ignore it; not armed with embedding_gelu = "epilogue" in effect: the route's GELU is the exact erf form)
     embedding_small_m_rows: int = 96              # token rows b*l up to which that route is taken (at most 128): the measured crossover, profiles/encoder_small_m.json
-    embedding_devices: Optional[list] = None      # GPUs of the corpus-encode replicas (BGEEmbedding.py:77 `device_map="auto"`): one copy of the layer stack each, bucketing windows dealt round them; None = `device` only
+    embedding_combine: int = 0                    # opt-in: W in 2..16 lets concurrent one-prompt encodes (ComoRAG's question threads) share ONE forward of up to W prompts of equal padded width, each caller with the bits of its solo call; needs embedding_fused_small_m (otherwise not armed); 0 = off (`combine_stats()`)
+    embedding_combine_wait_us: int = 0            # that queue's gather window: the first caller waits until W prompts have joined or the window has passed; 0 = batches form only from calls that arrive while an earlier forward runs
+    embedding_devices: Optional[list] = None     # GPUs of the corpus-encode replicas (BGEEmbedding.py:77 `device_map="auto"`): one copy of the layer stack each, bucketing windows dealt round them; None = `device` only
     embedding_encode_replicas: int = 0            # > the device count: logical replicas going round `embedding_devices` (rehearsal on a one-GPU box); 0 = one per device
     embedding_query_cache: int = 256              # single-string batch_encode results kept (by prompt, max_length, normalisation): a question is encoded three times per tri_retrieve — the same prompt each time; 0 = off
     embedding_gelu: str = "exact"                 # fused encoder: "exact" = erf-form GELU kernel (the reference's function); "epilogue" = opt-in: FFN-up bias + GELU inside the hipBLASLt GEMM (TANH form, <= 4.8e-4 per activation away, ~7 % faster forward)

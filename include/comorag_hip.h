@@ -214,7 +214,8 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  * A call with a NaN / Inf query, or with arguments the call refuses, never joins a batch: it gets its own error.
  * Read-only: "combine_batches" (device calls made for combined work), "combine_queries" (queries they served), "combine_max_width".
  * NOT combined: cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
- * cmr_mindex_* (the option has no effect on searches issued through a multi-device handle) and the encoder.                       */
+ * cmr_mindex_* (the option has no effect on searches issued through a multi-device handle).  The encoder is not combined HERE: concurrent
+ * one-question encodes share one forward through the Python-level option `embedding_combine` (cmr_encoder_linear_rows* below).      */
 /* Which path served the last call (read-only): "last_route", written by the host when a search or all-scores call on this index is
  * planned (for a batch of several corpus passes: its first pass); 0 before the first call.  Concurrent callers overwrite each other.
  *   bits 0..3   the path, CMR_ROUTE_*
@@ -572,6 +573,23 @@ int32_t cmr_encoder_add_layernorm_partials_pool(int32_t device_id, const float* 
                                                 const void* residual_dev, const void* gamma_dev, const void* beta_dev, float eps,
                                                 int32_t b, int32_t l, int32_t d, int32_t dtype, const int32_t* lens_dev, int32_t normalize,
                                                 float* pool_partial_dev, float* out_dev, void* stream);
+
+/* ---- encoder: the same linear layers over MANY token rows (several short queries in one forward) ------------------------------
+ * cmr_encoder_linear_rows / cmr_encoder_linear_rows_partials are cmr_encoder_linear_small / _partials for 1 <= m <= CMR_ENCODER_ROWS_MAX
+ * token rows: the concatenated rows of up to 16 one-question forwards (embedding_combine).  Operands, alignment, act and
+ * dtype rules, the checks and their order are those of the block above; only the row limit differs (m > CMR_ENCODER_ROWS_MAX is
+ * CMR_ERR_UNSUPPORTED).  The partials form writes partials_dev [n_split, m, n] with the n_split cmr_encoder_linear_small_split reports
+ * for (n, k, dtype) (ask it with any m <= 128: n_split does not depend on m; the slabs take n_split * m * n floats); the unchanged
+ * cmr_encoder_add_layernorm_partials(_pool) consume them.
+ * CONTRACT: for every row r the output bits are those cmr_encoder_linear_small(_partials) produces for that row in ANY call that contains
+ * it — independent of m, of the row's position and of the other rows.  (The kernel is the same weight stream: m > 128 runs row tiles of
+ * 128 over the grid's third dimension, each tile the sums of the one-query kernel in the same order; later tiles re-read the weights,
+ * which no packed copy is made of.)                                                                                                    */
+#define CMR_ENCODER_ROWS_MAX 2048   /* 16 questions x 128 token rows */
+int32_t cmr_encoder_linear_rows(int32_t device_id, const void* x_dev, const void* w_dev, const void* bias_dev, int32_t m, int32_t n,
+                                int32_t k, int32_t dtype, int32_t act, void* out16_dev, void* stream);
+int32_t cmr_encoder_linear_rows_partials(int32_t device_id, const void* x_dev, const void* w_dev, int32_t m, int32_t n, int32_t k,
+                                         int32_t dtype, float* partials_dev, void* stream);
 
 /* ---- measurement ------------------------------------------------------------------------
  * HIP-event timing of the dominant kernel (the corpus scan) on the stream it is launched on.
