@@ -124,6 +124,8 @@ SIGNATURES = {
     "cmr_encoder_linear_rows_partials": (_i32, [_i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "cmr_encoder_add_layernorm_partials": (_i32, [_i32, _p, _i32, _p, _p, _p, _p, _f32, _i64, _i32, _i32, _p, _p]),
     "cmr_encoder_add_layernorm_partials_pool": (_i32, [_i32, _p, _i32, _p, _p, _p, _p, _f32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
+    "cmr_encoder_attention_cls": (_i32, [_i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "cmr_encoder_cls_head": (_i32, [_i32, _p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p]),
     "cmr_profile_enable": (_i32, [_p, _i32]),
     "cmr_profile_collect": (_i32, [_p, _P(_i64), _P(_f64), _P(_f64)]),
 }

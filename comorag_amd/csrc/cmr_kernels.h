@@ -177,6 +177,11 @@ hipError_t cmr_launch_add_layernorm_partials(const float* part, int n_split, con
                                              long long rows, int d, int dtype, void* out, hipStream_t s);
 hipError_t cmr_launch_add_layernorm_partials_pool(const float* slabs, int n_split, const void* bias, const void* res, const void* gamma, const void* beta, float eps, int b,
                                                   int l, int d, int dtype, const int* lens, int normalize, float* partial, float* out, hipStream_t s);
+// cross-encoder tail: the attention of ONE query row (token 0) per sequence and head, out [b, hidden] (head_dim 64 or 32; bf16 / fp16 / fp32), and the
+// one-logit classification head out[s] = b2 + w2 . tanh(b1 + w1 x[s]) over rows x_stride elements apart (d % 8 == 0, d <= 2048; b1 / b2 may be NULL)
+hipError_t cmr_launch_attention_cls(const void* qkv, int dtype, const int* lens, int b, int L, int n_heads, int head_dim /* 64 or 32 */, void* out, hipStream_t s);
+hipError_t cmr_launch_cls_head(const void* x, long long x_stride, const void* w1, const void* b1, const void* w2, const void* b2, int b, int d, int dtype,
+                               float* out, hipStream_t s);
 // exact top-k of a 16-bit index (cmr_index_search_exact): rows fp32 [n, dim] (device) -> atomicMax of (max ||round(x)||, max ||round(x) - x||)
 // into stats[2] (fp32, device), skipped when *flag (the append's non-finite flag, may be NULL) is set; no-op for fp32 indexes
 hipError_t cmr_launch_round_stats(int dtype, const float* rows, long long n, int dim, const int* flag, float* stats, hipStream_t s);

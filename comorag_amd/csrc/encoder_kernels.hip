@@ -1432,6 +1432,233 @@ hipError_t cmr_launch_add_layernorm_partials(const float* part, int n_split, con
     return launch_add_ln_partials<CMR_DT_F16>(part, n_split, bias, res, gamma, beta, eps, rows, d, out, s);
 }
 
+// ------------------------------------------------------------------------------------------------ cross-encoder tail
+// A cross-encoder's head reads token 0 of every sequence only, so the LAST layer needs its attention for ONE query row per (sequence, head):
+// a memory-bound read of the head's K and V rows with fp32 arithmetic on the VALU (a one-row query has no use for the matrix pipe).
+// attn_cls_kernel: one workgroup of CLS_WAVES waves per (sequence, head).  Wave w takes the 64-key chunks w, w + CLS_WAVES, ...; in a chunk a
+// lane owns a key for q.k (16-byte loads of its K row), then the lanes regroup — NSEG lanes per V row, one 16-byte segment each, 64 / NSEG rows per
+// pass — and pick their key's weight up by a lane shuffle.  Every wave keeps a running (max, sum, o[HD]) of its chunks; the waves' partials
+// meet in LDS and are combined in wave order.  Keys >= len are neither read nor weighted.
+// Measured at b = 100, l = 512 (profiles/rerank.json): 31 us (12 heads, bf16), 45 us (12 heads, f16), 49 / 72 us (16 heads), against 140 - 195 us
+// of the all-rows kernel; f16 pays its conversions (v_cvt per element, where bf16 is a shift).
+#define CLS_WAVES 4
+template <int DT> __device__ __forceinline__ void cls_load(const void* p, float (&t)[DT == CMR_DT_F32 ? 4 : 8]) {      // one 16-byte segment, widened
+    if constexpr (DT == CMR_DT_F32) {
+        const float4 a = *reinterpret_cast<const float4*>(p);
+        t[0] = a.x; t[1] = a.y; t[2] = a.z; t[3] = a.w;
+    } else {
+        enc_get8<DT>(t, *reinterpret_cast<const uint4*>(p));
+    }
+}
+template <int DT> __device__ __forceinline__ float cls_elem(const void* p, int i) {
+    if constexpr (DT == CMR_DT_F32) {
+        return reinterpret_cast<const float*>(p)[i];
+    } else {
+        float a, b;
+        enc_unpack2<DT>((unsigned)reinterpret_cast<const unsigned short*>(p)[i], a, b);
+        return a;
+    }
+}
+
+template <int DT, int HD>
+__global__ __launch_bounds__(CLS_WAVES * 64) void attn_cls_kernel(const void* __restrict__ qkv, const int* __restrict__ lens, int L, int hidden, int n_heads,
+                                                                  float sc /* log2(e) / sqrt(HD) */, void* __restrict__ out) {
+    constexpr int ES = DT == CMR_DT_F32 ? 4 : 2, SEG = 16 / ES, NSEG = HD / SEG, KPP = 64 / NSEG;       // element bytes; elements, segments of a row; V rows per pass
+    __shared__ __attribute__((aligned(16))) float q_lds[HD];
+    __shared__ float o_lds[CLS_WAVES][HD];
+    __shared__ float m_lds[CLS_WAVES], l_lds[CLS_WAVES];
+    const int seq = (int)blockIdx.x / n_heads, head = (int)blockIdx.x % n_heads;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int len = lens[seq];
+    len = len < L ? len : L;
+    len = len > 1 ? len : 1;                               // (the contract says lens >= 1: token 0 is always read)
+    const size_t rs = (size_t)3 * hidden * ES;             // bytes between token rows
+    const char* qrow = reinterpret_cast<const char*>(qkv) + (size_t)seq * L * rs + (size_t)head * HD * ES;
+    const char* kbase = qrow + (size_t)hidden * ES;
+    const char* vbase = qrow + 2 * (size_t)hidden * ES;
+    if (tid < NSEG) {
+        float t[SEG];
+        cls_load<DT>(qrow + tid * 16, t);
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) q_lds[tid * SEG + i] = t[i];
+    }
+    __syncthreads();
+
+    const int sg = lane % NSEG, kg = lane / NSEG;
+    float o[SEG];
+#pragma unroll
+    for (int i = 0; i < SEG; ++i) o[i] = 0.0f;
+    float m = ATT_NEG, lsum = 0.0f;
+    for (int k0 = wave * 64; k0 < len; k0 += CLS_WAVES * 64) {         // (wave-uniform bounds: every lane of the wave runs the shuffles)
+        const int key = k0 + lane;
+        float s = ATT_NEG;
+        if (key < len) {
+            const char* kr = kbase + (size_t)key * rs;
+            float acc = 0.0f;
+#pragma unroll
+            for (int g = 0; g < NSEG; ++g) {
+                float t[SEG];
+                cls_load<DT>(kr + g * 16, t);
+                float a = 0.0f;
+#pragma unroll
+                for (int i = 0; i < SEG; ++i) a = fmaf(t[i], q_lds[g * SEG + i], a);
+                acc += a;
+            }
+            s = acc;
+        }
+        float cm = s;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cm = fmaxf(cm, __shfl_xor(cm, off));
+        const float mn = fmaxf(m, cm);
+        const float alpha = __builtin_amdgcn_exp2f((m - mn) * sc);
+        const float p = key < len ? __builtin_amdgcn_exp2f((s - mn) * sc) : 0.0f;
+        lsum = fmaf(lsum, alpha, p);
+        m = mn;
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) o[i] *= alpha;
+#pragma unroll
+        for (int ps = 0; ps < NSEG; ++ps) {                // 64 keys = NSEG passes of KPP rows
+            const int kk = ps * KPP + kg;
+            const float pk = __shfl(p, kk);
+            if (k0 + kk < len) {
+                float t[SEG];
+                cls_load<DT>(vbase + (size_t)(k0 + kk) * rs + sg * 16, t);
+#pragma unroll
+                for (int i = 0; i < SEG; ++i) o[i] = fmaf(pk, t[i], o[i]);
+            }
+        }
+    }
+    // the wave's partial: o summed over the lanes of a segment, the weights over all lanes
+#pragma unroll
+    for (int off = NSEG; off < 64; off <<= 1)
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) o[i] += __shfl_xor(o[i], off);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off);
+    if (kg == 0) {
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) o_lds[wave][sg * SEG + i] = o[i];
+    }
+    if (lane == 0) {
+        m_lds[wave] = m;
+        l_lds[wave] = lsum;
+    }
+    __syncthreads();
+    if (tid < HD / 2) {                                    // two output elements per thread, the waves in wave order
+        float mx = m_lds[0];
+#pragma unroll
+        for (int w = 1; w < CLS_WAVES; ++w) mx = fmaxf(mx, m_lds[w]);
+        float a0 = 0.0f, a1 = 0.0f, lt = 0.0f;
+#pragma unroll
+        for (int w = 0; w < CLS_WAVES; ++w) {
+            const float f = __builtin_amdgcn_exp2f((m_lds[w] - mx) * sc);     // a wave without keys: exp2(-huge) = 0 times its zeros
+            lt = fmaf(l_lds[w], f, lt);
+            a0 = fmaf(o_lds[w][2 * tid], f, a0);
+            a1 = fmaf(o_lds[w][2 * tid + 1], f, a1);
+        }
+        const float inv = 1.0f / lt;
+        char* orow = reinterpret_cast<char*>(out) + ((size_t)seq * hidden + (size_t)head * HD) * ES;
+        if constexpr (DT == CMR_DT_F32) reinterpret_cast<float2*>(orow)[tid] = make_float2(a0 * inv, a1 * inv);
+        else reinterpret_cast<unsigned*>(orow)[tid] = enc_pack2<DT>(a0 * inv, a1 * inv);
+    }
+}
+
+template <int DT, int HD>
+static hipError_t launch_attention_cls(const void* qkv, const int* lens, int b, int L, int n_heads, void* out, hipStream_t s) {
+    if ((long long)b * n_heads > (1LL << 30)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn_cls_kernel<DT, HD>), dim3((unsigned)(b * n_heads)), dim3(CLS_WAVES * 64), 0, s, qkv, lens, L, n_heads * HD, n_heads, att_scale<HD>(), out);
+    return hipGetLastError();
+}
+
+hipError_t cmr_launch_attention_cls(const void* qkv, int dtype, const int* lens, int b, int L, int n_heads, int head_dim, void* out, hipStream_t s) {
+    if (head_dim != 64 && head_dim != 32) return hipErrorInvalidValue;
+#define ENC_CLS(T) (head_dim == 64 ? launch_attention_cls<T, 64>(qkv, lens, b, L, n_heads, out, s) : launch_attention_cls<T, 32>(qkv, lens, b, L, n_heads, out, s))
+    if (dtype == CMR_DT_F32) return ENC_CLS(CMR_DT_F32);
+    if (dtype == CMR_DT_BF16) return ENC_CLS(CMR_DT_BF16);
+    return ENC_CLS(CMR_DT_F16);
+#undef ENC_CLS
+}
+
+// cls_head_kernel: out[s] = b2 + sum_j w2[j] tanh(b1[j] + w1[j, :] . x[s]) — one workgroup per sequence; its x row sits in LDS as fp32.  A group
+// of HEAD_LPR lanes owns a row of w1 (16-byte loads, 256 contiguous bytes per group and instruction; the b workgroups read w1 out of L2): the
+// workgroup's 32 groups take rows 32 apart, HEAD_U of them at a time, reduce each dot product over the group's lanes and add w2[j] tanhf(.) to the
+// group's running sum in j order.  The 32 sums are added in group order: a row's bits depend on (d, dtype) alone.
+// Measured at b = 100 (tools/rerank_bench.py, profiles/rerank.json): 34 - 36 us at d = 768, 53 - 58 us at d = 1024.  The first form — a whole wave
+// per row, four rows at a time, 32 dependent load-and-reduce rounds per wave at d = 1024 — took 65 - 67 and 85 - 88 us.  A weight-streaming form
+// over all b rows (w1 read once, as the small-M linear kernels do) was not tried: four head launches are about 1 % of a 100-pair call at the base shape and less at the large one.
+#define HEAD_WAVES 8
+#define HEAD_LPR 16
+#define HEAD_U 2
+#define HEAD_MAXD 2048
+template <int DT>
+__global__ __launch_bounds__(HEAD_WAVES * 64) void cls_head_kernel(const void* __restrict__ x, long long x_stride, const void* __restrict__ w1, const void* __restrict__ b1,
+                                                                   const void* __restrict__ w2, const void* __restrict__ b2, int d, float* __restrict__ out) {
+    constexpr int ES = DT == CMR_DT_F32 ? 4 : 2, SEG = 16 / ES;
+    constexpr int GROUPS = 64 / HEAD_LPR, SLOTS = HEAD_WAVES * GROUPS;        // lane groups of a wave; weight rows in flight per workgroup and unroll step
+    __shared__ __attribute__((aligned(16))) float x_lds[HEAD_MAXD];
+    __shared__ float part[SLOTS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nvec = d / SEG;
+    const char* xrow = reinterpret_cast<const char*>(x) + (size_t)blockIdx.x * (size_t)x_stride * ES;
+    for (int v = tid; v < nvec; v += HEAD_WAVES * 64) {
+        float t[SEG];
+        cls_load<DT>(xrow + (size_t)v * 16, t);
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) x_lds[v * SEG + i] = t[i];
+    }
+    __syncthreads();
+    const size_t wrow = (size_t)d * ES;
+    const int grp = lane / HEAD_LPR, sub = lane % HEAD_LPR;
+    float acc = 0.0f;
+    for (int jb = wave * GROUPS; jb < d; jb += SLOTS * HEAD_U) {       // wave-uniform bounds: every lane runs the shuffles
+        float dot[HEAD_U];
+#pragma unroll
+        for (int r = 0; r < HEAD_U; ++r) dot[r] = 0.0f;
+#pragma unroll 4
+        for (int v = sub; v < nvec; v += HEAD_LPR) {
+            float xv[SEG];
+#pragma unroll
+            for (int i = 0; i < SEG; ++i) xv[i] = x_lds[v * SEG + i];
+#pragma unroll
+            for (int r = 0; r < HEAD_U; ++r) {
+                const int j = jb + grp + SLOTS * r;
+                if (j < d) {
+                    float t[SEG];
+                    cls_load<DT>(reinterpret_cast<const char*>(w1) + (size_t)j * wrow + (size_t)v * 16, t);
+#pragma unroll
+                    for (int i = 0; i < SEG; ++i) dot[r] = fmaf(t[i], xv[i], dot[r]);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < HEAD_U; ++r) {
+#pragma unroll
+            for (int off = HEAD_LPR / 2; off > 0; off >>= 1) dot[r] += __shfl_xor(dot[r], off);
+            const int j = jb + grp + SLOTS * r;
+            if (j < d) acc = fmaf(cls_elem<DT>(w2, j), tanhf(dot[r] + (b1 ? cls_elem<DT>(b1, j) : 0.0f)), acc);
+        }
+    }
+    if (sub == 0) part[wave * GROUPS + grp] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        float t = b2 ? cls_elem<DT>(b2, 0) : 0.0f;
+#pragma unroll
+        for (int w = 0; w < SLOTS; ++w) t += part[w];
+        out[blockIdx.x] = t;
+    }
+}
+
+hipError_t cmr_launch_cls_head(const void* x, long long x_stride, const void* w1, const void* b1, const void* w2, const void* b2, int b, int d, int dtype,
+                               float* out, hipStream_t s) {
+    if (d <= 0 || d % 8 || d > HEAD_MAXD) return hipErrorInvalidValue;
+#define ENC_HEAD(T) hipLaunchKernelGGL(cls_head_kernel<T>, dim3((unsigned)b), dim3(HEAD_WAVES * 64), 0, s, x, x_stride, w1, b1, w2, b2, d, out)
+    if (dtype == CMR_DT_F32) ENC_HEAD(CMR_DT_F32);
+    else if (dtype == CMR_DT_BF16) ENC_HEAD(CMR_DT_BF16);
+    else ENC_HEAD(CMR_DT_F16);
+#undef ENC_HEAD
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ C-ABI (include/comorag_hip.h)
 // argument checks of the encoder entry points; each ends in one launcher call above
 extern "C" {
@@ -1448,6 +1675,39 @@ int32_t cmr_encoder_attention(int32_t device_id, const void* qkv_dev, int32_t dt
     rc = cmr_set_device(device_id);
     if (rc) return rc;
     HIP_TRY(cmr_launch_attention(qkv_dev, dtype, lens_dev, b, l, n_heads, head_dim, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_attention_cls(int32_t device_id, const void* qkv_dev, int32_t dtype, const int32_t* lens_dev, int32_t b, int32_t l,
+                                  int32_t n_heads, int32_t head_dim, void* out_dev, void* stream) {
+    if (!qkv_dev || !lens_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (b <= 0 || l <= 0 || n_heads <= 0) return cmr_fail(CMR_ERR_INVALID, "b, l, n_heads must be > 0");
+    if (head_dim != 64 && head_dim != 32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention_cls: head_dim must be 64 or 32");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention_cls: dtype must be bf16 or f16 or f32");
+    if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & 15) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_attention_cls: buffers must be 16-byte aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_attention_cls(qkv_dev, dtype, lens_dev, b, l, n_heads, head_dim, out_dev, (hipStream_t)stream));
+    return CMR_OK;
+}
+
+int32_t cmr_encoder_cls_head(int32_t device_id, const void* x_dev, int64_t x_stride, const void* w1_dev, const void* b1_dev, const void* w2_dev,
+                             const void* b2_dev, int32_t b, int32_t d, int32_t dtype, float* out_dev, void* stream) {
+    if (!x_dev || !w1_dev || !w2_dev || !out_dev) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (b <= 0 || d <= 0 || x_stride < d) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_cls_head: b, d must be > 0 and x_stride >= d");
+    if (dtype != CMR_BF16 && dtype != CMR_F16 && dtype != CMR_F32) return cmr_fail(CMR_ERR_INVALID, "cmr_encoder_cls_head: dtype must be bf16 or f16 or f32");
+    if (d % 8 || d > HEAD_MAXD) return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_cls_head: d must be a multiple of 8 and <= 2048");
+    const int es = dtype == CMR_F32 ? 4 : 2;
+    if ((((uintptr_t)x_dev | (uintptr_t)w1_dev) & 15) || (x_stride * es) % 16 || (((uintptr_t)b1_dev | (uintptr_t)w2_dev | (uintptr_t)b2_dev) & (es - 1)) ||
+        ((uintptr_t)out_dev & 3))
+        return cmr_fail(CMR_ERR_UNSUPPORTED, "cmr_encoder_cls_head: x and w1 rows must be 16-byte aligned, the vectors element-aligned");
+    int rc = cmr_check_device(device_id);
+    if (rc) return rc;
+    rc = cmr_set_device(device_id);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_cls_head(x_dev, (long long)x_stride, w1_dev, b1_dev, w2_dev, b2_dev, b, d, dtype, out_dev, (hipStream_t)stream));
     return CMR_OK;
 }
 

@@ -19,6 +19,9 @@ three times): tests/test_encoder_fused_gpu.py compares both with the fp32 oracle
 
 Used when `why_not(model)` is None: BERT / RoBERTa / XLM-R architecture (bge-base / -large, bge-m3), absolute positions, exact GELU,
 64-wide heads (32-wide with `head32=True`), bf16 / fp16 weights (fp32 with `fp32=True`); any other model keeps the transformers forward (`HipBGEEmbeddingModel.encoder_path` says which one runs).
+
+`forward_cls` is the same stack ending in a one-logit classification head instead of the pooling tail (cross-encoder rerankers, rerank.py):
+cmr_encoder_cls_head over the CLS rows, and optionally the last layer for those rows alone (cmr_encoder_attention_cls).
 """
 from __future__ import annotations
 
@@ -396,6 +399,76 @@ class FusedBertLayers:
                                                                 1 if normalize else 0, C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
+    def attention_cls(self, qkv, lens_dev, b: int, l: int, stream: Optional[int] = None):
+        """The attention of token 0 of every sequence alone (cmr_encoder_attention_cls): [b, hidden] of qkv's dtype."""
+        import torch
+        out = torch.empty((b, self.hidden), dtype=qkv.dtype, device=qkv.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(qkv.device).cuda_stream
+        L.check(L.lib().cmr_encoder_attention_cls(qkv.device.index or 0, C.c_void_p(qkv.data_ptr()), self.cmr_dtype, C.c_void_p(lens_dev.data_ptr()),
+                                                  b, l, self.n_heads, self.hidden // self.n_heads, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
+    def cls_head(self, x, x_stride: int, head, b: int, stream: Optional[int] = None):
+        """One logit per sequence (cmr_encoder_cls_head): head = (w1 [d, d], b1 [d] | None, w2 [d], b2 [1] | None) of the model's dtype, x the
+        b rows of d elements that sit x_stride elements apart -> [b] fp32."""
+        import torch
+        w1, b1, w2, b2 = head
+        out = torch.empty((b,), dtype=torch.float32, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        L.check(L.lib().cmr_encoder_cls_head(x.device.index or 0, C.c_void_p(x.data_ptr()), int(x_stride), C.c_void_p(w1.data_ptr()),
+                                             C.c_void_p(b1.data_ptr() if b1 is not None else 0), C.c_void_p(w2.data_ptr()),
+                                             C.c_void_p(b2.data_ptr() if b2 is not None else 0), b, w1.shape[0], self.cmr_dtype,
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out
+
+    def _cls_tail(self, x, lens_dev, b: int, l: int, head, stream):
+        """The LAST layer of a forward that ends in a classification head, x [b*l, hidden] the layer's input: the packed projection over
+        every token row (the keys and values), then attention, O-projection + LayerNorm, FFN and LayerNorm for the b CLS rows alone, then the
+        head.  The b-row linear layers take the route `_layers` picks for a mini-batch of b token rows."""
+        import torch
+        import torch.nn.functional as F
+        wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2 = self.layers[-1]
+        qkv = self.linear_small(x, wqkv, bqkv, False, stream) if 0 < b * l <= self.small_m_rows else F.linear(x, wqkv, bqkv)
+        ctx = self.attention_cls(qkv, lens_dev, b, l, stream)
+        res = x.view(b, l, self.hidden)[:, 0].contiguous()                # the residual rows: token 0 of the layer's input
+        if 0 < b <= self.small_m_rows:
+            y = self.add_layernorm_partials(self.linear_small_partials(ctx, wo, stream), bo, res, g1, be1, stream)
+            h = self.linear_small(y, w1, b1, True, stream)
+            y = self.add_layernorm_partials(self.linear_small_partials(h, w2, stream), b2, y, g2, be2, stream)
+        else:
+            y = self.add_layernorm(F.linear(ctx, wo), bo, res, g1, be1, stream)
+            if self.gelu_path == "hipblaslt-epilogue-tanh":
+                h = torch._addmm_activation(b1, y, w1.t(), use_gelu=True)
+            else:
+                h = F.gelu(F.linear(y, w1, b1))
+            y = self.add_layernorm(F.linear(h, w2), b2, y, g2, be2, stream)
+        return self.cls_head(y, self.hidden, head, b, stream)
+
+    def forward_cls(self, input_ids, lens, token_type_ids=None, head=None, cls_tail: bool = True):
+        """A cross-encoder's forward: input_ids [b, l] int64 on the GPU (right-padded pairs), lens[b] real token counts (host array or int32
+        GPU tensor), token_type_ids [b, l] or None, head = the classification head's tensors (`cls_head`) -> [b] fp32 logits.
+        cls_tail = True: layers 0 .. n-2 run as in `__call__`, the last one for the b CLS rows alone (`_cls_tail`); False: the unchanged
+        stack writes the whole last hidden state and the head reads its CLS rows in place.  Launched eagerly (no captured graphs)."""
+        import torch
+        if head is None:
+            raise ValueError("forward_cls needs the classification head's tensors")
+        b, l = input_ids.shape
+        with torch.no_grad():
+            if isinstance(lens, torch.Tensor) and lens.is_cuda:
+                lens_dev = lens.to(torch.int32)
+            else:
+                lens_dev = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).pin_memory().to(input_ids.device, non_blocking=True)
+            with _GATE.shared():
+                stream = torch.cuda.current_stream(input_ids.device).cuda_stream
+                x = self.embed(input_ids, token_type_ids, stream)
+                if not cls_tail:
+                    x = self._layers(x, lens_dev, b, l, None, stream)
+                    return self.cls_head(x, l * self.hidden, head, b, stream)
+                x = self._layers(x, lens_dev, b, l, None, stream, layers=self.layers[:-1])
+                return self._cls_tail(x.reshape(b * l, self.hidden), lens_dev, b, l, head, stream)
+
     def can_pool(self, l: int) -> bool:
         """Can the encoder tail be folded into the last layer's LayerNorm for mini-batches of l (padded) tokens?"""
         return self.fold_pool and l % 16 == 0 and self.hidden % 8 == 0
@@ -418,15 +491,17 @@ class FusedBertLayers:
         x = self.embed_ragged(packed[2 * b + 1:], packed[b:2 * b + 1], b, l, stream)
         return self._layers(x, packed[:b], b, l, pool, stream, rows_route)
 
-    def _layers(self, x, lens_dev, b: int, l: int, pool, stream, rows_route: bool = False):
+    def _layers(self, x, lens_dev, b: int, l: int, pool, stream, rows_route: bool = False, layers=None):
+        """layers = None: the whole stack; a prefix of `self.layers` (forward_cls: every layer but the last) runs those alone."""
         import torch
         import torch.nn.functional as F
         if rows_route:                                 # asked for by the caller, never chosen by size: an ordinary mini-batch keeps hipBLASLt
             return self._layers_rows(x, lens_dev, b, l, pool, stream)
         if 0 < b * l <= self.small_m_rows:
-            return self._layers_small_m(x, lens_dev, b, l, pool, stream)
-        last = len(self.layers) - 1
-        for n, (wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2) in enumerate(self.layers):
+            return self._layers_small_m(x, lens_dev, b, l, pool, stream) if layers is None else self._layers_small_m(x, lens_dev, b, l, pool, stream, layers=layers)
+        layers = self.layers if layers is None else layers
+        last = len(layers) - 1
+        for n, (wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2) in enumerate(layers):
             qkv = F.linear(x, wqkv, bqkv)
             ctx = self.attention(qkv, lens_dev, b, l, stream)
             x = self.add_layernorm(F.linear(ctx, wo), bo, x, g1, be1, stream)
@@ -439,11 +514,12 @@ class FusedBertLayers:
             x = self.add_layernorm(F.linear(h, w2), b2, x, g2, be2, stream)
         return x.view(b, l, self.hidden)
 
-    def _layers_small_m(self, x, lens_dev, b: int, l: int, pool, stream):
+    def _layers_small_m(self, x, lens_dev, b: int, l: int, pool, stream, layers=None):
         """The short-row route: seven launches per layer, none of them a PyTorch GEMM or GELU kernel.  The two K-split projections hand
         fp32 slabs to the LayerNorm launch that follows them; nothing waits inside a launch.  The GELU is the exact erf form."""
-        last = len(self.layers) - 1
-        for n, (wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2) in enumerate(self.layers):
+        layers = self.layers if layers is None else layers
+        last = len(layers) - 1
+        for n, (wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2) in enumerate(layers):
             qkv = self.linear_small(x, wqkv, bqkv, False, stream)
             ctx = self.attention(qkv, lens_dev, b, l, stream)
             x = self.add_layernorm_partials(self.linear_small_partials(ctx, wo, stream), bo, x, g1, be1, stream)

@@ -49,6 +49,13 @@ class BaseConfig:
     embedding_devices: Optional[list] = None     # GPUs of the corpus-encode replicas (BGEEmbedding.py:77 `device_map="auto"`): one copy of the layer stack each, bucketing windows dealt round them; None = `device` only
     embedding_encode_replicas: int = 0            # > the device count: logical replicas going round `embedding_devices` (rehearsal on a one-GPU box); 0 = one per device
     embedding_query_cache: int = 256              # single-string batch_encode results kept (by prompt, max_length, normalisation): a question is encoded three times per tri_retrieve — the same prompt each time; 0 = off
+    # cross-encoder reranker (rerank.CrossEncoderReranker); inert unless one is constructed.  It also reads embedding_fused_fp32, embedding_fused_head32,
+    # embedding_fused_small_m, embedding_small_m_rows, embedding_gelu and embedding_length_bucketing with the meaning they have above
+    rerank_model_name: Optional[str] = None       # a one-logit sequence classifier (bge-reranker-base / -large / -v2-m3): AutoModelForSequenceClassification.from_pretrained
+    rerank_model_dtype: str = "bf16"              # "bf16" | "f16"; anything else keeps the checkpoint's dtype (fp32 runs fused with embedding_fused_fp32)
+    rerank_batch_size: int = 32                   # pairs per forward mini-batch
+    rerank_max_seq_len: int = 512                 # pair truncation, clamped to the model's positions
+    rerank_cls_tail: bool = False                 # True: the last layer runs for the CLS rows alone (cmr_encoder_attention_cls); off by measurement: 0.95 - 0.97 x the whole stack at 512 tokens, a tie by the rule at large bf16 (profiles/rerank.json)
     embedding_gelu: str = "exact"                 # fused encoder: "exact" = erf-form GELU kernel (the reference's function); "epilogue" = opt-in: FFN-up bias + GELU inside the hipBLASLt GEMM (TANH form, <= 4.8e-4 per activation away, ~7 % faster forward)
 
 

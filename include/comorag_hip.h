@@ -591,6 +591,27 @@ int32_t cmr_encoder_linear_rows(int32_t device_id, const void* x_dev, const void
 int32_t cmr_encoder_linear_rows_partials(int32_t device_id, const void* x_dev, const void* w_dev, int32_t m, int32_t n, int32_t k,
                                          int32_t dtype, float* partials_dev, void* stream);
 
+/* ---- encoder: the tail of a CROSS-ENCODER (bge-reranker-*: an XLM-R / BERT encoder with a one-logit classification head) ------
+ * Only token 0 of every sequence feeds the head, so the last layer needs every stage behind its K / V projection for b rows, not b*l.
+ *
+ * out[s, h*head_dim ..] = softmax(q K^T / sqrt(head_dim), keys >= lens[s] masked) V for the ONE query row q = token 0 of
+ * sequence s, per head; qkv_dev is the packed projection [b*l, 3*hidden] of cmr_encoder_attention (same column groups),
+ * lens_dev[b] int32 >= 1, out_dev [b, hidden] of `dtype` (CMR_BF16 / CMR_F16: fp32 arithmetic, rounded once on the store;
+ * CMR_F32: nothing rounded).  head_dim 64 or 32.  Rows >= lens[s] of qkv are never read.  A sequence's result does not depend on the
+ * other sequences or heads of the call.  NULL, b / l / n_heads <= 0, another head_dim or dtype and buffers that are not 16-byte aligned are
+ * CMR_ERR_INVALID, checked before any device call (as cmr_encoder_attention).                                                    */
+int32_t cmr_encoder_attention_cls(int32_t device_id, const void* qkv_dev, int32_t dtype, const int32_t* lens_dev,
+                                  int32_t b, int32_t l, int32_t n_heads, int32_t head_dim, void* out_dev, void* stream);
+/* out[s] = b2 + sum_j w2[j] * tanh(b1[j] + sum_i w1[j, i] * x[s*x_stride + i]),  s < b:  RobertaClassificationHead
+ * (dense -> tanh -> out_proj, one label) and BertPooler + classifier are this same map.  w1 [d, d] row-major (nn.Linear's own
+ * tensor), b1 [d] or NULL, w2 [d], b2 [1] or NULL, x rows x_stride elements apart (x_stride >= d: the CLS rows of a
+ * [b*l, d] hidden state are read in place with x_stride = l*d).  All of `dtype`; fp32 arithmetic, tanhf, out_dev [b] fp32.
+ * d % 8 == 0, d <= 2048, 16-byte aligned rows: CMR_ERR_UNSUPPORTED otherwise.  NULL x / w1 / w2 / out, b or d <= 0, x_stride < d and an
+ * unknown dtype are CMR_ERR_INVALID; all of it is checked before any device call.  No atomics: partial sums meet in a fixed order, and a
+ * row's bits do not depend on b or on the other rows.                                                                             */
+int32_t cmr_encoder_cls_head(int32_t device_id, const void* x_dev, int64_t x_stride, const void* w1_dev, const void* b1_dev,
+                             const void* w2_dev, const void* b2_dev, int32_t b, int32_t d, int32_t dtype, float* out_dev, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------
  * HIP-event timing of the dominant kernel (the corpus scan) on the stream it is launched on.
  * enable → run searches → collect returns launches, summed kernel ms and the algorithmic bytes
