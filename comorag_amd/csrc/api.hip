@@ -274,8 +274,9 @@ struct PassStreams {
 
 // One pass (<= 64 queries, or one wide / query-split pass) of the fused search, as plan_pass shaped it (search_plan.h): this
 // function only allocates, launches, records and waits.
+// row_mask: the allow words of a filtered pass (p.masked; device, one word per panel) — its sampling levels and its main scan are the masked variant
 int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const PassPlan& p, const float* q_dev, const float* min_score,
-                 int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev) {
+                 int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, const unsigned* row_mask = nullptr) {
     hipStream_t const sp = st.sp, sm = st.sm, sq = st.sq;
     const CmrScanGeom& g = p.g;
     const int nqp = p.nqp, k = p.k, G = p.G;
@@ -301,6 +302,10 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
     a.corpus = idx->corpus; a.qfrag = ws->qfrag.p; a.nrows = idx->n; a.npanels = (int)idx->npanels(); a.k = k;
     a.nq = nqp;
     a.qgroups = G;
+    if (p.masked) {
+        if (!row_mask) return fail(CMR_ERR_INVALID, "filtered pass without allow words");
+        a.row_mask = row_mask;
+    }
     if (min_score) {
         // key > tau  <=>  score >= *min_score: tau = (smallest key with that score) - 1
         HIP_TRY(cmr_launch_fill_threshold(*min_score, p.NQA, (u64*)ws->tau.p, sp));
@@ -319,7 +324,7 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
             a.tau_init = tau_out;
             continue;
         }
-        HIP_TRY(p.wide ? cmr_launch_scan_wide(gs, as, sp) : cmr_launch_scan_topk(gs, as, sp));
+        HIP_TRY(p.wide ? cmr_launch_scan_wide(gs, as, sp) : p.masked ? cmr_launch_scan_masked(gs, as, sp) : cmr_launch_scan_topk(gs, as, sp));
         if (p.tau_in_scan) {      // the main scan's workgroups derive the thresholds from these lists themselves
             a.sample_lists = (const u64*)ws->s_lists.p; a.sample_cnt = (const int*)ws->s_cnt.p; a.sample_W = L.Wl;
             a.tau_init = nullptr;
@@ -368,7 +373,7 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
         if (ws->done_ptr && idx->single_block()) a.fin_done = ws->done_ptr;
     }
     if (p.prefilter) { if ((rc = q8_filter(idx, f, a, sm))) return rc; }
-    else HIP_TRY(p.wide ? cmr_launch_scan_wide(g, a, sm) : p.fin ? cmr_launch_scan_fin(g, a, sm) : cmr_launch_scan_topk(g, a, sm));
+    else HIP_TRY(p.wide ? cmr_launch_scan_wide(g, a, sm) : p.fin ? cmr_launch_scan_fin(g, a, sm) : p.masked ? cmr_launch_scan_masked(g, a, sm) : cmr_launch_scan_topk(g, a, sm));
     if (prof) {
         HIP_TRY(hipEventRecord(pe.b, sm));
         std::lock_guard<std::mutex> pg(idx->prof_mu);
@@ -431,6 +436,28 @@ int search_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, in
     const PassStreams st = PassStreams::one(ws->stream);
     for (PassSplit ps(idx, nq); ps.next();) {
         int rc = plan_and_enqueue_pass(idx, ws, st, ps, k, 0, q_dev, min_score, ids_dev, scores_dev, min_dev, max_dev);
+        if (rc) return rc;
+    }
+    return CMR_OK;
+}
+
+// Filtered search (cmr_index_search_masked*): the best k among the local rows whose bit is set in allow_dev (one word per
+// 32-row panel, on the device).  Narrow passes of the pack / [sample] / scan / merge chain on the masked scan variant, all on
+// ws->stream; one mask serves every query.  k <= CMR_MAX_K (checked by the caller).
+int search_masked_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, int k, const unsigned* allow_dev, int64_t* ids_dev,
+                          float* scores_dev, float* min_dev, float* max_dev) {
+    const PassStreams st = PassStreams::one(ws->stream);
+    const int per_pass = idx->narrow_width(nq);
+    for (int q0 = 0; q0 < nq; q0 += per_pass) {
+        const int nqp = std::min(per_pass, nq - q0);
+        PassPlan plan;
+        PassRequest rq = st.request(nqp, k, Route::narrow, false, 0);
+        rq.masked = true;
+        int rc = plan_pass(idx, rq, &plan);
+        if (rc) return rc;
+        if (q0 == 0) idx->last_route.store(route_code(plan, false) | (nqp < nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
+        rc = enqueue_pass(idx, ws, st, plan, q_dev + (size_t)q0 * idx->dim, nullptr, ids_dev + (size_t)q0 * k, scores_dev + (size_t)q0 * k,
+                          min_dev ? min_dev + q0 : nullptr, max_dev ? max_dev + q0 : nullptr, allow_dev);
         if (rc) return rc;
     }
     return CMR_OK;
@@ -925,6 +952,84 @@ int32_t cmr_index_search_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, i
     Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
     if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
     return search_enqueue(idx, ws, q_dev, nq, k, ids_dev, scores_dev, min_dev, max_dev);
+}
+
+// ---- filtered search (include/comorag_hip.h: cmr_index_search_masked*).  Never combined, never pre-filtered: the
+// calls go straight to search_masked_enqueue.
+static int masked_check(const cmr_index* idx, int nq, int k, int64_t n_words) {      // (under the index lock; no device call)
+    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
+    if (k <= 0) return fail(CMR_ERR_INVALID, "k must be > 0");
+    if (n_words != panels_of(idx->n)) return fail(CMR_ERR_INVALID, "n_words %lld != ceil(%lld rows / 32) = %lld", (long long)n_words, idx->n, panels_of(idx->n));
+    if (k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "filtered search supports k <= %d", CMR_MAX_K);
+    return CMR_OK;
+}
+
+int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words,
+                                    int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
+    if (!idx || !q_dev || !allow_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    int rc = masked_check(idx, nq, k, n_words);
+    if (rc) return rc;
+    rc = cmr_set_device(idx->device);
+    if (rc) return rc;
+    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
+    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
+    return search_masked_enqueue(idx, ws, q_dev, nq, k, allow_dev, ids_dev, scores_dev, min_dev, max_dev);
+}
+
+int32_t cmr_index_search_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words,
+                                int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+    if (!idx || !q || !allow || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
+    SyncCall call(idx);
+    int rc = masked_check(idx, nq, k, n_words);
+    if (rc) return rc;
+    rc = call.open();
+    if (rc) return rc;
+    Workspace* const ws = call.ws;
+    hipStream_t const s = call.s;
+    // packed device buffer [flag (8 B) | ids nq*k i64 | scores nq*k f32 | min nq | max nq] and its pinned host twin, as the copy path of
+    // cmr_index_search; queries and allow words go up through the pinned buffer into this workspace's own scratch
+    const size_t o_ids = 8, o_sc = o_ids + (size_t)nq * k * 8, o_min = o_sc + (size_t)nq * k * 4, o_max = o_min + (size_t)nq * 4,
+                 out_bytes = o_max + (size_t)nq * 4, q_bytes = (size_t)nq * idx->dim * 4, m_bytes = (size_t)n_words * 4;
+    HIP_TRY(ws->d_q.ensure(q_bytes));
+    HIP_TRY(ws->d_mask.ensure(std::max<size_t>(m_bytes, 4)));
+    if (out_bytes > ws->d_pack.cap || !ws->d_pack.p) {        // (re)allocation moves the flag: re-arm it at the new place
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(ws->d_pack.ensure(std::max<size_t>(out_bytes, 4096)));
+        HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, 8, s));
+    }
+    char* const pk = (char*)ws->d_pack.p;
+    auto body = [&]() -> int {
+        FlagOverride flag(ws, (int*)pk);
+        HIP_TRY(ws->ensure_pin(std::max(out_bytes, q_bytes + m_bytes)));
+        char* const hp = (char*)ws->h_pin;
+        memcpy(hp, q, q_bytes);
+        memcpy(hp + q_bytes, allow, m_bytes);
+        HIP_TRY(hipMemcpyAsync(ws->d_q.p, hp, q_bytes, hipMemcpyHostToDevice, s));
+        if (m_bytes) HIP_TRY(hipMemcpyAsync(ws->d_mask.p, hp + q_bytes, m_bytes, hipMemcpyHostToDevice, s));
+        const int rc_ = search_masked_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, (const unsigned*)ws->d_mask.p, (int64_t*)(pk + o_ids), (float*)(pk + o_sc),
+                                              (float*)(pk + o_min), (float*)(pk + o_max));
+        if (rc_) return rc_;
+        // (the pinned buffer still holds what the H2D copies read: stream order puts the D2H copy behind them)
+        HIP_TRY(hipMemcpyAsync(hp, pk, out_bytes, hipMemcpyDeviceToHost, s));
+        return CMR_OK;
+    };
+    rc = body();
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    HIP_TRY(hipStreamSynchronize(s));
+    const char* const hp = (const char*)ws->h_pin;
+    int flagged = 0;
+    memcpy(&flagged, hp, sizeof(int));
+    if (flagged) {
+        HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, sizeof(int), s));
+        return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf or a value that rounds to Inf in the index dtype");
+    }
+    const size_t nk = (size_t)nq * k;
+    memcpy(out_ids, hp + o_ids, nk * 8);
+    memcpy(out_scores, hp + o_sc, nk * 4);
+    if (out_min) memcpy(out_min, hp + o_min, (size_t)nq * 4);
+    if (out_max) memcpy(out_max, hp + o_max, (size_t)nq * 4);
+    return CMR_OK;
 }
 
 int32_t cmr_index_search_min_score_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, float min_score, int64_t* ids_dev,

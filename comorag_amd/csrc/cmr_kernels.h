@@ -74,6 +74,9 @@ struct CmrScanArgs {
     // 2 = a list overflowed (the merge launch is still due).  The synchronous host API polls it instead of waiting for the end-of-kernel
     // signal (5.5 us per call on MI355X: tools/probe/poll_probe.hip) and launches the merge only in state 2.
     int* fin_done;
+    // filtered scan (cmr_launch_scan_masked): one allow word per 32-row panel, [npanels] on the device — bit (r & 31) of word
+    // (r >> 5) keeps local row r; bits beyond nrows are ignored.  Main pass and sampling passes take the same words.
+    const unsigned* row_mask;
 };
 // control words (ints) — every counter on a 128-byte line of its own: device atomics on one line serialise
 #define CMR_FIN_DONE 0        // workgroups whose waves have all published their first-panel maxima
@@ -91,6 +94,8 @@ struct CmrScanArgs {
 
 hipError_t cmr_launch_scan_topk(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);
 hipError_t cmr_launch_scan_scores(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);
+// cmr_launch_scan_topk among the rows a.row_mask keeps (geom.asm_ring is ignored: the compiler-counted ring)
+hipError_t cmr_launch_scan_masked(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);
 // top-k scan of <= 32 queries (k <= 64) that also derives its thresholds (no sampling launch) and selects the final k best per
 // query (no merge launch); a.fin[CMR_FIN_STATE] tells the merge launch behind it whether anything is left to do
 hipError_t cmr_launch_scan_fin(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);

@@ -6,17 +6,26 @@
 // Slow path, part 1 (inline, a handful of registers, no waits on global memory): push the keys of
 // one 32x32 score tile that beat the lane's threshold into the (wave, query) lists.  Returns the
 // mask of this tile's queries whose list is nearly full.
+// `valid`: bit i = row row0 + i of the tile may be pushed (wave-uniform).  The corpus' last, partial panel is
+// topk_tail_mask(row0, nrows); a filtered scan ANDs its panel's word of the caller's allow bitmap into it.
+__device__ __forceinline__ unsigned topk_tail_mask(long long row0, long long nrows) {
+    const long long left = nrows - row0;
+    return left >= 32 ? 0xFFFFFFFFu : left <= 0 ? 0u : (1u << (int)left) - 1u;
+}
 template <int CAP>
-__device__ __forceinline__ u64 topk_push(const f32x16& acc, long long row0, long long nrows, u64 tau_key, int* cnt_t,
+__device__ __forceinline__ u64 topk_push(const f32x16& acc, long long row0, unsigned valid, u64 tau_key, int* cnt_t,
                                          u64* list_t, int lane) {
     const int ql = lane & 31;
     const unsigned hrow = 4u * (unsigned)(lane >> 5);
+    // this lane's rows of the panel are (r & 3) + 8 * (r >> 2) + hrow: shifted by hrow once, the bit of accumulator register r sits at a
+    // compile-time position (sixteen lane-dependent masks 1 << row would be loop-invariant values hipcc keeps in registers across the scan)
+    const unsigned vh = valid >> hrow;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float v = acc[r];
         const long long row = row0 + (r & 3) + 8 * (r >> 2) + hrow;
         const u64 key = cmr_make_key(v, (unsigned)row);
-        if (row < nrows && v == v && key > tau_key) {
+        if ((vh & (1u << ((r & 3) + 8 * (r >> 2)))) && v == v && key > tau_key) {
             const int slot = atomicAdd(&cnt_t[ql], 1);  // ds_add_rtn_u32; <= 32 pushes per query per panel
             list_t[(size_t)ql * CAP + slot] = key;
         }
@@ -77,9 +86,9 @@ __device__ __forceinline__ void topk_compact(u64 need, int k, u64& tau_key, floa
 }
 
 template <int CAP>
-__device__ __forceinline__ void topk_slow_path(const f32x16& acc, long long row0, long long nrows, int k,
+__device__ __forceinline__ void topk_slow_path(const f32x16& acc, long long row0, unsigned valid, int k,
                                                u64& tau_key, float& tau_f, int* cnt_t, u64* list_t,
                                                u64* stage, int lane) {
-    const u64 need = topk_push<CAP>(acc, row0, nrows, tau_key, cnt_t, list_t, lane);
+    const u64 need = topk_push<CAP>(acc, row0, valid, tau_key, cnt_t, list_t, lane);
     if (need) topk_compact<CAP>(need, k, tau_key, tau_f, cnt_t, list_t, stage, lane);
 }

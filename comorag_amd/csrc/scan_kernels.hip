@@ -40,6 +40,13 @@
 // mid-size or large corpus: the sampling scan, its merge and the candidate merge are a chain of dependent launches around a
 // short scan there) — see "finishing stage" in scan_kernel
 #define MODE_FIN 2
+// MODE_MASKED: top-k among the rows an allow bitmap keeps (cmr_index_search_masked*): one 32-bit word per panel
+// (ScanP::row_mask, bit i = row i of the panel), ANDed with the tail mask of the corpus' last panel and used wherever MODE_TOPK
+// tests row < nrows — the min / max fold, the panel-max-against-threshold test and the slow path's push.  Every panel is
+// potentially partial; a word of all ones costs one compare in front of MODE_TOPK's own epilogue.  The sampling passes run the
+// same variant with the same words indexed by the GLOBAL panel, so a sample's lists hold allowed rows only and its k-th best is a
+// lower bound of the filtered k-th best.  Compiler-counted ring only (ASMRING = 0).
+#define MODE_MASKED 3
 
 // Cache policy of the corpus stream's loads: non-temporal.  Every byte of the corpus is read once per launch by one CU,
 // so keeping the lines in L2 / MALL only evicts what the other kernels of the pipeline use; measured against the default
@@ -84,6 +91,8 @@ struct ScanP {
     float* out_max;
     long long id_base;
     int* fin_done;         // mapped host word (or nullptr): the state once more, stored LAST — what a synchronous caller polls
+    // MODE_MASKED
+    const unsigned* row_mask;   // [npanels] allow words: bit (r & 31) of word (r >> 5) keeps local row r
 };
 
 // MODE_FIN: the threshold of query q from the published first-panel maxima of the ns supplying waves (one selection chunk:
@@ -113,7 +122,9 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
     constexpr int NQ = NQT * 32;
     constexpr bool TOPK = MODE != MODE_SCORES;
     constexpr bool FIN = MODE == MODE_FIN;
+    constexpr bool MASKED = MODE == MODE_MASKED;
     static_assert(!FIN || NQT == 1, "the finishing stage handles one query tile");
+    static_assert(!MASKED || !ASMRING, "the masked scan runs on the compiler-counted ring");
 
     v4u* qf = reinterpret_cast<v4u*>(smem);
     int* cnt_all = reinterpret_cast<int*>(smem + (size_t)NQT * KS * 1024);
@@ -176,7 +187,9 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
     // k distinct rows at or above it — and nearly as tight as the exact k-th best of the sample (the 20 best of 4096 sample keys
     // sit in ~17 different lanes).  Every workgroup does this for itself (~2 us beside the query-tile fill): the merge launch
     // between the two scans (21 us + its launch gap at 1 M rows) is gone.  Any valid lower bound leaves the results unchanged.
-    if constexpr (MODE == MODE_TOPK && NQT == 1) {
+    // (MASKED: the sample's lists hold allowed rows only, so the bound holds for the filtered k-th best; a sample with fewer than k
+    // allowed rows has fewer than k lanes with a key — no threshold)
+    if constexpr ((MODE == MODE_TOPK || MASKED) && NQT == 1) {
         if (P.slists) {                          // wave-uniform
             if (wave < nq_g) {
                 u64 best = 0ull;
@@ -374,10 +387,19 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
             const long long row0 = (long long)p * CMR_PANEL_ROWS;
             if (TOPK) {
                 const bool partial = row0 + CMR_PANEL_ROWS > P.nrows;
+                // MASKED: the rows of this panel that count — its word of the allow bitmap (p is the GLOBAL panel, in a sampling pass
+                // too; one wave-uniform load), less the rows beyond the corpus' end.  All ones: MODE_TOPK's own epilogue.
+                [[maybe_unused]] unsigned valid = 0xFFFFFFFFu;
+                if constexpr (MASKED) {
+                    valid = (unsigned)__builtin_amdgcn_readfirstlane((int)P.row_mask[p]);
+                    if (partial) valid &= topk_tail_mask(row0, P.nrows);
+                }
+                const bool whole = MASKED ? valid == 0xFFFFFFFFu : !partial;
+                [[maybe_unused]] const unsigned vh = valid >> (4 * (lane >> 5));      // this lane's half: the bit of accumulator register r at (r & 3) + 8 * (r >> 2)
 #pragma unroll
                 for (int t = 0; t < NQT; ++t) {
                     float mx, mn;
-                    if (!partial) {
+                    if (whole) {
                         mx = acc[t][0]; mn = acc[t][0];
 #pragma unroll
                         for (int r = 1; r < 16; ++r) { mx = fmaxf(mx, acc[t][r]); mn = fminf(mn, acc[t][r]); }
@@ -385,7 +407,7 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                         mx = -__builtin_inff(); mn = __builtin_inff();
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const bool ok = row0 + cmr_acc_row(r, lane) < P.nrows;
+                            const bool ok = MASKED ? (vh & (1u << ((r & 3) + 8 * (r >> 2)))) != 0u : row0 + cmr_acc_row(r, lane) < P.nrows;
                             mx = fmaxf(mx, ok ? acc[t][r] : -__builtin_inff());
                             mn = fminf(mn, ok ? acc[t][r] : __builtin_inff());
                         }
@@ -414,8 +436,10 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                             continue;
                         }
                     }
-                    if (__any(mx >= tau_f[t])) {
-                        topk_slow_path<CAP>(acc[t], row0, P.nrows, P.k, tau_key[t], tau_f[t], cnt_w + t * 32,
+                    // (MASKED: a panel whose allowed rows all miss the threshold stays on the fast path; one without allowed rows has
+                    // mx = -inf, which "reaches" a threshold of -inf — nothing to push there)
+                    if ((!MASKED || valid != 0u) && __any(mx >= tau_f[t])) {
+                        topk_slow_path<CAP>(acc[t], row0, MASKED ? valid : topk_tail_mask(row0, P.nrows), P.k, tau_key[t], tau_f[t], cnt_w + t * 32,
                                             list_w + (size_t)t * 32 * CAP, stage, lane);
                     }
                 }
@@ -751,21 +775,26 @@ static hipError_t launch_one(const CmrScanGeom& g, const ScanP& p, hipStream_t s
         hipLaunchKernelGGL(kern, dim3(g.grid), dim3(CMR_SCAN_THREADS), g.lds, s, p);
         return hipGetLastError();
     };
-    if constexpr (MODE == MODE_TOPK) {
-        if (g.stream_default_policy) {
-            if (g.asm_ring) return launch(scan_kernel<DT, NQT, CAP, R, MODE, 1, 0>);
-            return launch(scan_kernel<DT, NQT, CAP, R, MODE, 0, 0>);
+    // masked scans: the compiler-counted ring and the non-temporal policy only (one query group per pass: nobody re-reads a line)
+    if constexpr (MODE == MODE_MASKED) {
+        return launch(scan_kernel<DT, NQT, CAP, R, MODE, 0>);
+    } else {
+        if constexpr (MODE == MODE_TOPK) {
+            if (g.stream_default_policy) {
+                if (g.asm_ring) return launch(scan_kernel<DT, NQT, CAP, R, MODE, 1, 0>);
+                return launch(scan_kernel<DT, NQT, CAP, R, MODE, 0, 0>);
+            }
         }
+        if (g.asm_ring) return launch(scan_kernel<DT, NQT, CAP, R, MODE, 1>);
+        return launch(scan_kernel<DT, NQT, CAP, R, MODE, 0>);
     }
-    if (g.asm_ring) return launch(scan_kernel<DT, NQT, CAP, R, MODE, 1>);
-    return launch(scan_kernel<DT, NQT, CAP, R, MODE, 0>);
 }
 
 template <int DT, int MODE>
 static hipError_t dispatch(const CmrScanGeom& g, const ScanP& p, hipStream_t s) {
 #define CASE(NQT, CAP, R) \
     if (g.nqt == NQT && g.cap == CAP && g.ring == R) return launch_one<DT, NQT, CAP, R, MODE>(g, p, s);
-    if constexpr (MODE == MODE_TOPK) {
+    if constexpr (MODE == MODE_TOPK || MODE == MODE_MASKED) {
         CASE(1, 128, 8) CASE(1, 128, 16) CASE(1, 256, 8) CASE(1, 256, 16)
         CASE(2, 128, 8) CASE(2, 128, 16) CASE(2, 256, 8) CASE(2, 256, 16)
     } else if constexpr (MODE == MODE_FIN) {
@@ -788,6 +817,7 @@ static ScanP to_p(const CmrScanGeom& g, const CmrScanArgs& a) {
     p.sample_waves = a.sample_waves; p.sample_stride = a.sample_stride; p.sample_chunk_log2 = a.sample_chunk_log2; p.tau_init = a.tau_init;
     p.slists = a.sample_lists; p.scnt = a.sample_cnt; p.sW = a.sample_W;
     p.qgroups = a.qgroups > 1 ? a.qgroups : 1;
+    p.row_mask = a.row_mask;
     p.fin_mm = a.fin_mm;
     p.fin = a.fin; p.fin_pmax = a.fin_pmax; p.fin_tau = a.fin_tau; p.fin_dense = a.fin_dense; p.fin_wgs = a.fin_wgs; p.fin_mul = a.fin_mul; p.fin_dcap = a.fin_dcap; p.fin_spin = a.fin_spin; p.fin_done = a.fin_done; p.fin_first = a.fin_first;
     p.out_ids = a.out_ids; p.out_scores = a.out_scores; p.out_min = a.out_min; p.out_max = a.out_max; p.id_base = a.id_base;
@@ -1438,6 +1468,18 @@ hipError_t cmr_launch_scan_topk(const CmrScanGeom& g, const CmrScanArgs& a, hipS
         case CMR_DT_BF16: return dispatch<CMR_DT_BF16, MODE_TOPK>(g, p, s);
         case CMR_DT_F16: return dispatch<CMR_DT_F16, MODE_TOPK>(g, p, s);
         case CMR_DT_F32: return dispatch<CMR_DT_F32, MODE_TOPK>(g, p, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// top-k scan of the rows a.row_mask keeps (MODE_MASKED: main pass or sampling pass; one query group, compiler-counted ring)
+hipError_t cmr_launch_scan_masked(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s) {
+    if (!a.row_mask || a.qgroups > 1) return hipErrorInvalidValue;
+    const ScanP p = to_p(g, a);
+    switch (g.dtype) {
+        case CMR_DT_BF16: return dispatch<CMR_DT_BF16, MODE_MASKED>(g, p, s);
+        case CMR_DT_F16: return dispatch<CMR_DT_F16, MODE_MASKED>(g, p, s);
+        case CMR_DT_F32: return dispatch<CMR_DT_F32, MODE_MASKED>(g, p, s);
     }
     return hipErrorInvalidValue;
 }

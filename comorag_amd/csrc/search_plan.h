@@ -78,6 +78,7 @@ struct PassRequest {
     bool pipelined = false;          // the pre-phase has a stream of its own
     int reserve_cus = 0;             // CUs the main scan leaves free (< 0: by corpus size)
     int prefilter = 0;               // the call may take the int8 pre-filter (prefilter_eligible, prefilter_host.h: 1; 2: with a filter that keeps every row) if the pass is eligible
+    bool masked = false;             // filtered search (cmr_index_search_masked*): the narrow chain on the masked scan variant — no finishing stage, no pre-filter
 };
 
 struct PassPlan {
@@ -85,6 +86,7 @@ struct PassPlan {
     bool wide = false;
     CmrScanGeom g{};                 // the main scan's, g.grid = its launch grid (all query groups)
     bool fin = false;                // scan with the finishing stage: no sampling launches, no merge of its own
+    bool masked = false;             // every scan of the pass (sampling levels and main) is the masked variant over the caller's allow words
     int prefilter = 0;               // 1 | 2: the int8 filter in the place of the main scan, the re-score in front of the merge (W: the re-score's lists)
     int rescore_grid = 0;
     int pair_cap = 0;                // pre-filter: hit records per query for the threshold tightening (0: none, every hit is re-scored)
@@ -111,6 +113,8 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     const int nqp = rq.nqp, k = rq.k;
     const bool wide = rq.route == Route::wide, quad = rq.route == Route::quad;
     p.nqp = nqp; p.k = k; p.wide = wide;
+    if (rq.masked && (wide || quad || rq.prefilter)) return cmr_fail(CMR_ERR_INVALID, "a filtered pass is a narrow pass without the pre-filter");
+    p.masked = rq.masked;
     CmrScanGeom& g = p.g;
     const long long npanels = idx->npanels();
     int rc = make_geom(idx, quad ? std::min(nqp, idx->narrow_max()) : nqp, k, true, &g);
@@ -124,7 +128,7 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     // A synchronous caller's handful of queries (everything on ONE stream) on a corpus beyond the single-launch path: the scan
     // with the finishing stage — no sampling launches, no merge of its own (scan_kernel MODE_FIN; 2 M x 768 bf16 rows, one
     // query: pack 5 + sample 15 + scan 471 + merge 46 us before, pack + scan with ~10 us of finishing after)
-    bool fin = idx->scan_fin && !idx->no_sample && !wide && G == 1 && !rq.has_min_score && rq.single_stream && g.nqt == 1 && nqp <= idx->fin_max_q &&
+    bool fin = !rq.masked && idx->scan_fin && !idx->no_sample && !wide && G == 1 && !rq.has_min_score && rq.single_stream && g.nqt == 1 && nqp <= idx->fin_max_q &&
                k <= 64 && npanels >= 4096 && npanels >= (long long)idx->n_cu * 2 * CMR_SCAN_WAVES;      // (every wave of the grid has a first panel)
     if (fin) {
         // scan_fin_cap = 256: longer lists than k asks for — the panels a wave scans before the thresholds arrive go to its lists whole (32 keys
@@ -358,14 +362,14 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
 }
 
 // "last_route" (include/comorag_hip.h): path | sampling levels << 4 | tau_in_scan << 6 | single 128-panel level << 7 | query tiles per workgroup << 8 |
-// threshold search << 10 (| CMR_ROUTE_MORE_PASSES where the batch is cut into several passes: plan_and_enqueue_pass)
+// threshold search << 10 | filtered << 12 (| CMR_ROUTE_MORE_PASSES where the batch is cut into several passes: plan_and_enqueue_pass)
 long long route_code(int path, int n_levels = 0, bool tau_in_scan = false, bool single_level = false, int nqt = 1, bool threshold = false) {
     return (long long)path | ((long long)n_levels << 4) | ((long long)(tau_in_scan ? 1 : 0) << 6) | ((long long)(single_level ? 1 : 0) << 7) | ((long long)nqt << 8) |
            ((long long)(threshold ? 1 : 0) << 10);
 }
 long long route_code(const PassPlan& p, bool threshold) {
     const int path = p.wide ? CMR_ROUTE_WIDE : p.G > 1 ? CMR_ROUTE_QUERY_SPLIT : p.fin ? CMR_ROUTE_FIN : CMR_ROUTE_CHAIN;
-    return route_code(path, p.n_levels, p.tau_in_scan, p.single_level, p.g.nqt, threshold);
+    return route_code(path, p.n_levels, p.tau_in_scan, p.single_level, p.g.nqt, threshold) | (p.masked ? CMR_ROUTE_FILTERED : 0);
 }
 
 // ---- a batch splits into passes
@@ -420,6 +424,7 @@ struct PassSplit {
 
 // 0: the general pack / [sample] / scan / merge chain; 1: single launch, <= 1024 rows; 2: single launch, hierarchical
 // selection (<= 16 queries, k <= 64, up to 64 K rows while workgroups x k <= 1024) — see tiny_search_kernel
+// (a filtered search never asks: the single-launch kernels take no allow words, search_masked_enqueue plans narrow passes only)
 int small_path_kind(const cmr_index* idx, int nq, int k, bool threshold_search) {
     if (idx->no_tiny || threshold_search || idx->n <= 0 || nq > 16 || k > CMR_MAX_K) return 0;
     if (idx->npanels() > idx->small_max_panels) return 0;

@@ -28,6 +28,56 @@ def _ptr(a: np.ndarray) -> int:
     return a.__array_interface__["data"][0]
 
 
+def pack_row_mask(n_rows: int, allow=None, exclude=None) -> np.ndarray:
+    """Allow bitmap of a filtered search (`DenseIndex.search_filtered`, cmr_index_search_masked): uint32 [ceil(n_rows / 32)],
+    bit (r & 31) of word (r >> 5) set when local row r is kept; bits at or beyond n_rows are zero.
+    `allow`: a bool array [n_rows], or an iterable of row ids to keep; `exclude`: row ids to drop from an all-ones mask; neither:
+    every row.  Giving both is an error; ids outside [0, n_rows) raise ValueError.  Pure numpy."""
+    n_rows = int(n_rows)
+    if n_rows < 0:
+        raise ValueError(f"n_rows = {n_rows} < 0")
+    if allow is not None and exclude is not None:
+        raise ValueError("give allow or exclude, not both")
+
+    def _ids(a) -> np.ndarray:
+        ids = np.asarray(a if isinstance(a, np.ndarray) else list(a))
+        if ids.size == 0:
+            return np.empty(0, dtype=np.int64)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("row ids must be a 1-d sequence of integers")
+        ids = ids.astype(np.int64)
+        if ids.min() < 0 or ids.max() >= n_rows:
+            raise ValueError(f"row id outside [0, {n_rows})")
+        return ids
+
+    if isinstance(allow, np.ndarray) and allow.dtype == np.bool_:
+        if allow.shape != (n_rows,):
+            raise ValueError(f"a bool allow array must be [{n_rows}], got {allow.shape}")
+        keep = allow
+    elif allow is not None:
+        keep = np.zeros(n_rows, dtype=bool)
+        keep[_ids(allow)] = True
+    else:
+        keep = np.ones(n_rows, dtype=bool)
+        if exclude is not None:
+            keep[_ids(exclude)] = False
+    n_words = (n_rows + 31) // 32
+    bits = np.zeros(n_words * 32, dtype=np.uint8)
+    bits[:n_rows] = keep
+    return np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32, copy=False)
+
+
+def _mask_popcount(words: np.ndarray, n_rows: int) -> int:
+    """Set bits among the first n_rows of an allow bitmap (bits at or beyond n_rows do not count)."""
+    if len(words) == 0:
+        return 0
+    count = (lambda w: int(np.bitwise_count(w).sum())) if hasattr(np, "bitwise_count") else (lambda w: int(np.unpackbits(w.view(np.uint8)).sum()))
+    total = count(words)
+    if n_rows % 32:
+        total -= count(words[-1:] & np.uint32(~((1 << (n_rows % 32)) - 1) & 0xFFFFFFFF))
+    return total
+
+
 # the calls whose host-array marshalling `DenseIndex` (cmr_index_*) and `MultiDeviceIndex` (cmr_mindex_*) share
 _HOST_CALLS = ("destroy", "size", "info", "append", "search", "search_exact", "search_min_score", "scores", "sorted_scores",
                "rescore", "get_rows")
@@ -280,6 +330,57 @@ class DenseIndex(HostArrayIndex):
             stream = torch.cuda.current_stream(dev).cuda_stream
         L.check(L.lib().cmr_index_search_dev(
             self._h, C.c_void_p(q_t.data_ptr()), nq, k, C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
+            C.c_void_p(out_min.data_ptr()) if out_min is not None else None,
+            C.c_void_p(out_max.data_ptr()) if out_max is not None else None, C.c_void_p(stream)))
+        return out_ids, out_scores
+
+    # -- filtered search (cmr_index_search_masked*): top-k among the rows an allow bitmap keeps
+    def search_filtered(self, q, k: int, mask=None, *, allow=None, exclude=None, with_minmax: bool = True
+                        ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """`search` among the allowed LOCAL rows only (row r = the r-th appended row; returned ids carry the id base / block table as
+        ever): what `search` returns on an index that holds just those rows, ids mapped back — the filter that tri_retrieve's pool dedup
+        (ComoRAG.py:499-505, 515-522, 535-540) applies after its top-k, applied inside it.  `mask`: uint32 words of `pack_row_mask`
+        ([ceil(len / 32)]), or give `allow` / `exclude` as `pack_row_mask` takes them.  One mask serves every query; k <= 128.
+        → (ids [nq,k'], raw scores [nq,k'], min [nq], max [nq]) with k' = min(k, allowed rows); min / max over the allowed rows
+        (+inf / -inf when there is none)."""
+        n = len(self)
+        if mask is None:
+            mask = pack_row_mask(n, allow=allow, exclude=exclude)
+        elif allow is not None or exclude is not None:
+            raise ValueError("give mask or allow / exclude, not both")
+        mask = np.ascontiguousarray(mask, dtype=np.uint32)
+        if mask.ndim != 1:
+            raise ValueError("mask must be a 1-d uint32 array")
+        q = self._queries(q)
+        nq = q.shape[0]
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        mn = np.empty(nq, dtype=np.float32) if with_minmax else None
+        mx = np.empty(nq, dtype=np.float32) if with_minmax else None
+        L.check(L.lib().cmr_index_search_masked(self._h, _ptr(q), nq, k, _ptr(mask), mask.shape[0], _ptr(ids), _ptr(sc),
+                                                _ptr(mn) if with_minmax else None, _ptr(mx) if with_minmax else None))
+        kk = min(k, _mask_popcount(mask, n))
+        return ids[:, :kk], sc[:, :kk], mn, mx
+
+    def search_filtered_dev(self, q_t, k: int, mask_t, out_ids=None, out_scores=None, out_min=None, out_max=None,
+                            stream: Optional[int] = None):
+        """`search_filtered` on torch CUDA tensors, enqueued on torch's current stream without synchronising (as `search_dev`).
+        mask_t: the words of `pack_row_mask` on the device — int32 (torch has no uint32 arithmetic: `torch.from_numpy(words.view(np.int32))`)
+        or uint32, contiguous, [ceil(len / 32)], read in place: upload a mask once and reuse it.  → (out_ids [nq,k], out_scores [nq,k]),
+        -1 / -inf padded when fewer than k rows are allowed."""
+        import torch
+        assert q_t.is_cuda and q_t.dtype == torch.float32 and q_t.is_contiguous() and q_t.shape[1] == self.dim
+        assert mask_t.is_cuda and mask_t.element_size() == 4 and not mask_t.dtype.is_floating_point and mask_t.is_contiguous() and mask_t.dim() == 1
+        nq, dev = q_t.shape[0], q_t.device
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().cmr_index_search_masked_dev(
+            self._h, C.c_void_p(q_t.data_ptr()), nq, k, C.c_void_p(mask_t.data_ptr()), mask_t.shape[0],
+            C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
             C.c_void_p(out_min.data_ptr()) if out_min is not None else None,
             C.c_void_p(out_max.data_ptr()) if out_max is not None else None, C.c_void_p(stream)))
         return out_ids, out_scores

@@ -63,6 +63,20 @@ def dense_passage_topk(index: DenseIndex, query_embeddings, k: int) -> Tuple[np.
     return ids, norm.astype(np.float32)
 
 
+def dense_passage_topk_filtered(index: DenseIndex, query_embeddings, k: int, exclude_rows=None, allow_rows=None
+                                ) -> Tuple[np.ndarray, np.ndarray]:
+    """`dense_passage_topk` among the rows not excluded: the k best rows of `index` less `exclude_rows` (or among `allow_rows` only) —
+    tri_retrieve's top qa_*_top_k chunks / summaries / episodes with the ones already in the question's memory pool left out BEFORE the
+    top-k (ComoRAG.py:499-505, 515-522, 535-540 drop them after it, so the caller gets fewer than k).  Rows are local row ids: callers
+    map `hash_id_to_idx` themselves.  Scores are min-max normalised from the min / max over the ALLOWED rows with the reference formula.
+    ids [nq,k'], scores [nq,k'] with k' = min(k, allowed rows)."""
+    ids, sc, mn, mx = index.search_filtered(_as_query(query_embeddings), k, allow=allow_rows, exclude=exclude_rows)
+    rng = (mx - mn)[:, None]
+    flat = (rng == 0) | ~np.isfinite(rng)          # (no allowed row: min = +inf, max = -inf, and k' = 0 anyway)
+    norm = np.where(flat, np.ones_like(sc), (sc - mn[:, None]) / np.where(flat, 1, rng))
+    return ids, norm.astype(np.float32)
+
+
 def get_fact_scores(index: Optional[DenseIndex], query_embedding) -> np.ndarray:
     """ComoRAG.get_fact_scores (ComoRAG.py:937-948): full normalised vector over the fact matrix."""
     if index is None or len(index) == 0:

@@ -144,6 +144,36 @@ int32_t cmr_index_search_dev(cmr_index_t* idx, const float* q_f32_dev, int32_t n
                              int64_t* out_ids_dev, float* out_scores_dev, float* out_min_dev,
                              float* out_max_dev, void* stream);
 
+/* Filtered search: the k best among the rows an allow bitmap keeps ("top-k among the rows not excluded").  Serves tri_retrieve's
+ * memory-pool dedup (ComoRAG.py:499-505, 515-522, 535-540: the top qa_*_top_k chunks / summaries / episodes, less the ones whose hash
+ * is already in the question's pool — the reference filters AFTER the top-k and so returns fewer than k; here the excluded rows never
+ * compete) and one index that holds several levels or namespaces with a mask each (get_similar_summaries, utils/embed_utils.py:152-158).
+ *   allow_words  one uint32 per 32-row panel over the LOCAL rows of this index (row r = the r-th appended row, before
+ *                cmr_index_set_id_base / the block table): bit (r & 31) of word (r >> 5) keeps row r.  n_words == ceil(size / 32)
+ *                exactly; bits at or beyond size are ignored.  One mask serves every query of the call.
+ *   result       exactly what cmr_index_search returns on an index that holds only the allowed rows in their original order, every id
+ *                mapped back to the original row and then translated by the id base / block table: score descending, then row id
+ *                ascending; a row's score bits are those of the unfiltered search; out_min / out_max over the allowed rows only; fewer
+ *                than k allowed rows: -1 / -inf padded; none: CMR_OK, all padding, min = +inf, max = -inf.
+ *   k <= CMR_MAX_K (above: CMR_ERR_UNSUPPORTED), any nq >= 1 (more than 64 queries run as several narrow passes).  NULL mask / output,
+ *   wrong n_words, k <= 0: CMR_ERR_INVALID, checked before any device call.  The synchronous form reports non-finite queries as
+ *   cmr_index_search does; the _dev form as the other _dev calls do (cmr_index_query_status).
+ * Route: always the narrow kernel's pack / [sample] / scan / merge chain on the masked variant of the scan — the panel's word stands
+ * wherever the scan tests "row < rows" (min / max, threshold test, candidate push), the sampling passes read the same words, so their
+ * thresholds are bounds among ALLOWED rows.  A filtered call never joins a combined batch ("combine"), never takes the int8
+ * pre-filter, the single-launch paths or the finishing stage, and changes nothing any other call returns.  last_route: CMR_ROUTE_CHAIN
+ * with CMR_ROUTE_FILTERED set.
+ * The host form uploads the words into scratch of its own call (concurrent calls each have theirs); the _dev form reads the caller's
+ * device words in place on `stream` — a caller that reuses one mask (a namespace, the pool's exclusion set) uploads it once.          */
+int32_t cmr_index_search_masked(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k,
+                                const uint32_t* allow_words, int64_t n_words,
+                                int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
+/* ComoRAG.py:499-505, 515-522, 535-540 on device buffers (see above): enqueued on `stream`, no synchronisation. */
+int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_f32_dev, int32_t nq, int32_t k,
+                                    const uint32_t* allow_words_dev, int64_t n_words,
+                                    int64_t* out_ids_dev, float* out_scores_dev,
+                                    float* out_min_dev, float* out_max_dev, void* stream);
+
 /* Throughput mode for a stream of independent query batches (serving; bench.py).  Work is enqueued on streams owned by
  * the index: query packing + sampling passes of batch i+1 overlap the HBM-bound main scan of batch i.  On a 256-CU device
  * main scans shorter than ~1 ms (shards up to ~4 M x 768 bf16 rows) of batches of <= 64 queries run on a CU-masked pair of
@@ -224,8 +254,10 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  *   bit  7      that level is the single 128-panel sample of a small batch (sample_single)
  *   bits 8..9   query tiles of 32 per workgroup (1, 2)
  *   bit  10     threshold search (cmr_index_search_min_score*)
- *   bit  11     the batch took more than one corpus pass: the bits above describe its first, later passes may be routed otherwise   */
+ *   bit  11     the batch took more than one corpus pass: the bits above describe its first, later passes may be routed otherwise
+ *   bit  12     filtered search (cmr_index_search_masked*): every scan of the pass is the masked variant                            */
 #define CMR_ROUTE_MORE_PASSES (1 << 11)
+#define CMR_ROUTE_FILTERED (1 << 12)
 #define CMR_ROUTE_TINY 1          /* single launch, <= 1024 rows */
 #define CMR_ROUTE_SMALL 2         /* single launch, hierarchical selection */
 #define CMR_ROUTE_CHAIN 3         /* narrow kernel: pack / [sample] / scan / merge */
