@@ -57,6 +57,8 @@ SIGNATURES = {
     "cmr_index_search_dev": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p]),
     "cmr_index_search_masked": (_i32, [_p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p]),
     "cmr_index_search_masked_dev": (_i32, [_p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p]),
+    "cmr_index_search_masked_each": (_i32, [_p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p]),
+    "cmr_index_search_masked_each_dev": (_i32, [_p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p]),
     "cmr_index_search_pipelined": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _P(_p)]),
     "cmr_index_set_id_base": (_i32, [_p, _i64]),
     "cmr_index_set_id_blocks": (_i32, [_p, _i32, _p, _p]),

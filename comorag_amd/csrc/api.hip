@@ -101,6 +101,8 @@ const Option kOptions[] = {
      "combine must be 0 (off) or in [2, " CMR_STR(CMR_PPR_MAX_BATCH) "]", OPT_READ(i->combine.load(std::memory_order_relaxed))},
     {"combine_wait_us", [](cmr_index* i, long long v) { i->combine_wait_us.store(v, std::memory_order_relaxed); }, Option::clamp, 0, 10000000, 0, nullptr,
      OPT_READ(i->combine_wait_us.load(std::memory_order_relaxed))},
+    {"combine_filtered", [](cmr_index* i, long long v) { i->combine_filtered.store((int)v, std::memory_order_relaxed); }, Option::range, 0, 1, 0,
+     "combine_filtered must be 0 or 1", OPT_READ(i->combine_filtered.load(std::memory_order_relaxed))},
     {"prefilter", OPT_FIELD(prefilter), Option::range, -1, 2, 0, "prefilter must be -1 (auto), 0 (off), 1 (on) or 2 (on, the filter keeps every row)", OPT_READ(i->prefilter)},
     {"prefilter_rescore_wgs", OPT_FIELD(pf_rescore_wgs), Option::clamp, 0, 1024, 0, nullptr, nullptr},
     {"prefilter_tighten", OPT_FIELD(pf_tighten), Option::range, 0, 1, 0, "prefilter_tighten must be 0 or 1", OPT_READ(i->pf_tighten)},
@@ -275,8 +277,9 @@ struct PassStreams {
 // One pass (<= 64 queries, or one wide / query-split pass) of the fused search, as plan_pass shaped it (search_plan.h): this
 // function only allocates, launches, records and waits.
 // row_mask: the allow words of a filtered pass (p.masked; device, one word per panel) — its sampling levels and its main scan are the masked variant
+// mask_stride: p.masked_each — row_mask holds a block of mask_stride words for each of the pass's nqp queries, the first query's first
 int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const PassPlan& p, const float* q_dev, const float* min_score,
-                 int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, const unsigned* row_mask = nullptr) {
+                 int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, const unsigned* row_mask = nullptr, long long mask_stride = 0) {
     hipStream_t const sp = st.sp, sm = st.sm, sq = st.sq;
     const CmrScanGeom& g = p.g;
     const int nqp = p.nqp, k = p.k, G = p.G;
@@ -305,6 +308,10 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
     if (p.masked) {
         if (!row_mask) return fail(CMR_ERR_INVALID, "filtered pass without allow words");
         a.row_mask = row_mask;
+        if (p.masked_each) {
+            if (mask_stride < idx->npanels()) return fail(CMR_ERR_INVALID, "per-query allow words: stride %lld < %lld panels", mask_stride, idx->npanels());
+            a.row_mask_stride = mask_stride;
+        }
     }
     if (min_score) {
         // key > tau  <=>  score >= *min_score: tau = (smallest key with that score) - 1
@@ -324,7 +331,7 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
             a.tau_init = tau_out;
             continue;
         }
-        HIP_TRY(p.wide ? cmr_launch_scan_wide(gs, as, sp) : p.masked ? cmr_launch_scan_masked(gs, as, sp) : cmr_launch_scan_topk(gs, as, sp));
+        HIP_TRY(p.wide ? cmr_launch_scan_wide(gs, as, sp) : p.masked_each ? cmr_launch_scan_masked_each(gs, as, sp) : p.masked ? cmr_launch_scan_masked(gs, as, sp) : cmr_launch_scan_topk(gs, as, sp));
         if (p.tau_in_scan) {      // the main scan's workgroups derive the thresholds from these lists themselves
             a.sample_lists = (const u64*)ws->s_lists.p; a.sample_cnt = (const int*)ws->s_cnt.p; a.sample_W = L.Wl;
             a.tau_init = nullptr;
@@ -373,7 +380,7 @@ int enqueue_pass(cmr_index* idx, Workspace* ws, const PassStreams& st, const Pas
         if (ws->done_ptr && idx->single_block()) a.fin_done = ws->done_ptr;
     }
     if (p.prefilter) { if ((rc = q8_filter(idx, f, a, sm))) return rc; }
-    else HIP_TRY(p.wide ? cmr_launch_scan_wide(g, a, sm) : p.fin ? cmr_launch_scan_fin(g, a, sm) : p.masked ? cmr_launch_scan_masked(g, a, sm) : cmr_launch_scan_topk(g, a, sm));
+    else HIP_TRY(p.wide ? cmr_launch_scan_wide(g, a, sm) : p.fin ? cmr_launch_scan_fin(g, a, sm) : p.masked_each ? cmr_launch_scan_masked_each(g, a, sm) : p.masked ? cmr_launch_scan_masked(g, a, sm) : cmr_launch_scan_topk(g, a, sm));
     if (prof) {
         HIP_TRY(hipEventRecord(pe.b, sm));
         std::lock_guard<std::mutex> pg(idx->prof_mu);
@@ -444,8 +451,10 @@ int search_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, in
 // Filtered search (cmr_index_search_masked*): the best k among the local rows whose bit is set in allow_dev (one word per
 // 32-row panel, on the device).  Narrow passes of the pack / [sample] / scan / merge chain on the masked scan variant, all on
 // ws->stream; one mask serves every query.  k <= CMR_MAX_K (checked by the caller).
+// mask_stride > 0 (cmr_index_search_masked_each*): allow_dev is [nq][mask_stride], query i's words at allow_dev + i * mask_stride;
+// the pass that starts at query q0 gets the pointer advanced by q0 blocks, its kernel indexes the pass's own queries from 0.
 int search_masked_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, int k, const unsigned* allow_dev, int64_t* ids_dev,
-                          float* scores_dev, float* min_dev, float* max_dev) {
+                          float* scores_dev, float* min_dev, float* max_dev, long long mask_stride = 0) {
     const PassStreams st = PassStreams::one(ws->stream);
     const int per_pass = idx->narrow_width(nq);
     for (int q0 = 0; q0 < nq; q0 += per_pass) {
@@ -453,11 +462,12 @@ int search_masked_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int
         PassPlan plan;
         PassRequest rq = st.request(nqp, k, Route::narrow, false, 0);
         rq.masked = true;
+        rq.masked_each = mask_stride > 0;
         int rc = plan_pass(idx, rq, &plan);
         if (rc) return rc;
         if (q0 == 0) idx->last_route.store(route_code(plan, false) | (nqp < nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
         rc = enqueue_pass(idx, ws, st, plan, q_dev + (size_t)q0 * idx->dim, nullptr, ids_dev + (size_t)q0 * k, scores_dev + (size_t)q0 * k,
-                          min_dev ? min_dev + q0 : nullptr, max_dev ? max_dev + q0 : nullptr, allow_dev);
+                          min_dev ? min_dev + q0 : nullptr, max_dev ? max_dev + q0 : nullptr, allow_dev + (size_t)q0 * (size_t)mask_stride, mask_stride);
         if (rc) return rc;
     }
     return CMR_OK;
@@ -954,8 +964,9 @@ int32_t cmr_index_search_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, i
     return search_enqueue(idx, ws, q_dev, nq, k, ids_dev, scores_dev, min_dev, max_dev);
 }
 
-// ---- filtered search (include/comorag_hip.h: cmr_index_search_masked*).  Never combined, never pre-filtered: the
-// calls go straight to search_masked_enqueue.
+// ---- filtered search (include/comorag_hip.h: cmr_index_search_masked*, cmr_index_search_masked_each*).  Never
+// pre-filtered; the _dev forms go straight to search_masked_enqueue, the host forms through the combiner where "combine_filtered" is set
+// (further down, beside the other combined calls).
 static int masked_check(const cmr_index* idx, int nq, int k, int64_t n_words) {      // (under the index lock; no device call)
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
     if (k <= 0) return fail(CMR_ERR_INVALID, "k must be > 0");
@@ -977,20 +988,35 @@ int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_dev, int32_
     return search_masked_enqueue(idx, ws, q_dev, nq, k, allow_dev, ids_dev, scores_dev, min_dev, max_dev);
 }
 
-int32_t cmr_index_search_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words,
-                                int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
-    if (!idx || !q || !allow || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    SyncCall call(idx);
+int32_t cmr_index_search_masked_each_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words,
+                                         int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
+    if (!idx || !q_dev || !allow_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
     int rc = masked_check(idx, nq, k, n_words);
     if (rc) return rc;
-    rc = call.open();
+    rc = cmr_set_device(idx->device);
+    if (rc) return rc;
+    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
+    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
+    return search_masked_enqueue(idx, ws, q_dev, nq, k, allow_dev, ids_dev, scores_dev, min_dev, max_dev, n_words);
+}
+
+}  // extern "C"
+
+// The synchronous filtered search behind cmr_index_search_masked (each = false: `allow` is [n_words], one mask for every query) and
+// cmr_index_search_masked_each (each = true: `allow` is [nq][n_words]).  The caller holds the index lock (`call`) and has checked the
+// arguments (masked_check).
+static int masked_sync(SyncCall& call, const float* q, int nq, int k, const uint32_t* allow, int64_t n_words, bool each,
+                       int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+    cmr_index* const idx = call.idx;
+    int rc = call.ws ? CMR_OK : call.open();
     if (rc) return rc;
     Workspace* const ws = call.ws;
     hipStream_t const s = call.s;
     // packed device buffer [flag (8 B) | ids nq*k i64 | scores nq*k f32 | min nq | max nq] and its pinned host twin, as the copy path of
     // cmr_index_search; queries and allow words go up through the pinned buffer into this workspace's own scratch
     const size_t o_ids = 8, o_sc = o_ids + (size_t)nq * k * 8, o_min = o_sc + (size_t)nq * k * 4, o_max = o_min + (size_t)nq * 4,
-                 out_bytes = o_max + (size_t)nq * 4, q_bytes = (size_t)nq * idx->dim * 4, m_bytes = (size_t)n_words * 4;
+                 out_bytes = o_max + (size_t)nq * 4, q_bytes = (size_t)nq * idx->dim * 4, m_bytes = (size_t)n_words * 4 * (each ? (size_t)nq : 1);
     HIP_TRY(ws->d_q.ensure(q_bytes));
     HIP_TRY(ws->d_mask.ensure(std::max<size_t>(m_bytes, 4)));
     if (out_bytes > ws->d_pack.cap || !ws->d_pack.p) {        // (re)allocation moves the flag: re-arm it at the new place
@@ -1008,7 +1034,7 @@ int32_t cmr_index_search_masked(cmr_index_t* idx, const float* q, int32_t nq, in
         HIP_TRY(hipMemcpyAsync(ws->d_q.p, hp, q_bytes, hipMemcpyHostToDevice, s));
         if (m_bytes) HIP_TRY(hipMemcpyAsync(ws->d_mask.p, hp + q_bytes, m_bytes, hipMemcpyHostToDevice, s));
         const int rc_ = search_masked_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, (const unsigned*)ws->d_mask.p, (int64_t*)(pk + o_ids), (float*)(pk + o_sc),
-                                              (float*)(pk + o_min), (float*)(pk + o_max));
+                                              (float*)(pk + o_min), (float*)(pk + o_max), each ? (long long)n_words : 0);
         if (rc_) return rc_;
         // (the pinned buffer still holds what the H2D copies read: stream order puts the D2H copy behind them)
         HIP_TRY(hipMemcpyAsync(hp, pk, out_bytes, hipMemcpyDeviceToHost, s));
@@ -1031,6 +1057,8 @@ int32_t cmr_index_search_masked(cmr_index_t* idx, const float* q, int32_t nq, in
     if (out_max) memcpy(out_max, hp + o_max, (size_t)nq * 4);
     return CMR_OK;
 }
+
+extern "C" {
 
 int32_t cmr_index_search_min_score_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, float min_score, int64_t* ids_dev,
                                        float* scores_dev, void* stream) {
@@ -1411,6 +1439,91 @@ int32_t cmr_index_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t k
     key.w[0] = 1; key.w[1] = (uint64_t)k;
     idx->combiner.submit(key, &r, W, idx->combine_wait_us.load(std::memory_order_relaxed), combined_search_run, idx);
     return combine_result(r);
+}
+
+// ---- filtered host calls.  With "combine" >= 2 AND "combine_filtered" = 1, concurrent cmr_index_search_masked /
+// cmr_index_search_masked_each calls of one k and one word count share ONE per-query-mask search: the leader lays the participants'
+// queries and masks out as one [total][n_words] block (a shared-mask participant's words once per query of its own) and scatters the
+// rows, which hold the bits of each caller's solo call (4.15b's contract).  A batch of one is the caller's own call, unchanged.
+struct CombinedMasked { const float* q; int nq, k; const uint32_t* allow; int64_t n_words; bool each; int64_t* ids; float* scores; float* mn; float* mx; };
+
+static int masked_single(cmr_index* idx, const CombinedMasked& a) {
+    SyncCall call(idx);
+    const int rc = masked_check(idx, a.nq, a.k, a.n_words);
+    return rc ? rc : masked_sync(call, a.q, a.nq, a.k, a.allow, a.n_words, a.each, a.ids, a.scores, a.mn, a.mx);
+}
+
+// one lock for the batch; every participant's word count is judged under it (an append may have come in since it queued) and a
+// participant that fails is answered alone
+static void combined_masked_run(void* ctx, cmr_combine::Request** reqs, int n) {
+    cmr_index* const idx = (cmr_index*)ctx;
+    if (n == 1) { combine_answer(reqs[0], masked_single(idx, *(const CombinedMasked*)reqs[0]->args)); return; }
+    SyncCall call(idx);
+    cmr_combine::Request* live[cmr_combine::kMaxWidth];
+    int nl = 0, NQ = 0;
+    for (int i = 0; i < n; ++i) {
+        const CombinedMasked* a = (const CombinedMasked*)reqs[i]->args;
+        const int rc = masked_check(idx, a->nq, a->k, a->n_words);
+        if (rc) { combine_answer(reqs[i], rc); continue; }
+        live[nl++] = reqs[i];
+        NQ += reqs[i]->nq;
+    }
+    if (nl == 0) return;
+    const CombinedMasked* a0 = (const CombinedMasked*)live[0]->args;
+    if (nl == 1) { combine_answer(live[0], masked_sync(call, a0->q, a0->nq, a0->k, a0->allow, a0->n_words, a0->each, a0->ids, a0->scores, a0->mn, a0->mx)); return; }
+    const int k = a0->k;
+    const size_t dim = (size_t)idx->dim, nw = (size_t)a0->n_words;      // (k and the word count are part of the batch's key)
+    std::vector<float> q((size_t)NQ * dim), sc((size_t)NQ * k), mm((size_t)NQ * 2);
+    std::vector<int64_t> ids((size_t)NQ * k);
+    std::vector<uint32_t> words((size_t)NQ * nw);
+    for (int i = 0, at = 0; i < nl; at += live[i++]->nq) {
+        const CombinedMasked* a = (const CombinedMasked*)live[i]->args;
+        memcpy(q.data() + (size_t)at * dim, a->q, (size_t)a->nq * dim * 4);
+        for (int qi = 0; qi < a->nq; ++qi) memcpy(words.data() + (size_t)(at + qi) * nw, a->allow + (a->each ? (size_t)qi * nw : 0), nw * 4);
+    }
+    const int rc = masked_sync(call, q.data(), NQ, k, words.data(), (int64_t)nw, true, ids.data(), sc.data(), mm.data(), mm.data() + NQ);
+    for (int i = 0, at = 0; i < nl; at += live[i++]->nq) {
+        const CombinedMasked* a = (const CombinedMasked*)live[i]->args;
+        combine_answer(live[i], rc);
+        if (rc) continue;
+        const size_t nk = (size_t)a->nq * k;
+        memcpy(a->ids, ids.data() + (size_t)at * k, nk * 8);
+        memcpy(a->scores, sc.data() + (size_t)at * k, nk * 4);
+        if (a->mn) memcpy(a->mn, mm.data() + at, (size_t)a->nq * 4);
+        if (a->mx) memcpy(a->mx, mm.data() + NQ + at, (size_t)a->nq * 4);
+    }
+}
+
+static int32_t host_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words, bool each,
+                           int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+    if (!idx || !q || !allow || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
+    const CombinedMasked a{q, nq, k, allow, n_words, each, out_ids, out_scores, out_min, out_max};
+    const int W = idx->combine_filtered.load(std::memory_order_relaxed) ? idx->combine.load(std::memory_order_relaxed) : 0;
+    // joins a batch: as cmr_index_search — fewer queries than the batch holds, arguments that pass the checks which need no lock, finite queries
+    // (the batch carries one non-finite flag); everything else takes the single call and gets its result or its error there
+    if (!W || nq <= 0 || nq >= W || k <= 0 || k > CMR_MAX_K || n_words <= 0 || !cmr_combine::all_finite(q, (size_t)nq * idx->dim, idx->dtype))
+        return masked_single(idx, a);
+    {   // a word count the index refuses gets its error here, alone (the lock is let go before the call queues: a queued caller holds none)
+        std::shared_lock<std::shared_mutex> lk(idx->mu);
+        const int rc = masked_check(idx, nq, k, n_words);
+        if (rc) return rc;
+    }
+    cmr_combine::Request r;
+    r.args = (void*)&a; r.nq = nq;
+    cmr_combine::Key key;
+    key.w[0] = 5; key.w[1] = (uint64_t)k; key.w[2] = (uint64_t)n_words;      // (one kind for both forms: they share batches; never with kind 1, the unfiltered search)
+    idx->combiner.submit(key, &r, W, idx->combine_wait_us.load(std::memory_order_relaxed), combined_masked_run, idx);
+    return combine_result(r);
+}
+
+int32_t cmr_index_search_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words,
+                                int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+    return host_masked(idx, q, nq, k, allow, n_words, false, out_ids, out_scores, out_min, out_max);
+}
+
+int32_t cmr_index_search_masked_each(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words,
+                                     int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+    return host_masked(idx, q, nq, k, allow, n_words, true, out_ids, out_scores, out_min, out_max);
 }
 
 int32_t cmr_index_search_min_score(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, float min_score, int64_t* out_ids,

@@ -77,6 +77,9 @@ struct CmrScanArgs {
     // filtered scan (cmr_launch_scan_masked): one allow word per 32-row panel, [npanels] on the device — bit (r & 31) of word
     // (r >> 5) keeps local row r; bits beyond nrows are ignored.  Main pass and sampling passes take the same words.
     const unsigned* row_mask;
+    // per-query filtered scan (cmr_launch_scan_masked_each): row_mask is [nq][row_mask_stride] — query i's words start at
+    // row_mask + i * row_mask_stride (words; >= npanels), each block laid out as above.  Queries at or beyond nq have no words.
+    long long row_mask_stride;
 };
 // control words (ints) — every counter on a 128-byte line of its own: device atomics on one line serialise
 #define CMR_FIN_DONE 0        // workgroups whose waves have all published their first-panel maxima
@@ -96,6 +99,8 @@ hipError_t cmr_launch_scan_topk(const CmrScanGeom& g, const CmrScanArgs& a, hipS
 hipError_t cmr_launch_scan_scores(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);
 // cmr_launch_scan_topk among the rows a.row_mask keeps (geom.asm_ring is ignored: the compiler-counted ring)
 hipError_t cmr_launch_scan_masked(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);
+// the same with allow words of its own for every query of the pass (a.row_mask [a.nq][a.row_mask_stride])
+hipError_t cmr_launch_scan_masked_each(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);
 // top-k scan of <= 32 queries (k <= 64) that also derives its thresholds (no sampling launch) and selects the final k best per
 // query (no merge launch); a.fin[CMR_FIN_STATE] tells the merge launch behind it whether anything is left to do
 hipError_t cmr_launch_scan_fin(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s);

@@ -6,8 +6,10 @@
 // Slow path, part 1 (inline, a handful of registers, no waits on global memory): push the keys of
 // one 32x32 score tile that beat the lane's threshold into the (wave, query) lists.  Returns the
 // mask of this tile's queries whose list is nearly full.
-// `valid`: bit i = row row0 + i of the tile may be pushed (wave-uniform).  The corpus' last, partial panel is
-// topk_tail_mask(row0, nrows); a filtered scan ANDs its panel's word of the caller's allow bitmap into it.
+// `valid`: bit i = row row0 + i of the tile may be pushed for THIS LANE's query (lane & 31).  The corpus' last, partial panel is
+// topk_tail_mask(row0, nrows); a filtered scan ANDs its panel's word of the caller's allow bitmap into it — one word for the
+// whole wave (shared mask) or a word per query column (per-query masks): the shift and the compile-time bit tests below are
+// per lane either way.
 __device__ __forceinline__ unsigned topk_tail_mask(long long row0, long long nrows) {
     const long long left = nrows - row0;
     return left >= 32 ? 0xFFFFFFFFu : left <= 0 ? 0u : (1u << (int)left) - 1u;

@@ -22,6 +22,8 @@
 // Errors are per request: the owner's last-error text is thread-local, so the callback records code and text in the request and
 // each participant publishes them in its own thread after submit() returns.
 //
+// Filtered searches (cmr_index_search_masked, cmr_index_search_masked_each) are queued only where the index option "combine_filtered" is set:
+// a batch of them runs as ONE per-query-mask search, every query with its caller's mask.
 // Not combined (the owner never queues them): cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact,
 // cmr_graph_ppr, every _dev / pipelined call, cmr_mindex_* (searches through a multi-device handle do not pass here).  The encoder
 // does not pass here either: concurrent one-question encodes are combined one level up, by the Python restatement of this protocol

@@ -72,7 +72,7 @@ struct Workspace {
     bool fin_ctl_armed = false;      // scan with the finishing stage (cmr_launch_scan_fin)
     // host-API staging
     DevBuf d_q, d_ids, d_scores, d_min, d_max, d_cand, d_out;
-    DevBuf d_mask;               // cmr_index_search_masked: the call's allow words (a workspace per concurrent call, so a mask per call)
+    DevBuf d_mask;               // cmr_index_search_masked: the call's allow words (a workspace per concurrent call, so a mask per call); cmr_index_search_masked_each: [nq][n_words]
     // synchronous search: queries in, (ids | scores | min | max | non-finite flag) out through ONE pinned host buffer and
     // one copy each way — five pageable D2H copies cost more than the search of a small corpus
     DevBuf d_pack;
@@ -209,6 +209,9 @@ struct cmr_index {
     // ONE batched call (combine.h); combine_wait_us: the leader's gather window.  Read by the entry points before any lock.
     std::atomic<int> combine{0};
     std::atomic<long long> combine_wait_us{0};
+    // combine_filtered (0 | 1): with combine on, the filtered host calls (cmr_index_search_masked, cmr_index_search_masked_each) go through the
+    // combiner too and share one per-query-mask search.  Off: they never combine and never move the combiner's counters.
+    std::atomic<int> combine_filtered{0};
     cmr_combine::Combiner combiner;
     long long id_base = 0;   // added to every returned row id (global ids of a row shard)
     // A row shard that took incremental appends holds several runs of consecutive global ids (cmr_index_set_id_blocks): the

@@ -47,6 +47,12 @@
 // same variant with the same words indexed by the GLOBAL panel, so a sample's lists hold allowed rows only and its k-th best is a
 // lower bound of the filtered k-th best.  Compiler-counted ring only (ASMRING = 0).
 #define MODE_MASKED 3
+// MODE_MASKED_EACH: MODE_MASKED with allow words of its own for every query of the pass (cmr_index_search_masked_each*, DESIGN
+// 4.15b).  In the epilogue a lane owns one query column (lane & 31) of each 32 x 32 score tile, so the lane of query q loads
+// row_mask[q * mask_stride + p] (p: the GLOBAL panel, in a sampling pass too) and uses it where MODE_MASKED uses its wave-uniform
+// word.  The word of the NEXT panel is requested as soon as this panel's epilogue is through: it arrives with the ring's first
+// blocks, the epilogue never waits for a load of its own.  The shared-mask variant keeps its code: its word is one scalar load.
+#define MODE_MASKED_EACH 4
 
 // Cache policy of the corpus stream's loads: non-temporal.  Every byte of the corpus is read once per launch by one CU,
 // so keeping the lines in L2 / MALL only evicts what the other kernels of the pipeline use; measured against the default
@@ -93,6 +99,8 @@ struct ScanP {
     int* fin_done;         // mapped host word (or nullptr): the state once more, stored LAST — what a synchronous caller polls
     // MODE_MASKED
     const unsigned* row_mask;   // [npanels] allow words: bit (r & 31) of word (r >> 5) keeps local row r
+    // MODE_MASKED_EACH: row_mask is [nq][mask_stride], query q's words at row_mask + q * mask_stride
+    long long mask_stride;
 };
 
 // MODE_FIN: the threshold of query q from the published first-panel maxima of the ns supplying waves (one selection chunk:
@@ -122,7 +130,8 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
     constexpr int NQ = NQT * 32;
     constexpr bool TOPK = MODE != MODE_SCORES;
     constexpr bool FIN = MODE == MODE_FIN;
-    constexpr bool MASKED = MODE == MODE_MASKED;
+    constexpr bool EACH = MODE == MODE_MASKED_EACH;             // per-query allow words
+    constexpr bool MASKED = MODE == MODE_MASKED || EACH;
     static_assert(!FIN || NQT == 1, "the finishing stage handles one query tile");
     static_assert(!MASKED || !ASMRING, "the masked scan runs on the compiler-counted ring");
 
@@ -352,6 +361,18 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
         const long long ngroups = (long long)(p1 - p0) * GPP;
         int gi = 0;
         int p = p0;
+        // EACH: this lane's query's allow word of the current panel, per tile.  A lane whose query index is at or beyond the pass's
+        // query count must NOT load: row_mask holds nq blocks of mask_stride words and no more, so row_mask[q * mask_stride + p]
+        // of a padding query lies past the caller's array (a memory fault, not a wrong answer).  Such a lane keeps the word 0:
+        // no allowed row, nothing folded, nothing pushed.
+        [[maybe_unused]] unsigned mword[NQT];
+        if constexpr (EACH) {
+#pragma unroll
+            for (int t = 0; t < NQT; ++t) {
+                const int q = t * 32 + (lane & 31);
+                mword[t] = q < nq_g ? P.row_mask[(size_t)q * (size_t)P.mask_stride + (size_t)p] : 0u;
+            }
+        }
         [[maybe_unused]] unsigned fin_hint = 0u, fin_zoff = 0u;
         [[maybe_unused]] bool fin_hint_valid = false;
         asm volatile("" : "+v"(fin_zoff));
@@ -390,14 +411,23 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                 // MASKED: the rows of this panel that count — its word of the allow bitmap (p is the GLOBAL panel, in a sampling pass
                 // too; one wave-uniform load), less the rows beyond the corpus' end.  All ones: MODE_TOPK's own epilogue.
                 [[maybe_unused]] unsigned valid = 0xFFFFFFFFu;
-                if constexpr (MASKED) {
+                if constexpr (MASKED && !EACH) {
                     valid = (unsigned)__builtin_amdgcn_readfirstlane((int)P.row_mask[p]);
                     if (partial) valid &= topk_tail_mask(row0, P.nrows);
                 }
-                const bool whole = MASKED ? valid == 0xFFFFFFFFu : !partial;
-                [[maybe_unused]] const unsigned vh = valid >> (4 * (lane >> 5));      // this lane's half: the bit of accumulator register r at (r & 3) + 8 * (r >> 2)
+                [[maybe_unused]] bool whole = MASKED ? valid == 0xFFFFFFFFu : !partial;
+                [[maybe_unused]] unsigned vh = valid >> (4 * (lane >> 5));      // this lane's half: the bit of accumulator register r at (r & 3) + 8 * (r >> 2)
 #pragma unroll
                 for (int t = 0; t < NQT; ++t) {
+                    if constexpr (EACH) {
+                        // the lane's own word for this tile's query column (requested a panel ago), less the rows beyond the corpus' end.
+                        // `whole` must be wave-uniform: every query of the tile keeps all 32 rows (a padding lane's 0 stands for "no
+                        // query", not for "no row": it does not force the others onto the per-row path)
+                        valid = mword[t];
+                        if (partial) valid &= topk_tail_mask(row0, P.nrows);
+                        whole = __all(valid == 0xFFFFFFFFu || t * 32 + (lane & 31) >= nq_g);
+                        vh = valid >> (4 * (lane >> 5));
+                    }
                     float mx, mn;
                     if (whole) {
                         mx = acc[t][0]; mn = acc[t][0];
@@ -438,7 +468,9 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
                     }
                     // (MASKED: a panel whose allowed rows all miss the threshold stays on the fast path; one without allowed rows has
                     // mx = -inf, which "reaches" a threshold of -inf — nothing to push there)
-                    if ((!MASKED || valid != 0u) && __any(mx >= tau_f[t])) {
+                    // (EACH: valid is the lane's own, so the test is per lane — a lane without an allowed row has mx = -inf and must not
+                    // count as reaching its threshold of -inf)
+                    if (EACH ? __any(valid != 0u && mx >= tau_f[t]) : (!MASKED || valid != 0u) && __any(mx >= tau_f[t])) {
                         topk_slow_path<CAP>(acc[t], row0, MASKED ? valid : topk_tail_mask(row0, P.nrows), P.k, tau_key[t], tau_f[t], cnt_w + t * 32,
                                             list_w + (size_t)t * 32 * CAP, stage, lane);
                     }
@@ -555,6 +587,17 @@ __global__ __launch_bounds__(CMR_SCAN_THREADS, 2) void scan_kernel(ScanP P) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
             ++p;
+            if constexpr (EACH) {
+                // the next panel's words, in flight behind the ring's blocks (same guard as above; no panel beyond this wave's range:
+                // the last query's block ends with the corpus' last panel)
+                if (p < p1) {
+#pragma unroll
+                    for (int t = 0; t < NQT; ++t) {
+                        const int q = t * 32 + (lane & 31);
+                        mword[t] = q < nq_g ? P.row_mask[(size_t)q * (size_t)P.mask_stride + (size_t)p] : 0u;
+                    }
+                }
+            }
         }
         if constexpr (FIN && ASMRING) {
             // The ring prefetched R blocks past the end of the range and hipcc knows nothing of them: the selection code behind
@@ -776,7 +819,7 @@ static hipError_t launch_one(const CmrScanGeom& g, const ScanP& p, hipStream_t s
         return hipGetLastError();
     };
     // masked scans: the compiler-counted ring and the non-temporal policy only (one query group per pass: nobody re-reads a line)
-    if constexpr (MODE == MODE_MASKED) {
+    if constexpr (MODE == MODE_MASKED || MODE == MODE_MASKED_EACH) {
         return launch(scan_kernel<DT, NQT, CAP, R, MODE, 0>);
     } else {
         if constexpr (MODE == MODE_TOPK) {
@@ -794,7 +837,7 @@ template <int DT, int MODE>
 static hipError_t dispatch(const CmrScanGeom& g, const ScanP& p, hipStream_t s) {
 #define CASE(NQT, CAP, R) \
     if (g.nqt == NQT && g.cap == CAP && g.ring == R) return launch_one<DT, NQT, CAP, R, MODE>(g, p, s);
-    if constexpr (MODE == MODE_TOPK || MODE == MODE_MASKED) {
+    if constexpr (MODE == MODE_TOPK || MODE == MODE_MASKED || MODE == MODE_MASKED_EACH) {
         CASE(1, 128, 8) CASE(1, 128, 16) CASE(1, 256, 8) CASE(1, 256, 16)
         CASE(2, 128, 8) CASE(2, 128, 16) CASE(2, 256, 8) CASE(2, 256, 16)
     } else if constexpr (MODE == MODE_FIN) {
@@ -817,7 +860,7 @@ static ScanP to_p(const CmrScanGeom& g, const CmrScanArgs& a) {
     p.sample_waves = a.sample_waves; p.sample_stride = a.sample_stride; p.sample_chunk_log2 = a.sample_chunk_log2; p.tau_init = a.tau_init;
     p.slists = a.sample_lists; p.scnt = a.sample_cnt; p.sW = a.sample_W;
     p.qgroups = a.qgroups > 1 ? a.qgroups : 1;
-    p.row_mask = a.row_mask;
+    p.row_mask = a.row_mask; p.mask_stride = a.row_mask_stride;
     p.fin_mm = a.fin_mm;
     p.fin = a.fin; p.fin_pmax = a.fin_pmax; p.fin_tau = a.fin_tau; p.fin_dense = a.fin_dense; p.fin_wgs = a.fin_wgs; p.fin_mul = a.fin_mul; p.fin_dcap = a.fin_dcap; p.fin_spin = a.fin_spin; p.fin_done = a.fin_done; p.fin_first = a.fin_first;
     p.out_ids = a.out_ids; p.out_scores = a.out_scores; p.out_min = a.out_min; p.out_max = a.out_max; p.id_base = a.id_base;
@@ -1480,6 +1523,19 @@ hipError_t cmr_launch_scan_masked(const CmrScanGeom& g, const CmrScanArgs& a, hi
         case CMR_DT_BF16: return dispatch<CMR_DT_BF16, MODE_MASKED>(g, p, s);
         case CMR_DT_F16: return dispatch<CMR_DT_F16, MODE_MASKED>(g, p, s);
         case CMR_DT_F32: return dispatch<CMR_DT_F32, MODE_MASKED>(g, p, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// the same with a block of allow words per query (MODE_MASKED_EACH): a.row_mask [a.nq][a.row_mask_stride], stride >= npanels — the
+// kernel reads words [0, npanels) of blocks [0, nq) and nothing else
+hipError_t cmr_launch_scan_masked_each(const CmrScanGeom& g, const CmrScanArgs& a, hipStream_t s) {
+    if (!a.row_mask || a.qgroups > 1 || a.nq < 1 || a.nq > g.nqt * 32 || a.row_mask_stride < a.npanels) return hipErrorInvalidValue;
+    const ScanP p = to_p(g, a);
+    switch (g.dtype) {
+        case CMR_DT_BF16: return dispatch<CMR_DT_BF16, MODE_MASKED_EACH>(g, p, s);
+        case CMR_DT_F16: return dispatch<CMR_DT_F16, MODE_MASKED_EACH>(g, p, s);
+        case CMR_DT_F32: return dispatch<CMR_DT_F32, MODE_MASKED_EACH>(g, p, s);
     }
     return hipErrorInvalidValue;
 }

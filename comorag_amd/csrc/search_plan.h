@@ -79,6 +79,7 @@ struct PassRequest {
     int reserve_cus = 0;             // CUs the main scan leaves free (< 0: by corpus size)
     int prefilter = 0;               // the call may take the int8 pre-filter (prefilter_eligible, prefilter_host.h: 1; 2: with a filter that keeps every row) if the pass is eligible
     bool masked = false;             // filtered search (cmr_index_search_masked*): the narrow chain on the masked scan variant — no finishing stage, no pre-filter
+    bool masked_each = false;        // with masked: every query of the pass has allow words of its own (cmr_index_search_masked_each*)
 };
 
 struct PassPlan {
@@ -87,6 +88,7 @@ struct PassPlan {
     CmrScanGeom g{};                 // the main scan's, g.grid = its launch grid (all query groups)
     bool fin = false;                // scan with the finishing stage: no sampling launches, no merge of its own
     bool masked = false;             // every scan of the pass (sampling levels and main) is the masked variant over the caller's allow words
+    bool masked_each = false;        // ... the per-query variant: a block of allow words per query
     int prefilter = 0;               // 1 | 2: the int8 filter in the place of the main scan, the re-score in front of the merge (W: the re-score's lists)
     int rescore_grid = 0;
     int pair_cap = 0;                // pre-filter: hit records per query for the threshold tightening (0: none, every hit is re-scored)
@@ -114,7 +116,8 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
     const bool wide = rq.route == Route::wide, quad = rq.route == Route::quad;
     p.nqp = nqp; p.k = k; p.wide = wide;
     if (rq.masked && (wide || quad || rq.prefilter)) return cmr_fail(CMR_ERR_INVALID, "a filtered pass is a narrow pass without the pre-filter");
-    p.masked = rq.masked;
+    if (rq.masked_each && !rq.masked) return cmr_fail(CMR_ERR_INVALID, "per-query allow words belong to a filtered pass");
+    p.masked = rq.masked; p.masked_each = rq.masked_each;
     CmrScanGeom& g = p.g;
     const long long npanels = idx->npanels();
     int rc = make_geom(idx, quad ? std::min(nqp, idx->narrow_max()) : nqp, k, true, &g);
@@ -362,14 +365,14 @@ int plan_pass(const cmr_index* idx, const PassRequest& rq, PassPlan* out) {
 }
 
 // "last_route" (include/comorag_hip.h): path | sampling levels << 4 | tau_in_scan << 6 | single 128-panel level << 7 | query tiles per workgroup << 8 |
-// threshold search << 10 | filtered << 12 (| CMR_ROUTE_MORE_PASSES where the batch is cut into several passes: plan_and_enqueue_pass)
+// threshold search << 10 | filtered << 12 | filtered with per-query masks << 13 (| CMR_ROUTE_MORE_PASSES where the batch is cut into several passes: plan_and_enqueue_pass)
 long long route_code(int path, int n_levels = 0, bool tau_in_scan = false, bool single_level = false, int nqt = 1, bool threshold = false) {
     return (long long)path | ((long long)n_levels << 4) | ((long long)(tau_in_scan ? 1 : 0) << 6) | ((long long)(single_level ? 1 : 0) << 7) | ((long long)nqt << 8) |
            ((long long)(threshold ? 1 : 0) << 10);
 }
 long long route_code(const PassPlan& p, bool threshold) {
     const int path = p.wide ? CMR_ROUTE_WIDE : p.G > 1 ? CMR_ROUTE_QUERY_SPLIT : p.fin ? CMR_ROUTE_FIN : CMR_ROUTE_CHAIN;
-    return route_code(path, p.n_levels, p.tau_in_scan, p.single_level, p.g.nqt, threshold) | (p.masked ? CMR_ROUTE_FILTERED : 0);
+    return route_code(path, p.n_levels, p.tau_in_scan, p.single_level, p.g.nqt, threshold) | (p.masked ? CMR_ROUTE_FILTERED : 0) | (p.masked_each ? CMR_ROUTE_FILTERED_EACH : 0);
 }
 
 // ---- a batch splits into passes

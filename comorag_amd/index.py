@@ -67,6 +67,23 @@ def pack_row_mask(n_rows: int, allow=None, exclude=None) -> np.ndarray:
     return np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32, copy=False)
 
 
+def pack_row_masks(n_rows: int, allow=None, exclude=None) -> np.ndarray:
+    """Allow bitmaps of a per-query filtered search (`DenseIndex.search_filtered_each`, cmr_index_search_masked_each): uint32
+    [nq, ceil(n_rows / 32)], row i exactly `pack_row_mask(n_rows, allow=allow[i])` (or `exclude=exclude[i]`).  `allow` / `exclude`: a
+    sequence with one entry per query, each whatever `pack_row_mask` takes (a 2-d bool array [nq, n_rows] is a sequence of bool rows).
+    Exactly one of the two must be given: the number of queries comes from its length."""
+    if (allow is None) == (exclude is None):
+        raise ValueError("give allow or exclude (one entry per query), not both and not neither")
+    per_query = allow if allow is not None else exclude
+    if isinstance(per_query, (str, bytes)) or not hasattr(per_query, "__len__"):
+        raise ValueError("allow / exclude must be a sequence with one entry per query")
+    n_words = (int(n_rows) + 31) // 32
+    out = np.zeros((len(per_query), n_words), dtype=np.uint32)
+    for i, entry in enumerate(per_query):
+        out[i] = pack_row_mask(n_rows, allow=entry) if allow is not None else pack_row_mask(n_rows, exclude=entry)
+    return out
+
+
 def _mask_popcount(words: np.ndarray, n_rows: int) -> int:
     """Set bits among the first n_rows of an allow bitmap (bits at or beyond n_rows do not count)."""
     if len(words) == 0:
@@ -272,7 +289,7 @@ class DenseIndex(HostArrayIndex):
 
     def combine_stats(self) -> dict:
         """Counters of the combiner (option "combine" = 2..16: concurrent single search / scores / PPR calls of this index's callers share
-        one batched call): device calls made for combined work, queries served by them, the widest batch so far."""
+        one batched call; with "combine_filtered" = 1 the filtered searches too): device calls made for combined work, queries served by them, the widest batch so far."""
         return {name: self.get_option("combine_" + name) for name in ("batches", "queries", "max_width")}
 
     def append_dev(self, rows_t, stream: Optional[int] = None) -> None:
@@ -380,6 +397,57 @@ class DenseIndex(HostArrayIndex):
             stream = torch.cuda.current_stream(dev).cuda_stream
         L.check(L.lib().cmr_index_search_masked_dev(
             self._h, C.c_void_p(q_t.data_ptr()), nq, k, C.c_void_p(mask_t.data_ptr()), mask_t.shape[0],
+            C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
+            C.c_void_p(out_min.data_ptr()) if out_min is not None else None,
+            C.c_void_p(out_max.data_ptr()) if out_max is not None else None, C.c_void_p(stream)))
+        return out_ids, out_scores
+
+    # -- filtered search with a mask per query (cmr_index_search_masked_each*)
+    def search_filtered_each(self, q, k: int, masks=None, *, allow=None, exclude=None, with_minmax: bool = True
+                             ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """`search_filtered` with an allow bitmap of its own for every query, in ONE corpus pass: row i is bit for bit what
+        `search_filtered(q[i:i+1], k, mask=masks[i])` returns — every question of a ComoRAG batch (ComoRAG.try_answer, ComoRAG.py:432-453)
+        has its own memory pool to keep out of tri_retrieve's top-k; so have the namespaces of one serving index.  `masks`: uint32
+        [nq, ceil(len / 32)] as `pack_row_masks` lays them out, or give `allow` / `exclude` with one entry per query.  k <= 128.
+        → (ids [nq,k], raw scores [nq,k], min [nq], max [nq]): always k columns, -1 / -inf padded behind a query's allowed rows (the
+        counts differ per query); min / max over that query's allowed rows (+inf / -inf when it allows none)."""
+        n = len(self)
+        q = self._queries(q)
+        nq = q.shape[0]
+        if masks is None:
+            masks = pack_row_masks(n, allow=allow, exclude=exclude)
+        elif allow is not None or exclude is not None:
+            raise ValueError("give masks or allow / exclude, not both")
+        masks = np.ascontiguousarray(masks, dtype=np.uint32)
+        if masks.ndim != 2 or masks.shape != (nq, (n + 31) // 32):
+            raise ValueError(f"masks must be uint32 [{nq}, {(n + 31) // 32}] (one row of pack_row_mask words per query), got {masks.shape}")
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        mn = np.empty(nq, dtype=np.float32) if with_minmax else None
+        mx = np.empty(nq, dtype=np.float32) if with_minmax else None
+        L.check(L.lib().cmr_index_search_masked_each(self._h, _ptr(q), nq, k, _ptr(masks), masks.shape[1], _ptr(ids), _ptr(sc),
+                                                     _ptr(mn) if with_minmax else None, _ptr(mx) if with_minmax else None))
+        return ids, sc, mn, mx
+
+    def search_filtered_each_dev(self, q_t, k: int, masks_t, out_ids=None, out_scores=None, out_min=None, out_max=None,
+                                 stream: Optional[int] = None):
+        """`search_filtered_each` on torch CUDA tensors, enqueued on torch's current stream without synchronising (as
+        `search_filtered_dev`).  masks_t: the words of `pack_row_masks` on the device — int32 or uint32, contiguous,
+        [nq, ceil(len / 32)], read in place.  → (out_ids [nq,k], out_scores [nq,k]), -1 / -inf padded."""
+        import torch
+        assert q_t.is_cuda and q_t.dtype == torch.float32 and q_t.is_contiguous() and q_t.shape[1] == self.dim
+        assert masks_t.is_cuda and masks_t.element_size() == 4 and not masks_t.dtype.is_floating_point and masks_t.is_contiguous()
+        nq, dev = q_t.shape[0], q_t.device
+        if masks_t.dim() != 2 or masks_t.shape[0] != nq:
+            raise ValueError(f"masks_t must be [{nq}, n_words], got {tuple(masks_t.shape)}")
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().cmr_index_search_masked_each_dev(
+            self._h, C.c_void_p(q_t.data_ptr()), nq, k, C.c_void_p(masks_t.data_ptr()), masks_t.shape[1],
             C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
             C.c_void_p(out_min.data_ptr()) if out_min is not None else None,
             C.c_void_p(out_max.data_ptr()) if out_max is not None else None, C.c_void_p(stream)))

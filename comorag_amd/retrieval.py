@@ -77,6 +77,20 @@ def dense_passage_topk_filtered(index: DenseIndex, query_embeddings, k: int, exc
     return ids, norm.astype(np.float32)
 
 
+def dense_passage_topk_filtered_each(index: DenseIndex, query_embeddings, k: int, exclude_rows=None, allow_rows=None
+                                     ) -> Tuple[np.ndarray, np.ndarray]:
+    """`dense_passage_topk_filtered` for a batch of questions with a memory pool each (ComoRAG.try_answer answers up to 16 at once,
+    ComoRAG.py:432-453): `exclude_rows` / `allow_rows` hold one entry per query (local row ids, or a bool array), and ONE corpus pass
+    serves them all.  Every query's scores are min-max normalised from the min / max over ITS allowed rows with the reference formula.
+    ids [nq,k], scores [nq,k]; behind a query's allowed rows the ids are -1 and the scores -inf."""
+    ids, sc, mn, mx = index.search_filtered_each(_as_query(query_embeddings), k, allow=allow_rows, exclude=exclude_rows)
+    rng = (mx - mn)[:, None]
+    flat = (rng == 0) | ~np.isfinite(rng)          # (no allowed row: min = +inf, max = -inf, the row is all padding)
+    with np.errstate(invalid="ignore"):
+        norm = np.where(flat, np.ones_like(sc), (sc - np.where(flat, 0, mn[:, None])) / np.where(flat, 1, rng))
+    return ids, np.where(ids < 0, -np.inf, norm).astype(np.float32)
+
+
 def get_fact_scores(index: Optional[DenseIndex], query_embedding) -> np.ndarray:
     """ComoRAG.get_fact_scores (ComoRAG.py:937-948): full normalised vector over the fact matrix."""
     if index is None or len(index) == 0:

@@ -160,9 +160,9 @@ int32_t cmr_index_search_dev(cmr_index_t* idx, const float* q_f32_dev, int32_t n
  *   cmr_index_search does; the _dev form as the other _dev calls do (cmr_index_query_status).
  * Route: always the narrow kernel's pack / [sample] / scan / merge chain on the masked variant of the scan — the panel's word stands
  * wherever the scan tests "row < rows" (min / max, threshold test, candidate push), the sampling passes read the same words, so their
- * thresholds are bounds among ALLOWED rows.  A filtered call never joins a combined batch ("combine"), never takes the int8
- * pre-filter, the single-launch paths or the finishing stage, and changes nothing any other call returns.  last_route: CMR_ROUTE_CHAIN
- * with CMR_ROUTE_FILTERED set.
+ * thresholds are bounds among ALLOWED rows.  A filtered call joins a combined batch only where "combine_filtered" is set (see
+ * "combine" below; by default never), never takes the int8 pre-filter, the single-launch paths or the finishing stage, and changes
+ * nothing any other call returns.  last_route: CMR_ROUTE_CHAIN with CMR_ROUTE_FILTERED set.
  * The host form uploads the words into scratch of its own call (concurrent calls each have theirs); the _dev form reads the caller's
  * device words in place on `stream` — a caller that reuses one mask (a namespace, the pool's exclusion set) uploads it once.          */
 int32_t cmr_index_search_masked(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k,
@@ -173,6 +173,30 @@ int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_f32_dev, in
                                     const uint32_t* allow_words_dev, int64_t n_words,
                                     int64_t* out_ids_dev, float* out_scores_dev,
                                     float* out_min_dev, float* out_max_dev, void* stream);
+
+/* Filtered search with an allow bitmap PER QUERY: ComoRAG answers up to 16 questions at once (ComoRAG.try_answer,
+ * ComoRAG.py:432-453), every question with a memory pool of its own, so the rows to keep out of tri_retrieve's top-k differ per query; a
+ * serving process with several namespaces in one index has the same shape.  One corpus pass serves the batch where B one-query
+ * cmr_index_search_masked calls read the corpus B times.
+ *   allow_words  [nq][n_words], query-major and contiguous: query i's words at allow_words + i * n_words, each block exactly one
+ *                cmr_index_search_masked bitmap (n_words == ceil(size / 32)).
+ *   result       row i is bit for bit what cmr_index_search_masked(q + i * dim, 1, k, allow_words + i * n_words, ...) returns: ids, score
+ *                bits, out_min[i] / out_max[i] over the rows query i allows, -1 / -inf padding.  A query that allows nothing gets all
+ *                padding, min = +inf, max = -inf (the call still returns CMR_OK) and does not disturb its neighbours.
+ *   Argument rules, non-finite queries and the _dev form's conventions are those of cmr_index_search_masked; any nq >= 1 (batches above
+ *   the narrow kernel's width run as several passes, each on its own queries' words).
+ * Route: the same chain on the per-query variant of the masked scan — in the scan's epilogue a lane owns one query column of the score
+ * tile and loads that query's word of the panel; sampling passes read the same words, so each query's threshold is a bound among ITS
+ * allowed rows.  last_route: CMR_ROUTE_CHAIN | CMR_ROUTE_FILTERED | CMR_ROUTE_FILTERED_EACH.
+ * The host form uploads all nq blocks into scratch of its own call; the _dev form reads the caller's device words in place.
+ * Not filtered, as before: cmr_mindex_*, the pipelined, exact, sorted, threshold and all-scores calls, PageRank.                    */
+int32_t cmr_index_search_masked_each(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k,
+                                     const uint32_t* allow_words, int64_t n_words,
+                                     int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
+int32_t cmr_index_search_masked_each_dev(cmr_index_t* idx, const float* q_f32_dev, int32_t nq, int32_t k,
+                                         const uint32_t* allow_words_dev, int64_t n_words,
+                                         int64_t* out_ids_dev, float* out_scores_dev,
+                                         float* out_min_dev, float* out_max_dev, void* stream);
 
 /* Throughput mode for a stream of independent query batches (serving; bench.py).  Work is enqueued on streams owned by
  * the index: query packing + sampling passes of batch i+1 overlap the HBM-bound main scan of batch i.  On a 256-CU device
@@ -243,7 +267,12 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  * batches form only from calls that arrive while an earlier batch is on the device, and a caller alone runs its unchanged single call.
  * A call with a NaN / Inf query, or with arguments the call refuses, never joins a batch: it gets its own error.
  * Read-only: "combine_batches" (device calls made for combined work), "combine_queries" (queries they served), "combine_max_width".
- * NOT combined: cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
+ * "combine_filtered" = 0 (default) | 1: with "combine" on, cmr_index_search_masked and cmr_index_search_masked_each calls (same k, same
+ * n_words, k <= CMR_MAX_K, nq < W) are combined too — with each other, never with unfiltered calls: the batch runs as ONE
+ * cmr_index_search_masked_each over the participants' queries, every query with its caller's mask (a shared mask repeated per query), and
+ * each caller gets the bits of its own call.  A participant whose n_words no longer fits the index when the batch runs (an append came in
+ * between) gets its own CMR_ERR_INVALID; the others are served.  At 0 filtered calls never join a batch and never move the counters.
+ * NOT combined: cmr_index_search_masked* unless "combine_filtered" is set, cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
  * cmr_mindex_* (the option has no effect on searches issued through a multi-device handle).  The encoder is not combined HERE: concurrent
  * one-question encodes share one forward through the Python-level option `embedding_combine` (cmr_encoder_linear_rows* below).      */
 /* Which path served the last call (read-only): "last_route", written by the host when a search or all-scores call on this index is
@@ -255,9 +284,11 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  *   bits 8..9   query tiles of 32 per workgroup (1, 2)
  *   bit  10     threshold search (cmr_index_search_min_score*)
  *   bit  11     the batch took more than one corpus pass: the bits above describe its first, later passes may be routed otherwise
- *   bit  12     filtered search (cmr_index_search_masked*): every scan of the pass is the masked variant                            */
+ *   bit  12     filtered search (cmr_index_search_masked*): every scan of the pass is the masked variant
+ *   bit  13     with bit 12: the per-query variant (cmr_index_search_masked_each*, or a combined batch of filtered calls)             */
 #define CMR_ROUTE_MORE_PASSES (1 << 11)
 #define CMR_ROUTE_FILTERED (1 << 12)
+#define CMR_ROUTE_FILTERED_EACH (1 << 13)
 #define CMR_ROUTE_TINY 1          /* single launch, <= 1024 rows */
 #define CMR_ROUTE_SMALL 2         /* single launch, hierarchical selection */
 #define CMR_ROUTE_CHAIN 3         /* narrow kernel: pack / [sample] / scan / merge */
