@@ -18,6 +18,7 @@ CMR_ERR_INVALID, CMR_ERR_NO_DEVICE, CMR_ERR_HIP, CMR_ERR_OOM, CMR_ERR_NONFINITE,
 CMR_F32, CMR_BF16, CMR_F16 = 0, 1, 2
 CMR_FLAG_KEEP_F32 = 1
 CMR_MAX_K = 128
+CMR_IDS_EXCLUDE, CMR_IDS_ALLOW = 0, 1     # cmr_index_search_ids*: mode
 ABI_VERSION = 2        # include/comorag_hip.h: CMR_ABI_VERSION
 CMR_MAX_K_2PASS = 4096
 CMR_MAX_K_EXACT = 64      # cmr_index_search_exact
@@ -59,6 +60,9 @@ SIGNATURES = {
     "cmr_index_search_masked_dev": (_i32, [_p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p]),
     "cmr_index_search_masked_each": (_i32, [_p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p]),
     "cmr_index_search_masked_each_dev": (_i32, [_p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p]),
+    "cmr_index_row_masks_dev": (_i32, [_p, _i32, _i32, _p, _p, _i64, _p, _i64, _p]),
+    "cmr_index_search_ids": (_i32, [_p, _p, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p]),
+    "cmr_index_search_ids_dev": (_i32, [_p, _p, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "cmr_index_search_pipelined": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _P(_p)]),
     "cmr_index_set_id_base": (_i32, [_p, _i64]),
     "cmr_index_set_id_blocks": (_i32, [_p, _i32, _p, _p]),
@@ -105,6 +109,7 @@ SIGNATURES = {
     "cmr_mindex_append": (_i32, [_p, _p, _i64]),
     "cmr_mindex_append_dev": (_i32, [_p, _p, _i64, _i32, _p]),
     "cmr_mindex_search": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p]),
+    "cmr_mindex_search_ids": (_i32, [_p, _p, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p]),
     "cmr_mindex_search_min_score": (_i32, [_p, _p, _i32, _i32, _f32, _p, _p]),
     "cmr_mindex_scores": (_i32, [_p, _p, _i32, _p, _i64]),
     "cmr_mindex_sorted_scores": (_i32, [_p, _p, _i32, _p, _p, _p, _p]),

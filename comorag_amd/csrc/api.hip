@@ -1363,6 +1363,162 @@ void cmr_index_search_abandon(CmrPending* P) {
     pending_release(P);
 }
 
+// ---- filtered search from row-id lists (include/comorag_hip.h: cmr_index_row_masks_dev, cmr_index_search_ids*).  The
+// caller hands over row ids in the domain the searches return; the device builds the allow words next to the corpus (aux_kernels.hip:
+// row_mask_fill, row_mask_apply_ids) and the masked scans of 4.15 / 4.15b run on them unchanged.  Never combined.
+
+// every check of the id-list calls that needs neither the index nor a device; off_host: CSR offsets the host can read (nullptr: a shared
+// list, or device offsets, which the kernel clamps instead)
+int cmr_ids_args_check(int mode, int nq, int k, const int64_t* off_host, const int64_t* ids, int64_t n_ids) {
+    if (mode != CMR_IDS_EXCLUDE && mode != CMR_IDS_ALLOW) return fail(CMR_ERR_INVALID, "mode %d is neither CMR_IDS_EXCLUDE nor CMR_IDS_ALLOW", mode);
+    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
+    if (k <= 0) return fail(CMR_ERR_INVALID, "k must be > 0");
+    if (n_ids < 0) return fail(CMR_ERR_INVALID, "n_ids %lld < 0", (long long)n_ids);
+    if (n_ids > 0 && !ids) return fail(CMR_ERR_INVALID, "NULL ids with n_ids = %lld", (long long)n_ids);
+    if (off_host) {
+        if (off_host[0] != 0) return fail(CMR_ERR_INVALID, "id_offsets[0] = %lld, not 0", (long long)off_host[0]);
+        for (int i = 0; i < nq; ++i)
+            if (off_host[i + 1] < off_host[i]) return fail(CMR_ERR_INVALID, "id_offsets decrease at query %d (%lld after %lld)", i, (long long)off_host[i + 1], (long long)off_host[i]);
+        if (off_host[nq] != n_ids) return fail(CMR_ERR_INVALID, "id_offsets[nq] = %lld, not n_ids = %lld", (long long)off_host[nq], (long long)n_ids);
+    }
+    if (k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "filtered search supports k <= %d", CMR_MAX_K);
+    return CMR_OK;
+}
+
+namespace {
+
+constexpr int kIdsGroup = 64;      // queries whose words are built and scanned together: the scratch never holds more than this many masks
+
+// words [nm][npanels] (nm = nq with offsets, 1 without) from the lists, on s
+int row_masks_enqueue(cmr_index* idx, int mode, int nq, const int64_t* off_dev, const int64_t* ids_dev, int64_t n_ids, unsigned* words, hipStream_t s) {
+    const int nm = off_dev ? nq : 1, nb = (int)idx->blk_local.size(), exclude = mode == CMR_IDS_EXCLUDE;
+    HIP_TRY(cmr_launch_row_mask_fill(words, nm, idx->npanels(), idx->n, exclude, s));
+    HIP_TRY(cmr_launch_row_mask_apply_ids(words, idx->npanels(), idx->n, exclude, (const long long*)off_dev, nm, (const long long*)ids_dev, n_ids,
+                                          kernel_id_base(idx), nb > 1 ? idx->d_blk : nullptr, nb, s));
+    return CMR_OK;
+}
+
+// Build and scan on ws->stream.  A shared list: one mask in ws->d_mask, every query on the shared-mask scan.  Per-query lists: groups of
+// kIdsGroup queries, each group's words built into the same scratch behind the previous group's scan (stream order) and scanned by the
+// per-query variant; a query's row does not depend on the group it falls into.
+int search_ids_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, int k, int mode, const int64_t* off_dev, const int64_t* ids_dev,
+                       int64_t n_ids, int64_t* ids_out, float* scores_out, float* min_out, float* max_out) {
+    const long long nw = idx->npanels();
+    const int group = off_dev ? kIdsGroup : nq;
+    HIP_TRY(ws->d_mask.ensure(std::max<size_t>((size_t)(off_dev ? std::min(nq, kIdsGroup) : 1) * (size_t)nw * 4, 4)));
+    unsigned* const words = (unsigned*)ws->d_mask.p;
+    long long route = 0;
+    for (int q0 = 0; q0 < nq; q0 += group) {
+        const int nqg = std::min(group, nq - q0);
+        int rc = row_masks_enqueue(idx, mode, nqg, off_dev ? off_dev + q0 : nullptr, ids_dev, n_ids, words, ws->stream);
+        if (rc) return rc;
+        rc = search_masked_enqueue(idx, ws, q_dev + (size_t)q0 * idx->dim, nqg, k, words, ids_out + (size_t)q0 * k, scores_out + (size_t)q0 * k,
+                                   min_out ? min_out + q0 : nullptr, max_out ? max_out + q0 : nullptr, off_dev ? nw : 0);
+        if (rc) return rc;
+        if (q0 == 0) route = idx->last_route.load(std::memory_order_relaxed);
+    }
+    idx->last_route.store(route | CMR_ROUTE_FILTERED_IDS | (group < nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
+    return CMR_OK;
+}
+
+}  // namespace
+
+// cmr_index_search_ids in two halves, as cmr_index_search_begin: arguments checked by the caller (cmr_ids_args_check); finished or
+// abandoned through cmr_index_search_finish / _abandon.  Queries, offsets and ids go up through the pinned buffer into this workspace's
+// scratch, the results come back by one copy.
+int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, int mode, const int64_t* off, const int64_t* ids, int64_t n_ids,
+                               bool take_lock, CmrPending** out) {
+    if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    CmrPending* P = new CmrPending();
+    P->idx = idx; P->nq = nq; P->k = k;
+    if (take_lock) { idx->mu.lock_shared(); P->locked = true; }
+    int rc = cmr_set_device(idx->device);
+    if (rc) { pending_release(P); return rc; }
+    Workspace* ws = acquire_ws(idx, nullptr, false);
+    if (!ws) { pending_release(P); return fail(CMR_ERR_HIP, "could not create a workspace stream"); }
+    P->ws = ws;
+    hipStream_t s = ws->stream;
+    // packed result buffer [flag (8 B) | ids nq*k i64 | scores nq*k f32 | min nq | max nq]; inputs [queries | offsets (nq + 1) | ids]
+    const size_t o_ids = 8, o_sc = o_ids + (size_t)nq * k * 8, o_min = o_sc + (size_t)nq * k * 4, o_max = o_min + (size_t)nq * 4,
+                 out_bytes = o_max + (size_t)nq * 4, q_bytes = (size_t)nq * idx->dim * 4, o_list = (q_bytes + 7) & ~(size_t)7,
+                 off_bytes = off ? ((size_t)nq + 1) * 8 : 0, list_bytes = off_bytes + (size_t)n_ids * 8;
+    P->o_ids = o_ids; P->o_sc = o_sc; P->o_min = o_min; P->o_max = o_max;
+    auto body = [&]() -> int {
+        HIP_TRY(ws->d_q.ensure(q_bytes));
+        HIP_TRY(ws->d_lists.ensure(std::max<size_t>(list_bytes, 8)));
+        if (out_bytes > ws->d_pack.cap || !ws->d_pack.p) {        // (re)allocation moves the flag: re-arm it at the new place
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(ws->d_pack.ensure(std::max<size_t>(out_bytes, 4096)));
+            HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, 8, s));
+        }
+        char* const pk = (char*)ws->d_pack.p;
+        FlagOverride flag(ws, (int*)pk);
+        HIP_TRY(ws->ensure_pin(std::max(out_bytes, o_list + list_bytes)));
+        char* const hp = (char*)ws->h_pin;
+        memcpy(hp, q, q_bytes);
+        if (off) memcpy(hp + o_list, off, off_bytes);
+        if (n_ids) memcpy(hp + o_list + off_bytes, ids, (size_t)n_ids * 8);
+        HIP_TRY(hipMemcpyAsync(ws->d_q.p, hp, q_bytes, hipMemcpyHostToDevice, s));
+        if (list_bytes) HIP_TRY(hipMemcpyAsync(ws->d_lists.p, hp + o_list, list_bytes, hipMemcpyHostToDevice, s));
+        const int64_t* const d_off = off ? (const int64_t*)ws->d_lists.p : nullptr;
+        const int rc_ = search_ids_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, mode, d_off, (const int64_t*)((char*)ws->d_lists.p + off_bytes), n_ids,
+                                           (int64_t*)(pk + o_ids), (float*)(pk + o_sc), (float*)(pk + o_min), (float*)(pk + o_max));
+        if (rc_) return rc_;
+        // (the pinned buffer still holds what the H2D copies read: stream order puts the D2H copy behind them)
+        HIP_TRY(hipMemcpyAsync(hp, pk, out_bytes, hipMemcpyDeviceToHost, s));
+        return CMR_OK;
+    };
+    rc = body();
+    if (rc) { (void)hipStreamSynchronize(s); pending_release(P); return rc; }
+    *out = P;
+    return CMR_OK;
+}
+
+extern "C" {
+
+int32_t cmr_index_row_masks_dev(cmr_index_t* idx, int32_t mode, int32_t nq, const int64_t* id_offsets_dev, const int64_t* ids_dev, int64_t n_ids,
+                                uint32_t* words_dev, int64_t n_words, void* stream) {
+    if (!words_dev) return fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = cmr_ids_args_check(mode, nq, 1, nullptr, ids_dev, n_ids);
+    if (rc) return rc;
+    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if (n_words != panels_of(idx->n)) return fail(CMR_ERR_INVALID, "n_words %lld != ceil(%lld rows / 32) = %lld", (long long)n_words, idx->n, panels_of(idx->n));
+    rc = cmr_set_device(idx->device);
+    if (rc) return rc;
+    return row_masks_enqueue(idx, mode, nq, id_offsets_dev, ids_dev, n_ids, words_dev, (hipStream_t)stream);
+}
+
+int32_t cmr_index_search_ids_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets_dev,
+                                 const int64_t* ids_dev, int64_t n_ids, int64_t* ids_out_dev, float* scores_out_dev, float* min_dev, float* max_dev,
+                                 void* stream) {
+    if (!q_dev || !ids_out_dev || !scores_out_dev) return fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = cmr_ids_args_check(mode, nq, k, nullptr, ids_dev, n_ids);
+    if (rc) return rc;
+    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    rc = cmr_set_device(idx->device);
+    if (rc) return rc;
+    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
+    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
+    return search_ids_enqueue(idx, ws, q_dev, nq, k, mode, id_offsets_dev, ids_dev, n_ids, ids_out_dev, scores_out_dev, min_dev, max_dev);
+}
+
+int32_t cmr_index_search_ids(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
+                             int64_t n_ids, int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+    if (!q || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = cmr_ids_args_check(mode, nq, k, id_offsets, ids, n_ids);
+    if (rc) return rc;
+    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
+    CmrPending* p = nullptr;
+    rc = cmr_index_search_ids_begin(idx, q, nq, k, mode, id_offsets, ids, n_ids, true, &p);
+    if (rc) return rc;
+    return cmr_index_search_finish(p, out_ids, out_scores, out_min, out_max);
+}
+
+}  // extern "C"
+
 // roll a shard back to n_rows (multi.hip: an append that failed on a later shard).  Slots beyond n_rows keep stale data:
 // every kernel masks by row index, and the next append rewrites them.
 int cmr_index_truncate(cmr_index_t* idx, long long n_rows) {

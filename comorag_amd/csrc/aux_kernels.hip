@@ -870,6 +870,84 @@ hipError_t cmr_launch_remap_ids(int64_t* ids, long long n, const long long* tab,
 }
 
 // ------------------------------------------------------------------------------------------
+// Allow words of a filtered search from row-id lists (cmr_index_row_masks_dev / cmr_index_search_ids*): fill, then
+// one bit per list entry.  words is [nq_masks][n_words], one uint32 per 32-row panel over the LOCAL rows [0, size).
+// fill: exclude mode starts from every row (bits at or beyond `size` in the last word zero, as pack_row_mask leaves them), allow
+// mode from none.
+__global__ __launch_bounds__(256) void row_mask_fill_kernel(unsigned* __restrict__ words, long long nq_masks, long long n_words, long long size, int exclude) {
+    const int tail = (int)(size & 31);
+    for (long long m = blockIdx.y; m < nq_masks; m += gridDim.y)
+        for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n_words; p += (long long)gridDim.x * 256)
+            words[m * n_words + p] = !exclude ? 0u : p * 32 + 32 <= size ? 0xFFFFFFFFu : p * 32 < size ? (1u << tail) - 1u : 0u;
+}
+
+// One list entry per thread, grid-strided over the entries [off[0], off[nq]) of `nq` queries (off == nullptr: ONE list of n_ids
+// entries, mask 0).  The entry's query is found by binary search over off[0 .. nq] and clamped into [0, nq); the entry range is
+// clamped into [0, n_ids] — offsets of any content (the _dev forms cannot check theirs) give unspecified words, never an access
+// outside ids[0, n_ids) or words[0, nq * n_words).  The id is translated as the search results are (id_base, or the block table
+// tab = [local0[nb] | global0[nb]]); a negative id, or one this index does not hold (beyond the last row, in a gap between
+// blocks, on another shard), is skipped.  OR / AND without a return value: they commute, so neither the order of the threads nor
+// duplicates change a word.
+__global__ __launch_bounds__(256) void row_mask_apply_ids_kernel(unsigned* __restrict__ words, long long n_words, long long size, int exclude,
+                                                                 const long long* __restrict__ off, int nq, const long long* __restrict__ ids,
+                                                                 long long n_ids, long long id_base, const long long* __restrict__ tab, int nb) {
+    long long e0 = 0, e1 = n_ids;
+    if (off) {
+        const long long a = off[0], b = off[nq];
+        e0 = a < 0 ? 0 : a > n_ids ? n_ids : a;
+        e1 = b < e0 ? e0 : b > n_ids ? n_ids : b;
+    }
+    const long long step = (long long)gridDim.x * 256;
+    for (long long e = e0 + (long long)blockIdx.x * 256 + threadIdx.x; e < e1; e += step) {
+        const long long id = ids[e];
+        if (id < 0) continue;
+        int qi = 0;
+        if (off) {                               // last query with off[qi] <= e
+            int lo = 0, hi = nq - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (off[mid] <= e) lo = mid; else hi = mid - 1;
+            }
+            qi = lo;
+        }
+        long long r;
+        if (nb <= 1) {
+            if (id < id_base) continue;
+            r = id - id_base;
+        } else {
+            int lo = 0, hi = nb - 1;             // last block with global0 <= id
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (tab[nb + mid] <= id) lo = mid; else hi = mid - 1;
+            }
+            if (id < tab[nb + lo]) continue;
+            const long long d = id - tab[nb + lo];
+            const long long room = (lo + 1 < nb ? tab[lo + 1] : size) - tab[lo];
+            if (d >= room) continue;
+            r = tab[lo] + d;
+        }
+        if (r < 0 || r >= size || (r >> 5) >= n_words) continue;
+        unsigned* const w = words + (size_t)qi * (size_t)n_words + (size_t)(r >> 5);
+        const unsigned bit = 1u << (unsigned)(r & 31);
+        if (exclude) atomicAnd(w, ~bit); else atomicOr(w, bit);
+    }
+}
+
+hipError_t cmr_launch_row_mask_fill(unsigned* words, long long nq_masks, long long n_words, long long size, int exclude, hipStream_t s) {
+    if (nq_masks <= 0 || n_words <= 0) return hipSuccess;
+    const dim3 grid((unsigned)std::min<long long>((n_words + 255) / 256, 1024), (unsigned)std::min<long long>(nq_masks, 64));
+    hipLaunchKernelGGL(row_mask_fill_kernel, grid, dim3(256), 0, s, words, nq_masks, n_words, size, exclude);
+    return hipGetLastError();
+}
+hipError_t cmr_launch_row_mask_apply_ids(unsigned* words, long long n_words, long long size, int exclude, const long long* off, int nq,
+                                         const long long* ids, long long n_ids, long long id_base, const long long* tab, int nb, hipStream_t s) {
+    if (n_ids <= 0 || n_words <= 0 || size <= 0 || nq <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<long long>((n_ids + 255) / 256, 4096);
+    hipLaunchKernelGGL(row_mask_apply_ids_kernel, dim3(grid), dim3(256), 0, s, words, n_words, size, exclude, off, nq, ids, n_ids, id_base, tab, nb);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
 // Row access in the panel-major layout.
 template <int DT>
 __device__ __forceinline__ float cmr_load_elem(const unsigned char* corpus, int ks_total, long long row, int kidx) {

@@ -53,6 +53,11 @@ struct CmrPending;
 int cmr_index_search_begin(cmr_index_t* idx, const float* q, int nq, int k, const float* min_score, bool take_lock, CmrPending** out);
 int cmr_index_search_finish(CmrPending* p, int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
 void cmr_index_search_abandon(CmrPending* p);
+// cmr_index_search_ids the same way: cmr_ids_args_check is every argument check that needs neither an index nor a device
+// (off_host: CSR offsets readable here, or NULL); `begin` takes checked arguments, the pending search ends in cmr_index_search_finish / _abandon
+int cmr_ids_args_check(int mode, int nq, int k, const int64_t* off_host, const int64_t* ids, int64_t n_ids);
+int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, int mode, const int64_t* id_offsets, const int64_t* ids, int64_t n_ids,
+                               bool take_lock, CmrPending** out);
 
 // shrink an index to its first n_rows rows (roll-back of a multi-shard append that failed on a later shard)
 int cmr_index_truncate(cmr_index_t* idx, long long n_rows);

@@ -159,6 +159,14 @@ hipError_t cmr_launch_gather_rows(int dtype, const void* corpus, int dim, int dp
                                   const int64_t* ids, long long n, float* out, hipStream_t s);
 // ids[i] (shard-local row, < 0 = empty) -> global id through the block table [local0[nb] | global0[nb]] (device)
 hipError_t cmr_launch_remap_ids(int64_t* ids, long long n, const long long* tab, int nb, hipStream_t s);
+// allow words [nq_masks][n_words] of a filtered search from row-id lists.  fill: exclude = every row of [0, size) set, tail
+// bits zero; allow = none.  apply: entry e of ids[0, n_ids) clears (exclude) / sets (allow) the bit of its LOCAL row in the words of the
+// query that owns it (off: nq + 1 CSR offsets on the device, nullptr = one list, mask 0); ids are global (id_base, or nb > 1: the block
+// table tab = [local0[nb] | global0[nb]]); negative ids and ids this index does not hold are skipped.  No access out of bounds whatever
+// ids and offsets hold.
+hipError_t cmr_launch_row_mask_fill(unsigned* words, long long nq_masks, long long n_words, long long size, int exclude, hipStream_t s);
+hipError_t cmr_launch_row_mask_apply_ids(unsigned* words, long long n_words, long long size, int exclude, const long long* off, int nq,
+                                         const long long* ids, long long n_ids, long long id_base, const long long* tab, int nb, hipStream_t s);
 // masked mean-pool + L2 norm
 hipError_t cmr_launch_pool(const void* hidden, int hidden_dtype, const int64_t* mask, int b, int l, int d,
                            int normalize, float* partial, float* out, int splits, hipStream_t s);

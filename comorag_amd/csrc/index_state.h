@@ -73,6 +73,7 @@ struct Workspace {
     // host-API staging
     DevBuf d_q, d_ids, d_scores, d_min, d_max, d_cand, d_out;
     DevBuf d_mask;               // cmr_index_search_masked: the call's allow words (a workspace per concurrent call, so a mask per call); cmr_index_search_masked_each: [nq][n_words]
+    DevBuf d_lists;              // cmr_index_search_ids: the call's CSR offsets and row ids [offsets (nq + 1) | ids]; its words are built into d_mask, at most 64 queries' at a time
     // synchronous search: queries in, (ids | scores | min | max | non-finite flag) out through ONE pinned host buffer and
     // one copy each way — five pageable D2H copies cost more than the search of a small corpus
     DevBuf d_pack;
@@ -110,6 +111,7 @@ struct Workspace {
         fin_ctl.release(); fin_pmax.release(); fin_tau.release(); fin_dense.release(); fin_mm.release();
         d_q.release(); d_ids.release(); d_scores.release(); d_min.release(); d_max.release(); d_cand.release(); d_out.release();
         d_mask.release();
+        d_lists.release();
         d_pack.release();
         q8.release();
         x.release();

@@ -478,11 +478,11 @@ int32_t cmr_mindex_append_dev(cmr_mindex_t* m, const float* rows_dev, int64_t n,
     });
 }
 
-static int32_t mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, const float* min_score, int64_t* out_ids, float* out_scores,
-                             float* out_min, float* out_max) {
-    if (!m || !q || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    if (nq <= 0) return cmr_fail(CMR_ERR_INVALID, "nq must be > 0");
-    if (k <= 0 || k > CMR_MAX_K_2PASS) return cmr_fail(CMR_ERR_UNSUPPORTED, "k = %d outside [1, %d]", k, CMR_MAX_K_2PASS);
+// A top-k search over the shards (arguments checked by the caller): `begin` starts it on one shard; it begins on every active shard before
+// it finishes on any (from parallel_min_shards shards up the shards' worker threads issue the enqueues), the host merges the sorted lists
+// and takes min / max over the shards (a shard with nothing to offer reports +inf / -inf).  No active shard: all padding.
+static int32_t mindex_gather(cmr_mindex_t* m, int32_t nq, int32_t k, const std::function<int(int, CmrPending**)>& begin, int64_t* out_ids,
+                             float* out_scores, float* out_min, float* out_max) {
     std::shared_lock<std::shared_mutex> lk(m->mu);
     const std::vector<int> act = active_shards(m);
     const int A = (int)act.size();
@@ -494,7 +494,7 @@ static int32_t mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_
     }
     std::vector<CmrPending*> pend((size_t)A, nullptr);
     int rc = for_active(m, act, A >= m->parallel_min_shards, [&](int a, int s) {
-        return cmr_index_search_begin(m->shard[s], q, nq, k, min_score, false, &pend[a]);
+        return begin(s, &pend[a]);
     });
     if (rc) {
         const std::string keep = cmr_last_error();
@@ -519,6 +519,27 @@ static int32_t mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_
         if (out_max) out_max[i] = hi;
     }
     return CMR_OK;
+}
+
+static int32_t mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, const float* min_score, int64_t* out_ids, float* out_scores,
+                             float* out_min, float* out_max) {
+    if (!m || !q || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (nq <= 0) return cmr_fail(CMR_ERR_INVALID, "nq must be > 0");
+    if (k <= 0 || k > CMR_MAX_K_2PASS) return cmr_fail(CMR_ERR_UNSUPPORTED, "k = %d outside [1, %d]", k, CMR_MAX_K_2PASS);
+    return mindex_gather(m, nq, k, [&](int s, CmrPending** p) { return cmr_index_search_begin(m->shard[s], q, nq, k, min_score, false, p); },
+                         out_ids, out_scores, out_min, out_max);
+}
+
+// Filtered search from GLOBAL row ids: every non-empty shard gets the whole list and keeps the ids it holds — the kernel's
+// "not held, so skipped" rule does the routing, there is no host-side split — and answers in global ids through its block table.
+int32_t cmr_mindex_search_ids(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
+                              int64_t n_ids, int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+    if (!q || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    const int rc = cmr_ids_args_check(mode, nq, k, id_offsets, ids, n_ids);
+    if (rc) return rc;
+    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
+    return mindex_gather(m, nq, k, [&](int s, CmrPending** p) { return cmr_index_search_ids_begin(m->shard[s], q, nq, k, mode, id_offsets, ids, n_ids, false, p); },
+                         out_ids, out_scores, out_min, out_max);
 }
 
 int32_t cmr_mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores, float* out_min,

@@ -84,6 +84,51 @@ def pack_row_masks(n_rows: int, allow=None, exclude=None) -> np.ndarray:
     return out
 
 
+def pack_id_lists(allow=None, exclude=None) -> Tuple[Optional[np.ndarray], np.ndarray]:
+    """Row-id lists of `search_filtered_ids` (cmr_index_search_ids) as CSR: → (offsets int64 [nq + 1] | None, ids int64 [n_ids]).
+    A 1-d integer array or a flat sequence of ints is ONE list shared by every query (offsets None).  A sequence with one entry per
+    query — each a 1-d integer array or a flat sequence of ints, empty entries allowed; a 2-d integer array such as the ids an earlier
+    search returned counts as one row per query — gives per-query lists: query i owns ids[offsets[i]:offsets[i + 1]].  The ids are not
+    range-checked here: the device ignores negative ids (-1 padding) and ids the index does not hold.  Exactly one of `allow` /
+    `exclude` must be given; anything else raises ValueError.  Pure numpy."""
+    if (allow is None) == (exclude is None):
+        raise ValueError("give allow or exclude, not both and not neither")
+    lists = allow if allow is not None else exclude
+
+    def _flat(a) -> np.ndarray:
+        ids = np.asarray(a)
+        if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+            raise ValueError("a row-id list must be a 1-d sequence of integers")
+        return ids.astype(np.int64)
+
+    if isinstance(lists, np.ndarray):
+        if lists.dtype.kind not in "iu" or lists.ndim not in (1, 2):
+            raise ValueError("row ids must be a 1-d (shared) or 2-d (one row per query) integer array")
+        ids = np.ascontiguousarray(lists, dtype=np.int64)
+        if ids.ndim == 1:
+            return None, ids
+        return np.arange(ids.shape[0] + 1, dtype=np.int64) * ids.shape[1], ids.reshape(-1)
+    if isinstance(lists, (str, bytes)) or not hasattr(lists, "__len__") or not hasattr(lists, "__iter__"):
+        raise ValueError("allow / exclude must be an integer array or a sequence")
+    entries = list(lists)
+    if all(isinstance(e, (int, np.integer)) and not isinstance(e, (bool, np.bool_)) for e in entries):
+        return None, np.asarray(entries, dtype=np.int64).reshape(-1)      # (an empty sequence: one shared, empty list)
+    if any(isinstance(e, (int, float, complex, bool, np.generic, str, bytes)) or not hasattr(e, "__len__") for e in entries):
+        raise ValueError("allow / exclude must be a flat sequence of ints or a sequence with one list of ints per query")
+    per_query = [_flat(e) for e in entries]
+    offsets = np.zeros(len(per_query) + 1, dtype=np.int64)
+    np.cumsum([len(e) for e in per_query], out=offsets[1:])
+    return offsets, (np.concatenate(per_query) if per_query else np.empty(0, dtype=np.int64))
+
+
+def _ids_mode(mode) -> int:
+    if mode in ("exclude", L.CMR_IDS_EXCLUDE):
+        return L.CMR_IDS_EXCLUDE
+    if mode in ("allow", L.CMR_IDS_ALLOW):
+        return L.CMR_IDS_ALLOW
+    raise ValueError(f"mode must be 'exclude' or 'allow', got {mode!r}")
+
+
 def _mask_popcount(words: np.ndarray, n_rows: int) -> int:
     """Set bits among the first n_rows of an allow bitmap (bits at or beyond n_rows do not count)."""
     if len(words) == 0:
@@ -97,7 +142,7 @@ def _mask_popcount(words: np.ndarray, n_rows: int) -> int:
 
 # the calls whose host-array marshalling `DenseIndex` (cmr_index_*) and `MultiDeviceIndex` (cmr_mindex_*) share
 _HOST_CALLS = ("destroy", "size", "info", "append", "search", "search_exact", "search_min_score", "scores", "sorted_scores",
-               "rescore", "get_rows")
+               "rescore", "get_rows", "search_ids")
 _bound = {}
 
 
@@ -173,6 +218,31 @@ class HostArrayIndex:
                                _ptr(mn) if with_minmax else None, _ptr(mx) if with_minmax else None))
         kk = min(k, len(self))
         return ids[:, :kk], sc[:, :kk], mn, mx
+
+    # -- filtered search from row-id lists (cmr_index_search_ids / cmr_mindex_search_ids)
+    def search_filtered_ids(self, q, k: int, *, allow=None, exclude=None, with_minmax: bool = True
+                            ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """`search` among the rows the id lists leave: `exclude` = every row except the listed ones, `allow` = only the listed rows.  The
+        ids are row ids AS THE SEARCHES RETURN THEM (id base / block table applied; over a `MultiDeviceIndex`: global ids), so what an
+        earlier search returned — -1 padding included — goes straight back in: tri_retrieve's pool dedup (ComoRAG.py:499-505, 515-522,
+        535-540) without a bitmap.  Lists as `pack_id_lists` takes them: one shared list, or one entry per query.  The device builds the
+        allow words next to the corpus; nothing of the size of the corpus is packed or uploaded.  k <= 128.
+        → (ids [nq,k], raw scores [nq,k], min [nq], max [nq]): always k columns, -1 / -inf padded, bit for bit what
+        `DenseIndex.search_filtered_each` returns on the masks of the same rows; min / max over a query's allowed rows (+inf / -inf when
+        it allows none)."""
+        offsets, lst = pack_id_lists(allow=allow, exclude=exclude)
+        q = self._queries(q)
+        nq = q.shape[0]
+        if offsets is not None and len(offsets) != nq + 1:
+            raise ValueError(f"{len(offsets) - 1} id lists for {nq} queries")
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        mn = np.empty(nq, dtype=np.float32) if with_minmax else None
+        mx = np.empty(nq, dtype=np.float32) if with_minmax else None
+        L.check(self._c.search_ids(self._h, _ptr(q), nq, k, L.CMR_IDS_ALLOW if allow is not None else L.CMR_IDS_EXCLUDE,
+                                   _ptr(offsets) if offsets is not None else None, _ptr(lst) if len(lst) else None, len(lst),
+                                   _ptr(ids), _ptr(sc), _ptr(mn) if with_minmax else None, _ptr(mx) if with_minmax else None))
+        return ids, sc, mn, mx
 
     def search_min_score(self, q, k: int, min_score: float) -> Tuple[np.ndarray, np.ndarray]:
         """The k best rows among those with raw score >= min_score: (ids [nq,k], scores [nq,k]), -1 / -inf padded."""
@@ -448,6 +518,62 @@ class DenseIndex(HostArrayIndex):
             stream = torch.cuda.current_stream(dev).cuda_stream
         L.check(L.lib().cmr_index_search_masked_each_dev(
             self._h, C.c_void_p(q_t.data_ptr()), nq, k, C.c_void_p(masks_t.data_ptr()), masks_t.shape[1],
+            C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
+            C.c_void_p(out_min.data_ptr()) if out_min is not None else None,
+            C.c_void_p(out_max.data_ptr()) if out_max is not None else None, C.c_void_p(stream)))
+        return out_ids, out_scores
+
+    # -- filtered search from row-id lists on device tensors (cmr_index_row_masks_dev, cmr_index_search_ids_dev)
+    @staticmethod
+    def _id_list_tensors(ids_t, offsets_t):
+        import torch
+        assert ids_t.is_cuda and ids_t.dtype == torch.int64 and ids_t.is_contiguous() and ids_t.dim() == 1
+        if offsets_t is not None:
+            assert offsets_t.is_cuda and offsets_t.dtype == torch.int64 and offsets_t.is_contiguous() and offsets_t.dim() == 1
+            assert offsets_t.device == ids_t.device
+
+    def row_masks_dev(self, ids_t, offsets_t=None, nq: int = 1, mode="exclude", out=None, stream: Optional[int] = None):
+        """The allow words `search_filtered_dev` / `search_filtered_each_dev` take, built on the device from row ids (as the searches
+        return them; torch int64 CUDA tensor [n_ids]) — build once, search many times.  offsets_t: int64 [nq + 1] CSR offsets on the
+        device (query i owns ids_t[offsets_t[i]:offsets_t[i + 1]]) → words int32 [nq, ceil(len / 32)]; None: one shared list → words
+        [ceil(len / 32)].  Exactly the words of `pack_row_masks` / `pack_row_mask` on the local rows of the lists.  Enqueued on torch's
+        current stream without synchronising."""
+        import torch
+        self._id_list_tensors(ids_t, offsets_t)
+        n_words = (len(self) + 31) // 32
+        if offsets_t is not None:
+            nq = offsets_t.shape[0] - 1
+        shape = (nq, n_words) if offsets_t is not None else (n_words,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=ids_t.device)
+        assert out.is_cuda and out.element_size() == 4 and out.is_contiguous() and tuple(out.shape) == shape
+        if stream is None:
+            stream = torch.cuda.current_stream(ids_t.device).cuda_stream
+        L.check(L.lib().cmr_index_row_masks_dev(
+            self._h, _ids_mode(mode), nq if offsets_t is not None else 1, C.c_void_p(offsets_t.data_ptr()) if offsets_t is not None else None,
+            C.c_void_p(ids_t.data_ptr()) if ids_t.shape[0] else None, ids_t.shape[0], C.c_void_p(out.data_ptr()), n_words, C.c_void_p(stream)))
+        return out
+
+    def search_filtered_ids_dev(self, q_t, k: int, ids_t, offsets_t=None, mode="exclude", out_ids=None, out_scores=None, out_min=None,
+                                out_max=None, stream: Optional[int] = None):
+        """`search_filtered_ids` on torch CUDA tensors, enqueued on torch's current stream without synchronising: ids_t int64 [n_ids],
+        offsets_t int64 [nq + 1] or None (one shared list), mode "exclude" | "allow".  The words are built into scratch of this stream's
+        workspace.  → (out_ids [nq,k], out_scores [nq,k]), -1 / -inf padded."""
+        import torch
+        assert q_t.is_cuda and q_t.dtype == torch.float32 and q_t.is_contiguous() and q_t.shape[1] == self.dim
+        self._id_list_tensors(ids_t, offsets_t)
+        nq, dev = q_t.shape[0], q_t.device
+        if offsets_t is not None and offsets_t.shape[0] != nq + 1:
+            raise ValueError(f"offsets_t must be [{nq + 1}], got {tuple(offsets_t.shape)}")
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().cmr_index_search_ids_dev(
+            self._h, C.c_void_p(q_t.data_ptr()), nq, k, _ids_mode(mode), C.c_void_p(offsets_t.data_ptr()) if offsets_t is not None else None,
+            C.c_void_p(ids_t.data_ptr()) if ids_t.shape[0] else None, ids_t.shape[0],
             C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
             C.c_void_p(out_min.data_ptr()) if out_min is not None else None,
             C.c_void_p(out_max.data_ptr()) if out_max is not None else None, C.c_void_p(stream)))

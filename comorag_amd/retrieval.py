@@ -91,6 +91,20 @@ def dense_passage_topk_filtered_each(index: DenseIndex, query_embeddings, k: int
     return ids, np.where(ids < 0, -np.inf, norm).astype(np.float32)
 
 
+def dense_passage_topk_filtered_ids(index, query_embeddings, k: int, exclude_ids=None, allow_ids=None) -> Tuple[np.ndarray, np.ndarray]:
+    """`dense_passage_topk_filtered_each` from row IDS instead of bitmaps, on a `DenseIndex` or a `MultiDeviceIndex`: `exclude_ids` /
+    `allow_ids` are ids as the searches return them (one shared list, or one entry per query; the -1 padded ids of an earlier search
+    may be passed as they are) — what tri_retrieve's pool dedup holds (ComoRAG.py:499-505, 515-522, 535-540).  The device builds the
+    bitmaps; no per-query bool[n] is unpacked on the host.  Every query's scores are min-max normalised from the min / max over ITS
+    allowed rows with the reference formula.  ids [nq,k], scores [nq,k]; behind a query's allowed rows the ids are -1 and the scores -inf."""
+    ids, sc, mn, mx = index.search_filtered_ids(_as_query(query_embeddings), k, allow=allow_ids, exclude=exclude_ids)
+    rng = (mx - mn)[:, None]
+    flat = (rng == 0) | ~np.isfinite(rng)          # (no allowed row: min = +inf, max = -inf, the row is all padding)
+    with np.errstate(invalid="ignore"):
+        norm = np.where(flat, np.ones_like(sc), (sc - np.where(flat, 0, mn[:, None])) / np.where(flat, 1, rng))
+    return ids, np.where(ids < 0, -np.inf, norm).astype(np.float32)
+
+
 def get_fact_scores(index: Optional[DenseIndex], query_embedding) -> np.ndarray:
     """ComoRAG.get_fact_scores (ComoRAG.py:937-948): full normalised vector over the fact matrix."""
     if index is None or len(index) == 0:

@@ -189,7 +189,8 @@ int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_f32_dev, in
  * tile and loads that query's word of the panel; sampling passes read the same words, so each query's threshold is a bound among ITS
  * allowed rows.  last_route: CMR_ROUTE_CHAIN | CMR_ROUTE_FILTERED | CMR_ROUTE_FILTERED_EACH.
  * The host form uploads all nq blocks into scratch of its own call; the _dev form reads the caller's device words in place.
- * Not filtered, as before: cmr_mindex_*, the pipelined, exact, sorted, threshold and all-scores calls, PageRank.                    */
+ * Not filtered, as before: the pipelined, exact, sorted, threshold and all-scores calls, PageRank; of cmr_mindex_* only
+ * cmr_mindex_search_ids (below) filters.                                                                                           */
 int32_t cmr_index_search_masked_each(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k,
                                      const uint32_t* allow_words, int64_t n_words,
                                      int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
@@ -197,6 +198,40 @@ int32_t cmr_index_search_masked_each_dev(cmr_index_t* idx, const float* q_f32_de
                                          const uint32_t* allow_words_dev, int64_t n_words,
                                          int64_t* out_ids_dev, float* out_scores_dev,
                                          float* out_min_dev, float* out_max_dev, void* stream);
+
+/* Filtered search from ROW-ID LISTS: tri_retrieve's pool dedup has the rows to keep out as the ids earlier searches
+ * returned, not as a bitmap, and a bitmap over local rows cannot cross the shards of a multi-device index.  The caller hands over ids;
+ * the device builds the allow words next to the corpus (two small launches) and the masked scans above run on them unchanged.
+ *   mode        CMR_IDS_EXCLUDE: every row except the listed ones; CMR_IDS_ALLOW: only the listed rows.
+ *   ids         int64 row ids AS THE SEARCH ENTRY POINTS RETURN THEM (id base / block table applied), so a -1 padded result of an earlier
+ *               search can be passed as it is; negative ids and ids this index does not hold are ignored; duplicates are harmless.
+ *   id_offsets  int64 [nq + 1], CSR: query i owns ids[id_offsets[i] .. id_offsets[i+1]); NULL = ONE list of n_ids entries shared by
+ *               every query.
+ * cmr_index_row_masks_dev writes exactly the words cmr_index_search_masked(_each)_dev takes — [nq][n_words] with offsets, [n_words] without
+ * (nq is then not used beyond nq >= 1), n_words == ceil(size / 32), bits at or beyond size zero — on `stream`, without synchronising: build
+ * once, search many times.  Device offsets cannot be checked: malformed ones give unspecified words, never an access out of bounds.
+ * cmr_index_search_ids returns, bit for bit, what cmr_index_search_masked_each returns on those words (with id_offsets == NULL:
+ * cmr_index_search_masked on the one mask, on the shared-mask scan): ids, score bits, min / max over the allowed rows, -1 / -inf padding to
+ * k columns; a query that allows nothing gets all padding, min = +inf, max = -inf, and CMR_OK.  n_ids == 0 is legal (exclude: every row
+ * competes; allow: all padding).  k <= CMR_MAX_K (above: CMR_ERR_UNSUPPORTED), any nq >= 1.
+ * CMR_ERR_INVALID, before any device call: a NULL handle, query or output; NULL ids with n_ids > 0; n_ids < 0; a mode other than 0 / 1;
+ * nq or k <= 0; wrong n_words in the builder; in the host forms also id_offsets[0] != 0, decreasing offsets, id_offsets[nq] != n_ids.
+ * Non-finite queries are reported as the masked calls report them.
+ * Scratch: the words live in the call's own workspace (concurrent calls each have theirs) and never exceed 64 queries' worth: a larger
+ * batch builds and scans group by group on one stream.  The host form uploads ids and offsets through the pinned buffer, like the
+ * queries.  last_route: the masked route's bits plus CMR_ROUTE_FILTERED_IDS.  These calls are never combined (see "combine").
+ * cmr_mindex_search_ids takes GLOBAL ids: every non-empty shard gets the whole list and keeps the ids it holds (no host-side split), the
+ * search begins on every shard before it finishes on any, the host merges as cmr_mindex_search does; min / max over the shards (a shard
+ * with nothing allowed contributes +inf / -inf); no active shard: all padding.                                                        */
+#define CMR_IDS_EXCLUDE 0   /* every row except the listed ones */
+#define CMR_IDS_ALLOW   1   /* only the listed rows */
+int32_t cmr_index_row_masks_dev(cmr_index_t* idx, int32_t mode, int32_t nq, const int64_t* id_offsets_dev, const int64_t* ids_dev,
+                                int64_t n_ids, uint32_t* words_dev /* [nq or 1][n_words] */, int64_t n_words, void* stream);
+int32_t cmr_index_search_ids(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets,
+                             const int64_t* ids, int64_t n_ids, int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
+int32_t cmr_index_search_ids_dev(cmr_index_t* idx, const float* q_f32_dev, int32_t nq, int32_t k, int32_t mode,
+                                 const int64_t* id_offsets_dev, const int64_t* ids_dev, int64_t n_ids, int64_t* out_ids_dev,
+                                 float* out_scores_dev, float* out_min_dev, float* out_max_dev, void* stream);
 
 /* Throughput mode for a stream of independent query batches (serving; bench.py).  Work is enqueued on streams owned by
  * the index: query packing + sampling passes of batch i+1 overlap the HBM-bound main scan of batch i.  On a 256-CU device
@@ -272,7 +307,7 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  * cmr_index_search_masked_each over the participants' queries, every query with its caller's mask (a shared mask repeated per query), and
  * each caller gets the bits of its own call.  A participant whose n_words no longer fits the index when the batch runs (an append came in
  * between) gets its own CMR_ERR_INVALID; the others are served.  At 0 filtered calls never join a batch and never move the counters.
- * NOT combined: cmr_index_search_masked* unless "combine_filtered" is set, cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
+ * NOT combined: cmr_index_search_masked* unless "combine_filtered" is set, cmr_index_search_ids* and cmr_mindex_search_ids whether or not it is set, cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
  * cmr_mindex_* (the option has no effect on searches issued through a multi-device handle).  The encoder is not combined HERE: concurrent
  * one-question encodes share one forward through the Python-level option `embedding_combine` (cmr_encoder_linear_rows* below).      */
 /* Which path served the last call (read-only): "last_route", written by the host when a search or all-scores call on this index is
@@ -285,10 +320,12 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  *   bit  10     threshold search (cmr_index_search_min_score*)
  *   bit  11     the batch took more than one corpus pass: the bits above describe its first, later passes may be routed otherwise
  *   bit  12     filtered search (cmr_index_search_masked*): every scan of the pass is the masked variant
- *   bit  13     with bit 12: the per-query variant (cmr_index_search_masked_each*, or a combined batch of filtered calls)             */
+ *   bit  13     with bit 12: the per-query variant (cmr_index_search_masked_each*, or a combined batch of filtered calls)
+ *   bit  14     with bit 12: the allow words were built on the device from row-id lists (cmr_index_search_ids*)                      */
 #define CMR_ROUTE_MORE_PASSES (1 << 11)
 #define CMR_ROUTE_FILTERED (1 << 12)
 #define CMR_ROUTE_FILTERED_EACH (1 << 13)
+#define CMR_ROUTE_FILTERED_IDS (1 << 14)
 #define CMR_ROUTE_TINY 1          /* single launch, <= 1024 rows */
 #define CMR_ROUTE_SMALL 2         /* single launch, hierarchical selection */
 #define CMR_ROUTE_CHAIN 3         /* narrow kernel: pack / [sample] / scan / merge */
@@ -521,6 +558,9 @@ int32_t cmr_mindex_append(cmr_mindex_t* m, const float* rows_f32, int64_t n);
 int32_t cmr_mindex_append_dev(cmr_mindex_t* m, const float* rows_f32_dev, int64_t n, int32_t src_device, void* stream);
 int32_t cmr_mindex_search(cmr_mindex_t* m, const float* q_f32, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores,
                           float* out_min, float* out_max);
+int32_t cmr_mindex_search_ids(cmr_mindex_t* m, const float* q_f32, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets,
+                              const int64_t* ids /* GLOBAL row ids */, int64_t n_ids, int64_t* out_ids, float* out_scores, float* out_min,
+                              float* out_max);
 int32_t cmr_mindex_search_min_score(cmr_mindex_t* m, const float* q_f32, int32_t nq, int32_t k, float min_score,
                                     int64_t* out_ids, float* out_scores);
 int32_t cmr_mindex_scores(cmr_mindex_t* m, const float* q_f32, int32_t nq, float* out, int64_t ld);
