@@ -123,6 +123,9 @@ const Option kOptions[] = {
     {"prefilter_pairs", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::pairs))},
     {"prefilter_pair_overflow", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::pair_overflow))},
     {"prefilter_wave_overflow", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(q8_read_counter(i, Q8Counter::wave_overflow))},
+    {"remove_stage_panels", [](cmr_index* i, long long v) { i->rm_stage_panels = v <= 0 ? 0 : (int)std::max(2ll, v); }, Option::clamp, 0, 1 << 22, 0, nullptr,
+     OPT_READ(i->rm_stage_panels)},
+    {"remove_chunks_last", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->rm_chunks_last)},
     {"last_route", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->last_route.load(std::memory_order_relaxed))},
     {"pipe_dual_scan_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_active)},
     {"pipe_dual_scan_wide_active", nullptr, Option::any, 0, 0, 0, nullptr, OPT_READ(i->dual_wide_active)},
@@ -846,6 +849,7 @@ int32_t cmr_index_destroy(cmr_index_t* idx) {
         }
         idx->pipe.destroy_streams();
         idx->stage.release();
+        idx->rm_buf.release();
         if (idx->h_pin) { (void)hipHostFree(idx->h_pin); idx->h_pin = nullptr; idx->h_pin_cap = 0; }
         if (idx->corpus) (void)hipFree(idx->corpus);
         if (idx->shadow) (void)hipFree(idx->shadow);
@@ -1528,6 +1532,84 @@ int cmr_index_truncate(cmr_index_t* idx, long long n_rows) {
     idx->n = n_rows;
     idx->q8c.rows = std::min(idx->q8c.rows, n_rows);      // (the next append rewrites the slots behind: their int8 companion is stale then)
     return CMR_OK;
+}
+
+// ---- row removal by stable in-place compaction (include/comorag_hip.h: cmr_index_remove_ids; compact_kernels.hip).
+// The exclusive lock is held by the caller.  Everything that can fail for want of memory happens before the first row moves.
+static int remove_ids_locked(cmr_index* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
+    idx->rm_chunks_last = 0;
+    if (n_ids == 0 || idx->n == 0) return CMR_OK;
+    int rc = cmr_set_device(idx->device);
+    if (rc) return rc;
+    // searches hold the shared lock only while they enqueue (_dev, pipelined) or until they finish (host API): whatever this process
+    // has in flight on the device — the pipeline's streams, the workspaces', callers' streams — reads the rows where they are now
+    HIP_TRY(hipDeviceSynchronize());
+    const long long n = idx->n, nw = idx->npanels();
+    hipStream_t s = nullptr;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_words = 16, o_kb = o_words + up16((size_t)nw * 4), o_ids = o_kb + up16(((size_t)nw + 1) * 4);
+    HIP_TRY(idx->rm_buf.ensure(o_ids + (size_t)n_ids * 8));
+    char* const b = (char*)idx->rm_buf.p;
+    long long* const info = (long long*)b;
+    unsigned* const words = (unsigned*)(b + o_words);
+    unsigned* const kept_before = (unsigned*)(b + o_kb);
+    HIP_TRY(hipMemcpy(b + o_ids, ids, (size_t)n_ids * 8, hipMemcpyHostToDevice));
+    // the keep words by the builder of the id-list searches: its ignoring rules (negative ids, ids this index does not hold, duplicates), its translation
+    rc = row_masks_enqueue(idx, CMR_IDS_EXCLUDE, 1, nullptr, (const int64_t*)(b + o_ids), n_ids, words, s);
+    if (rc) return rc;
+    HIP_TRY(cmr_launch_keep_prefix(words, nw, n, kept_before, info, s));
+    long long h[2] = {n, n};
+    HIP_TRY(hipMemcpy(h, info, sizeof(h), hipMemcpyDeviceToHost));
+    const long long kept = h[0], first = h[1];
+    if (kept < 0 || kept > n || first < 0 || first > n) return fail(CMR_ERR_HIP, "row removal: prefix sum returned %lld kept rows, first removed row %lld of %lld", kept, first, n);
+    if (kept == n) return CMR_OK;
+    if (first < kept) {      // (first == kept: the removed rows are the tail — a truncate)
+        const long long p0 = first / CMR_PANEL_ROWS, affected = nw - p0;
+        const size_t pb = idx->panel_bytes();
+        long long sp = idx->rm_stage_panels ? idx->rm_stage_panels : std::max<long long>(2, (long long)((64ull << 20) / pb));
+        sp = std::max<long long>(2, std::min(sp, affected + 1));
+        const size_t stage_bytes = (size_t)sp * pb;
+        HIP_TRY(idx->stage.ensure(stage_bytes));
+        // from here on rows move: whatever happens, the int8 companion is no longer trusted behind the first removed row
+        idx->q8c.rows = std::min(idx->q8c.rows, first);
+        const int ks = idx->ks();
+        const long long c_panels = sp - 1;      // the destination rows of c_panels source panels may straddle one panel more
+        for (long long p = p0; p < nw; p += c_panels) {
+            HIP_TRY(cmr_launch_compact_chunk(idx->corpus, ks, words, kept_before, p, std::min(nw, p + c_panels), idx->stage.p, sp, s));
+            ++idx->rm_chunks_last;
+        }
+        if (idx->shadow) {      // the same buffer, at row granularity: sp * panel bytes >= 2 * 32 * dpad * 2 bytes hold at least one panel's 32 fp32 rows
+            const long long stage_rows = (long long)(stage_bytes / ((size_t)idx->dim * 4)), s_panels = stage_rows / CMR_PANEL_ROWS;
+            for (long long p = p0; p < nw; p += s_panels)
+                HIP_TRY(cmr_launch_compact_shadow_chunk(idx->shadow, idx->dim, words, kept_before, p, std::min(nw, p + s_panels), idx->stage.p, stage_rows, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    idx->n = kept;
+    idx->q8c.rows = std::min(idx->q8c.rows, first);      // the int8 companion is not compacted: the next pre-filtered call quantises again from the first removed row's panel
+    if (n_removed) *n_removed = n - kept;
+    return CMR_OK;
+}
+
+// cmr_index_remove_ids without the block-table restriction, for an owner that replaces the table itself right after (multi.hip:
+// the ids are translated through the table the shard has NOW; the shard's table is stale when this returns with *n_removed > 0)
+int cmr_index_compact_ids(cmr_index_t* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
+    if (n_removed) *n_removed = 0;
+    if (!idx || (n_ids > 0 && !ids) || n_ids < 0) return fail(CMR_ERR_INVALID, "bad argument");
+    std::unique_lock<std::shared_mutex> lk(idx->mu);
+    return remove_ids_locked(idx, ids, n_ids, n_removed);
+}
+
+extern "C" int32_t cmr_index_remove_ids(cmr_index_t* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
+    if (n_removed) *n_removed = 0;
+    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
+    if (n_ids < 0) return fail(CMR_ERR_INVALID, "n_ids %lld < 0", (long long)n_ids);
+    if (n_ids > 0 && !ids) return fail(CMR_ERR_INVALID, "NULL ids with n_ids = %lld", (long long)n_ids);
+    std::unique_lock<std::shared_mutex> lk(idx->mu);
+    if (!idx->single_block())
+        return fail(CMR_ERR_UNSUPPORTED, "row removal on an index with a block table of %d blocks (cmr_index_set_id_blocks): the owner of the table removes (cmr_mindex_remove_ids)",
+                    (int)idx->blk_local.size());
+    return remove_ids_locked(idx, ids, n_ids, n_removed);
 }
 
 extern "C" {

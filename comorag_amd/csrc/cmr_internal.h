@@ -61,6 +61,9 @@ int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, 
 
 // shrink an index to its first n_rows rows (roll-back of a multi-shard append that failed on a later shard)
 int cmr_index_truncate(cmr_index_t* idx, long long n_rows);
+// cmr_index_remove_ids for the owner of a shard's block table (multi.hip): ids in the domain the shard returns NOW (its current table), any
+// number of blocks; the table is stale once rows went and the owner sets the new one (cmr_index_set_id_blocks) before the next search
+int cmr_index_compact_ids(cmr_index_t* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed);
 
 // for ppr.hip: scores of nb host queries [nb, dim] into a device buffer [nb, n] of the index's workspace, row b holding the bits a
 // one-query scan of q_host[b] gives (shared index lock held, workspace reserved for the calling thread) until

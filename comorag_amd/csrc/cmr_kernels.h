@@ -167,6 +167,16 @@ hipError_t cmr_launch_remap_ids(int64_t* ids, long long n, const long long* tab,
 hipError_t cmr_launch_row_mask_fill(unsigned* words, long long nq_masks, long long n_words, long long size, int exclude, hipStream_t s);
 hipError_t cmr_launch_row_mask_apply_ids(unsigned* words, long long n_words, long long size, int exclude, const long long* off, int nq,
                                          const long long* ids, long long n_ids, long long id_base, const long long* tab, int nb, hipStream_t s);
+// row removal by in-place compaction (compact_kernels.hip).  keep_prefix: kept_before[n_words + 1] = exclusive prefix of the
+// keep words' popcounts (one workgroup), info[0] = kept rows, info[1] = first removed row (size when none).  compact_chunk: the kept rows of
+// the source panels [p_first, p_end) move to their destination rows through `stage` (room for stage_panels >= p_end - p_first + 1 panels);
+// compact_shadow_chunk: the same for the row-major fp32 shadow (`stage`: room for stage_rows >= 32 * (p_end - p_first) rows of dim floats).
+// Chunks must be enqueued in ascending order on ONE stream.
+hipError_t cmr_launch_keep_prefix(const unsigned* words, long long n_words, long long size, unsigned* kept_before, long long* info, hipStream_t s);
+hipError_t cmr_launch_compact_chunk(void* corpus, int ks, const unsigned* words, const unsigned* kept_before, long long p_first, long long p_end,
+                                    void* stage, long long stage_panels, hipStream_t s);
+hipError_t cmr_launch_compact_shadow_chunk(float* shadow, int dim, const unsigned* words, const unsigned* kept_before, long long p_first,
+                                           long long p_end, void* stage, long long stage_rows, hipStream_t s);
 // masked mean-pool + L2 norm
 hipError_t cmr_launch_pool(const void* hidden, int hidden_dtype, const int64_t* mask, int b, int l, int d,
                            int normalize, float* partial, float* out, int splits, hipStream_t s);

@@ -157,7 +157,10 @@ struct cmr_index {
     std::mutex ws_mu;
     std::vector<Workspace*> free_ws;            // for the synchronous host API
     std::map<hipStream_t, Workspace*> stream_ws;  // for the _dev API
-    DevBuf stage;                // append staging
+    DevBuf stage;                // append staging; row removal stages its chunks here too (both hold the exclusive lock)
+    DevBuf rm_buf;               // row removal: [info (kept rows, first removed row) | keep words | kept_before | uploaded ids]
+    int rm_stage_panels = 0;     // remove_stage_panels: panels the staging buffer of a removal holds (0: 64 MiB worth; at least 2)
+    long long rm_chunks_last = 0;   // read-only ("remove_chunks_last"): chunks the corpus pass of the last removal ran (0: nothing moved)
     void* h_pin = nullptr;       // small appends: pinned, device-mapped rows + flag (exclusive lock held)
     void* h_pin_dev = nullptr;
     size_t h_pin_cap = 0;

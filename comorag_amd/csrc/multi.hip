@@ -249,9 +249,143 @@ Where locate(const cmr_mindex* m, long long gid) {
     return {-1, -1};
 }
 
+// The shards' block tables after the global ids `ids` are gone: global ids stay dense in the old global order, so a block's new
+// global start is its old one minus the removed ids below it, its length shrinks by the removed ids inside it, empty blocks go, a shard's
+// local starts are the running sum of what is left.  Negative ids, ids no block holds, ids of a shard marked in `skip` and duplicates are ignored.
+// Pure host arithmetic.
+struct RemovePlan {
+    std::vector<std::vector<long long>> local, global;
+    std::vector<long long> rows;
+    long long removed = 0;
+};
+void plan_remove(int S, const long long* rows, const std::vector<std::vector<long long>>& bl, const std::vector<std::vector<long long>>& bg,
+                 const int64_t* ids, int64_t n_ids, const std::vector<char>* skip, RemovePlan& out) {
+    struct Run { long long g, len; int shard; };
+    std::vector<Run> runs;
+    for (int s = 0; s < S; ++s)
+        for (size_t b = 0; b < bl[s].size(); ++b) runs.push_back({bg[s][b], (b + 1 < bl[s].size() ? bl[s][b + 1] : rows[s]) - bl[s][b], s});
+    std::sort(runs.begin(), runs.end(), [](const Run& a, const Run& b) { return a.g < b.g; });
+    std::vector<long long> gone;
+    for (int64_t i = 0; i < n_ids; ++i) {
+        const long long id = ids[i];
+        if (id < 0) continue;
+        size_t r = std::upper_bound(runs.begin(), runs.end(), id, [](long long v, const Run& x) { return v < x.g; }) - runs.begin();
+        if (r == 0) continue;
+        --r;
+        if (id - runs[r].g >= runs[r].len || (skip && (*skip)[(size_t)runs[r].shard])) continue;
+        gone.push_back(id);
+    }
+    std::sort(gone.begin(), gone.end());
+    gone.erase(std::unique(gone.begin(), gone.end()), gone.end());
+    out.local.assign((size_t)S, {}); out.global.assign((size_t)S, {}); out.rows.assign((size_t)S, 0);
+    out.removed = (long long)gone.size();
+    for (int s = 0; s < S; ++s) {
+        long long at = 0;
+        for (size_t b = 0; b < bl[s].size(); ++b) {
+            const long long g = bg[s][b], len = (b + 1 < bl[s].size() ? bl[s][b + 1] : rows[s]) - bl[s][b];
+            const long long below = std::lower_bound(gone.begin(), gone.end(), g) - gone.begin();
+            const long long inside = (std::lower_bound(gone.begin(), gone.end(), g + len) - gone.begin()) - below;
+            if (len - inside <= 0) continue;
+            out.local[(size_t)s].push_back(at);
+            out.global[(size_t)s].push_back(g - below);
+            at += len - inside;
+        }
+        out.rows[(size_t)s] = at;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t cmr_mindex_plan_remove(int32_t n_shards, const int64_t* shard_rows, const int32_t* n_blocks, const int64_t* local_start,
+                               const int64_t* global_start, const int64_t* ids, int64_t n_ids, const int32_t* skip_shards, int64_t* new_shard_rows,
+                               int32_t* new_n_blocks, int64_t* new_local_start, int64_t* new_global_start, int64_t* n_removed) {
+    if (n_shards <= 0 || !shard_rows || !n_blocks || n_ids < 0 || (n_ids > 0 && !ids)) return cmr_fail(CMR_ERR_INVALID, "bad argument");
+    std::vector<std::vector<long long>> bl((size_t)n_shards), bg((size_t)n_shards);
+    std::vector<long long> rows(shard_rows, shard_rows + n_shards);
+    size_t at = 0;
+    for (int s = 0; s < n_shards; ++s) {
+        if (n_blocks[s] < 0 || (n_blocks[s] > 0 && (!local_start || !global_start))) return cmr_fail(CMR_ERR_INVALID, "bad block table of shard %d", s);
+        for (int b = 0; b < n_blocks[s]; ++b, ++at) {
+            const long long end = b + 1 < n_blocks[s] ? local_start[at + 1] : rows[(size_t)s];
+            if (local_start[at] < 0 || end < local_start[at] || global_start[at] < 0) return cmr_fail(CMR_ERR_INVALID, "shard %d, block %d: local starts must ascend up to the shard's rows", s, b);
+            bl[(size_t)s].push_back(local_start[at]);
+            bg[(size_t)s].push_back(global_start[at]);
+        }
+    }
+    RemovePlan plan;
+    std::vector<char> skip((size_t)n_shards, 0);
+    if (skip_shards) for (int s = 0; s < n_shards; ++s) skip[(size_t)s] = skip_shards[s] != 0;
+    plan_remove(n_shards, rows.data(), bl, bg, ids, n_ids, skip_shards ? &skip : nullptr, plan);
+    at = 0;
+    for (int s = 0; s < n_shards; ++s) {
+        if (new_shard_rows) new_shard_rows[s] = plan.rows[(size_t)s];
+        if (new_n_blocks) new_n_blocks[s] = (int32_t)plan.local[(size_t)s].size();
+        for (size_t b = 0; b < plan.local[(size_t)s].size(); ++b, ++at) {      // (never more blocks than came in)
+            if (new_local_start) new_local_start[at] = plan.local[(size_t)s][b];
+            if (new_global_start) new_global_start[at] = plan.global[(size_t)s][b];
+        }
+    }
+    if (n_removed) *n_removed = plan.removed;
+    return CMR_OK;
+}
+
+int32_t cmr_mindex_remove_ids(cmr_mindex_t* m, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
+    if (n_removed) *n_removed = 0;
+    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
+    if (n_ids < 0) return cmr_fail(CMR_ERR_INVALID, "n_ids %lld < 0", (long long)n_ids);
+    if (n_ids > 0 && !ids) return cmr_fail(CMR_ERR_INVALID, "NULL ids with n_ids = %lld", (long long)n_ids);
+    std::unique_lock<std::shared_mutex> lk(m->mu);
+    {   // throughput-mode batches whose enqueue jobs are still with the worker threads: let them finish issuing first (the shards wait for the device)
+        std::lock_guard<std::mutex> pg(m->pipe_mu);
+        for (PipeTicket& t : m->ticket) if (t.busy) t.latch.wait();
+    }
+    // everything on the host first: the only step that can fail afterwards is a shard's compaction
+    RemovePlan plan;
+    plan_remove(m->S, m->rows.data(), m->blk_local, m->blk_global, ids, n_ids, nullptr, plan);
+    if (plan.removed == 0) return CMR_OK;
+    std::vector<int> act;
+    for (int s = 0; s < m->S; ++s) if (plan.rows[(size_t)s] != m->rows[(size_t)s]) act.push_back(s);
+    const int A = (int)act.size();
+    std::vector<int> rcs((size_t)A, 0);
+    std::vector<char> miscount((size_t)A, 0);
+    std::vector<std::string> errs((size_t)A);
+    // every shard that loses rows gets the whole list and drops the ids it holds (its current table translates them), all shards at once
+    (void)for_active(m, act, A > 1, [&](int a, int s) {
+        int64_t r = 0;
+        int rc = cmr_index_compact_ids(m->shard[s], ids, n_ids, &r);
+        if (!rc && r != m->rows[(size_t)s] - plan.rows[(size_t)s]) miscount[(size_t)a] = 1;
+        if (miscount[(size_t)a])
+            rc = cmr_fail(CMR_ERR_HIP, "removed %lld rows where the plan has %lld", (long long)r, m->rows[(size_t)s] - plan.rows[(size_t)s]);
+        rcs[(size_t)a] = rc;
+        if (rc) { const char* e = cmr_last_error(); errs[(size_t)a] = e ? e : ""; }
+        return CMR_OK;
+    });
+    // a shard that went through but lost another number of rows than the host planned: no table the host can compute describes it
+    for (int a = 0; a < A; ++a)
+        if (miscount[(size_t)a])
+            return cmr_fail(CMR_ERR_HIP, "shard %d: %s — the shards' rows and the block tables no longer agree: destroy this index", act[(size_t)a], errs[(size_t)a].c_str());
+    int rc = CMR_OK, bad = -1;
+    std::vector<char> skip((size_t)m->S, 0);
+    for (int a = 0; a < A; ++a) if (rcs[(size_t)a]) { skip[(size_t)act[(size_t)a]] = 1; if (!rc) { rc = rcs[(size_t)a]; bad = a; } }
+    if (rc) plan_remove(m->S, m->rows.data(), m->blk_local, m->blk_global, ids, n_ids, &skip, plan);      // the tables of what did go
+    m->total -= plan.removed;
+    for (int s = 0; s < m->S; ++s) {
+        const bool same = plan.local[(size_t)s] == m->blk_local[(size_t)s] && plan.global[(size_t)s] == m->blk_global[(size_t)s];
+        m->blk_local[(size_t)s] = plan.local[(size_t)s];
+        m->blk_global[(size_t)s] = plan.global[(size_t)s];
+        m->rows[(size_t)s] = plan.rows[(size_t)s];
+        if (same) continue;
+        const int prc = push_blocks(m, s);
+        if (prc && !rc) { rc = prc; const char* e = cmr_last_error(); errs.assign(1, e ? e : ""); bad = 0; act.assign(1, s); }
+    }
+    // (the open block — m->cur, m->room — stays: the next append continues the shard's last run when that run still ends at the
+    // last global id and opens a new block otherwise, mindex_append decides from the tables)
+    if (n_removed) *n_removed = plan.removed;
+    if (rc) return cmr_fail(rc, "shard %d: %s", act[(size_t)bad], errs[(size_t)bad].c_str());
+    return CMR_OK;
+}
 
 int32_t cmr_mindex_plan_append(const int64_t* shard_rows, int32_t n_shards, int32_t cur_shard, int64_t cur_room, int64_t m, int64_t block_rows,
                                int32_t max_chunks, int32_t* out_shard, int64_t* out_count, int32_t* n_chunks, int32_t* new_cur, int64_t* new_room) {

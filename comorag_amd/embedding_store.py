@@ -19,6 +19,8 @@ ComoRAG.py / timeline_utils.py / cluster_utils.py run on it unchanged.  What dif
   matrix; `vdb_{ns}.meta.json` holds the dim) and updates the dicts incrementally; a load cuts off whatever a crash
   left behind the last complete (id line, vector) pair; `export_parquet()` writes the reference-schema file
   on demand, and an existing `vdb_{ns}.parquet` is imported on first load.
+* `delete(hash_ids)` (the reference has none): rows leave the matrix, the id / text lists, the four maps, the persisted files and the
+  HBM mirror (`DenseIndex.remove_ids`: compaction on the device), so row ids keep equalling `hash_id_to_idx`.
 
 Conscious deviations: `hash_id_to_text` / `text_to_hash_id` exist on an empty store too (the
 reference leaves them undefined until the first save, embedding_store.py:106-107).
@@ -114,6 +116,7 @@ class EmbeddingStore:
         (a) whole vectors without an id line, (b) a torn last vector, (c) a torn last id line.  The id lines that are
         complete AND have their vector are the store; everything behind them is cut off both files."""
         import json
+        self._finish_delete()
         if not os.path.exists(self._rows_file):
             # The very first append crashed between the vectors and the id lines: whole orphan vectors and no id file.
             # They are zero valid rows — left in place, the next append would write behind them and the following load
@@ -175,6 +178,98 @@ class EmbeddingStore:
             for h, t in zip(hash_ids, texts):
                 f.write(json.dumps([h, t], ensure_ascii=False) + "\n")
             f.flush(); os.fsync(f.fileno())
+
+    def _finish_delete(self) -> None:
+        """A `delete` in sidecar mode that a crash interrupted (see `_rewrite_sidecar`).  With the commit marker on disk the new
+        files were complete: whichever of them is still waiting under its `.del` name is moved into place (roll forward).  Without
+        it the old files are the store and `.del` leftovers are dropped (roll back).  Either the old or the new store, never a mix."""
+        marker = self._rows_file + ".del.commit"
+        pending = [(self._mat_file + ".del", self._mat_file), (self._rows_file + ".del", self._rows_file)]
+        if os.path.exists(marker):
+            for tmp, dst in pending:
+                if os.path.exists(tmp):
+                    os.replace(tmp, dst)
+            os.remove(marker)
+        else:
+            for tmp, _ in pending:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+        if os.path.exists(marker + ".tmp"):
+            os.remove(marker + ".tmp")
+
+    def _rewrite_sidecar(self) -> None:
+        """The whole store to the sidecar files, atomically as a pair.  Step 1: the new matrix and the new id lines are written next
+        to the old files as `vdb_{ns}.f32.del` / `vdb_{ns}.rows.jsonl.del` and synced.  Step 2: the commit marker
+        `vdb_{ns}.rows.jsonl.del.commit` appears (temporary file + os.replace) — THE commit point.  Step 3: os.replace of the matrix,
+        then of the id lines, then the marker goes.  A load (`_finish_delete`) that finds the marker finishes step 3, one that finds
+        `.del` files without it drops them.  The files are synced before the marker, and the directory after the marker's replace and
+        after the two data replaces, so the order also holds across a power loss."""
+        import json
+        marker = self._rows_file + ".del.commit"
+        with open(self._mat_file + ".del", "wb") as f:
+            np.ascontiguousarray(self._mat[:self._n], dtype=np.float32).tofile(f)
+            f.flush(); os.fsync(f.fileno())
+        with open(self._rows_file + ".del", "w", encoding="utf-8") as f:
+            for h, t in zip(self.hash_ids, self.texts):
+                f.write(json.dumps([h, t], ensure_ascii=False) + "\n")
+            f.flush(); os.fsync(f.fileno())
+        with open(marker + ".tmp", "w") as f:
+            json.dump({"rows": int(self._n)}, f)
+            f.flush(); os.fsync(f.fileno())
+        os.replace(marker + ".tmp", marker)
+        self._sync_dir()                       # the marker is durable before either data file is replaced: a power loss cannot reorder them
+        os.replace(self._mat_file + ".del", self._mat_file)
+        os.replace(self._rows_file + ".del", self._rows_file)
+        self._sync_dir()                       # ... and both replaces are durable before the marker goes
+        os.remove(marker)
+
+    def _sync_dir(self) -> None:
+        fd = os.open(os.path.dirname(self._rows_file) or ".", os.O_RDONLY)
+        try:
+            os.fsync(fd)
+        finally:
+            os.close(fd)
+
+    def delete(self, hash_ids) -> int:
+        """Remove the rows of the given hash ids (unknown ids are ignored) → rows removed.  The surviving rows keep their order and
+        are renumbered densely — in the matrix, `hash_ids`, `texts`, the four maps and, when it exists, the HBM mirror
+        (`remove_ids`), so row ids keep equalling `hash_id_to_idx`.  The result is persisted: parquet mode rewrites the file as every
+        save does; sidecar mode rewrites both files through temporary files and a commit marker (`_rewrite_sidecar`), so a crash
+        leaves the old or the new store.  A deleted text can be inserted again and then gets a new last row."""
+        if isinstance(hash_ids, str):
+            hash_ids = [hash_ids]
+        with self._lock:
+            rows = sorted({self.hash_id_to_idx[h] for h in hash_ids if h in self.hash_id_to_idx})
+            if not rows:
+                return 0
+            if self._index is not None:
+                try:
+                    gone = self._index.remove_ids(np.asarray(rows, dtype=np.int64))
+                    if gone != len(rows):
+                        raise RuntimeError(f"the device mirror removed {gone} rows of {len(rows)}")
+                except Exception:
+                    # the mirror may have moved rows while the host side has not: drop it, the next device_index() rebuilds it from
+                    # the (unchanged) host matrix, so row ids keep equalling hash_id_to_idx
+                    try:
+                        self._index.close()
+                    finally:
+                        self._index = None
+                    raise
+            keep = np.ones(self._n, dtype=bool)
+            keep[rows] = False
+            n_new = self._n - len(rows)
+            self._mat[:n_new] = self._mat[:self._n][keep]
+            self._n = n_new
+            self.hash_ids = [h for h, k in zip(self.hash_ids, keep) if k]
+            self.texts = [t for t, k in zip(self.texts, keep) if k]
+            self._rebuild_maps()
+            if self.persist == "sidecar":
+                if os.path.exists(self._rows_file) or os.path.exists(self._mat_file):
+                    self._rewrite_sidecar()
+            else:
+                self._save_data()
+            logger.info(f"Deleted {len(rows)} records, {self._n} left.")
+            return len(rows)
 
     def export_parquet(self, path: Optional[str] = None) -> str:
         """Write the reference-schema parquet (`hash_id`, `content`, `embedding: list<float>`)."""

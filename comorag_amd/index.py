@@ -140,9 +140,24 @@ def _mask_popcount(words: np.ndarray, n_rows: int) -> int:
     return total
 
 
+def renumber_after_removal(ids, removed) -> np.ndarray:
+    """Row ids held outside an index (cached result ids, a graph's vertex_of_row, the ids behind prepacked mask words) in the numbering
+    after `remove_ids(removed)`: int64 array of the shape of `ids`, each entry its new id — id minus the distinct removed ids below it —
+    or -1 where the entry itself was removed; negative entries (-1 padding) stay -1.  `removed`: the ids that were REMOVED, in the old
+    numbering (what `remove_ids` was given, restricted to ids the index held; negative entries and duplicates are ignored).  Pure numpy."""
+    ids = np.asarray(ids, dtype=np.int64)
+    gone = np.unique(np.asarray(removed, dtype=np.int64).ravel())
+    gone = gone[gone >= 0]
+    below = np.searchsorted(gone, ids, side="left")
+    hit = np.zeros(ids.shape, dtype=bool)
+    if len(gone):
+        hit = gone[np.minimum(below, len(gone) - 1)] == ids
+    return np.where((ids < 0) | hit, np.int64(-1), ids - below).astype(np.int64)
+
+
 # the calls whose host-array marshalling `DenseIndex` (cmr_index_*) and `MultiDeviceIndex` (cmr_mindex_*) share
 _HOST_CALLS = ("destroy", "size", "info", "append", "search", "search_exact", "search_min_score", "scores", "sorted_scores",
-               "rescore", "get_rows", "search_ids")
+               "rescore", "get_rows", "search_ids", "remove_ids")
 _bound = {}
 
 
@@ -202,6 +217,19 @@ class HostArrayIndex:
         if rows.ndim != 2 or rows.shape[1] != self.dim:
             raise ValueError(f"rows must be [n,{self.dim}], got {rows.shape}")
         L.check(self._c.append(self._h, _ptr(rows), rows.shape[0]))
+
+    # -- remove (cmr_index_remove_ids / cmr_mindex_remove_ids)
+    def remove_ids(self, ids) -> int:
+        """Remove the listed rows (FAISS `IndexFlat.remove_ids`): survivors keep their order and are renumbered densely — row r becomes
+        r minus the removed rows below it — and the index then answers every call bit for bit like a fresh one built from the surviving
+        rows.  `ids`: anything `np.asarray(..., int64)` takes, row ids AS THE SEARCHES RETURN THEM (id base applied; `MultiDeviceIndex`:
+        global ids); -1 padding, other negative ids, ids the index does not hold and duplicates are ignored, so a padded 2-d result of
+        an earlier search goes in as it is.  → rows actually removed.  Row numbers held outside the index are stale afterwards
+        (`renumber_after_removal`).  Exclusive like `append`; waits for everything in flight on the device."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64)).reshape(-1)
+        n = C.c_int64(0)
+        L.check(self._c.remove_ids(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(n)))
+        return n.value
 
     # -- search
     def search(self, q, k: int, with_minmax: bool = True

@@ -233,6 +233,35 @@ int32_t cmr_index_search_ids_dev(cmr_index_t* idx, const float* q_f32_dev, int32
                                  const int64_t* id_offsets_dev, const int64_t* ids_dev, int64_t n_ids, int64_t* out_ids_dev,
                                  float* out_scores_dev, float* out_min_dev, float* out_max_dev, void* stream);
 
+/* ROW REMOVAL by stable in-place compaction on the device (FAISS IndexFlat.remove_ids).  The listed rows go, the
+ * survivors keep their relative order and are renumbered densely: local row r becomes r - #{removed rows < r}.  Afterwards the index IS
+ * the shorter index — every entry point returns, bit for bit, what a fresh index built by appending the surviving rows in their old order
+ * returns (ids, score bits, min / max, complete rankings, get_rows, the exact search's flags), on every route.  Two things may differ from
+ * that fresh index: the index-wide maxima behind cmr_index_round_stats / cmr_index_prefilter_stats / the exact search's certificate may
+ * stay at their old, larger values (still valid upper bounds: certified results do not change), and device_bytes does not shrink
+ * (capacity is kept).  Row numbers held outside the index — prepacked mask words, a graph's vertex_of_row, cached result ids — are stale
+ * afterwards; the caller renumbers them.
+ *   ids        int64 row ids AS THE SEARCH ENTRY POINTS RETURN THEM (id base applied; cmr_mindex_remove_ids: global ids), by the rules of
+ *              the id-list searches above: -1 padding, other negative ids, ids the index does not hold and duplicates are ignored, so a
+ *              padded [nq, k] result of an earlier search goes in as it is.  An id base stays as it is.
+ *   n_removed  (may be NULL) rows actually removed.  Removing nothing is legal and changes nothing; removing every row leaves an empty
+ *              index that accepts appends.
+ * Synchronous and exclusive, like an append: it waits for the searches that hold the index and then for EVERYTHING this process has
+ * enqueued on the device (a device synchronise: removal is a maintenance call), so the results of _dev / pipelined calls issued before
+ * the removal are complete when it returns, and calls issued after it see the shorter index.
+ * CMR_ERR_INVALID, before any device call: a NULL handle, NULL ids with n_ids > 0, n_ids < 0.  CMR_ERR_UNSUPPORTED, index untouched: a
+ * user-set block table of more than one block (cmr_index_set_id_blocks) — its owner removes (cmr_mindex_remove_ids).  Out of memory for
+ * the scratch or the staging buffer is reported before any row moves (index untouched); after a HIP error from the copy launches the
+ * rows are unspecified (the int8 companion is already marked stale from the first removed row on).
+ * How: the keep words by the builder of the id-list searches, a one-workgroup prefix sum over their popcounts, then — unless nothing
+ * goes or only a tail goes (a truncate) — the 16-byte slots of the panels from the first removed row's on move chunk by chunk through a
+ * bounded staging buffer (the append's), ordered by one stream; the fp32 shadow of a CMR_FLAG_KEEP_F32 index likewise row by row.  The
+ * int8 companion of the pre-filter is not compacted: the next pre-filtered call quantises again from the first removed row's panel.
+ * Route selector "remove_stage_panels": panels the staging buffer holds (0 = default: 64 MiB worth; at least 2; never more than the
+ * affected panels + 1); a chunk is that many source panels less one, because its destination rows may straddle one panel more.  Results
+ * never depend on it.  Read-only "remove_chunks_last": chunks the corpus pass of the last removal ran (0: nothing moved).              */
+int32_t cmr_index_remove_ids(cmr_index_t* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed /* may be NULL */);
+
 /* Throughput mode for a stream of independent query batches (serving; bench.py).  Work is enqueued on streams owned by
  * the index: query packing + sampling passes of batch i+1 overlap the HBM-bound main scan of batch i.  On a 256-CU device
  * main scans shorter than ~1 ms (shards up to ~4 M x 768 bf16 rows) of batches of <= 64 queries run on a CU-masked pair of
@@ -583,6 +612,29 @@ int32_t cmr_mindex_profile(cmr_mindex_t* m, int32_t reset, int64_t* n_batches, d
 int32_t cmr_mindex_plan_append(const int64_t* shard_rows, int32_t n_shards, int32_t cur_shard, int64_t cur_room, int64_t m,
                                int64_t block_rows, int32_t max_chunks, int32_t* out_shard, int64_t* out_count, int32_t* n_chunks,
                                int32_t* new_cur, int64_t* new_room);
+/* Row removal over the shards (cmr_index_remove_ids above has the semantics): GLOBAL ids in, global ids dense again in the old global
+ * order afterwards — results equal ONE cmr_index_t that removed the same ids.  The new block tables are planned on the host first
+ * (cmr_mindex_plan_remove), then every shard that loses rows compacts its own, all shards at once, then the tables, the shards' row
+ * counts and the total are replaced; later appends keep global ids dense in append order (the open block stays open: an append continues
+ * a shard's last run only while that run ends at the last global id).  Exclusive over the handle; uncollected tickets of
+ * cmr_mindex_search_pipelined issued before stay collectable with the ids of before.
+ * The only fallible step is a shard's compaction.  If one fails, the call returns its error, *n_removed = the rows that did go, and the
+ * index is left CONSISTENT as if only the ids held by the shards that succeeded had been listed: those rows are gone, global ids are
+ * dense, the failed shard's listed rows are all still there (out of memory: it is untouched) — the caller may call again with the same
+ * list.  (After a HIP error inside a shard's copy launches that shard's rows are unspecified, as in cmr_index_remove_ids.)  One case is NOT
+ * consistent: a shard that reports success but another number of removed rows than the host planned — CMR_ERR_HIP, the tables are left as
+ * they were and no longer describe the shards; destroy the index.
+ * cmr_mindex_plan_remove is the table arithmetic on its own (pure host, no device): the shards' tables — n_blocks[s] blocks each,
+ * concatenated in shard order in local_start / global_start, block b of a shard holding local rows [local_start[b], next local start or
+ * shard_rows[s]) = global ids global_start[b] + ... — and the ids to remove give the new row counts and tables (same layout; never more
+ * blocks than came in; any output may be NULL).  skip_shards (NULL: none): ids held by a shard with a non-zero entry are ignored, as
+ * if they had not been listed — the tables cmr_mindex_remove_ids installs when those shards' compaction failed.  A block's new global start is its old one minus the removed ids below it, its length
+ * shrinks by the removed ids inside it, empty blocks are dropped, local starts are the running sum.                                  */
+int32_t cmr_mindex_remove_ids(cmr_mindex_t* m, const int64_t* ids /* GLOBAL row ids */, int64_t n_ids, int64_t* n_removed /* may be NULL */);
+int32_t cmr_mindex_plan_remove(int32_t n_shards, const int64_t* shard_rows, const int32_t* n_blocks /*[n_shards]*/, const int64_t* local_start,
+                               const int64_t* global_start, const int64_t* ids, int64_t n_ids, const int32_t* skip_shards /*[n_shards] or NULL*/,
+                               int64_t* new_shard_rows /*[n_shards]*/, int32_t* new_n_blocks /*[n_shards]*/, int64_t* new_local_start,
+                               int64_t* new_global_start, int64_t* n_removed);
 
 /* ---- encoder tail -----------------------------------------------------------------------
  * Fused masked mean-pool + L2-normalise of the encoder's last hidden state; replaces
