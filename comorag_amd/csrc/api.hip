@@ -707,9 +707,8 @@ int cmr_index_scores_to_device_batch(cmr_index_t* idx, const float* q_host, int 
     if (!idx || !q_host || !scores_dev || !n || !stream || nb < 1) return fail(CMR_ERR_INVALID, "NULL argument");
     if (tl_scores_ws) return fail(CMR_ERR_INVALID, "nested cmr_index_scores_to_device on one thread");
     idx->mu.lock_shared();
-    int rc = cmr_set_device(idx->device);
-    Workspace* ws = rc ? nullptr : acquire_ws(idx, nullptr, false);
-    if (!rc && !ws) rc = fail(CMR_ERR_HIP, "could not create a workspace stream");
+    Workspace* ws = nullptr;
+    int rc = open_ws(idx, nullptr, false, &ws);
     if (!rc) {
         hipStream_t s = ws->stream;
         auto body = [&]() -> int {
@@ -960,109 +959,48 @@ int32_t cmr_index_search_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, i
     if (!idx || !q_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
     if (k <= 0 || k > CMR_MAX_K_2PASS) return fail(CMR_ERR_UNSUPPORTED, "k = %d outside [1, %d]", k, CMR_MAX_K_2PASS);
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    int rc = cmr_set_device(idx->device);
+    DevCall call(idx);
+    int rc = call.open(stream);
     if (rc) return rc;
-    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
-    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
-    return search_enqueue(idx, ws, q_dev, nq, k, ids_dev, scores_dev, min_dev, max_dev);
+    return search_enqueue(idx, call.ws, q_dev, nq, k, ids_dev, scores_dev, min_dev, max_dev);
 }
 
 // ---- filtered search (include/comorag_hip.h: cmr_index_search_masked*, cmr_index_search_masked_each*).  Never
 // pre-filtered; the _dev forms go straight to search_masked_enqueue, the host forms through the combiner where "combine_filtered" is set
 // (further down, beside the other combined calls).
+static int words_check(const cmr_index* idx, int64_t n_words) {      // a mask is one word per 32-row panel (under the index lock)
+    if (n_words != panels_of(idx->n)) return fail(CMR_ERR_INVALID, "n_words %lld != ceil(%lld rows / 32) = %lld", (long long)n_words, idx->n, panels_of(idx->n));
+    return CMR_OK;
+}
 static int masked_check(const cmr_index* idx, int nq, int k, int64_t n_words) {      // (under the index lock; no device call)
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
     if (k <= 0) return fail(CMR_ERR_INVALID, "k must be > 0");
-    if (n_words != panels_of(idx->n)) return fail(CMR_ERR_INVALID, "n_words %lld != ceil(%lld rows / 32) = %lld", (long long)n_words, idx->n, panels_of(idx->n));
+    if (int rc = words_check(idx, n_words)) return rc;
     if (k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "filtered search supports k <= %d", CMR_MAX_K);
     return CMR_OK;
 }
 
-int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words,
-                                    int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
+// each = false: allow_dev is [n_words], one mask for every query; each = true: [nq][n_words]
+static int32_t masked_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words, bool each,
+                          int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
     if (!idx || !q_dev || !allow_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    DevCall call(idx);
     int rc = masked_check(idx, nq, k, n_words);
     if (rc) return rc;
-    rc = cmr_set_device(idx->device);
+    rc = call.open(stream);
     if (rc) return rc;
-    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
-    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
-    return search_masked_enqueue(idx, ws, q_dev, nq, k, allow_dev, ids_dev, scores_dev, min_dev, max_dev);
+    return search_masked_enqueue(idx, call.ws, q_dev, nq, k, allow_dev, ids_dev, scores_dev, min_dev, max_dev, each ? (long long)n_words : 0);
+}
+
+int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words,
+                                    int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
+    return masked_dev(idx, q_dev, nq, k, allow_dev, n_words, false, ids_dev, scores_dev, min_dev, max_dev, stream);
 }
 
 int32_t cmr_index_search_masked_each_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words,
                                          int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
-    if (!idx || !q_dev || !allow_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    int rc = masked_check(idx, nq, k, n_words);
-    if (rc) return rc;
-    rc = cmr_set_device(idx->device);
-    if (rc) return rc;
-    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
-    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
-    return search_masked_enqueue(idx, ws, q_dev, nq, k, allow_dev, ids_dev, scores_dev, min_dev, max_dev, n_words);
+    return masked_dev(idx, q_dev, nq, k, allow_dev, n_words, true, ids_dev, scores_dev, min_dev, max_dev, stream);
 }
-
-}  // extern "C"
-
-// The synchronous filtered search behind cmr_index_search_masked (each = false: `allow` is [n_words], one mask for every query) and
-// cmr_index_search_masked_each (each = true: `allow` is [nq][n_words]).  The caller holds the index lock (`call`) and has checked the
-// arguments (masked_check).
-static int masked_sync(SyncCall& call, const float* q, int nq, int k, const uint32_t* allow, int64_t n_words, bool each,
-                       int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
-    cmr_index* const idx = call.idx;
-    int rc = call.ws ? CMR_OK : call.open();
-    if (rc) return rc;
-    Workspace* const ws = call.ws;
-    hipStream_t const s = call.s;
-    // packed device buffer [flag (8 B) | ids nq*k i64 | scores nq*k f32 | min nq | max nq] and its pinned host twin, as the copy path of
-    // cmr_index_search; queries and allow words go up through the pinned buffer into this workspace's own scratch
-    const size_t o_ids = 8, o_sc = o_ids + (size_t)nq * k * 8, o_min = o_sc + (size_t)nq * k * 4, o_max = o_min + (size_t)nq * 4,
-                 out_bytes = o_max + (size_t)nq * 4, q_bytes = (size_t)nq * idx->dim * 4, m_bytes = (size_t)n_words * 4 * (each ? (size_t)nq : 1);
-    HIP_TRY(ws->d_q.ensure(q_bytes));
-    HIP_TRY(ws->d_mask.ensure(std::max<size_t>(m_bytes, 4)));
-    if (out_bytes > ws->d_pack.cap || !ws->d_pack.p) {        // (re)allocation moves the flag: re-arm it at the new place
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(ws->d_pack.ensure(std::max<size_t>(out_bytes, 4096)));
-        HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, 8, s));
-    }
-    char* const pk = (char*)ws->d_pack.p;
-    auto body = [&]() -> int {
-        FlagOverride flag(ws, (int*)pk);
-        HIP_TRY(ws->ensure_pin(std::max(out_bytes, q_bytes + m_bytes)));
-        char* const hp = (char*)ws->h_pin;
-        memcpy(hp, q, q_bytes);
-        memcpy(hp + q_bytes, allow, m_bytes);
-        HIP_TRY(hipMemcpyAsync(ws->d_q.p, hp, q_bytes, hipMemcpyHostToDevice, s));
-        if (m_bytes) HIP_TRY(hipMemcpyAsync(ws->d_mask.p, hp + q_bytes, m_bytes, hipMemcpyHostToDevice, s));
-        const int rc_ = search_masked_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, (const unsigned*)ws->d_mask.p, (int64_t*)(pk + o_ids), (float*)(pk + o_sc),
-                                              (float*)(pk + o_min), (float*)(pk + o_max), each ? (long long)n_words : 0);
-        if (rc_) return rc_;
-        // (the pinned buffer still holds what the H2D copies read: stream order puts the D2H copy behind them)
-        HIP_TRY(hipMemcpyAsync(hp, pk, out_bytes, hipMemcpyDeviceToHost, s));
-        return CMR_OK;
-    };
-    rc = body();
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    HIP_TRY(hipStreamSynchronize(s));
-    const char* const hp = (const char*)ws->h_pin;
-    int flagged = 0;
-    memcpy(&flagged, hp, sizeof(int));
-    if (flagged) {
-        HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, sizeof(int), s));
-        return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf or a value that rounds to Inf in the index dtype");
-    }
-    const size_t nk = (size_t)nq * k;
-    memcpy(out_ids, hp + o_ids, nk * 8);
-    memcpy(out_scores, hp + o_sc, nk * 4);
-    if (out_min) memcpy(out_min, hp + o_min, (size_t)nq * 4);
-    if (out_max) memcpy(out_max, hp + o_max, (size_t)nq * 4);
-    return CMR_OK;
-}
-
-extern "C" {
 
 int32_t cmr_index_search_min_score_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, float min_score, int64_t* ids_dev,
                                        float* scores_dev, void* stream) {
@@ -1070,12 +1008,10 @@ int32_t cmr_index_search_min_score_dev(cmr_index_t* idx, const float* q_dev, int
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
     if (k <= 0 || k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "threshold search supports k in [1, %d]", CMR_MAX_K);
     if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    int rc = cmr_set_device(idx->device);
+    DevCall call(idx);
+    int rc = call.open(stream);
     if (rc) return rc;
-    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
-    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
-    return search_enqueue(idx, ws, q_dev, nq, k, ids_dev, scores_dev, nullptr, nullptr, &min_score);
+    return search_enqueue(idx, call.ws, q_dev, nq, k, ids_dev, scores_dev, nullptr, nullptr, &min_score);
 }
 
 int32_t cmr_index_search_pipelined(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, int64_t* ids_dev, float* scores_dev,
@@ -1234,14 +1170,26 @@ int32_t cmr_event_synchronize(void* event) {
 // ---- synchronous host-buffer search in two halves (cmr_internal.h): `begin` enqueues everything on the workspace's stream and
 // returns without waiting, `finish` waits, checks the non-finite flag and copies the results out.  cmr_index_search is begin +
 // finish; the multi-device index (multi.hip) begins on every shard before it finishes on any, so all devices scan at once.
+// Every synchronous top-k call — unfiltered, masked, from id lists, on one index or on the shards of a multi-device one — is begin +
+// finish on a CmrPending; everything but the mapped branch of cmr_index_search_begin begins in packed_begin.
+
+// the packed result buffer of such a call, on the device and in the pinned host buffer: [flag 8 B | ids nq*k i64 | scores nq*k f32 | min nq | max nq]
+struct PackLayout {
+    size_t o_ids = 8, o_sc, o_min, o_max, bytes;
+    PackLayout(int nq, int k) {
+        o_sc = o_ids + (size_t)nq * k * 8; o_min = o_sc + (size_t)nq * k * 4; o_max = o_min + (size_t)nq * 4; bytes = o_max + (size_t)nq * 4;
+    }
+};
+
 struct CmrPending {
-    cmr_index* idx = nullptr;
+    cmr_index* idx;
     Workspace* ws = nullptr;
     bool locked = false;          // holds idx->mu shared (released by finish / abandon ON THE SAME THREAD)
     bool mapped = false;          // results land in the pinned buffer by themselves (zero-copy) / by the enqueued D2H copy
     bool poll = false;            // the search's last kernel sets the done word of the pinned buffer (Workspace::done_ptr): finish polls it
-    int nq = 0, k = 0;
-    size_t o_ids = 0, o_sc = 0, o_min = 0, o_max = 0;
+    int nq, k;
+    PackLayout at;
+    CmrPending(cmr_index* i, int nq_, int k_) : idx(i), nq(nq_), k(k_), at(nq_, k_) {}
 };
 
 static void pending_release(CmrPending* p) {
@@ -1249,27 +1197,94 @@ static void pending_release(CmrPending* p) {
     if (p->locked) p->idx->mu.unlock_shared();
     delete p;
 }
+// a begin that failed with work possibly enqueued: nothing of it outlives the call
+static int pending_fail(CmrPending* p, int rc) {
+    (void)hipStreamSynchronize(p->ws->stream);
+    pending_release(p);
+    return rc;
+}
+
+// the index's shared lock (take_lock), the device, a pooled workspace
+static int pending_open(cmr_index* idx, int nq, int k, bool take_lock, CmrPending** out) {
+    CmrPending* P = new CmrPending(idx, nq, k);
+    if (take_lock) { idx->mu.lock_shared(); P->locked = true; }
+    const int rc = open_ws(idx, nullptr, false, &P->ws);
+    if (rc) { pending_release(P); return rc; }
+    *out = P;
+    return CMR_OK;
+}
+
+// One host input of a packed call: up to two host pieces that go up as ONE block, into a buffer of the workspace.
+struct PackedInput { DevBuf Workspace::* dst; const void* a; size_t a_bytes; const void* b = nullptr; size_t b_bytes = 0; };
+
+// The copy path of a synchronous top-k call, on an opened pending call: the inputs staged in the pinned buffer (each at an 8-byte
+// boundary) and copied up, one copy per input (none for an empty one); `enqueue(ws, ids, scores, min, max)` — the device work, writing
+// the four areas of the packed device buffer, whose head is the call's non-finite flag; the pack copied down into the pinned buffer (which
+// still holds what the H2D copies read: stream order puts the D2H copy behind them).  Ends in cmr_index_search_finish / _abandon; a
+// failure releases the pending call here.
+template <int N, class Enqueue>
+static int packed_enqueue(CmrPending* P, const PackedInput (&in)[N], Enqueue&& enqueue) {
+    Workspace* const ws = P->ws;
+    hipStream_t const s = ws->stream;
+    const PackLayout& at = P->at;
+    auto body = [&]() -> int {
+        size_t o_in[N], staged = 0;
+        for (int i = 0; i < N; ++i) {
+            const size_t bytes = in[i].a_bytes + in[i].b_bytes;
+            HIP_TRY((ws->*in[i].dst).ensure(std::max<size_t>(bytes, 8)));
+            o_in[i] = staged;
+            staged += (bytes + 7) & ~(size_t)7;
+        }
+        if (at.bytes > ws->d_pack.cap || !ws->d_pack.p) {        // (re)allocation moves the flag: re-arm it at the new place
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(ws->d_pack.ensure(std::max<size_t>(at.bytes, 4096)));
+            HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, 8, s));
+        }
+        char* const pk = (char*)ws->d_pack.p;
+        FlagOverride flag(ws, (int*)pk);
+        HIP_TRY(ws->ensure_pin(std::max(at.bytes, staged)));
+        char* const hp = (char*)ws->h_pin;
+        for (int i = 0; i < N; ++i) {
+            if (in[i].a_bytes) memcpy(hp + o_in[i], in[i].a, in[i].a_bytes);
+            if (in[i].b_bytes) memcpy(hp + o_in[i] + in[i].a_bytes, in[i].b, in[i].b_bytes);
+        }
+        // (everything staged first: the copies then reach the stream back to back, with no host memcpy of a mask between two submissions)
+        for (int i = 0; i < N; ++i)
+            if (const size_t bytes = in[i].a_bytes + in[i].b_bytes) HIP_TRY(hipMemcpyAsync((ws->*in[i].dst).p, hp + o_in[i], bytes, hipMemcpyHostToDevice, s));
+        const int rc_ = enqueue(ws, (int64_t*)(pk + at.o_ids), (float*)(pk + at.o_sc), (float*)(pk + at.o_min), (float*)(pk + at.o_max));
+        if (rc_) return rc_;
+        HIP_TRY(hipMemcpyAsync(hp, pk, at.bytes, hipMemcpyDeviceToHost, s));
+        return CMR_OK;
+    };
+    const int rc = body();
+    return rc ? pending_fail(P, rc) : CMR_OK;
+}
+
+template <int N, class Enqueue>
+static int packed_begin(cmr_index* idx, int nq, int k, bool take_lock, const PackedInput (&in)[N], Enqueue&& enqueue, CmrPending** out) {
+    CmrPending* P = nullptr;
+    int rc = pending_open(idx, nq, k, take_lock, &P);
+    if (rc) return rc;
+    rc = packed_enqueue(P, in, enqueue);
+    if (rc) return rc;
+    *out = P;
+    return CMR_OK;
+}
 
 int cmr_index_search_begin(cmr_index_t* idx, const float* q, int nq, int k, const float* min_score, bool take_lock, CmrPending** out) {
     if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
     *out = nullptr;
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
     if (k <= 0 || k > CMR_MAX_K_2PASS) return fail(CMR_ERR_UNSUPPORTED, "k = %d outside [1, %d]", k, CMR_MAX_K_2PASS);
-    CmrPending* P = new CmrPending();
-    P->idx = idx; P->nq = nq; P->k = k;
-    if (take_lock) { idx->mu.lock_shared(); P->locked = true; }
-    int rc = cmr_set_device(idx->device);
-    if (rc) { pending_release(P); return rc; }
-    Workspace* ws = acquire_ws(idx, nullptr, false);
-    if (!ws) { pending_release(P); return fail(CMR_ERR_HIP, "could not create a workspace stream"); }
-    P->ws = ws;
-    hipStream_t s = ws->stream;
-    // packed result buffer [flag (8 B) | ids nq*k i64 | scores nq*k f32 | min nq | max nq]
-    const size_t o_ids = 8, o_sc = o_ids + (size_t)nq * k * 8, o_min = o_sc + (size_t)nq * k * 4, o_max = o_min + (size_t)nq * 4,
-                 out_bytes = o_max + (size_t)nq * 4, q_bytes = (size_t)nq * idx->dim * 4;
-    P->o_ids = o_ids; P->o_sc = o_sc; P->o_min = o_min; P->o_max = o_max;
-    auto body = [&]() -> int {
-        if (idx->zero_copy && k <= CMR_MAX_K && q_bytes <= kZeroCopyMax && out_bytes <= kZeroCopyMax) {
+    CmrPending* P = nullptr;
+    int rc = pending_open(idx, nq, k, take_lock, &P);
+    if (rc) return rc;
+    Workspace* const ws = P->ws;
+    hipStream_t const s = ws->stream;
+    const PackLayout& at = P->at;
+    const size_t q_bytes = (size_t)nq * idx->dim * 4;
+    if (idx->zero_copy && k <= CMR_MAX_K && q_bytes <= kZeroCopyMax && at.bytes <= kZeroCopyMax) {
+        auto body = [&]() -> int {
             // (the hierarchical single-launch path packs the queries in up to 64 workgroups: they read a device copy, not
             // 64 times across the link)
             const bool map_in = small_path_kind(idx, nq, k, min_score != nullptr) != 2;
@@ -1279,7 +1294,7 @@ int cmr_index_search_begin(cmr_index_t* idx, const float* q, int nq, int k, cons
             // (fine-grained: kernel stores are visible once the stream has been synchronised) that the kernels read and
             // write over PCIe themselves — a few KiB either way.
             MappedStage m;
-            { int rc_ = stage_mapped(ws, out_bytes, q_bytes, true, &m); if (rc_) return rc_; }
+            { int rc_ = stage_mapped(ws, at.bytes, q_bytes, true, &m); if (rc_) return rc_; }
             char* const d = m.d;
             memcpy(m.h + m.o_in, q, q_bytes);
             const float* q_in = (const float*)(d + m.o_in);
@@ -1290,35 +1305,23 @@ int cmr_index_search_begin(cmr_index_t* idx, const float* q, int nq, int k, cons
             }
             FlagOverride flag(ws, (int*)d);
             ws->done_ptr = idx->sync_poll ? (int*)(d + 4) : nullptr; ws->done_used = false; ws->lazy.due = false;      // (bytes 4..7 of the header were zeroed by stage_mapped)
-            const int rc_ = search_enqueue(idx, ws, q_in, nq, k, (int64_t*)(d + o_ids), (float*)(d + o_sc), (float*)(d + o_min), (float*)(d + o_max), min_score);
+            const int rc_ = search_enqueue(idx, ws, q_in, nq, k, (int64_t*)(d + at.o_ids), (float*)(d + at.o_sc), (float*)(d + at.o_min), (float*)(d + at.o_max), min_score);
             ws->done_ptr = nullptr;
             P->mapped = true;
             P->poll = rc_ == CMR_OK && ws->done_used;
             return rc_;
-        }
+        };
+        rc = body();
+        if (rc) return pending_fail(P, rc);
+    } else {
         // packed device buffer and its pinned host twin, one copy each way; the queries go through the pinned buffer too (a
         // pageable H2D is staged by the runtime anyway)
-        HIP_TRY(ws->d_q.ensure(q_bytes));
-        if (out_bytes > ws->d_pack.cap || !ws->d_pack.p) {        // (re)allocation moves the flag: re-arm it at the new place
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(ws->d_pack.ensure(std::max<size_t>(out_bytes, 4096)));
-            HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, 8, s));
-        }
-        char* pk = (char*)ws->d_pack.p;
-        {
-            FlagOverride flag(ws, (int*)pk);
-            HIP_TRY(ws->ensure_pin(std::max(out_bytes, q_bytes)));
-            memcpy(ws->h_pin, q, q_bytes);
-            HIP_TRY(hipMemcpyAsync(ws->d_q.p, ws->h_pin, q_bytes, hipMemcpyHostToDevice, s));
-            const int rc_ = search_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, (int64_t*)(pk + o_ids), (float*)(pk + o_sc), (float*)(pk + o_min), (float*)(pk + o_max), min_score);
-            if (rc_) return rc_;
-        }
-        // (the pinned buffer still holds the queries the H2D copy reads: stream order puts the D2H copy behind it)
-        HIP_TRY(hipMemcpyAsync(ws->h_pin, pk, out_bytes, hipMemcpyDeviceToHost, s));
-        return CMR_OK;
-    };
-    rc = body();
-    if (rc) { (void)hipStreamSynchronize(s); pending_release(P); return rc; }
+        const PackedInput in[] = {{&Workspace::d_q, q, q_bytes}};
+        rc = packed_enqueue(P, in, [&](Workspace* w, int64_t* ids, float* sc, float* mn, float* mx) {
+            return search_enqueue(idx, w, (const float*)w->d_q.p, nq, k, ids, sc, mn, mx, min_score);
+        });
+        if (rc) return rc;
+    }
     *out = P;
     return CMR_OK;
 }
@@ -1350,10 +1353,10 @@ int cmr_index_search_finish(CmrPending* P, int64_t* out_ids, float* out_scores, 
         return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf or a value that rounds to Inf in the index dtype");
     }
     const size_t nk = (size_t)P->nq * P->k;
-    if (out_ids) memcpy(out_ids, hp + P->o_ids, nk * 8);
-    if (out_scores) memcpy(out_scores, hp + P->o_sc, nk * 4);
-    if (out_min) memcpy(out_min, hp + P->o_min, (size_t)P->nq * 4);
-    if (out_max) memcpy(out_max, hp + P->o_max, (size_t)P->nq * 4);
+    if (out_ids) memcpy(out_ids, hp + P->at.o_ids, nk * 8);
+    if (out_scores) memcpy(out_scores, hp + P->at.o_sc, nk * 4);
+    if (out_min) memcpy(out_min, hp + P->at.o_min, (size_t)P->nq * 4);
+    if (out_max) memcpy(out_max, hp + P->at.o_max, (size_t)P->nq * 4);
     return CMR_OK;
 }
 
@@ -1428,55 +1431,18 @@ int search_ids_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq
 }  // namespace
 
 // cmr_index_search_ids in two halves, as cmr_index_search_begin: arguments checked by the caller (cmr_ids_args_check); finished or
-// abandoned through cmr_index_search_finish / _abandon.  Queries, offsets and ids go up through the pinned buffer into this workspace's
-// scratch, the results come back by one copy.
+// abandoned through cmr_index_search_finish / _abandon.  The packed round trip (packed_begin) with two inputs: the queries, and
+// [offsets (nq + 1) | ids] as one block into d_lists.
 int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, int mode, const int64_t* off, const int64_t* ids, int64_t n_ids,
                                bool take_lock, CmrPending** out) {
     if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    CmrPending* P = new CmrPending();
-    P->idx = idx; P->nq = nq; P->k = k;
-    if (take_lock) { idx->mu.lock_shared(); P->locked = true; }
-    int rc = cmr_set_device(idx->device);
-    if (rc) { pending_release(P); return rc; }
-    Workspace* ws = acquire_ws(idx, nullptr, false);
-    if (!ws) { pending_release(P); return fail(CMR_ERR_HIP, "could not create a workspace stream"); }
-    P->ws = ws;
-    hipStream_t s = ws->stream;
-    // packed result buffer [flag (8 B) | ids nq*k i64 | scores nq*k f32 | min nq | max nq]; inputs [queries | offsets (nq + 1) | ids]
-    const size_t o_ids = 8, o_sc = o_ids + (size_t)nq * k * 8, o_min = o_sc + (size_t)nq * k * 4, o_max = o_min + (size_t)nq * 4,
-                 out_bytes = o_max + (size_t)nq * 4, q_bytes = (size_t)nq * idx->dim * 4, o_list = (q_bytes + 7) & ~(size_t)7,
-                 off_bytes = off ? ((size_t)nq + 1) * 8 : 0, list_bytes = off_bytes + (size_t)n_ids * 8;
-    P->o_ids = o_ids; P->o_sc = o_sc; P->o_min = o_min; P->o_max = o_max;
-    auto body = [&]() -> int {
-        HIP_TRY(ws->d_q.ensure(q_bytes));
-        HIP_TRY(ws->d_lists.ensure(std::max<size_t>(list_bytes, 8)));
-        if (out_bytes > ws->d_pack.cap || !ws->d_pack.p) {        // (re)allocation moves the flag: re-arm it at the new place
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(ws->d_pack.ensure(std::max<size_t>(out_bytes, 4096)));
-            HIP_TRY(hipMemsetAsync(ws->d_pack.p, 0, 8, s));
-        }
-        char* const pk = (char*)ws->d_pack.p;
-        FlagOverride flag(ws, (int*)pk);
-        HIP_TRY(ws->ensure_pin(std::max(out_bytes, o_list + list_bytes)));
-        char* const hp = (char*)ws->h_pin;
-        memcpy(hp, q, q_bytes);
-        if (off) memcpy(hp + o_list, off, off_bytes);
-        if (n_ids) memcpy(hp + o_list + off_bytes, ids, (size_t)n_ids * 8);
-        HIP_TRY(hipMemcpyAsync(ws->d_q.p, hp, q_bytes, hipMemcpyHostToDevice, s));
-        if (list_bytes) HIP_TRY(hipMemcpyAsync(ws->d_lists.p, hp + o_list, list_bytes, hipMemcpyHostToDevice, s));
-        const int64_t* const d_off = off ? (const int64_t*)ws->d_lists.p : nullptr;
-        const int rc_ = search_ids_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, mode, d_off, (const int64_t*)((char*)ws->d_lists.p + off_bytes), n_ids,
-                                           (int64_t*)(pk + o_ids), (float*)(pk + o_sc), (float*)(pk + o_min), (float*)(pk + o_max));
-        if (rc_) return rc_;
-        // (the pinned buffer still holds what the H2D copies read: stream order puts the D2H copy behind them)
-        HIP_TRY(hipMemcpyAsync(hp, pk, out_bytes, hipMemcpyDeviceToHost, s));
-        return CMR_OK;
-    };
-    rc = body();
-    if (rc) { (void)hipStreamSynchronize(s); pending_release(P); return rc; }
-    *out = P;
-    return CMR_OK;
+    const size_t off_bytes = off ? ((size_t)nq + 1) * 8 : 0;
+    const PackedInput in[] = {{&Workspace::d_q, q, (size_t)nq * idx->dim * 4}, {&Workspace::d_lists, off, off_bytes, ids, (size_t)n_ids * 8}};
+    return packed_begin(idx, nq, k, take_lock, in, [&](Workspace* ws, int64_t* ids_out, float* sc, float* mn, float* mx) {
+        return search_ids_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, mode, off ? (const int64_t*)ws->d_lists.p : nullptr,
+                                  (const int64_t*)((char*)ws->d_lists.p + off_bytes), n_ids, ids_out, sc, mn, mx);
+    }, out);
 }
 
 extern "C" {
@@ -1487,9 +1453,10 @@ int32_t cmr_index_row_masks_dev(cmr_index_t* idx, int32_t mode, int32_t nq, cons
     int rc = cmr_ids_args_check(mode, nq, 1, nullptr, ids_dev, n_ids);
     if (rc) return rc;
     if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    if (n_words != panels_of(idx->n)) return fail(CMR_ERR_INVALID, "n_words %lld != ceil(%lld rows / 32) = %lld", (long long)n_words, idx->n, panels_of(idx->n));
-    rc = cmr_set_device(idx->device);
+    DevCall call(idx);
+    rc = words_check(idx, n_words);
+    if (rc) return rc;
+    rc = call.open();      // (no workspace: the words are the caller's)
     if (rc) return rc;
     return row_masks_enqueue(idx, mode, nq, id_offsets_dev, ids_dev, n_ids, words_dev, (hipStream_t)stream);
 }
@@ -1501,12 +1468,10 @@ int32_t cmr_index_search_ids_dev(cmr_index_t* idx, const float* q_dev, int32_t n
     int rc = cmr_ids_args_check(mode, nq, k, nullptr, ids_dev, n_ids);
     if (rc) return rc;
     if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    rc = cmr_set_device(idx->device);
+    DevCall call(idx);
+    rc = call.open(stream);
     if (rc) return rc;
-    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
-    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
-    return search_ids_enqueue(idx, ws, q_dev, nq, k, mode, id_offsets_dev, ids_dev, n_ids, ids_out_dev, scores_out_dev, min_dev, max_dev);
+    return search_ids_enqueue(idx, call.ws, q_dev, nq, k, mode, id_offsets_dev, ids_dev, n_ids, ids_out_dev, scores_out_dev, min_dev, max_dev);
 }
 
 int32_t cmr_index_search_ids(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
@@ -1628,6 +1593,7 @@ static int32_t host_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t
 // (DESIGN 4.9b), scattered to the participants.
 struct CombinedSearch { const float* q; int nq, k; int64_t* ids; float* scores; float* mn; float* mx; };
 struct CombinedScores { const float* q; int nq; float* out; long long ld; };
+static const CombinedSearch* search_args(const cmr_combine::Request* r) { return (const CombinedSearch*)r->args; }
 
 // code and (on failure) this thread's message into the request; the participant publishes them in its own thread
 static void combine_answer(cmr_combine::Request* r, int rc) {
@@ -1639,28 +1605,41 @@ static int combine_result(const cmr_combine::Request& r) {
     return r.rc;
 }
 
+// The one call of a batch of top-k calls of one k (search_args of every request: a CombinedSearch, or what extends it): the participants'
+// queries gathered into one block, room for the batch's rows (`all`), and the answer with each participant's rows scattered to it.
+struct CombinedTopk {
+    std::vector<float> q, sc, mm;
+    std::vector<int64_t> ids;
+    CombinedSearch all;
+    CombinedTopk(cmr_combine::Request** reqs, int n, size_t dim) {
+        int NQ = 0;
+        for (int i = 0; i < n; ++i) NQ += reqs[i]->nq;
+        const int k = search_args(reqs[0])->k;
+        q.resize((size_t)NQ * dim); sc.resize((size_t)NQ * k); mm.resize((size_t)NQ * 2); ids.resize((size_t)NQ * k);
+        for (int i = 0, q0 = 0; i < n; q0 += reqs[i++]->nq) memcpy(q.data() + (size_t)q0 * dim, search_args(reqs[i])->q, (size_t)reqs[i]->nq * dim * 4);
+        all = CombinedSearch{q.data(), NQ, k, ids.data(), sc.data(), mm.data(), mm.data() + NQ};
+    }
+    CombinedTopk(const CombinedTopk&) = delete;      // (`all` points into this object's vectors)
+    void answer(cmr_combine::Request** reqs, int n, int rc) const {
+        for (int i = 0, q0 = 0; i < n; q0 += reqs[i++]->nq) {
+            const CombinedSearch* a = search_args(reqs[i]);
+            combine_answer(reqs[i], rc);
+            if (rc) continue;
+            const size_t nk = (size_t)a->nq * all.k;
+            memcpy(a->ids, all.ids + (size_t)q0 * all.k, nk * 8);
+            memcpy(a->scores, all.scores + (size_t)q0 * all.k, nk * 4);
+            if (a->mn) memcpy(a->mn, all.mn + q0, (size_t)a->nq * 4);
+            if (a->mx) memcpy(a->mx, all.mx + q0, (size_t)a->nq * 4);
+        }
+    }
+};
+
 static void combined_search_run(void* ctx, cmr_combine::Request** reqs, int n) {
     cmr_index* const idx = (cmr_index*)ctx;
-    const CombinedSearch* a0 = (const CombinedSearch*)reqs[0]->args;
+    const CombinedSearch* a0 = search_args(reqs[0]);
     if (n == 1) { combine_answer(reqs[0], host_search(idx, a0->q, a0->nq, a0->k, a0->ids, a0->scores, a0->mn, a0->mx, nullptr)); return; }
-    int NQ = 0;
-    for (int i = 0; i < n; ++i) NQ += reqs[i]->nq;
-    const int k = a0->k;
-    const size_t dim = (size_t)idx->dim;
-    std::vector<float> q((size_t)NQ * dim), sc((size_t)NQ * k), mm((size_t)NQ * 2);
-    std::vector<int64_t> ids((size_t)NQ * k);
-    for (int i = 0, at = 0; i < n; at += reqs[i++]->nq) memcpy(q.data() + (size_t)at * dim, ((const CombinedSearch*)reqs[i]->args)->q, (size_t)reqs[i]->nq * dim * 4);
-    const int rc = host_search(idx, q.data(), NQ, k, ids.data(), sc.data(), mm.data(), mm.data() + NQ, nullptr);
-    for (int i = 0, at = 0; i < n; at += reqs[i++]->nq) {
-        const CombinedSearch* a = (const CombinedSearch*)reqs[i]->args;
-        combine_answer(reqs[i], rc);
-        if (rc) continue;
-        const size_t nk = (size_t)a->nq * k;
-        memcpy(a->ids, ids.data() + (size_t)at * k, nk * 8);
-        memcpy(a->scores, sc.data() + (size_t)at * k, nk * 4);
-        if (a->mn) memcpy(a->mn, mm.data() + at, (size_t)a->nq * 4);
-        if (a->mx) memcpy(a->mx, mm.data() + NQ + at, (size_t)a->nq * 4);
-    }
+    const CombinedTopk b(reqs, n, (size_t)idx->dim);
+    b.answer(reqs, n, host_search(idx, b.all.q, b.all.nq, b.all.k, b.all.ids, b.all.scores, b.all.mn, b.all.mx, nullptr));
 }
 
 int32_t cmr_index_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores,
@@ -1683,59 +1662,59 @@ int32_t cmr_index_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t k
 // cmr_index_search_masked_each calls of one k and one word count share ONE per-query-mask search: the leader lays the participants'
 // queries and masks out as one [total][n_words] block (a shared-mask participant's words once per query of its own) and scatters the
 // rows, which hold the bits of each caller's solo call (4.15b's contract).  A batch of one is the caller's own call, unchanged.
-struct CombinedMasked { const float* q; int nq, k; const uint32_t* allow; int64_t n_words; bool each; int64_t* ids; float* scores; float* mn; float* mx; };
+// each = false: `allow` is [n_words], one mask for every query; each = true: [nq][n_words]
+struct CombinedMasked : CombinedSearch { const uint32_t* allow; int64_t n_words; bool each; };
+static const CombinedMasked* masked_args(const cmr_combine::Request* r) { return static_cast<const CombinedMasked*>(search_args(r)); }
+
+// The synchronous filtered search behind cmr_index_search_masked and cmr_index_search_masked_each: the packed round trip (packed_begin)
+// with the queries and the allow words as inputs.  The caller holds the index's shared lock and has checked the arguments under it
+// (masked_check), so the pending call takes none.
+static int masked_call(cmr_index* idx, const CombinedMasked& a) {
+    const PackedInput in[] = {{&Workspace::d_q, a.q, (size_t)a.nq * idx->dim * 4},
+                              {&Workspace::d_mask, a.allow, (size_t)a.n_words * 4 * (a.each ? (size_t)a.nq : 1)}};
+    CmrPending* p = nullptr;
+    const int rc = packed_begin(idx, a.nq, a.k, false, in, [&](Workspace* ws, int64_t* ids, float* sc, float* mn, float* mx) {
+        return search_masked_enqueue(idx, ws, (const float*)ws->d_q.p, a.nq, a.k, (const unsigned*)ws->d_mask.p, ids, sc, mn, mx, a.each ? (long long)a.n_words : 0);
+    }, &p);
+    return rc ? rc : cmr_index_search_finish(p, a.ids, a.scores, a.mn, a.mx);
+}
 
 static int masked_single(cmr_index* idx, const CombinedMasked& a) {
-    SyncCall call(idx);
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
     const int rc = masked_check(idx, a.nq, a.k, a.n_words);
-    return rc ? rc : masked_sync(call, a.q, a.nq, a.k, a.allow, a.n_words, a.each, a.ids, a.scores, a.mn, a.mx);
+    return rc ? rc : masked_call(idx, a);
 }
 
 // one lock for the batch; every participant's word count is judged under it (an append may have come in since it queued) and a
 // participant that fails is answered alone
 static void combined_masked_run(void* ctx, cmr_combine::Request** reqs, int n) {
     cmr_index* const idx = (cmr_index*)ctx;
-    if (n == 1) { combine_answer(reqs[0], masked_single(idx, *(const CombinedMasked*)reqs[0]->args)); return; }
-    SyncCall call(idx);
+    if (n == 1) { combine_answer(reqs[0], masked_single(idx, *masked_args(reqs[0]))); return; }
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
     cmr_combine::Request* live[cmr_combine::kMaxWidth];
-    int nl = 0, NQ = 0;
+    int nl = 0;
     for (int i = 0; i < n; ++i) {
-        const CombinedMasked* a = (const CombinedMasked*)reqs[i]->args;
+        const CombinedMasked* a = masked_args(reqs[i]);
         const int rc = masked_check(idx, a->nq, a->k, a->n_words);
         if (rc) { combine_answer(reqs[i], rc); continue; }
         live[nl++] = reqs[i];
-        NQ += reqs[i]->nq;
     }
     if (nl == 0) return;
-    const CombinedMasked* a0 = (const CombinedMasked*)live[0]->args;
-    if (nl == 1) { combine_answer(live[0], masked_sync(call, a0->q, a0->nq, a0->k, a0->allow, a0->n_words, a0->each, a0->ids, a0->scores, a0->mn, a0->mx)); return; }
-    const int k = a0->k;
-    const size_t dim = (size_t)idx->dim, nw = (size_t)a0->n_words;      // (k and the word count are part of the batch's key)
-    std::vector<float> q((size_t)NQ * dim), sc((size_t)NQ * k), mm((size_t)NQ * 2);
-    std::vector<int64_t> ids((size_t)NQ * k);
-    std::vector<uint32_t> words((size_t)NQ * nw);
+    if (nl == 1) { combine_answer(live[0], masked_call(idx, *masked_args(live[0]))); return; }
+    const CombinedTopk b(live, nl, (size_t)idx->dim);
+    const size_t nw = (size_t)masked_args(live[0])->n_words;      // (k and the word count are part of the batch's key)
+    std::vector<uint32_t> words((size_t)b.all.nq * nw);
     for (int i = 0, at = 0; i < nl; at += live[i++]->nq) {
-        const CombinedMasked* a = (const CombinedMasked*)live[i]->args;
-        memcpy(q.data() + (size_t)at * dim, a->q, (size_t)a->nq * dim * 4);
+        const CombinedMasked* a = masked_args(live[i]);
         for (int qi = 0; qi < a->nq; ++qi) memcpy(words.data() + (size_t)(at + qi) * nw, a->allow + (a->each ? (size_t)qi * nw : 0), nw * 4);
     }
-    const int rc = masked_sync(call, q.data(), NQ, k, words.data(), (int64_t)nw, true, ids.data(), sc.data(), mm.data(), mm.data() + NQ);
-    for (int i = 0, at = 0; i < nl; at += live[i++]->nq) {
-        const CombinedMasked* a = (const CombinedMasked*)live[i]->args;
-        combine_answer(live[i], rc);
-        if (rc) continue;
-        const size_t nk = (size_t)a->nq * k;
-        memcpy(a->ids, ids.data() + (size_t)at * k, nk * 8);
-        memcpy(a->scores, sc.data() + (size_t)at * k, nk * 4);
-        if (a->mn) memcpy(a->mn, mm.data() + at, (size_t)a->nq * 4);
-        if (a->mx) memcpy(a->mx, mm.data() + NQ + at, (size_t)a->nq * 4);
-    }
+    b.answer(live, nl, masked_call(idx, CombinedMasked{b.all, words.data(), (int64_t)nw, true}));
 }
 
 static int32_t host_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words, bool each,
                            int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
     if (!idx || !q || !allow || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    const CombinedMasked a{q, nq, k, allow, n_words, each, out_ids, out_scores, out_min, out_max};
+    const CombinedMasked a{{q, nq, k, out_ids, out_scores, out_min, out_max}, allow, n_words, each};
     const int W = idx->combine_filtered.load(std::memory_order_relaxed) ? idx->combine.load(std::memory_order_relaxed) : 0;
     // joins a batch: as cmr_index_search — fewer queries than the batch holds, arguments that pass the checks which need no lock, finite queries
     // (the batch carries one non-finite flag); everything else takes the single call and gets its result or its error there
@@ -1747,7 +1726,7 @@ static int32_t host_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t
         if (rc) return rc;
     }
     cmr_combine::Request r;
-    r.args = (void*)&a; r.nq = nq;
+    r.args = (void*)static_cast<const CombinedSearch*>(&a); r.nq = nq;      // (what search_args / masked_args read)
     cmr_combine::Key key;
     key.w[0] = 5; key.w[1] = (uint64_t)k; key.w[2] = (uint64_t)n_words;      // (one kind for both forms: they share batches; never with kind 1, the unfiltered search)
     idx->combiner.submit(key, &r, W, idx->combine_wait_us.load(std::memory_order_relaxed), combined_masked_run, idx);
@@ -1773,15 +1752,13 @@ int32_t cmr_index_search_min_score(cmr_index_t* idx, const float* q, int32_t nq,
 int32_t cmr_index_scores_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, float* out_dev, int64_t ld, void* stream) {
     if (!idx || !q_dev || !out_dev) return fail(CMR_ERR_INVALID, "NULL argument");
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    DevCall call(idx);
     if (ld == 0) ld = idx->n;
     if (ld < idx->n) return fail(CMR_ERR_INVALID, "ld %lld < rows %lld", (long long)ld, idx->n);
-    int rc = cmr_set_device(idx->device);
+    int rc = call.open(stream);
     if (rc) return rc;
-    Workspace* ws = acquire_ws(idx, (hipStream_t)stream, true);
-    if (!ws) return fail(CMR_ERR_HIP, "could not create a workspace stream");
     if (idx->n == 0) return CMR_OK;
-    return scores_enqueue(idx, ws, q_dev, nq, out_dev, ld);
+    return scores_enqueue(idx, call.ws, q_dev, nq, out_dev, ld);
 }
 
 // cmr_index_scores behind its argument checks: `call` holds the index's shared lock, ld >= idx->n > 0

@@ -316,6 +316,15 @@ void release_ws(cmr_index* idx, Workspace* w) {
     idx->free_ws.push_back(w);
 }
 
+// The device set and a workspace taken: the pooled one of a synchronous call (dev_api = false, given back with release_ws) or the
+// one that belongs to the caller's stream (dev_api = true, kept by the index).
+int open_ws(cmr_index* idx, hipStream_t stream, bool dev_api, Workspace** ws) {
+    int rc = cmr_set_device(idx->device);
+    if (rc) return rc;
+    *ws = acquire_ws(idx, stream, dev_api);
+    return *ws ? CMR_OK : cmr_fail(CMR_ERR_HIP, "could not create a workspace stream");
+}
+
 // Prologue of a synchronous entry point.  Construction takes the index's shared lock (argument checks that read the index go
 // between the two steps); open() sets the device and takes a pooled workspace (`ws`, its stream `s`).  Scope exit returns the
 // workspace(s) and drops the lock.
@@ -328,10 +337,8 @@ struct SyncCall {
     explicit SyncCall(cmr_index* i) : idx(i), lk(i->mu) {}
     SyncCall(const SyncCall&) = delete;
     int open() {
-        int rc = cmr_set_device(idx->device);
+        int rc = open_ws(idx, nullptr, false, &ws);
         if (rc) return rc;
-        ws = acquire_ws(idx, nullptr, false);
-        if (!ws) return cmr_fail(CMR_ERR_HIP, "could not create a workspace stream");
         s = ws->stream;
         return CMR_OK;
     }
@@ -343,6 +350,18 @@ struct SyncCall {
         if (ws2) release_ws(idx, ws2);
         if (ws) release_ws(idx, ws);
     }
+};
+
+// Prologue of a _dev entry point, shaped like SyncCall: construction takes the shared lock, open(stream) sets the device and takes
+// the workspace of the caller's stream (`ws`; it stays with the index, nothing to return); open() is for a call that needs none.
+struct DevCall {
+    cmr_index* idx;
+    std::shared_lock<std::shared_mutex> lk;
+    Workspace* ws = nullptr;
+    explicit DevCall(cmr_index* i) : idx(i), lk(i->mu) {}
+    DevCall(const DevCall&) = delete;
+    int open() { return cmr_set_device(idx->device); }
+    int open(void* stream) { return open_ws(idx, (hipStream_t)stream, true, &ws); }
 };
 
 // ws->flag_ptr points somewhere else (the header of a host API result buffer) for the enqueue calls of one scope
