@@ -64,6 +64,8 @@ SIGNATURES = {
     "cmr_index_search_ids": (_i32, [_p, _p, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p]),
     "cmr_index_search_ids_dev": (_i32, [_p, _p, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "cmr_index_remove_ids": (_i32, [_p, _p, _i64, _P(_i64)]),
+    "cmr_index_update_rows": (_i32, [_p, _p, _p, _i64, _P(_i64)]),
+    "cmr_index_update_rows_dev": (_i32, [_p, _p, _p, _i64, _p, _P(_i64)]),
     "cmr_index_search_pipelined": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _P(_p)]),
     "cmr_index_set_id_base": (_i32, [_p, _i64]),
     "cmr_index_set_id_blocks": (_i32, [_p, _i32, _p, _p]),
@@ -123,6 +125,8 @@ SIGNATURES = {
     "cmr_mindex_plan_append": (_i32, [_p, _i32, _i32, _i64, _i64, _i64, _i32, _p, _p, _P(_i32), _P(_i32), _P(_i64)]),
     "cmr_mindex_remove_ids": (_i32, [_p, _p, _i64, _P(_i64)]),
     "cmr_mindex_plan_remove": (_i32, [_i32, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _P(_i64)]),
+    "cmr_mindex_update_rows": (_i32, [_p, _p, _p, _i64, _P(_i64)]),
+    "cmr_mindex_plan_update": (_i32, [_i32, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _P(_i64)]),
     "cmr_pool_l2norm": (_i32, [_i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "cmr_encoder_embed_layernorm": (_i32, [_i32, _p, _p, _p, _p, _p, _p, _p, _f32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "cmr_encoder_embed_layernorm_ragged": (_i32, [_i32, _p, _p, _p, _p, _p, _p, _p, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),

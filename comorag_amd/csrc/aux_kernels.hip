@@ -133,6 +133,61 @@ hipError_t cmr_launch_convert_rows(int dtype, const float* rows, long long n, in
     return hipGetLastError();
 }
 
+// In-place row update (cmr_index_update_rows): entry i replaces local row dst_row[i] (strictly ascending, all below the
+// index's row count: the host's plan) by source row src_idx[i] of `rows`.  Work item = (entry, half, ks), mapped like
+// convert_rows_kernel: a wave handles 32 consecutive entries x 2 halves of ONE k-step, so a dense update writes adjacent slots like an
+// append and a sparse one isolated 16-byte stores.  The slot a lane packs is the one of the DESTINATION row's place in its panel
+// (cmr_pack_slot takes k from the half alone).  Nothing outside the listed rows is written, and nothing at all once the flag is up.
+//   CHECK = true: no store — raises the flag exactly where the packing reports `bad` (the whole call is checked before its first store).
+template <int DT, bool CHECK>
+__global__ __launch_bounds__(256) void update_rows_kernel(const float* __restrict__ rows, const long long* __restrict__ dst_row,
+                                                          const long long* __restrict__ src_idx, long long m, int dim, int ks_total,
+                                                          uint4* __restrict__ corpus, float* __restrict__ shadow, int* __restrict__ flag) {
+    if (!CHECK && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) return;
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;   // over ceil(m / 32) * ks * 64
+    const int lane = (int)(gid & 63);
+    const long long blk = gid >> 6;
+    const long long entry = (blk / ks_total) * 32 + (lane & 31);
+    const int ks = (int)(blk % ks_total);
+    if (entry >= m) return;
+    const float* src = rows + (size_t)src_idx[entry] * dim;
+    const long long row = dst_row[entry];
+    const int slot = (lane & 32) | (int)(row & 31);
+    bool bad = false;
+    const uint4 v = cmr_pack_slot<DT>(src, dim, ks, slot, bad);
+    if (CHECK) {
+        if (bad) __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);     // (every writer writes 1) the flag may live in mapped host memory
+        return;
+    }
+    corpus[((size_t)(row / CMR_PANEL_ROWS) * ks_total + ks) * 64 + slot] = v;
+    if (shadow && DT != CMR_DT_F32) {
+        // fp32 shadow, row-major [*, dim]: this thread owns the same 8 k of the row
+        const int k0 = cmr_blk_k<DT == CMR_DT_F32 ? CMR_DT_BF16 : DT>(ks, slot, 0);
+        for (int e = 0; e < 8; ++e)
+            if (k0 + e < dim) shadow[(size_t)row * dim + k0 + e] = src[k0 + e];
+    }
+}
+
+hipError_t cmr_launch_update_rows(int dtype, bool check, const float* rows, const long long* dst_row, const long long* src_idx, long long m, int dim,
+                                  int dpad, void* corpus, float* shadow, int* flag, hipStream_t s) {
+    if (m <= 0) return hipSuccess;
+    const int ks = dtype == CMR_DT_F32 ? dpad / 8 : dpad / 16;
+    const long long items = ((m + 31) / 32) * ks * 64;
+    dim3 grid((unsigned)((items + 255) / 256)), block(256);
+    uint4* o = reinterpret_cast<uint4*>(corpus);
+#define UR(DT)                                                                                                                              \
+    if (check) hipLaunchKernelGGL((update_rows_kernel<DT, true>), grid, block, 0, s, rows, dst_row, src_idx, m, dim, ks, o, shadow, flag);  \
+    else hipLaunchKernelGGL((update_rows_kernel<DT, false>), grid, block, 0, s, rows, dst_row, src_idx, m, dim, ks, o, shadow, flag);
+    switch (dtype) {
+        case CMR_DT_BF16: UR(CMR_DT_BF16) break;
+        case CMR_DT_F16:  UR(CMR_DT_F16) break;
+        case CMR_DT_F32:  UR(CMR_DT_F32) break;
+        default: return hipErrorInvalidValue;
+    }
+#undef UR
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------
 // Candidate merge: ONE workgroup (256 threads, one wave per SIMD) per query gathers the W per-wave lists of the
 // scan (sparse: the sampling threshold keeps them at a few entries each) and selects the k best
@@ -1211,13 +1266,13 @@ hipError_t cmr_launch_pool(const void* hidden, int hidden_dtype, const int64_t* 
 // same stream: a rejected append leaves the maxima as they were.
 template <int DT>
 __global__ __launch_bounds__(256) void round_stats_kernel(const float* __restrict__ rows, long long n, int dim, const int* __restrict__ flag,
-                                                          unsigned* __restrict__ stats) {
+                                                          unsigned* __restrict__ stats, const long long* __restrict__ src_idx) {
     __shared__ float part[2][4];
     if (flag && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float mx = 0.0f, mdx = 0.0f;
     for (long long r = (long long)blockIdx.x * 4 + wave; r < n; r += (long long)gridDim.x * 4) {
-        const float* x = rows + (size_t)r * dim;
+        const float* x = rows + (size_t)(src_idx ? src_idx[r] : r) * dim;      // (an update's winning rows, gathered)
         double sx = 0.0, sd = 0.0;
         for (int i = lane; i < dim; i += 64) {
             const float f = x[i];
@@ -1239,12 +1294,12 @@ __global__ __launch_bounds__(256) void round_stats_kernel(const float* __restric
     }
 }
 
-hipError_t cmr_launch_round_stats(int dtype, const float* rows, long long n, int dim, const int* flag, float* stats, hipStream_t s) {
+hipError_t cmr_launch_round_stats(int dtype, const float* rows, long long n, int dim, const int* flag, float* stats, hipStream_t s, const long long* src_idx) {
     if (n <= 0 || dtype == CMR_DT_F32) return hipSuccess;
     const unsigned grid = (unsigned)std::min<long long>((n + 3) / 4, 1024);
     unsigned* st = reinterpret_cast<unsigned*>(stats);
-    if (dtype == CMR_DT_BF16) hipLaunchKernelGGL(round_stats_kernel<CMR_DT_BF16>, dim3(grid), dim3(256), 0, s, rows, n, dim, flag, st);
-    else if (dtype == CMR_DT_F16) hipLaunchKernelGGL(round_stats_kernel<CMR_DT_F16>, dim3(grid), dim3(256), 0, s, rows, n, dim, flag, st);
+    if (dtype == CMR_DT_BF16) hipLaunchKernelGGL(round_stats_kernel<CMR_DT_BF16>, dim3(grid), dim3(256), 0, s, rows, n, dim, flag, st, src_idx);
+    else if (dtype == CMR_DT_F16) hipLaunchKernelGGL(round_stats_kernel<CMR_DT_F16>, dim3(grid), dim3(256), 0, s, rows, n, dim, flag, st, src_idx);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

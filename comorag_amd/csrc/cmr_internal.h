@@ -64,6 +64,11 @@ int cmr_index_truncate(cmr_index_t* idx, long long n_rows);
 // cmr_index_remove_ids for the owner of a shard's block table (multi.hip): ids in the domain the shard returns NOW (its current table), any
 // number of blocks; the table is stale once rows went and the owner sets the new one (cmr_index_set_id_blocks) before the next search
 int cmr_index_compact_ids(cmr_index_t* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed);
+// one shard's share of a row update (multi.hip plans: cmr_mindex_plan_update): entry i replaces local row local_rows[i] (strictly
+// ascending) by row src[i] of the host rows [n_rows, dim].  phases: CMR_UPD_CHECK — nothing is written, CMR_ERR_NONFINITE when a source row
+// would be refused; CMR_UPD_WRITE — the stores and the maxima, for entries checked before; both — cmr_index_update_rows' own order
+enum { CMR_UPD_CHECK = 1, CMR_UPD_WRITE = 2 };
+int cmr_index_update_planned(cmr_index_t* idx, const int64_t* local_rows, const int64_t* src, int64_t m, const float* rows, int64_t n_rows, int phases);
 
 // for ppr.hip: scores of nb host queries [nb, dim] into a device buffer [nb, n] of the index's workspace, row b holding the bits a
 // one-query scan of q_host[b] gives (shared index lock held, workspace reserved for the calling thread) until

@@ -119,6 +119,11 @@ hipError_t cmr_launch_fill_threshold(float min_score, int n, u64* tau, hipStream
 hipError_t cmr_launch_convert_rows(int dtype, const float* rows, long long n, int dim, int dpad,
                                    long long row0, void* corpus, float* shadow, int* nonfinite_flag,
                                    hipStream_t s);
+// in-place row update (cmr_index_update_rows): entry i < m replaces local row dst_row[i] (strictly ascending, < the index's rows) by
+// rows[src_idx[i]] (all three on the device, or in mapped host memory).  check = true: no store, raises *flag where a row is non-finite
+// or rounds to Inf in the index dtype; check = false: returns at once when *flag is set, else packs and stores (+ the fp32 shadow)
+hipError_t cmr_launch_update_rows(int dtype, bool check, const float* rows, const long long* dst_row, const long long* src_idx, long long m, int dim,
+                                  int dpad, void* corpus, float* shadow, int* flag, hipStream_t s);
 // per-wave candidate lists -> per-query top-k (ids/scores + min/max), or the sampling threshold
 // grouped = true: the lists come from a query-split scan ([group][W][nq_stride]): query q reads group q / nq_stride
 hipError_t cmr_launch_merge_query(const u64* lists, const int* cnt, int W, int nq_stride, int cap, int nq, int k,
@@ -211,8 +216,10 @@ hipError_t cmr_launch_attention_cls(const void* qkv, int dtype, const int* lens,
 hipError_t cmr_launch_cls_head(const void* x, long long x_stride, const void* w1, const void* b1, const void* w2, const void* b2, int b, int d, int dtype,
                                float* out, hipStream_t s);
 // exact top-k of a 16-bit index (cmr_index_search_exact): rows fp32 [n, dim] (device) -> atomicMax of (max ||round(x)||, max ||round(x) - x||)
-// into stats[2] (fp32, device), skipped when *flag (the append's non-finite flag, may be NULL) is set; no-op for fp32 indexes
-hipError_t cmr_launch_round_stats(int dtype, const float* rows, long long n, int dim, const int* flag, float* stats, hipStream_t s);
+// into stats[2] (fp32, device), skipped when *flag (the append's non-finite flag, may be NULL) is set; no-op for fp32 indexes.
+// src_idx (device, or NULL: rows 0 .. n-1): the n rows are rows[src_idx[0 .. n-1]] (an update's winning rows)
+hipError_t cmr_launch_round_stats(int dtype, const float* rows, long long n, int dim, const int* flag, float* stats, hipStream_t s,
+                                  const long long* src_idx = nullptr);
 // re-score the sorted stage-1 lists cand_ids / cand_sc [nq, kc] (global ids, -1 padded; 16-bit scan scores) from the fp32 shadow,
 // select the fp32 top-k (k <= 64, kc <= 4096) and certify each query (out_exact[nq] = 0 / 1) against stats = (M_x, M_dx).
 // part: cmr_exact_part_bytes(nq, kc) of scratch; arrive: nq zeroed ints (re-armed by the kernel); output ids carry id_base

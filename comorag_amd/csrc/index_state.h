@@ -124,7 +124,9 @@ struct Workspace {
 struct ProfEvent { hipEvent_t a, b; };
 
 constexpr size_t kMappedAppendMax = 128 * 1024;  // appends up to this many bytes of fp32 rows are read by the convert kernel from mapped host memory (BASELINE config 4 appends 25 rows x 768 = 75 KiB per cycle)
-constexpr size_t kZeroCopyMax = 256 * 1024;   // synchronous host API: queries / results up to this size are mapped, not copied
+constexpr size_t kMappedPlanMax = 64 * 1024;     // a row update through that buffer: its plan (16 bytes per replaced row) lies behind the rows
+constexpr size_t kMappedPinBytes = 256 + kMappedAppendMax + kMappedPlanMax;      // [flag, 256 | rows | plan]
+constexpr size_t kZeroCopyMax =256 * 1024;   // synchronous host API: queries / results up to this size are mapped, not copied
 
 struct PipeSlot { Workspace ws; hipEvent_t pre_done = nullptr, scan_done = nullptr, main_done = nullptr; bool used = false; };
 #define CMR_PIPE_SLOTS 4
@@ -161,7 +163,9 @@ struct cmr_index {
     DevBuf rm_buf;               // row removal: [info (kept rows, first removed row) | keep words | kept_before | uploaded ids]
     int rm_stage_panels = 0;     // remove_stage_panels: panels the staging buffer of a removal holds (0: 64 MiB worth; at least 2)
     long long rm_chunks_last = 0;   // read-only ("remove_chunks_last"): chunks the corpus pass of the last removal ran (0: nothing moved)
-    void* h_pin = nullptr;       // small appends: pinned, device-mapped rows + flag (exclusive lock held)
+    long long upd_stage_rows = 0;   // update_stage_rows: fp32 rows a staged chunk of a row update holds (0: 256 MiB worth, like the append's; a set value also keeps the call off the mapped buffer)
+    long long upd_chunks_last = 0;  // read-only ("update_chunks_last"): chunks the last row update wrote (0: nothing written)
+    void* h_pin = nullptr;       // small appends / row updates: pinned, device-mapped [flag | rows | an update's plan] (exclusive lock held)
     void* h_pin_dev = nullptr;
     size_t h_pin_cap = 0;
     int* d_flag = nullptr;       // non-finite flag for appends

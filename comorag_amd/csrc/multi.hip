@@ -294,26 +294,118 @@ void plan_remove(int S, const long long* rows, const std::vector<std::vector<lon
     }
 }
 
-}  // namespace
+// The work lists of a row update — the only parser of an update's ids: negative ids and ids no block holds are dropped, of an
+// id that occurs several times the LAST occurrence stays, and the entries come out grouped by shard and, inside a shard, by ascending
+// local row; `src` is the index of the winning input row.  Pure host arithmetic.
+struct UpdateEntry { int shard; long long local, src; };
+void plan_update(int S, const long long* rows, const std::vector<std::vector<long long>>& bl, const std::vector<std::vector<long long>>& bg,
+                 const int64_t* ids, int64_t n_ids, std::vector<UpdateEntry>& out) {
+    struct Run { long long g, len, local; int shard; };
+    std::vector<Run> runs;
+    for (int s = 0; s < S; ++s)
+        for (size_t b = 0; b < bl[s].size(); ++b) {
+            const long long len = (b + 1 < bl[s].size() ? bl[s][b + 1] : rows[s]) - bl[s][b];
+            if (len > 0) runs.push_back({bg[s][b], len, bl[s][b], s});
+        }
+    std::sort(runs.begin(), runs.end(), [](const Run& a, const Run& b) { return a.g < b.g; });
+    out.clear();
+    for (int64_t i = 0; i < n_ids; ++i) {
+        const long long id = ids[i];
+        if (id < 0) continue;
+        size_t r = std::upper_bound(runs.begin(), runs.end(), id, [](long long v, const Run& x) { return v < x.g; }) - runs.begin();
+        if (r == 0) continue;
+        --r;
+        if (id - runs[r].g >= runs[r].len) continue;
+        out.push_back({runs[r].shard, runs[r].local + (id - runs[r].g), (long long)i});
+    }
+    std::sort(out.begin(), out.end(), [](const UpdateEntry& a, const UpdateEntry& b) {
+        return a.shard != b.shard ? a.shard < b.shard : a.local != b.local ? a.local < b.local : a.src < b.src;
+    });
+    size_t w = 0;
+    for (size_t i = 0; i < out.size(); ++i)      // the last occurrence of a row is the last of its group
+        if (i + 1 == out.size() || out[i + 1].shard != out[i].shard || out[i + 1].local != out[i].local) out[w++] = out[i];
+    out.resize(w);
+}
 
-extern "C" {
-
-int32_t cmr_mindex_plan_remove(int32_t n_shards, const int64_t* shard_rows, const int32_t* n_blocks, const int64_t* local_start,
-                               const int64_t* global_start, const int64_t* ids, int64_t n_ids, const int32_t* skip_shards, int64_t* new_shard_rows,
-                               int32_t* new_n_blocks, int64_t* new_local_start, int64_t* new_global_start, int64_t* n_removed) {
-    if (n_shards <= 0 || !shard_rows || !n_blocks || n_ids < 0 || (n_ids > 0 && !ids)) return cmr_fail(CMR_ERR_INVALID, "bad argument");
-    std::vector<std::vector<long long>> bl((size_t)n_shards), bg((size_t)n_shards);
-    std::vector<long long> rows(shard_rows, shard_rows + n_shards);
+// the C-ABI's flat tables (n_blocks[s] blocks per shard, concatenated in shard order) -> per-shard vectors, checked
+int parse_tables(int32_t n_shards, const int64_t* shard_rows, const int32_t* n_blocks, const int64_t* local_start, const int64_t* global_start,
+                 std::vector<std::vector<long long>>& bl, std::vector<std::vector<long long>>& bg) {
+    bl.assign((size_t)n_shards, {}); bg.assign((size_t)n_shards, {});
     size_t at = 0;
     for (int s = 0; s < n_shards; ++s) {
         if (n_blocks[s] < 0 || (n_blocks[s] > 0 && (!local_start || !global_start))) return cmr_fail(CMR_ERR_INVALID, "bad block table of shard %d", s);
         for (int b = 0; b < n_blocks[s]; ++b, ++at) {
-            const long long end = b + 1 < n_blocks[s] ? local_start[at + 1] : rows[(size_t)s];
+            const long long end = b + 1 < n_blocks[s] ? local_start[at + 1] : shard_rows[s];
             if (local_start[at] < 0 || end < local_start[at] || global_start[at] < 0) return cmr_fail(CMR_ERR_INVALID, "shard %d, block %d: local starts must ascend up to the shard's rows", s, b);
             bl[(size_t)s].push_back(local_start[at]);
             bg[(size_t)s].push_back(global_start[at]);
         }
     }
+    return CMR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t cmr_mindex_plan_update(int32_t n_shards, const int64_t* shard_rows, const int32_t* n_blocks, const int64_t* local_start,
+                               const int64_t* global_start, const int64_t* ids, int64_t n_ids, int32_t* out_shard, int64_t* out_local, int64_t* out_src,
+                               int64_t* out_count, int64_t* n_updated) {
+    if (n_updated) *n_updated = 0;
+    if (n_shards <= 0 || !shard_rows || !n_blocks || n_ids < 0 || (n_ids > 0 && (!ids || !out_shard || !out_local || !out_src))) return cmr_fail(CMR_ERR_INVALID, "bad argument");
+    std::vector<std::vector<long long>> bl, bg;
+    if (int rc = parse_tables(n_shards, shard_rows, n_blocks, local_start, global_start, bl, bg)) return rc;
+    std::vector<long long> rows(shard_rows, shard_rows + n_shards);
+    std::vector<UpdateEntry> plan;
+    plan_update(n_shards, rows.data(), bl, bg, ids, n_ids, plan);
+    if (out_count) std::fill(out_count, out_count + n_shards, (int64_t)0);
+    for (size_t i = 0; i < plan.size(); ++i) {
+        out_shard[i] = plan[i].shard; out_local[i] = plan[i].local; out_src[i] = plan[i].src;
+        if (out_count) ++out_count[plan[i].shard];
+    }
+    if (n_updated) *n_updated = (int64_t)plan.size();
+    return CMR_OK;
+}
+
+int32_t cmr_mindex_update_rows(cmr_mindex_t* m, const int64_t* ids, const float* rows_f32, int64_t n, int64_t* n_updated) {
+    if (n_updated) *n_updated = 0;
+    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
+    if (n < 0) return cmr_fail(CMR_ERR_INVALID, "n %lld < 0", (long long)n);
+    if (n > 0 && (!ids || !rows_f32)) return cmr_fail(CMR_ERR_INVALID, "NULL ids or rows with n = %lld", (long long)n);
+    std::unique_lock<std::shared_mutex> lk(m->mu);
+    if (n == 0) return CMR_OK;
+    {   // throughput-mode batches whose enqueue jobs are still with the worker threads: let them finish issuing first (the shards wait for the device)
+        std::lock_guard<std::mutex> pg(m->pipe_mu);
+        for (PipeTicket& t : m->ticket) if (t.busy) t.latch.wait();
+    }
+    std::vector<UpdateEntry> plan;
+    plan_update(m->S, m->rows.data(), m->blk_local, m->blk_global, ids, n, plan);
+    if (plan.empty()) return CMR_OK;
+    std::vector<int64_t> local(plan.size()), src(plan.size());
+    std::vector<size_t> first((size_t)m->S + 1, 0);
+    for (size_t i = 0; i < plan.size(); ++i) { local[i] = plan[i].local; src[i] = plan[i].src; ++first[(size_t)plan[i].shard + 1]; }
+    std::vector<int> act;
+    for (int s = 0; s < m->S; ++s) { if (first[(size_t)s + 1]) act.push_back(s); first[(size_t)s + 1] += first[(size_t)s]; }
+    // every check before the first store: a refused row leaves every shard as it was; the write phase has nothing left to refuse
+    for (int phase : {(int)CMR_UPD_CHECK, (int)CMR_UPD_WRITE}) {
+        const int rc = for_active(m, act, act.size() > 1, [&](int, int s) {
+            const size_t o = first[(size_t)s];
+            return cmr_index_update_planned(m->shard[s], local.data() + o, src.data() + o, (int64_t)(first[(size_t)s + 1] - o), rows_f32, n, phase);
+        });
+        if (rc) return rc;
+    }
+    if (n_updated) *n_updated = (int64_t)plan.size();
+    return CMR_OK;
+}
+
+int32_t cmr_mindex_plan_remove(int32_t n_shards, const int64_t* shard_rows, const int32_t* n_blocks, const int64_t* local_start,
+                               const int64_t* global_start, const int64_t* ids, int64_t n_ids, const int32_t* skip_shards, int64_t* new_shard_rows,
+                               int32_t* new_n_blocks, int64_t* new_local_start, int64_t* new_global_start, int64_t* n_removed) {
+    if (n_shards <= 0 || !shard_rows || !n_blocks || n_ids < 0 || (n_ids > 0 && !ids)) return cmr_fail(CMR_ERR_INVALID, "bad argument");
+    std::vector<std::vector<long long>> bl, bg;
+    std::vector<long long> rows(shard_rows, shard_rows + n_shards);
+    if (int rc = parse_tables(n_shards, shard_rows, n_blocks, local_start, global_start, bl, bg)) return rc;
+    size_t at = 0;
     RemovePlan plan;
     std::vector<char> skip((size_t)n_shards, 0);
     if (skip_shards) for (int s = 0; s < n_shards; ++s) skip[(size_t)s] = skip_shards[s] != 0;

@@ -261,8 +261,12 @@ def install_memory_pool(pool, index_dtype: str = "f32", device: int = 0, index_f
     the last call are encoded with the reference's own `compute_probe_note_embeddings` and appended —
     BASELINE config 4's incremental append), the probe is scored against all of them in one scan.
     Selection semantics are the reference's: cosine, descending, ties in pool order, keep
-    max(1, int(n * top_percent)).  Nodes without an embedding are skipped like the reference does."""
-    state = {"index": None, "rows": []}      # rows[i] = pool position of index row i
+    max(1, int(n * top_percent)).  Nodes without an embedding are skipped like the reference does.
+    A node whose `embedding` has been REASSIGNED since it was mirrored — `compute_probe_note_embeddings(force_recompute=True)`, or any
+    `node.embedding = ...` — is found by object identity before scoring, and all such rows are replaced in place by one
+    `update_rows` call (normalised exactly as fresh rows are; nothing is re-appended, row ids stay).  An embedding array that is
+    mutated IN PLACE is the same object and is not detected: reassign it."""
+    state = {"index": None, "rows": [], "emb": []}      # rows[i] = pool position of index row i, emb[i] = the embedding object mirrored there
     lock = threading.Lock()
 
     def _to_np(x):
@@ -275,12 +279,22 @@ def install_memory_pool(pool, index_dtype: str = "f32", device: int = 0, index_f
             raise ValueError("Embedding model not provided")
         self.compute_probe_note_embeddings()
         probe = _to_np(self.embedding_model.encode([current_probe])[0])
+        def _unit_rows(embs):
+            mat = np.stack([_to_np(e) for e in embs])
+            return mat / np.maximum(np.linalg.norm(mat, axis=1, keepdims=True), 1e-12)   # cosine == dot of unit rows
+
         with lock:
             have = {id(self.pool[i]) for i in state["rows"] if i < len(self.pool)}
             fresh = [(i, n) for i, n in enumerate(self.pool) if n.embedding is not None and id(n) not in have]
+            stale = [r for r, i in enumerate(state["rows"])
+                     if i < len(self.pool) and self.pool[i].embedding is not None and self.pool[i].embedding is not state["emb"][r]]
+            if stale:      # re-encoded nodes: their rows are replaced where they are
+                embs = [self.pool[state["rows"][r]].embedding for r in stale]
+                state["index"].update_rows(np.asarray(stale, dtype=np.int64), _unit_rows(embs))
+                for r, e in zip(stale, embs):
+                    state["emb"][r] = e
             if fresh:
-                mat = np.stack([_to_np(n.embedding) for _, n in fresh])
-                mat = mat / np.maximum(np.linalg.norm(mat, axis=1, keepdims=True), 1e-12)   # cosine == dot of unit rows
+                mat = _unit_rows([n.embedding for _, n in fresh])
                 if state["index"] is None:      # index_factory(dim, dtype, device): test seam, as in install()
                     if index_factory:
                         state["index"] = index_factory(mat.shape[1], index_dtype, device)
@@ -289,6 +303,7 @@ def install_memory_pool(pool, index_dtype: str = "f32", device: int = 0, index_f
                         state["index"] = make_index(mat.shape[1], index_dtype, device=device, num_shards=num_shards, devices=devices)
                 state["index"].append(mat)
                 state["rows"].extend(i for i, _ in fresh)
+                state["emb"].extend(n.embedding for _, n in fresh)
             if state["index"] is None:
                 return []
             order = retrieval.retrieve_similar_rows(state["index"], probe, len(state["rows"]), top_percent)

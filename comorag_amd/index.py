@@ -157,7 +157,7 @@ def renumber_after_removal(ids, removed) -> np.ndarray:
 
 # the calls whose host-array marshalling `DenseIndex` (cmr_index_*) and `MultiDeviceIndex` (cmr_mindex_*) share
 _HOST_CALLS = ("destroy", "size", "info", "append", "search", "search_exact", "search_min_score", "scores", "sorted_scores",
-               "rescore", "get_rows", "search_ids", "remove_ids")
+               "rescore", "get_rows", "search_ids", "remove_ids", "update_rows")
 _bound = {}
 
 
@@ -229,6 +229,35 @@ class HostArrayIndex:
         ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64)).reshape(-1)
         n = C.c_int64(0)
         L.check(self._c.remove_ids(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(n)))
+        return n.value
+
+    # -- update in place (cmr_index_update_rows / cmr_mindex_update_rows)
+    def _update_args(self, ids, n_rows: int) -> np.ndarray:
+        ids = np.asarray(ids)
+        if ids.ndim == 0:
+            ids = ids.reshape(1)
+        if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+            raise ValueError("ids must be a 1-d sequence of integer row ids")
+        if len(ids) != n_rows:
+            raise ValueError(f"{len(ids)} ids for {n_rows} rows")
+        return np.ascontiguousarray(ids, dtype=np.int64)
+
+    def update_rows(self, ids, rows) -> int:
+        """Replace the content of the listed rows in place: row count, row ids, capacity and id base / block tables stay, and the index
+        then answers every call bit for bit like a fresh one built by appending the final row contents in order.  `ids` [n]: row ids AS
+        THE SEARCHES RETURN THEM (`MultiDeviceIndex`: global ids), entry i paired with fp32 row i of `rows` [n, dim]; a scalar id with a
+        1-d row is accepted.  Negative ids and ids the index does not hold are ignored with their rows; of an id that occurs several
+        times the last occurrence wins.  → distinct rows replaced.  All or nothing: a NaN / Inf row, or one that rounds to Inf in the
+        index dtype, among the rows that would be written raises `CmrError` (CMR_ERR_NONFINITE) with the index unchanged.  Exclusive
+        like `remove_ids`; waits for everything in flight on the device."""
+        rows = _f32c(rows)
+        if rows.ndim == 1 and np.ndim(ids) == 0:
+            rows = rows[None, :]
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n,{self.dim}], got {rows.shape}")
+        ids = self._update_args(ids, rows.shape[0])
+        n = C.c_int64(0)
+        L.check(self._c.update_rows(self._h, _ptr(ids) if len(ids) else None, _ptr(rows) if len(ids) else None, len(ids), C.byref(n)))
         return n.value
 
     # -- search
@@ -402,6 +431,23 @@ class DenseIndex(HostArrayIndex):
         if stream is None:
             stream = torch.cuda.current_stream(rows_t.device).cuda_stream
         L.check(L.lib().cmr_index_append_dev(self._h, C.c_void_p(rows_t.data_ptr()), rows_t.shape[0], C.c_void_p(stream)))
+
+    def update_rows_dev(self, ids, rows_t, stream: Optional[int] = None) -> int:
+        """`update_rows` with the rows in a torch float32 CUDA tensor [n, dim], contiguous (an encoder's output); the ids stay on the
+        host.  A tensor on another device than the index goes through the host, as in `append_dev`.  Synchronous."""
+        import torch
+        assert rows_t.is_cuda and rows_t.dtype == torch.float32 and rows_t.is_contiguous()
+        if rows_t.ndim != 2 or rows_t.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n,{self.dim}], got {tuple(rows_t.shape)}")
+        if rows_t.device.index != self.device:
+            return self.update_rows(ids, rows_t.cpu().numpy())
+        ids = self._update_args(ids, rows_t.shape[0])
+        if stream is None:
+            stream = torch.cuda.current_stream(rows_t.device).cuda_stream
+        n = C.c_int64(0)
+        if len(ids):
+            L.check(L.lib().cmr_index_update_rows_dev(self._h, _ptr(ids), C.c_void_p(rows_t.data_ptr()), len(ids), C.c_void_p(stream), C.byref(n)))
+        return n.value
 
     def search_min_score_dev(self, q_t, k: int, min_score: float, out_ids=None, out_scores=None, stream: Optional[int] = None):
         """`search_min_score` on torch CUDA tensors, enqueued on torch's current stream without synchronising."""

@@ -46,7 +46,8 @@ class MultiDeviceIndex(HostArrayIndex):
     """Host arrays in / out (append, search, search_exact, search_min_score, scores, sorted_scores, rescore, get_rows, len): the
     methods of `HostArrayIndex`, on cmr_mindex_*.  `search_filtered_ids` (cmr_mindex_search_ids) is the filtered search of this class:
     its lists hold GLOBAL row ids — what `search` returns — and every shard keeps the ids it holds.  `remove_ids` (cmr_mindex_remove_ids)
-    takes global ids too: every shard compacts its own rows and global ids are dense again afterwards, in the old order."""
+    takes global ids too: every shard compacts its own rows and global ids are dense again afterwards, in the old order.  `update_rows`
+    (cmr_mindex_update_rows) takes global ids as well: every shard checks its rows before any shard writes."""
     _PREFIX = "cmr_mindex_"
 
     def __init__(self, dim: int, dtype: str = "bf16", devices: Optional[Sequence[int]] = None, num_shards: Optional[int] = None,

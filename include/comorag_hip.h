@@ -262,6 +262,39 @@ int32_t cmr_index_search_ids_dev(cmr_index_t* idx, const float* q_f32_dev, int32
  * never depend on it.  Read-only "remove_chunks_last": chunks the corpus pass of the last removal ran (0: nothing moved).              */
 int32_t cmr_index_remove_ids(cmr_index_t* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed /* may be NULL */);
 
+/* IN-PLACE ROW UPDATE: the listed rows get new contents; row count, row ids, capacity, id base and block tables stay.
+ * Afterwards every entry point returns, bit for bit, what a fresh index built by appending the final row contents in order returns, on
+ * every route (a row's 16-byte slots are a function of that row alone).  As after a removal, two things may differ from that fresh
+ * index: the index-wide maxima behind cmr_index_round_stats / the exact search's certificate, and those of the int8 companion
+ * (cmr_index_prefilter_stats), are folded with an atomic max, not recomputed — they may stay larger and remain valid upper bounds.
+ *   ids        int64 row ids AS THE SEARCH ENTRY POINTS RETURN THEM (id base / block table applied; cmr_mindex_update_rows: global ids),
+ *              entry i paired with fp32 row i of rows [n, dim].  A negative id or an id the index does not hold is ignored together with
+ *              its row; of an id that occurs several times the LAST occurrence wins and the id counts once.  A user-set block table of
+ *              several blocks (cmr_index_set_id_blocks) is fine: nothing is renumbered.
+ *   n_updated  (may be NULL) distinct rows replaced.  n == 0 returns 0 and touches nothing.
+ * ALL OR NOTHING on bad input: a row that WOULD BE WRITTEN (the last occurrence of a held id) and is NaN / Inf or rounds to Inf in the
+ * index dtype makes the call return CMR_ERR_NONFINITE with the index unchanged bit for bit — every row is checked before the first store
+ * (an append may write first and check afterwards because it bumps the row count last; an update's rows are live).
+ * Synchronous and exclusive, like cmr_index_remove_ids: it waits for the searches that hold the index, then for EVERYTHING this process
+ * has enqueued on the device (_dev and pipelined calls hold the lock only while they enqueue: their kernels may still be reading), and
+ * returns when the rows are in.  A search on another thread sees the index before or after the update, never in between.
+ * CMR_ERR_INVALID, before any device call: a NULL handle, NULL ids or rows with n > 0, n < 0.
+ * How: the host plans (cmr_mindex_plan_update, the only id parser: this index is its one-shard case), then three launches on one stream,
+ * ordered by the stream alone — check (raises the call's flag where the packing would refuse a row), scatter (returns at once on a raised
+ * flag; one lane packs and stores one 16-byte slot, 32 consecutive entries x 2 halves of one k-step per wave, plus its 8 floats of the
+ * fp32 shadow on a CMR_FLAG_KEEP_F32 index; nothing outside the listed rows is written), maxima (over the winning rows).  Up to 128 KiB of
+ * rows go through the append's pinned, device-mapped buffer; otherwise the rows are staged in chunks like an append's, and a call of
+ * more than one chunk checks every chunk first and uploads again to write (twice the host-to-device traffic, for such calls only).
+ * The int8 companion of the pre-filter is marked stale from the first updated row on before the first store is enqueued: the next
+ * pre-filtered call quantises again from that row's panel and folds the new rows into the companion's maxima.
+ * cmr_index_update_rows_dev: rows on the index's device (an encoder's output; `stream` = the stream that produced them, the launches go
+ * there), ids on the HOST — they are few, and the host translates and orders them.  Synchronous like the host form.
+ * Route selector "update_stage_rows": fp32 rows one staged chunk holds (0 = default: 256 MiB worth; a set value also keeps the call
+ * off the mapped buffer).  Results never depend on it.  Read-only "update_chunks_last": chunks the last update wrote (0: nothing).   */
+int32_t cmr_index_update_rows(cmr_index_t* idx, const int64_t* ids, const float* rows_f32, int64_t n, int64_t* n_updated /* may be NULL */);
+int32_t cmr_index_update_rows_dev(cmr_index_t* idx, const int64_t* ids_host, const float* rows_f32_dev, int64_t n, void* stream,
+                                  int64_t* n_updated /* may be NULL */);
+
 /* Throughput mode for a stream of independent query batches (serving; bench.py).  Work is enqueued on streams owned by
  * the index: query packing + sampling passes of batch i+1 overlap the HBM-bound main scan of batch i.  On a 256-CU device
  * main scans shorter than ~1 ms (shards up to ~4 M x 768 bf16 rows) of batches of <= 64 queries run on a CU-masked pair of
@@ -635,6 +668,18 @@ int32_t cmr_mindex_plan_remove(int32_t n_shards, const int64_t* shard_rows, cons
                                const int64_t* global_start, const int64_t* ids, int64_t n_ids, const int32_t* skip_shards /*[n_shards] or NULL*/,
                                int64_t* new_shard_rows /*[n_shards]*/, int32_t* new_n_blocks /*[n_shards]*/, int64_t* new_local_start,
                                int64_t* new_global_start, int64_t* n_removed);
+/* Row update over the shards (cmr_index_update_rows above has the semantics): GLOBAL ids in; results equal ONE cmr_index_t that took
+ * the same update.  Planned once on the host, then the CHECK phase runs on every shard that has entries (on the shards' worker threads)
+ * — if any check fails the error is returned with nothing written anywhere — then the WRITE phase on every such shard.  A HIP error in
+ * the write phase is returned as it is; every row is then wholly old or wholly new.  Exclusive over the handle.
+ * cmr_mindex_plan_update is the planning on its own (pure host, no device), tables as in cmr_mindex_plan_remove: ignored ids dropped,
+ * the last occurrence of an id kept, the entries grouped by shard and, inside a shard, by ascending local row — entry j replaces
+ * local row out_local[j] of shard out_shard[j] by input row out_src[j].  Each output holds n_ids entries, the first *n_updated valid;
+ * out_count[s] (may be NULL) = entries of shard s.  One cmr_index_t is the one-shard case: its id base or block table is shard 0's.  */
+int32_t cmr_mindex_update_rows(cmr_mindex_t* m, const int64_t* ids /* GLOBAL row ids */, const float* rows_f32, int64_t n, int64_t* n_updated /* may be NULL */);
+int32_t cmr_mindex_plan_update(int32_t n_shards, const int64_t* shard_rows, const int32_t* n_blocks /*[n_shards]*/, const int64_t* local_start,
+                               const int64_t* global_start, const int64_t* ids, int64_t n_ids, int32_t* out_shard, int64_t* out_local,
+                               int64_t* out_src /* each [n_ids] */, int64_t* out_count /*[n_shards] or NULL*/, int64_t* n_updated);
 
 /* ---- encoder tail -----------------------------------------------------------------------
  * Fused masked mean-pool + L2-normalise of the encoder's last hidden state; replaces
