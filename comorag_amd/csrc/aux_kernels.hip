@@ -65,9 +65,11 @@ __global__ __launch_bounds__(64) void prep_queries_kernel(const float* __restric
 }
 
 // tau[i] = (smallest candidate key whose score is >= min_score) - 1, so that key > tau <=> score >= min_score
+// (min_score = -inf: 0, "no threshold" — the key below the keys of -inf is no score's: the scans' float pre-test, cmr_key_score(tau),
+// would decode a NaN from it and let nothing through)
 __global__ void fill_threshold_kernel(float min_score, int n, u64* __restrict__ tau) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) tau[i] = cmr_make_key(min_score, 0xFFFFFFFFu) - 1ull;
+    if (i < n) tau[i] = min_score == -__builtin_inff() ? 0ull : cmr_make_key(min_score, 0xFFFFFFFFu) - 1ull;
 }
 hipError_t cmr_launch_fill_threshold(float min_score, int n, u64* tau, hipStream_t s) {
     hipLaunchKernelGGL(fill_threshold_kernel, dim3((n + 255) / 256), dim3(256), 0, s, min_score, n, tau);

@@ -211,10 +211,10 @@ def test_min_score_at_and_below_zero(tag):
     rnd = ROUND[spec["dtype"]]
     exact = orc.exact_scores_f64(rnd(X), rnd(Q))
     tol = np.stack([vd.row_tol(q, rnd(X)) for q in rnd(Q)])
-    # -0.5: far more than k rows pass; and a bound between the 8th and 9th best score of query 0: a list that does not fill
+    # -0.5 (the row's "below" at 768-d): far more than k rows pass; and a bound between the 8th and 9th best score of query 0: a list that does not fill
     few = float(np.float32(np.sort(exact[0])[::-1][7:9].mean()))
     branches = set()
-    for bound in (-0.5, few):
+    for bound in (spec.get("below", vd.MIN_SCORE_BELOW), few):
         ids, sc, _, _, _ = _run(idx, spec, Q, min_score=bound)
         for i in range(len(Q)):
             may = np.flatnonzero(exact[i] >= bound - tol[i])
@@ -238,6 +238,7 @@ T_KS = {"tiny1": [1, 20, 32, 33, 100], "tiny1-1wg": [1, 20, 32, 33, 100], "small
         "chain1": [1, 20, 32, 33, 100], "chain2": [1, 20, 32, 33, 100], "single": [1, 20, 32], "tau-in-scan": [1, 20, 32], "fin1": [1, 20, 32, 33],
         "fin8": [1, 20, 32, 33], "two-tile": [1, 20, 32, 33, 100], "wide": [1, 20, 32, 33, 100], "quad": [1, 20, 32, 33, 100],
         "quad-f32": [1, 20, 32, 33, 100], "large-k": [500], "min-score-5003": [1, 20, 32, 33, 100], "min-score-big": [1, 20, 32, 33, 100],
+        "min-score-wide": [1, 20, 32, 33, 100], "min-score-quad": [1, 20, 32, 33, 100],
         "dev": [1, 20, 32, 33], "pipe": [1, 20, 32, 33, 100], "exact": [1, 10, 32, 33]}
 
 

@@ -48,7 +48,12 @@ SCORES_ROUTES = {
 MIN_SCORE_ROUTES = {
     "min-score-5003": dict(seed=30, dtype="bf16", d=64, n=5003, nq=3, k=20, opts={}, route=route_code(CHAIN, 0)),
     "min-score-big": dict(seed=31, dtype="bf16", d=64, n=N_BIG, nq=3, k=20, opts={}, route=route_code(CHAIN, 0)),
+    # the wide routes of the threshold search (no sampling level: the plain search's "wide" / "quad" rows have one).  below: at 768-d family
+    # Z's negative scores lie in -0.64 +- 0.04, so the bound that lets "far more than k rows" through is -0.62 there, not -0.5
+    "min-score-wide": dict(seed=32, dtype="bf16", d=768, n=8197, nq=70, k=20, opts={"wide_mode": 1}, route=route_code(WIDE, 0), below=-0.62),
+    "min-score-quad": dict(seed=33, dtype="f16", d=768, n=8197, nq=70, k=20, opts={"wide_mode": 2}, route=route_code(QSPLIT, 0), below=-0.62),
 }
+MIN_SCORE_BELOW = -0.5      # test_min_score_at_and_below_zero: the bound below zero that fills a list (a row's "below" replaces it)
 # the stream paths (search_dev, search_pipelined) and the exact search (its route depends on what stage 1 certifies: asserted in the test)
 STREAM_ROUTES = {
     "dev": dict(seed=41, dtype="bf16", d=64, n=13_061, nq=3, k=20, opts={}, route=route_code(SMALL)),
