@@ -24,6 +24,9 @@ CMR_MAX_K_2PASS = 4096
 CMR_MAX_K_EXACT = 64      # cmr_index_search_exact
 CMR_PPR_MAX_BATCH = 16    # cmr_graph_ppr_batch / cmr_index_ppr_batch: queries per power iteration
 CMR_PPR_RANK_TILE = 2048  # keys per workgroup of the ranked calls' radix sort
+CMR_RANGE_TILE = 2048     # rows per workgroup of the range search's count / compaction
+CMR_RANGE_MAX_TOTAL = 2**31 - 1   # cmr_index_range_search: hits per call unless max_total says otherwise
+CMR_ROUTE_RANGE = 11      # "last_route" & 0xF of a range search / count
 CMR_ENCODER_ROWS_MAX = 2048  # cmr_encoder_linear_rows*: 16 questions x 128 token rows
 DTYPES = {"f32": CMR_F32, "fp32": CMR_F32, "float32": CMR_F32, "bf16": CMR_BF16, "bfloat16": CMR_BF16,
           "f16": CMR_F16, "fp16": CMR_F16, "float16": CMR_F16}
@@ -78,6 +81,12 @@ SIGNATURES = {
     "cmr_index_scores": (_i32, [_p, _p, _i32, _p, _i64]),
     "cmr_index_scores_dev": (_i32, [_p, _p, _i32, _p, _i64, _p]),
     "cmr_index_sorted_scores": (_i32, [_p, _p, _i32, _p, _p, _p, _p]),
+    "cmr_index_range_count": (_i32, [_p, _p, _i32, _f32, _p]),
+    "cmr_index_range_count_dev": (_i32, [_p, _p, _i32, _f32, _p, _p]),
+    "cmr_index_range_search": (_i32, [_p, _p, _i32, _f32, _i64, _P(_p)]),
+    "cmr_range_result_view": (_i32, [_p, _P(_i32), _P(_p), _P(_p), _P(_p)]),
+    "cmr_range_result_destroy": (_i32, [_p]),
+    "cmr_range_merge": (_i32, [_i32, _i32, _p, _p, _p, _p, _p, _p]),
     "cmr_index_rescore": (_i32, [_p, _p, _i32, _p, _i32, _i32, _p, _p]),
     "cmr_index_get_rows": (_i32, [_p, _p, _i64, _p]),
     "cmr_index_search_exact": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),
@@ -116,6 +125,8 @@ SIGNATURES = {
     "cmr_mindex_search_min_score": (_i32, [_p, _p, _i32, _i32, _f32, _p, _p]),
     "cmr_mindex_scores": (_i32, [_p, _p, _i32, _p, _i64]),
     "cmr_mindex_sorted_scores": (_i32, [_p, _p, _i32, _p, _p, _p, _p]),
+    "cmr_mindex_range_count": (_i32, [_p, _p, _i32, _f32, _p]),
+    "cmr_mindex_range_search": (_i32, [_p, _p, _i32, _f32, _i64, _P(_p)]),
     "cmr_mindex_rescore": (_i32, [_p, _p, _i32, _p, _i32, _i32, _p, _p]),
     "cmr_mindex_get_rows": (_i32, [_p, _p, _i64, _p]),
     "cmr_mindex_search_exact": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),

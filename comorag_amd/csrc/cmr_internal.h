@@ -59,6 +59,15 @@ int cmr_ids_args_check(int mode, int nq, int k, const int64_t* off_host, const i
 int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, int mode, const int64_t* id_offsets, const int64_t* ids, int64_t n_ids,
                                bool take_lock, CmrPending** out);
 
+// the result of a range search (cmr_range_result_t): CSR lists in host arrays the library owns.  api.hip and multi.hip fill it.
+struct cmr_range_result {
+    int nq = 0;
+    int64_t* lims = nullptr;      // [nq + 1]
+    int64_t* ids = nullptr;       // [lims[nq]]
+    float* scores = nullptr;      // [lims[nq]]
+    ~cmr_range_result() { delete[] lims; delete[] ids; delete[] scores; }
+};
+
 // shrink an index to its first n_rows rows (roll-back of a multi-shard append that failed on a later shard)
 int cmr_index_truncate(cmr_index_t* idx, long long n_rows);
 // cmr_index_remove_ids for the owner of a shard's block table (multi.hip): ids in the domain the shard returns NOW (its current table), any

@@ -151,6 +151,25 @@ hipError_t cmr_launch_sort_scores(const float* scores, long long n, long long id
                                   float* out_scores, hipStream_t s);
 hipError_t cmr_launch_sort_scores_f64(const double* scores, long long n, int nb, long long n_out, void* workspace, int64_t** ids_at,
                                       double** scores_at, hipStream_t s);
+// the same sort over ready-made 64-bit keys with a 32-bit payload (one segment of n pairs): stable, ascending by the 8-bit digit positions
+// set in `digits`, lowest first; the passes alternate between (key_a, val_a) and (key_b, val_b) and the result ends in (*key_out, *val_out)
+size_t cmr_sort_keys64_hist_bytes(long long n);
+hipError_t cmr_launch_sort_keys64(u64* key_a, u64* key_b, unsigned* val_a, unsigned* val_b, unsigned* hist, long long n, unsigned digits, u64** key_out,
+                                  unsigned** val_out, hipStream_t s);
+// ---- range search (range_kernels.hip) over a materialised score block [nb][ld] (ld % 4 == 0, n < 2^32 rows)
+// bound_code: the code `lo` a score's code is compared with (score >= min_score <=> code >= lo; +inf: above every score's)
+// count: cnt (cmr_range_counter_bytes(n, nb)) = exclusive prefix of the hits per (query, tile of CMR_RANGE_TILE rows), query-major, the
+//        total behind it; counts[nb] = hits per query.  Two launches.
+// compact: the hits of queries [q_first, q_first + nq_group) — `hits` of them by cnt — as (query in group << 32 | ~code, row), per query by
+//        ascending row, into key / val [hits].
+// finish: sorted pairs -> row + id_base and the score's bits gathered from the block, out_ids / out_scores [hits]
+unsigned cmr_range_bound_code(float min_score);
+size_t cmr_range_counter_bytes(long long n, int nb);
+hipError_t cmr_launch_range_count(const float* scores, long long ld, long long n, int nb, unsigned lo, unsigned* cnt, long long* counts, hipStream_t s);
+hipError_t cmr_launch_range_compact(const float* scores, long long ld, long long n, unsigned lo, const unsigned* offs, int q_first, int nq_group, long long hits,
+                                    u64* key, unsigned* val, hipStream_t s);
+hipError_t cmr_launch_range_finish(const u64* key, const unsigned* val, long long hits, const float* scores, long long ld, int q_first, long long id_base,
+                                   int64_t* out_ids, float* out_scores, hipStream_t s);
 // shard merge: ids/scores [S][nq][k] -> [nq][k]
 hipError_t cmr_launch_merge_shards(const int64_t* ids, const float* scores, int S, int nq, int k,
                                    int64_t* out_ids, float* out_scores, hipStream_t s);

@@ -77,6 +77,7 @@ struct Workspace {
     // synchronous search: queries in, (ids | scores | min | max | non-finite flag) out through ONE pinned host buffer and
     // one copy each way — five pageable D2H copies cost more than the search of a small corpus
     DevBuf d_pack;
+    DevBuf r_cnt, r_counts, r_hits;   // range search: (query, tile) counters / offsets, per-query counts, a group's [keys a | keys b | rows a | rows b | histograms]
     Q8Scratch q8;                // certified int8 pre-filter
     ExactScratch x;              // cmr_index_search_exact
     int* flag_ptr = nullptr;     // the non-finite-query flag the kernels set: flag.p, or the head of d_pack for the host API
@@ -113,6 +114,7 @@ struct Workspace {
         d_mask.release();
         d_lists.release();
         d_pack.release();
+        r_cnt.release(); r_counts.release(); r_hits.release();
         q8.release();
         x.release();
         if (h_pin) (void)hipHostFree(h_pin);
@@ -165,6 +167,12 @@ struct cmr_index {
     long long rm_chunks_last = 0;   // read-only ("remove_chunks_last"): chunks the corpus pass of the last removal ran (0: nothing moved)
     long long upd_stage_rows = 0;   // update_stage_rows: fp32 rows a staged chunk of a row update holds (0: 256 MiB worth, like the append's; a set value also keeps the call off the mapped buffer)
     long long upd_chunks_last = 0;  // read-only ("update_chunks_last"): chunks the last row update wrote (0: nothing written)
+    // range search: range_block_queries — queries per materialised score block (0: as many as 2 GiB of scores hold);
+    // range_scratch_hits — hits compacted and sorted at once (0: 1 GiB of scratch worth, 24 bytes a hit); read-only range_blocks_last /
+    // range_groups_last — blocks and groups the last range search ran
+    int range_block_queries = 0;
+    long long range_scratch_hits = 0;
+    std::atomic<long long> range_blocks_last{0}, range_groups_last{0};
     void* h_pin = nullptr;       // small appends / row updates: pinned, device-mapped [flag | rows | an update's plan] (exclusive lock held)
     void* h_pin_dev = nullptr;
     size_t h_pin_cap = 0;

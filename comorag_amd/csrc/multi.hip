@@ -858,6 +858,80 @@ int32_t cmr_mindex_sorted_scores(cmr_mindex_t* m, const float* q, int32_t nq, in
     return CMR_OK;
 }
 
+// Range search over the shards.  A shard answers in global ids, each list in the exported order (local row order is global id
+// order inside a shard), so the host's per-query merge gives what one index holding all rows gives.
+static int range_check(const void* m, const void* q, const void* out, int nq, float min_score) {
+    if (!m || !q || !out) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (nq <= 0) return cmr_fail(CMR_ERR_INVALID, "nq must be > 0");
+    if (!(min_score == min_score)) return cmr_fail(CMR_ERR_INVALID, "min_score is NaN");
+    return CMR_OK;
+}
+// counts [A][nq] of the active shards, all shards at once
+static int range_shard_counts(cmr_mindex* m, const std::vector<int>& act, const float* q, int nq, float min_score, std::vector<int64_t>& counts) {
+    counts.assign(act.size() * (size_t)nq, 0);
+    return for_active(m, act, true, [&](int a, int s) { return cmr_index_range_count(m->shard[s], q, nq, min_score, counts.data() + (size_t)a * nq); });
+}
+
+int32_t cmr_mindex_range_count(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t* out_counts) {
+    int rc = range_check(m, q, out_counts, nq, min_score);
+    if (rc) return rc;
+    std::shared_lock<std::shared_mutex> lk(m->mu);
+    const std::vector<int> act = active_shards(m);
+    std::fill(out_counts, out_counts + nq, (int64_t)0);
+    if (act.empty()) return CMR_OK;
+    if (act.size() == 1) return cmr_index_range_count(m->shard[act[0]], q, nq, min_score, out_counts);
+    std::vector<int64_t> counts;
+    if ((rc = range_shard_counts(m, act, q, nq, min_score, counts))) return rc;
+    for (size_t a = 0; a < act.size(); ++a)
+        for (int i = 0; i < nq; ++i) out_counts[i] += counts[a * nq + i];
+    return CMR_OK;
+}
+
+int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, cmr_range_result_t** out) {
+    if (out) *out = nullptr;
+    int rc = range_check(m, q, out, nq, min_score);
+    if (rc) return rc;
+    const long long limit = max_total > 0 ? max_total : CMR_RANGE_MAX_TOTAL;
+    std::shared_lock<std::shared_mutex> lk(m->mu);
+    const std::vector<int> act = active_shards(m);
+    const int A = (int)act.size();
+    if (A == 0) {
+        cmr_range_result* res = new cmr_range_result();
+        res->nq = nq;
+        res->lims = new int64_t[(size_t)nq + 1]();
+        *out = res;
+        return CMR_OK;
+    }
+    if (A == 1) return cmr_index_range_search(m->shard[act[0]], q, nq, min_score, max_total, out);
+    // the limit is on the merged total: where the batch could exceed it, every shard counts before any shard compacts
+    if ((double)nq * (double)m->total > (double)limit) {
+        std::vector<int64_t> counts;
+        if ((rc = range_shard_counts(m, act, q, nq, min_score, counts))) return rc;
+        long long total = 0;
+        for (int64_t c : counts) total += c;
+        if (total > limit)
+            return cmr_fail(CMR_ERR_UNSUPPORTED, "range search: the batch has %lld hits, above the limit of %lld (cmr_mindex_range_count sizes a request)", total, limit);
+    }
+    // every shard's search on its worker thread: it begins on all of them before it finishes on any
+    std::vector<cmr_range_result_t*> part((size_t)A, nullptr);
+    struct Free { std::vector<cmr_range_result_t*>& p; ~Free() { for (cmr_range_result_t* r : p) (void)cmr_range_result_destroy(r); } } free_parts{part};
+    rc = for_active(m, act, true, [&](int a, int s) { return cmr_index_range_search(m->shard[s], q, nq, min_score, limit, &part[a]); });
+    if (rc) return rc;
+    std::vector<const int64_t*> lims((size_t)A), ids((size_t)A);
+    std::vector<const float*> sc((size_t)A);
+    long long total = 0;
+    for (int a = 0; a < A; ++a) { lims[a] = part[a]->lims; ids[a] = part[a]->ids; sc[a] = part[a]->scores; total += part[a]->lims[nq]; }
+    cmr_range_result* res = new cmr_range_result();
+    res->nq = nq;
+    res->lims = new int64_t[(size_t)nq + 1]();
+    res->ids = new int64_t[(size_t)std::max<long long>(total, 1)];
+    res->scores = new float[(size_t)std::max<long long>(total, 1)];
+    rc = cmr_range_merge(A, nq, lims.data(), ids.data(), sc.data(), res->lims, res->ids, res->scores);
+    if (rc) { delete res; return rc; }
+    *out = res;
+    return CMR_OK;
+}
+
 int32_t cmr_mindex_rescore(cmr_mindex_t* m, const float* q, int32_t nq, const int64_t* cand, int32_t n_cand, int32_t k, int64_t* out_ids,
                            float* out_scores) {
     if (!m || !q || !cand || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");

@@ -177,6 +177,34 @@ static hipError_t sort_enqueue(const S* scores, long long n, int nb, long long n
     return hipGetLastError();
 }
 
+// Ready-made 64-bit keys with a 32-bit payload each (the range search's hits, range_kernels.hip): one segment of n pairs, stable, ascending by
+// the 8-bit digit positions of `digits` (bit p = bits [8p, 8p + 8) of the key), lowest position first; a position left out must hold one
+// value in every key.  The passes alternate between the two buffer pairs: the sorted pairs end in (*key_out, *val_out), one of them.
+// hist: cmr_sort_keys64_hist_bytes(n).  The kernels are the fp64 ranking's.
+size_t cmr_sort_keys64_hist_bytes(long long n) { return (size_t)sort_tiles(n) * 256 * sizeof(unsigned); }
+hipError_t cmr_launch_sort_keys64(u64* key_a, u64* key_b, unsigned* val_a, unsigned* val_b, unsigned* hist, long long n, unsigned digits, u64** key_out,
+                                  unsigned** val_out, hipStream_t s) {
+    *key_out = key_a;
+    *val_out = val_a;
+    if (n <= 0) return hipSuccess;
+    if (n >= (1ll << 32)) return hipErrorInvalidValue;
+    const unsigned un = (unsigned)n, ntiles = sort_tiles(n);
+    u64 *ki = key_a, *ko = key_b;
+    unsigned *vi = val_a, *vo = val_b;
+    for (int p = 0; p < 8; ++p) {
+        if (!((digits >> p) & 1u)) continue;
+        const int shift = 8 * p;
+        hipLaunchKernelGGL((sort_hist_kernel<u64, 8>), dim3(ntiles, 1), dim3(SORT_T), 0, s, ki, un, shift, ntiles, hist);
+        hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, s, hist, ntiles << 8);
+        hipLaunchKernelGGL((sort_scatter_kernel<u64, 8>), dim3(ntiles, 1), dim3(SORT_T), 0, s, ki, vi, un, shift, ntiles, hist, ko, vo);
+        std::swap(ki, ko);
+        std::swap(vi, vo);
+    }
+    *key_out = ki;
+    *val_out = vi;
+    return hipGetLastError();
+}
+
 // scores [n] (device) -> out_ids [n], out_scores [n] sorted descending (ties: ascending row)
 hipError_t cmr_launch_sort_scores(const float* scores, long long n, long long id_base, void* workspace, int64_t* out_ids, float* out_scores, hipStream_t s) {
     return sort_enqueue<float, unsigned, 4>(scores, n, 1, n, id_base, workspace, out_ids, out_scores, s);

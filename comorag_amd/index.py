@@ -157,7 +157,7 @@ def renumber_after_removal(ids, removed) -> np.ndarray:
 
 # the calls whose host-array marshalling `DenseIndex` (cmr_index_*) and `MultiDeviceIndex` (cmr_mindex_*) share
 _HOST_CALLS = ("destroy", "size", "info", "append", "search", "search_exact", "search_min_score", "scores", "sorted_scores",
-               "rescore", "get_rows", "search_ids", "remove_ids", "update_rows")
+               "rescore", "get_rows", "search_ids", "remove_ids", "update_rows", "range_count", "range_search")
 _bound = {}
 
 
@@ -309,6 +309,41 @@ class HostArrayIndex:
         sc = np.empty((nq, k), dtype=np.float32)
         L.check(self._c.search_min_score(self._h, _ptr(q), nq, k, float(min_score), _ptr(ids), _ptr(sc)))
         return ids, sc
+
+    # -- range search (cmr_index_range_search / cmr_mindex_range_search)
+    def range_search(self, q, min_score: float, max_total: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """EVERY row with raw score >= min_score, per query (FAISS `range_search`): (lims int64 [nq + 1], ids int64 [lims[nq]], scores fp32
+        [lims[nq]]) — query i owns ids[lims[i]:lims[i + 1]], best first (score descending, then row id ascending): the head of row i of
+        `sorted_scores`, as long as the scores stay at or above the bound.  The comparison is `search_min_score`'s (a row that attains the
+        bound is in; -0.0 and +0.0 are one value), a row's score bits are those `scores` returns for it, ids are as the searches return
+        them.  +inf: empty lists; -inf: every row; NaN: `CmrError` (CMR_ERR_INVALID).  `max_total` (None: 2^31 - 1): a batch with more hits
+        in all raises `CmrError` (CMR_ERR_UNSUPPORTED, the total in the message) before anything is compacted, sorted or allocated —
+        `range_count` sizes a request.  The arrays are numpy copies: the library's result is gone when this returns."""
+        q = self._queries(q)
+        nq = q.shape[0]
+        res = C.c_void_p()
+        L.check(self._c.range_search(self._h, _ptr(q), nq, float(min_score), int(max_total) if max_total is not None else 0, C.byref(res)))
+        try:
+            n, lims_p, ids_p, sc_p = C.c_int32(0), C.c_void_p(), C.c_void_p(), C.c_void_p()
+            L.check(L.lib().cmr_range_result_view(res, C.byref(n), C.byref(lims_p), C.byref(ids_p), C.byref(sc_p)))
+            lims = np.ctypeslib.as_array(C.cast(lims_p, C.POINTER(C.c_int64)), shape=(nq + 1,)).copy()
+            total = int(lims[nq])
+            if total:
+                ids = np.ctypeslib.as_array(C.cast(ids_p, C.POINTER(C.c_int64)), shape=(total,)).copy()
+                sc = np.ctypeslib.as_array(C.cast(sc_p, C.POINTER(C.c_float)), shape=(total,)).copy()
+            else:
+                ids, sc = np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float32)
+        finally:
+            L.lib().cmr_range_result_destroy(res)
+        return lims, ids, sc
+
+    def range_count(self, q, min_score: float) -> np.ndarray:
+        """Rows with raw score >= min_score per query, int64 [nq]: `np.diff(lims)` of `range_search` without the lists, and without its
+        limit on the total."""
+        q = self._queries(q)
+        out = np.empty(q.shape[0], dtype=np.int64)
+        L.check(self._c.range_count(self._h, _ptr(q), q.shape[0], float(min_score), _ptr(out)))
+        return out
 
     # -- exact fp32 top-k (a 16-bit index created with keep_f32=True; an f32 index is exact already)
     def search_exact(self, q, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -463,6 +498,19 @@ class DenseIndex(HostArrayIndex):
         L.check(L.lib().cmr_index_search_min_score_dev(self._h, C.c_void_p(q_t.data_ptr()), nq, k, float(min_score),
                                                        C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()), C.c_void_p(stream)))
         return out_ids, out_scores
+
+    def range_count_dev(self, q_t, min_score: float, out=None, stream: Optional[int] = None):
+        """`range_count` on torch CUDA tensors (q_t float32 [nq, dim] → int64 [nq]), enqueued on torch's current stream without synchronising."""
+        import torch
+        assert q_t.is_cuda and q_t.dtype == torch.float32 and q_t.is_contiguous() and q_t.shape[1] == self.dim
+        if out is None:
+            out = torch.empty((q_t.shape[0],), dtype=torch.int64, device=q_t.device)
+        assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape[0] == q_t.shape[0]
+        if stream is None:
+            stream = torch.cuda.current_stream(q_t.device).cuda_stream
+        L.check(L.lib().cmr_index_range_count_dev(self._h, C.c_void_p(q_t.data_ptr()), q_t.shape[0], float(min_score), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(stream)))
+        return out
 
     def search_min_score_pipelined(self, q_t, k: int, min_score: float, out_ids, out_scores, wait_event=None):
         """`search_min_score` in throughput mode (the index's own streams; packing, scan and candidate merge of consecutive blocks

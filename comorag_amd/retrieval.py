@@ -144,6 +144,14 @@ def get_similar_summaries(query: str, level_store, embedding_model, top_k: int =
     return [level_texts[i] for i in sorted_indices], sorted_scores.tolist()
 
 
+def neighbours_within(index, query_embeddings, min_score: float) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """Every row of `index` (a `DenseIndex` or a `MultiDeviceIndex`) with raw score >= min_score, per query: a list of (ids int64, scores
+    fp32), best first (ties: lower row id first) — the neighbours ComoRAG.add_synonymy_edges reads down to synonymy_edge_sim_threshold
+    (ComoRAG.py:670-712), however many there are.  One range search (cmr_index_range_search)."""
+    lims, ids, sc = index.range_search(_as_query(query_embeddings), min_score)
+    return [(ids[lims[i]:lims[i + 1]], sc[lims[i]:lims[i + 1]]) for i in range(len(lims) - 1)]
+
+
 def _l2n(x: np.ndarray) -> np.ndarray:
     n = np.sqrt((x * x).sum(axis=1, keepdims=True, dtype=np.float32))
     return x / np.maximum(n, np.float32(1e-12))
@@ -151,7 +159,8 @@ def _l2n(x: np.ndarray) -> np.ndarray:
 
 def retrieve_knn(query_ids: Sequence[str], key_ids: Sequence[str], query_vecs, key_vecs, k: int = 2047,
                  query_batch_size: int = 1000, key_batch_size: int = 10000, index_dtype: str = "f32",
-                 device: int = 0, min_score: Optional[float] = None, max_neighbours: int = 128) -> Dict[str, Tuple[List[str], List[float]]]:
+                 device: int = 0, min_score: Optional[float] = None, max_neighbours: int = 128,
+                 full_lists: str = "large_k") -> Dict[str, Tuple[List[str], List[float]]]:
     """utils/embed_utils.py:8-97 — fp32 re-normalise both sides, exact top-k of every query over all keys,
     `{query_id: ([key ids], [scores])}`.  The reference's key-block loop + merge computes the global top-k, so one pass
     over a single HBM index gives the same answer; k <= 128 uses the fused scan+top-k kernel, larger k
@@ -164,7 +173,10 @@ def retrieve_knn(query_ids: Sequence[str], key_ids: Sequence[str], query_vecs, k
     each list holds the neighbours with score >= min_score only, best first, found by the fused kernel with its threshold
     started at min_score (cmr_index_search_min_score) — no [nq, N] score block, no 2047-wide selection.  A query with
     more than `max_neighbours` (<= 128) such neighbours is re-run through the exact large-k path, so every list is a
-    prefix-complete answer: what the consumer reads is identical."""
+    prefix-complete answer: what the consumer reads is identical.  `full_lists` = "range": those queries take their neighbours from
+    ONE range search (`neighbours_within`), cut at k, instead of the large-k re-run — the same dict."""
+    if full_lists not in ("large_k", "range"):
+        raise ValueError(f"full_lists must be 'large_k' or 'range', got {full_lists!r}")
     if len(key_vecs) == 0:
         return {}
     q = _l2n(np.asarray(query_vecs, dtype=np.float32))
@@ -203,7 +215,10 @@ def retrieve_knn(query_ids: Sequence[str], key_ids: Sequence[str], query_vecs, k
             if min_score is not None and kk > thr_k:
                 ids, sc = (thr_all[0][s:s + query_batch_size], thr_all[1][s:s + query_batch_size]) if thr_all is not None else index.search_min_score(qb, thr_k, min_score)
                 full = np.flatnonzero(ids[:, -1] >= 0)                  # lists that filled up: more neighbours may exist
-                redo = dict(zip(full.tolist(), zip(*index.search(qb[full], kk, with_minmax=False)[:2]))) if len(full) and kk <= CMR_MAX_K_2PASS else {}
+                if full_lists == "range" and len(full) and kk <= CMR_MAX_K_2PASS:
+                    redo = {r: (ri[:kk], rs[:kk]) for r, (ri, rs) in zip(full.tolist(), neighbours_within(index, qb[full], min_score))}
+                else:
+                    redo = dict(zip(full.tolist(), zip(*index.search(qb[full], kk, with_minmax=False)[:2]))) if len(full) and kk <= CMR_MAX_K_2PASS else {}
                 for r in range(len(qb)):
                     if r in redo:
                         ri, rs = redo[r]

@@ -369,7 +369,7 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  * cmr_index_search_masked_each over the participants' queries, every query with its caller's mask (a shared mask repeated per query), and
  * each caller gets the bits of its own call.  A participant whose n_words no longer fits the index when the batch runs (an append came in
  * between) gets its own CMR_ERR_INVALID; the others are served.  At 0 filtered calls never join a batch and never move the counters.
- * NOT combined: cmr_index_search_masked* unless "combine_filtered" is set, cmr_index_search_ids* and cmr_mindex_search_ids whether or not it is set, cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
+ * NOT combined: cmr_index_search_masked* unless "combine_filtered" is set, cmr_index_search_ids* and cmr_mindex_search_ids whether or not it is set, cmr_index_search_min_score, cmr_index_sorted_scores, cmr_index_range_search / _count, cmr_index_search_exact, cmr_graph_ppr, every _dev / pipelined call,
  * cmr_mindex_* (the option has no effect on searches issued through a multi-device handle).  The encoder is not combined HERE: concurrent
  * one-question encodes share one forward through the Python-level option `embedding_combine` (cmr_encoder_linear_rows* below).      */
 /* Which path served the last call (read-only): "last_route", written by the host when a search or all-scores call on this index is
@@ -398,6 +398,7 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
 #define CMR_ROUTE_SCORES_SINGLE 8 /* cmr_index_scores, single launch */
 #define CMR_ROUTE_SCORES 9        /* cmr_index_scores, general scan */
 #define CMR_ROUTE_SORTED 10       /* cmr_index_sorted_scores: general scan + radix sort */
+#define CMR_ROUTE_RANGE 11        /* cmr_index_range_search / _count: general scan + count / compaction / radix sort */
 /* What the pipeline actually does (read-only): "pipe_dual_scan_active" / "pipe_dual_scan_wide_active" (the last pipelined <= 64-query / wide pass alternated between
  * the two scan streams: by default only scans shorter than ~1 ms do — launches that overlap have no per-launch duration, so a
  * caller that times kernels must know), "pipe_cu_mask_active", "pipe_scan_cus".                                            */
@@ -430,6 +431,46 @@ int32_t cmr_index_scores_dev(cmr_index_t* idx, const float* q_f32_dev, int32_t n
  * need the complete ranking: scan on MFMA, then a stable device radix sort.                       */
 int32_t cmr_index_sorted_scores(cmr_index_t* idx, const float* q_f32, int32_t nq, int64_t* out_ids,
                                 float* out_scores, float* out_min, float* out_max);
+
+/* ---- range search ------------------------------------------------------------------------
+ * EVERY row with raw score >= min_score, as per-query lists (FAISS range_search): what the synonymy join asks for when it reads
+ * neighbours down to synonymy_edge_sim_threshold (ComoRAG.add_synonymy_edges, ComoRAG.py:670-712, over retrieve_knn,
+ * utils/embed_utils.py:8-97) without the cap of CMR_MAX_K entries that cmr_index_search_min_score has and cannot report.
+ *   list i     all rows r with score(i, r) >= min_score, compared as the threshold search compares (the order-preserving code of the
+ *              fp32 bits, -0.0 and +0.0 one value): a row that attains the bound is in, the next fp32 value below is out.  Order: score
+ *              descending, then row id ascending — the first c_i entries of row i of cmr_index_sorted_scores.  A row's score bits are
+ *              those cmr_index_scores returns for it (gathered, never decoded from a key: a -0.0 stays -0.0); ids carry the id base /
+ *              block table as every search's do.
+ *   result     CSR: lims int64 [nq + 1] (lims[0] = 0), ids int64 [lims[nq]], scores fp32 [lims[nq]].  The library owns the arrays
+ *              (their size is known only after the count): cmr_range_result_view's pointers are valid until cmr_range_result_destroy.
+ *   bounds     +inf: empty lists; -inf and -FLT_MAX: every row; NaN: CMR_ERR_INVALID.  Empty index: nq empty lists, CMR_OK.
+ *   max_total  <= 0: the library's limit, CMR_RANGE_MAX_TOTAL hits.  A batch whose total exceeds the limit: CMR_ERR_UNSUPPORTED with the
+ *              total in the message, *out = NULL, nothing allocated for the result, no compaction or sort run.  cmr_index_range_count has
+ *              no such limit: it is how a caller sizes a request.  cmr_index_range_count_dev enqueues on `stream` and never synchronises.
+ * Any nq >= 1; rows < 2^32.  A NULL handle, query or output, nq <= 0 or a NaN bound: CMR_ERR_INVALID, before any device call.  A NaN / Inf
+ * query: CMR_ERR_NONFINITE (the synchronous calls).  The calls take the shared lock like a search, use a workspace of their own and are
+ * never combined, pipelined or filtered and never take the int8 pre-filter.  last_route: CMR_ROUTE_RANGE.
+ * How: per block of queries (at most 2 GiB of scores; option "range_block_queries", 0 = that rule) the scan materialises the scores, a
+ * count kernel counts the hits per (query, tile of CMR_RANGE_TILE rows) by wave ballots, one workgroup turns the counters into offsets
+ * and per-query counts — the call's one small round trip per block —, a compaction kernel places every hit at its offset (no atomic
+ * decides a position) with the key (query << 32 | complemented score code), a stable LSD radix sort orders them, a last kernel gathers
+ * ids and score bits.  Option "range_scratch_hits" (0 = 1 GiB worth) bounds the hits compacted and sorted at once: a block with more is
+ * done in groups of consecutive queries from the same scores, one query is never split.  Results never depend on the two options; read-only
+ * "range_blocks_last" / "range_groups_last" tell how many blocks / groups the last call ran.
+ * cmr_range_merge (pure host, no device): per-shard results of the same nq queries — each list in the exported order, ids disjoint —
+ * merged per query by the exported tie rule; out_lims [nq + 1], out_ids / out_scores [sum of the shards' totals].                     */
+#define CMR_RANGE_TILE 2048
+#define CMR_RANGE_MAX_TOTAL 2147483647ll
+typedef struct cmr_range_result cmr_range_result_t;
+int32_t cmr_index_range_count(cmr_index_t* idx, const float* q_f32, int32_t nq, float min_score, int64_t* out_counts /*[nq]*/);
+int32_t cmr_index_range_count_dev(cmr_index_t* idx, const float* q_f32_dev, int32_t nq, float min_score, int64_t* out_counts_dev,
+                                  void* stream);
+int32_t cmr_index_range_search(cmr_index_t* idx, const float* q_f32, int32_t nq, float min_score, int64_t max_total,
+                               cmr_range_result_t** out);
+int32_t cmr_range_result_view(const cmr_range_result_t* res, int32_t* nq, const int64_t** lims, const int64_t** ids, const float** scores);
+int32_t cmr_range_result_destroy(cmr_range_result_t* res);      /* NULL is a no-op */
+int32_t cmr_range_merge(int32_t n_shards, int32_t nq, const int64_t* const* lims, const int64_t* const* ids, const float* const* scores,
+                        int64_t* out_lims, int64_t* out_ids, float* out_scores);
 
 /* Exact fp32 re-score of candidate rows (BASELINE config 5 "cross-scores on top-100").  The
  * reference's rerank.py is an LLM filter with no numeric scoring (rerank.py:100-123); this is
@@ -628,6 +669,14 @@ int32_t cmr_mindex_search_min_score(cmr_mindex_t* m, const float* q_f32, int32_t
 int32_t cmr_mindex_scores(cmr_mindex_t* m, const float* q_f32, int32_t nq, float* out, int64_t ld);
 int32_t cmr_mindex_sorted_scores(cmr_mindex_t* m, const float* q_f32, int32_t nq, int64_t* out_ids, float* out_scores,
                                  float* out_min, float* out_max);
+/* Range search over the shards (cmr_index_range_search above has the semantics): GLOBAL ids; the result equals ONE cmr_index_t holding the
+ * same rows, bit for bit.  Every non-empty shard runs its own range search — all of them at once, on the shards' worker threads — and the
+ * host merges per query with cmr_range_merge (a shard's list is in the exported order already: local row order is global id order inside
+ * a shard).  max_total applies to the merged total: where the batch could exceed it, every shard's count runs before any shard's
+ * compaction.                                                                                                                          */
+int32_t cmr_mindex_range_count(cmr_mindex_t* m, const float* q_f32, int32_t nq, float min_score, int64_t* out_counts /*[nq]*/);
+int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q_f32, int32_t nq, float min_score, int64_t max_total,
+                                cmr_range_result_t** out);
 int32_t cmr_mindex_rescore(cmr_mindex_t* m, const float* q_f32, int32_t nq, const int64_t* cand, int32_t n_cand, int32_t k,
                            int64_t* out_ids, float* out_scores);
 int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, float* out);
