@@ -87,6 +87,12 @@ SIGNATURES = {
     "cmr_range_result_view": (_i32, [_p, _P(_i32), _P(_p), _P(_p), _P(_p)]),
     "cmr_range_result_destroy": (_i32, [_p]),
     "cmr_range_merge": (_i32, [_i32, _i32, _p, _p, _p, _p, _p, _p]),
+    "cmr_index_search_min_score_masked": (_i32, [_p, _p, _i32, _i32, _f32, _p, _i64, _i32, _p, _p]),
+    "cmr_index_search_min_score_ids": (_i32, [_p, _p, _i32, _i32, _f32, _i32, _p, _p, _i64, _p, _p]),
+    "cmr_index_range_count_masked": (_i32, [_p, _p, _i32, _f32, _p, _i64, _i32, _p]),
+    "cmr_index_range_count_ids": (_i32, [_p, _p, _i32, _f32, _i32, _p, _p, _i64, _p]),
+    "cmr_index_range_search_masked": (_i32, [_p, _p, _i32, _f32, _i64, _p, _i64, _i32, _P(_p)]),
+    "cmr_index_range_search_ids": (_i32, [_p, _p, _i32, _f32, _i64, _i32, _p, _p, _i64, _P(_p)]),
     "cmr_index_rescore": (_i32, [_p, _p, _i32, _p, _i32, _i32, _p, _p]),
     "cmr_index_get_rows": (_i32, [_p, _p, _i64, _p]),
     "cmr_index_search_exact": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),
@@ -127,6 +133,9 @@ SIGNATURES = {
     "cmr_mindex_sorted_scores": (_i32, [_p, _p, _i32, _p, _p, _p, _p]),
     "cmr_mindex_range_count": (_i32, [_p, _p, _i32, _f32, _p]),
     "cmr_mindex_range_search": (_i32, [_p, _p, _i32, _f32, _i64, _P(_p)]),
+    "cmr_mindex_search_min_score_ids": (_i32, [_p, _p, _i32, _i32, _f32, _i32, _p, _p, _i64, _p, _p]),
+    "cmr_mindex_range_count_ids": (_i32, [_p, _p, _i32, _f32, _i32, _p, _p, _i64, _p]),
+    "cmr_mindex_range_search_ids": (_i32, [_p, _p, _i32, _f32, _i64, _i32, _p, _p, _i64, _P(_p)]),
     "cmr_mindex_rescore": (_i32, [_p, _p, _i32, _p, _i32, _i32, _p, _p]),
     "cmr_mindex_get_rows": (_i32, [_p, _p, _i64, _p]),
     "cmr_mindex_search_exact": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),

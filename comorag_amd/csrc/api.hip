@@ -462,20 +462,22 @@ int search_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, in
 // ws->stream; one mask serves every query.  k <= CMR_MAX_K (checked by the caller).
 // mask_stride > 0 (cmr_index_search_masked_each*): allow_dev is [nq][mask_stride], query i's words at allow_dev + i * mask_stride;
 // the pass that starts at query q0 gets the pointer advanced by q0 blocks, its kernel indexes the pass's own queries from 0.
+// min_score (cmr_index_search_min_score_masked / _ids): the filtered threshold search — the bound is every query's initial
+// threshold as in search_enqueue, so no sampling passes; the same masked scans, the same merge.
 int search_masked_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, int k, const unsigned* allow_dev, int64_t* ids_dev,
-                          float* scores_dev, float* min_dev, float* max_dev, long long mask_stride = 0) {
+                          float* scores_dev, float* min_dev, float* max_dev, long long mask_stride = 0, const float* min_score = nullptr) {
     const PassStreams st = PassStreams::one(ws->stream);
     const int per_pass = idx->narrow_width(nq);
     for (int q0 = 0; q0 < nq; q0 += per_pass) {
         const int nqp = std::min(per_pass, nq - q0);
         PassPlan plan;
-        PassRequest rq = st.request(nqp, k, Route::narrow, false, 0);
+        PassRequest rq = st.request(nqp, k, Route::narrow, min_score != nullptr, 0);
         rq.masked = true;
         rq.masked_each = mask_stride > 0;
         int rc = plan_pass(idx, rq, &plan);
         if (rc) return rc;
-        if (q0 == 0) idx->last_route.store(route_code(plan, false) | (nqp < nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
-        rc = enqueue_pass(idx, ws, st, plan, q_dev + (size_t)q0 * idx->dim, nullptr, ids_dev + (size_t)q0 * k, scores_dev + (size_t)q0 * k,
+        if (q0 == 0) idx->last_route.store(route_code(plan, min_score != nullptr) | (nqp < nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
+        rc = enqueue_pass(idx, ws, st, plan, q_dev + (size_t)q0 * idx->dim, min_score, ids_dev + (size_t)q0 * k, scores_dev + (size_t)q0 * k,
                           min_dev ? min_dev + q0 : nullptr, max_dev ? max_dev + q0 : nullptr, allow_dev + (size_t)q0 * (size_t)mask_stride, mask_stride);
         if (rc) return rc;
     }
@@ -1420,7 +1422,7 @@ int row_masks_enqueue(cmr_index* idx, int mode, int nq, const int64_t* off_dev, 
 // kIdsGroup queries, each group's words built into the same scratch behind the previous group's scan (stream order) and scanned by the
 // per-query variant; a query's row does not depend on the group it falls into.
 int search_ids_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, int k, int mode, const int64_t* off_dev, const int64_t* ids_dev,
-                       int64_t n_ids, int64_t* ids_out, float* scores_out, float* min_out, float* max_out) {
+                       int64_t n_ids, int64_t* ids_out, float* scores_out, float* min_out, float* max_out, const float* min_score = nullptr) {
     const long long nw = idx->npanels();
     const int group = off_dev ? kIdsGroup : nq;
     HIP_TRY(ws->d_mask.ensure(std::max<size_t>((size_t)(off_dev ? std::min(nq, kIdsGroup) : 1) * (size_t)nw * 4, 4)));
@@ -1431,7 +1433,7 @@ int search_ids_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq
         int rc = row_masks_enqueue(idx, mode, nqg, off_dev ? off_dev + q0 : nullptr, ids_dev, n_ids, words, ws->stream);
         if (rc) return rc;
         rc = search_masked_enqueue(idx, ws, q_dev + (size_t)q0 * idx->dim, nqg, k, words, ids_out + (size_t)q0 * k, scores_out + (size_t)q0 * k,
-                                   min_out ? min_out + q0 : nullptr, max_out ? max_out + q0 : nullptr, off_dev ? nw : 0);
+                                   min_out ? min_out + q0 : nullptr, max_out ? max_out + q0 : nullptr, off_dev ? nw : 0, min_score);
         if (rc) return rc;
         if (q0 == 0) route = idx->last_route.load(std::memory_order_relaxed);
     }
@@ -1445,14 +1447,14 @@ int search_ids_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq
 // abandoned through cmr_index_search_finish / _abandon.  The packed round trip (packed_begin) with two inputs: the queries, and
 // [offsets (nq + 1) | ids] as one block into d_lists.
 int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, int mode, const int64_t* off, const int64_t* ids, int64_t n_ids,
-                               bool take_lock, CmrPending** out) {
+                               bool take_lock, CmrPending** out, const float* min_score) {
     if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
     *out = nullptr;
     const size_t off_bytes = off ? ((size_t)nq + 1) * 8 : 0;
     const PackedInput in[] = {{&Workspace::d_q, q, (size_t)nq * idx->dim * 4}, {&Workspace::d_lists, off, off_bytes, ids, (size_t)n_ids * 8}};
     return packed_begin(idx, nq, k, take_lock, in, [&](Workspace* ws, int64_t* ids_out, float* sc, float* mn, float* mx) {
         return search_ids_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, mode, off ? (const int64_t*)ws->d_lists.p : nullptr,
-                                  (const int64_t*)((char*)ws->d_lists.p + off_bytes), n_ids, ids_out, sc, mn, mx);
+                                  (const int64_t*)((char*)ws->d_lists.p + off_bytes), n_ids, ids_out, sc, mn, mx, min_score);
     }, out);
 }
 
@@ -1835,7 +1837,8 @@ int32_t cmr_index_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t k
 // queries and masks out as one [total][n_words] block (a shared-mask participant's words once per query of its own) and scatters the
 // rows, which hold the bits of each caller's solo call (4.15b's contract).  A batch of one is the caller's own call, unchanged.
 // each = false: `allow` is [n_words], one mask for every query; each = true: [nq][n_words]
-struct CombinedMasked : CombinedSearch { const uint32_t* allow; int64_t n_words; bool each; };
+// min_score: the filtered threshold search (cmr_index_search_min_score_masked), which never queues
+struct CombinedMasked : CombinedSearch { const uint32_t* allow; int64_t n_words; bool each; const float* min_score = nullptr; };
 static const CombinedMasked* masked_args(const cmr_combine::Request* r) { return static_cast<const CombinedMasked*>(search_args(r)); }
 
 // The synchronous filtered search behind cmr_index_search_masked and cmr_index_search_masked_each: the packed round trip (packed_begin)
@@ -1846,7 +1849,8 @@ static int masked_call(cmr_index* idx, const CombinedMasked& a) {
                               {&Workspace::d_mask, a.allow, (size_t)a.n_words * 4 * (a.each ? (size_t)a.nq : 1)}};
     CmrPending* p = nullptr;
     const int rc = packed_begin(idx, a.nq, a.k, false, in, [&](Workspace* ws, int64_t* ids, float* sc, float* mn, float* mx) {
-        return search_masked_enqueue(idx, ws, (const float*)ws->d_q.p, a.nq, a.k, (const unsigned*)ws->d_mask.p, ids, sc, mn, mx, a.each ? (long long)a.n_words : 0);
+        return search_masked_enqueue(idx, ws, (const float*)ws->d_q.p, a.nq, a.k, (const unsigned*)ws->d_mask.p, ids, sc, mn, mx, a.each ? (long long)a.n_words : 0,
+                                     a.min_score);
     }, &p);
     return rc ? rc : cmr_index_search_finish(p, a.ids, a.scores, a.mn, a.mx);
 }
@@ -1919,6 +1923,56 @@ int32_t cmr_index_search_min_score(cmr_index_t* idx, const float* q, int32_t nq,
                                    float* out_scores) {
     if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
     return host_search(idx, q, nq, k, out_ids, out_scores, nullptr, nullptr, &min_score);
+}
+
+// ---- filtered threshold search: the masked / id-list searches above with the bound as every query's initial threshold.
+// Never combined: the words form is masked_single whatever "combine_filtered" says.
+// every check of the words forms that needs neither the index nor a device (n_words against the index: words_check, under its lock)
+static int mask_words_args_check(const void* allow, int nq, int64_t n_words, int n_masks) {
+    if (!allow) return fail(CMR_ERR_INVALID, "NULL allow words");
+    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
+    if (n_words < 0) return fail(CMR_ERR_INVALID, "n_words %lld < 0", (long long)n_words);
+    if (n_masks != 1 && n_masks != nq) return fail(CMR_ERR_INVALID, "n_masks %d is neither 1 nor nq = %d", n_masks, nq);
+    return CMR_OK;
+}
+
+static void threshold_padding(int nq, int k, int64_t* out_ids, float* out_scores) {
+    std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
+    std::fill(out_scores, out_scores + (size_t)nq * k, -INFINITY);
+}
+
+int32_t cmr_index_search_min_score_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, float min_score, const uint32_t* allow, int64_t n_words,
+                                          int32_t n_masks, int64_t* out_ids, float* out_scores) {
+    if (!q || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = mask_words_args_check(allow, nq, n_words, n_masks);
+    if (rc) return rc;
+    if (k <= 0) return fail(CMR_ERR_INVALID, "k must be > 0");
+    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "filtered threshold search supports k <= %d", CMR_MAX_K);
+    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
+    CombinedMasked a{{q, nq, k, out_ids, out_scores, nullptr, nullptr}, allow, n_words, n_masks > 1};
+    a.min_score = &min_score;
+    std::shared_lock<std::shared_mutex> lk(idx->mu);
+    if ((rc = masked_check(idx, nq, k, n_words))) return rc;
+    if (idx->n == 0) { threshold_padding(nq, k, out_ids, out_scores); return CMR_OK; }      // no row: no device call
+    return masked_call(idx, a);
+}
+
+int32_t cmr_index_search_min_score_ids(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, float min_score, int32_t mode, const int64_t* id_offsets,
+                                       const int64_t* ids, int64_t n_ids, int64_t* out_ids, float* out_scores) {
+    if (!q || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = cmr_ids_args_check(mode, nq, k, id_offsets, ids, n_ids);
+    if (rc) return rc;
+    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
+    {
+        std::shared_lock<std::shared_mutex> lk(idx->mu);
+        if (idx->n == 0) { threshold_padding(nq, k, out_ids, out_scores); return CMR_OK; }      // no row: no device call
+    }
+    CmrPending* p = nullptr;
+    rc = cmr_index_search_ids_begin(idx, q, nq, k, mode, id_offsets, ids, n_ids, true, &p, &min_score);
+    if (rc) return rc;
+    return cmr_index_search_finish(p, out_ids, out_scores, nullptr, nullptr);
 }
 
 int32_t cmr_index_scores_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, float* out_dev, int64_t ld, void* stream) {
@@ -2125,14 +2179,56 @@ static int range_args_check(const void* idx, const void* q, const void* out, int
 static int range_rows_check(const cmr_index* idx) {
     return idx->n < (1ll << 32) ? CMR_OK : fail(CMR_ERR_UNSUPPORTED, "range search needs fewer than 2^32 rows, the index holds %lld", idx->n);
 }
+// Filtered range search / count: the filter as the caller gave it (host pointers) ...
+struct RangeFilter {
+    const uint32_t* words = nullptr; int64_t n_words = 0; int n_masks = 0;                                            // the words forms: [n_masks][n_words]
+    bool by_ids = false; int mode = 0; const int64_t* off = nullptr; const int64_t* ids = nullptr; int64_t n_ids = 0;   // the id forms
+};
+// ... and in the call's workspace: the allow words the masked count / compaction kernels read (ws->d_mask).  Words forms and a shared id
+// list: every mask of the call, laid down once.  Per-query id lists (off_dev): the words of ONE block of at most kIdsGroup queries, built in
+// front of the block's count from the lists in ws->d_lists — the scratch never holds more than that many masks.
+struct RangeMasks {
+    unsigned* words = nullptr; long long stride = 0, route = 0;
+    int mode = 0; const int64_t* off_dev = nullptr; const int64_t* ids_dev = nullptr; int64_t n_ids = 0;
+    // the kernels' view for the block whose first query is query q0 of the call
+    CmrRangeMask kernel(int q0) const { return CmrRangeMask{words, stride, off_dev ? 0 : (long long)q0}; }
+};
+// (under the index lock, n > 0, n_words checked by the caller) uploads on ws->stream
+static int range_masks_open(cmr_index* idx, Workspace* ws, const RangeFilter& f, int nq, RangeMasks* mk) {
+    hipStream_t const s = ws->stream;
+    const size_t nw = (size_t)idx->npanels();
+    if (!f.by_ids) {
+        const size_t bytes = (size_t)f.n_masks * nw * 4;
+        HIP_TRY(ws->d_mask.ensure(std::max<size_t>(bytes, 4)));
+        HIP_TRY(hipMemcpyAsync(ws->d_mask.p, f.words, bytes, hipMemcpyHostToDevice, s));
+        mk->words = (unsigned*)ws->d_mask.p;
+        mk->stride = f.n_masks > 1 ? (long long)nw : 0;
+        mk->route = CMR_ROUTE_FILTERED | (f.n_masks > 1 ? CMR_ROUTE_FILTERED_EACH : 0);
+        return CMR_OK;
+    }
+    const size_t off_bytes = f.off ? ((size_t)nq + 1) * 8 : 0, ids_bytes = (size_t)f.n_ids * 8;
+    HIP_TRY(ws->d_lists.ensure(std::max<size_t>(off_bytes + ids_bytes, 8)));
+    if (off_bytes) HIP_TRY(hipMemcpyAsync(ws->d_lists.p, f.off, off_bytes, hipMemcpyHostToDevice, s));
+    if (ids_bytes) HIP_TRY(hipMemcpyAsync((char*)ws->d_lists.p + off_bytes, f.ids, ids_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(ws->d_mask.ensure(std::max<size_t>((size_t)(f.off ? std::min(nq, kIdsGroup) : 1) * nw * 4, 4)));
+    mk->words = (unsigned*)ws->d_mask.p;
+    mk->mode = f.mode; mk->ids_dev = (const int64_t*)((char*)ws->d_lists.p + off_bytes); mk->n_ids = f.n_ids;
+    mk->route = CMR_ROUTE_FILTERED | CMR_ROUTE_FILTERED_IDS | (f.off ? CMR_ROUTE_FILTERED_EACH : 0);
+    if (f.off) { mk->off_dev = (const int64_t*)ws->d_lists.p; mk->stride = (long long)nw; return CMR_OK; }
+    return row_masks_enqueue(idx, f.mode, 1, nullptr, mk->ids_dev, f.n_ids, mk->words, s);
+}
 // scores of nb queries into ws->d_out [nb][ld], the (query, tile) offsets into ws->r_cnt, the per-query counts to counts_dev [nb]
-static int range_count_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nb, long long ld, unsigned lo, long long* counts_dev) {
+// mk: only the allowed rows count; the block's first query is query q0 of the call
+static int range_count_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nb, long long ld, unsigned lo, long long* counts_dev,
+                               const RangeMasks* mk = nullptr, int q0 = 0) {
     HIP_TRY(ws->d_out.ensure((size_t)nb * ld * 4));
     HIP_TRY(ws->r_cnt.ensure(cmr_range_counter_bytes(idx->n, nb)));
     int rc = scores_enqueue(idx, ws, q_dev, nb, (float*)ws->d_out.p, ld);
     if (rc) return rc;
-    idx->last_route.store(route_code(CMR_ROUTE_RANGE), std::memory_order_relaxed);
-    HIP_TRY(cmr_launch_range_count((const float*)ws->d_out.p, ld, idx->n, nb, lo, (unsigned*)ws->r_cnt.p, counts_dev, ws->stream));
+    idx->last_route.store(route_code(CMR_ROUTE_RANGE) | (mk ? mk->route : 0), std::memory_order_relaxed);
+    if (mk && mk->off_dev && (rc = row_masks_enqueue(idx, mk->mode, nb, mk->off_dev + q0, mk->ids_dev, mk->n_ids, mk->words, ws->stream))) return rc;
+    const CmrRangeMask km = mk ? mk->kernel(q0) : CmrRangeMask{};
+    HIP_TRY(cmr_launch_range_count((const float*)ws->d_out.p, ld, idx->n, nb, lo, (unsigned*)ws->r_cnt.p, counts_dev, ws->stream, mk ? &km : nullptr));
     return CMR_OK;
 }
 // the counts of a block on the host (the block's round trip), with the non-finite flag of its queries
@@ -2148,14 +2244,15 @@ static int range_counts_to_host(Workspace* ws, int nb, int64_t* counts) {
     return CMR_OK;
 }
 // queries [g0, g1) of the block whose scores and offsets the workspace holds -> their `hits` sorted entries at out_ids / out_scores (host)
-static int range_group(cmr_index* idx, Workspace* ws, long long ld, unsigned lo, int g0, int g1, long long hits, int64_t* out_ids, float* out_scores) {
+static int range_group(cmr_index* idx, Workspace* ws, long long ld, unsigned lo, int g0, int g1, long long hits, int64_t* out_ids, float* out_scores,
+                       const CmrRangeMask* km = nullptr) {
     if (hits == 0) return CMR_OK;
     hipStream_t const s = ws->stream;
     const size_t h = (size_t)hits;
     HIP_TRY(ws->r_hits.ensure(h * 24 + cmr_sort_keys64_hist_bytes(hits)));
     u64 *ka = (u64*)ws->r_hits.p, *kb = ka + h;
     unsigned *va = (unsigned*)(kb + h), *vb = va + h, *hist = vb + h;
-    HIP_TRY(cmr_launch_range_compact((const float*)ws->d_out.p, ld, idx->n, lo, (const unsigned*)ws->r_cnt.p, g0, g1 - g0, hits, ka, va, s));
+    HIP_TRY(cmr_launch_range_compact((const float*)ws->d_out.p, ld, idx->n, lo, (const unsigned*)ws->r_cnt.p, g0, g1 - g0, hits, ka, va, s, km));
     // the four score digits first, then the query digits that can differ inside the group: equal scores keep ascending rows
     unsigned digits = 0x0Fu;
     for (unsigned span = (unsigned)(g1 - g0 - 1), p = 4; span; span >>= 8, ++p) digits |= 1u << p;
@@ -2188,33 +2285,42 @@ int32_t cmr_index_range_count_dev(cmr_index_t* idx, const float* q_dev, int32_t 
     return CMR_OK;
 }
 
-int32_t cmr_index_range_count(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t* out_counts) {
-    int rc = range_args_check(idx, q, out_counts, nq, min_score);
-    if (rc) return rc;
+// the arguments are checked; f: the filtered forms (nullptr: every row)
+static int range_count_host(cmr_index* idx, const float* q, int nq, float min_score, int64_t* out_counts, const RangeFilter* f) {
+    int rc;
     SyncCall call(idx);
     if ((rc = range_rows_check(idx))) return rc;
+    if (f && !f->by_ids && (rc = words_check(idx, f->n_words))) return rc;
     if (idx->n == 0) { std::fill(out_counts, out_counts + nq, (int64_t)0); return CMR_OK; }
     if ((rc = call.open())) return rc;
     Workspace* const ws = call.ws;
     const long long ld = (idx->n + 3) / 4 * 4;
-    const int blockq = range_block_queries(idx, nq, ld);
+    const int blockq = f && f->by_ids && f->off ? std::min(range_block_queries(idx, nq, ld), kIdsGroup) : range_block_queries(idx, nq, ld);
     const unsigned lo = cmr_range_bound_code(min_score);
     HIP_TRY(ws->d_q.ensure((size_t)nq * idx->dim * 4));
     HIP_TRY(ws->r_counts.ensure((size_t)nq * 8));
     HIP_TRY(hipMemcpyAsync(ws->d_q.p, q, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, call.s));
+    RangeMasks mk;
+    if (f) rc = range_masks_open(idx, ws, *f, nq, &mk);
     for (int q0 = 0; q0 < nq && !rc; q0 += blockq)
-        rc = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, std::min(blockq, nq - q0), ld, lo, (long long*)ws->r_counts.p + q0);
+        rc = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, std::min(blockq, nq - q0), ld, lo, (long long*)ws->r_counts.p + q0,
+                                 f ? &mk : nullptr, q0);
     if (rc) { (void)hipStreamSynchronize(call.s); return rc; }
     return range_counts_to_host(ws, nq, out_counts);
 }
 
-int32_t cmr_index_range_search(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t max_total, cmr_range_result_t** out) {
-    if (out) *out = nullptr;
-    int rc = range_args_check(idx, q, out, nq, min_score);
-    if (rc) return rc;
+int32_t cmr_index_range_count(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t* out_counts) {
+    const int rc = range_args_check(idx, q, out_counts, nq, min_score);
+    return rc ? rc : range_count_host(idx, q, nq, min_score, out_counts, nullptr);
+}
+
+// the arguments are checked, *out is NULL; f: the filtered forms (nullptr: every row)
+static int range_search_host(cmr_index* idx, const float* q, int nq, float min_score, int64_t max_total, cmr_range_result_t** out, const RangeFilter* f) {
+    int rc;
     const long long limit = max_total > 0 ? max_total : CMR_RANGE_MAX_TOTAL;
     SyncCall call(idx);
     if ((rc = range_rows_check(idx))) return rc;
+    if (f && !f->by_ids && (rc = words_check(idx, f->n_words))) return rc;
     std::unique_ptr<cmr_range_result> res(new cmr_range_result());
     res->nq = nq;
     res->lims = new int64_t[(size_t)nq + 1]();
@@ -2223,7 +2329,8 @@ int32_t cmr_index_range_search(cmr_index_t* idx, const float* q, int32_t nq, flo
     Workspace* const ws = call.ws;
     hipStream_t const s = call.s;
     const long long ld = (idx->n + 3) / 4 * 4;
-    const int blockq = range_block_queries(idx, nq, ld);
+    // (per-query id lists: a block is at most one group of masks)
+    const int blockq = f && f->by_ids && f->off ? std::min(range_block_queries(idx, nq, ld), kIdsGroup) : range_block_queries(idx, nq, ld);
     const int nblocks = (nq + blockq - 1) / blockq;
     const unsigned lo = cmr_range_bound_code(min_score);
     const long long cap_hits = idx->range_scratch_hits > 0 ? idx->range_scratch_hits : (1ll << 30) / 24;
@@ -2232,8 +2339,11 @@ int32_t cmr_index_range_search(cmr_index_t* idx, const float* q, int32_t nq, flo
     HIP_TRY(hipMemcpyAsync(ws->d_q.p, q, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, s));
     std::vector<int64_t> counts((size_t)nq);
     long long groups = 0;
+    RangeMasks mk;
+    const RangeMasks* const mkp = f ? &mk : nullptr;
+    if (f && (rc = range_masks_open(idx, ws, *f, nq, &mk))) { (void)hipStreamSynchronize(s); return rc; }
     auto count_block = [&](int q0, int nb) -> int {
-        int rc_ = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, nb, ld, lo, (long long*)ws->r_counts.p);
+        int rc_ = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, nb, ld, lo, (long long*)ws->r_counts.p, mkp, q0);
         if (!rc_) rc_ = range_counts_to_host(ws, nb, counts.data() + q0);
         return rc_;
     };
@@ -2250,17 +2360,18 @@ int32_t cmr_index_range_search(cmr_index_t* idx, const float* q, int32_t nq, flo
         for (int q0 = 0; q0 < nq; q0 += blockq) {
             const int nb = std::min(blockq, nq - q0);
             if (res->lims[q0 + nb] == res->lims[q0]) continue;          // no hit in the block
-            if (nblocks > 1) {      // the workspace holds the last block's scores: this block's again (same launches, same bits)
-                int rc_ = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, nb, ld, lo, (long long*)ws->r_counts.p);
+            if (nblocks > 1) {      // the workspace holds the last block's scores (and words): this block's again (same launches, same bits)
+                int rc_ = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, nb, ld, lo, (long long*)ws->r_counts.p, mkp, q0);
                 if (rc_) return rc_;
             }
+            const CmrRangeMask km = mkp ? mk.kernel(q0) : CmrRangeMask{};
             for (int g0 = 0; g0 < nb;) {      // groups of consecutive queries of at most cap_hits hits; a query is never split
                 int g1 = g0 + 1;
                 long long hits = counts[q0 + g0];
                 while (g1 < nb && hits + counts[q0 + g1] <= cap_hits) hits += counts[q0 + g1++];
                 if (hits) {
                     ++groups;
-                    int rc_ = range_group(idx, ws, ld, lo, g0, g1, hits, res->ids + res->lims[q0 + g0], res->scores + res->lims[q0 + g0]);
+                    int rc_ = range_group(idx, ws, ld, lo, g0, g1, hits, res->ids + res->lims[q0 + g0], res->scores + res->lims[q0 + g0], mkp ? &km : nullptr);
                     if (rc_) return rc_;
                 }
                 g0 = g1;
@@ -2276,6 +2387,70 @@ int32_t cmr_index_range_search(cmr_index_t* idx, const float* q, int32_t nq, flo
     idx->range_groups_last.store(groups, std::memory_order_relaxed);
     *out = res.release();
     return CMR_OK;
+}
+
+int32_t cmr_index_range_search(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t max_total, cmr_range_result_t** out) {
+    if (out) *out = nullptr;
+    const int rc = range_args_check(idx, q, out, nq, min_score);
+    return rc ? rc : range_search_host(idx, q, nq, min_score, max_total, out, nullptr);
+}
+
+// ---- filtered range search / count: the calls above among the rows an allow bitmap or id lists keep.  Every check that
+// needs no index comes first, the handle last (as cmr_index_search_ids).
+static int range_words_check(const void* idx, const void* q, const void* out, int nq, float min_score, const uint32_t* allow, int64_t n_words, int n_masks,
+                             RangeFilter* f) {
+    if (!q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = mask_words_args_check(allow, nq, n_words, n_masks);
+    if (rc) return rc;
+    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
+    f->words = allow; f->n_words = n_words; f->n_masks = n_masks;
+    return CMR_OK;
+}
+static int range_ids_check(const void* idx, const void* q, const void* out, int nq, float min_score, int mode, const int64_t* off, const int64_t* ids, int64_t n_ids) {
+    if (!q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
+    int rc = cmr_ids_args_check(mode, nq, 1, off, ids, n_ids);
+    if (rc) return rc;
+    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
+    return CMR_OK;
+}
+static RangeFilter range_ids_filter(int mode, const int64_t* off, const int64_t* ids, int64_t n_ids) {
+    RangeFilter f;
+    f.by_ids = true; f.mode = mode; f.off = off; f.ids = ids; f.n_ids = n_ids;
+    return f;
+}
+
+int32_t cmr_index_range_count_masked(cmr_index_t* idx, const float* q, int32_t nq, float min_score, const uint32_t* allow, int64_t n_words, int32_t n_masks,
+                                     int64_t* out_counts) {
+    RangeFilter f;
+    const int rc = range_words_check(idx, q, out_counts, nq, min_score, allow, n_words, n_masks, &f);
+    return rc ? rc : range_count_host(idx, q, nq, min_score, out_counts, &f);
+}
+
+int32_t cmr_index_range_count_ids(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
+                                  int64_t n_ids, int64_t* out_counts) {
+    const int rc = range_ids_check(idx, q, out_counts, nq, min_score, mode, id_offsets, ids, n_ids);
+    if (rc) return rc;
+    const RangeFilter f = range_ids_filter(mode, id_offsets, ids, n_ids);
+    return range_count_host(idx, q, nq, min_score, out_counts, &f);
+}
+
+int32_t cmr_index_range_search_masked(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t max_total, const uint32_t* allow, int64_t n_words,
+                                      int32_t n_masks, cmr_range_result_t** out) {
+    if (out) *out = nullptr;
+    RangeFilter f;
+    const int rc = range_words_check(idx, q, out, nq, min_score, allow, n_words, n_masks, &f);
+    return rc ? rc : range_search_host(idx, q, nq, min_score, max_total, out, &f);
+}
+
+int32_t cmr_index_range_search_ids(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t max_total, int32_t mode, const int64_t* id_offsets,
+                                   const int64_t* ids, int64_t n_ids, cmr_range_result_t** out) {
+    if (out) *out = nullptr;
+    const int rc = range_ids_check(idx, q, out, nq, min_score, mode, id_offsets, ids, n_ids);
+    if (rc) return rc;
+    const RangeFilter f = range_ids_filter(mode, id_offsets, ids, n_ids);
+    return range_search_host(idx, q, nq, min_score, max_total, out, &f);
 }
 
 int32_t cmr_range_result_view(const cmr_range_result_t* res, int32_t* nq, const int64_t** lims, const int64_t** ids, const float** scores) {

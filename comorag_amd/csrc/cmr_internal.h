@@ -54,10 +54,11 @@ int cmr_index_search_begin(cmr_index_t* idx, const float* q, int nq, int k, cons
 int cmr_index_search_finish(CmrPending* p, int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
 void cmr_index_search_abandon(CmrPending* p);
 // cmr_index_search_ids the same way: cmr_ids_args_check is every argument check that needs neither an index nor a device
-// (off_host: CSR offsets readable here, or NULL); `begin` takes checked arguments, the pending search ends in cmr_index_search_finish / _abandon
+// (off_host: CSR offsets readable here, or NULL); `begin` takes checked arguments, the pending search ends in cmr_index_search_finish / _abandon.
+// min_score (read during `begin` only): the filtered threshold search, entries below the bound come back as padding
 int cmr_ids_args_check(int mode, int nq, int k, const int64_t* off_host, const int64_t* ids, int64_t n_ids);
 int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, int mode, const int64_t* id_offsets, const int64_t* ids, int64_t n_ids,
-                               bool take_lock, CmrPending** out);
+                               bool take_lock, CmrPending** out, const float* min_score = nullptr);
 
 // the result of a range search (cmr_range_result_t): CSR lists in host arrays the library owns.  api.hip and multi.hip fill it.
 struct cmr_range_result {

@@ -163,11 +163,17 @@ hipError_t cmr_launch_sort_keys64(u64* key_a, u64* key_b, unsigned* val_a, unsig
 // compact: the hits of queries [q_first, q_first + nq_group) — `hits` of them by cnt — as (query in group << 32 | ~code, row), per query by
 //        ascending row, into key / val [hits].
 // finish: sorted pairs -> row + id_base and the score's bits gathered from the block, out_ids / out_scores [hits]
+// mask (filtered range search; nullptr: the unfiltered kernels): a hit also needs its allow bit — the masked variants of count
+//        and compact.  words: device, one uint32 per 32-row panel and mask, ceil(n / 32) words each (none beyond is read); query q of the
+//        block [nb] reads the mask at words + (q0 + q) * stride: stride 0 = one mask for every query, q0 = where in `words` the block's
+//        first query has its mask (the block's place in the call's batch, or 0 where the words were built for the block alone).
+struct CmrRangeMask { const unsigned* words; long long stride; long long q0; };
 unsigned cmr_range_bound_code(float min_score);
 size_t cmr_range_counter_bytes(long long n, int nb);
-hipError_t cmr_launch_range_count(const float* scores, long long ld, long long n, int nb, unsigned lo, unsigned* cnt, long long* counts, hipStream_t s);
+hipError_t cmr_launch_range_count(const float* scores, long long ld, long long n, int nb, unsigned lo, unsigned* cnt, long long* counts, hipStream_t s,
+                                  const CmrRangeMask* mask = nullptr);
 hipError_t cmr_launch_range_compact(const float* scores, long long ld, long long n, unsigned lo, const unsigned* offs, int q_first, int nq_group, long long hits,
-                                    u64* key, unsigned* val, hipStream_t s);
+                                    u64* key, unsigned* val, hipStream_t s, const CmrRangeMask* mask = nullptr);
 hipError_t cmr_launch_range_finish(const u64* key, const unsigned* val, long long hits, const float* scores, long long ld, int q_first, long long id_base,
                                    int64_t* out_ids, float* out_scores, hipStream_t s);
 // shard merge: ids/scores [S][nq][k] -> [nq][k]

@@ -768,6 +768,18 @@ int32_t cmr_mindex_search_ids(cmr_mindex_t* m, const float* q, int32_t nq, int32
                          out_ids, out_scores, out_min, out_max);
 }
 
+// ... and with a score bound: every shard pads below the bound, the merge of padded sorted lists is the padded merge
+int32_t cmr_mindex_search_min_score_ids(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, float min_score, int32_t mode, const int64_t* id_offsets,
+                                        const int64_t* ids, int64_t n_ids, int64_t* out_ids, float* out_scores) {
+    if (!q || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    const int rc = cmr_ids_args_check(mode, nq, k, id_offsets, ids, n_ids);
+    if (rc) return rc;
+    if (!(min_score == min_score)) return cmr_fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
+    return mindex_gather(m, nq, k, [&](int s, CmrPending** p) { return cmr_index_search_ids_begin(m->shard[s], q, nq, k, mode, id_offsets, ids, n_ids, false, p, &min_score); },
+                         out_ids, out_scores, nullptr, nullptr);
+}
+
 int32_t cmr_mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores, float* out_min,
                           float* out_max) {
     return mindex_search(m, q, nq, k, nullptr, out_ids, out_scores, out_min, out_max);
@@ -867,30 +879,58 @@ static int range_check(const void* m, const void* q, const void* out, int nq, fl
     return CMR_OK;
 }
 // counts [A][nq] of the active shards, all shards at once
-static int range_shard_counts(cmr_mindex* m, const std::vector<int>& act, const float* q, int nq, float min_score, std::vector<int64_t>& counts) {
+// the id lists of the filtered forms (nullptr: every row): GLOBAL ids — every shard gets the whole lists and keeps the ids it holds
+struct RangeIds { int mode; const int64_t* off; const int64_t* ids; int64_t n_ids; };
+static int range_ids_check(const void* m, const void* q, const void* out, int nq, float min_score, const RangeIds& f) {
+    if (!q || !out) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    const int rc = cmr_ids_args_check(f.mode, nq, 1, f.off, f.ids, f.n_ids);
+    if (rc) return rc;
+    if (!(min_score == min_score)) return cmr_fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
+    return CMR_OK;
+}
+static int shard_range_count(cmr_index_t* idx, const float* q, int nq, float min_score, const RangeIds* f, int64_t* counts) {
+    return f ? cmr_index_range_count_ids(idx, q, nq, min_score, f->mode, f->off, f->ids, f->n_ids, counts) : cmr_index_range_count(idx, q, nq, min_score, counts);
+}
+static int shard_range_search(cmr_index_t* idx, const float* q, int nq, float min_score, int64_t max_total, const RangeIds* f, cmr_range_result_t** out) {
+    return f ? cmr_index_range_search_ids(idx, q, nq, min_score, max_total, f->mode, f->off, f->ids, f->n_ids, out)
+             : cmr_index_range_search(idx, q, nq, min_score, max_total, out);
+}
+static int range_shard_counts(cmr_mindex* m, const std::vector<int>& act, const float* q, int nq, float min_score, const RangeIds* f, std::vector<int64_t>& counts) {
     counts.assign(act.size() * (size_t)nq, 0);
-    return for_active(m, act, true, [&](int a, int s) { return cmr_index_range_count(m->shard[s], q, nq, min_score, counts.data() + (size_t)a * nq); });
+    return for_active(m, act, true, [&](int a, int s) { return shard_range_count(m->shard[s], q, nq, min_score, f, counts.data() + (size_t)a * nq); });
 }
 
-int32_t cmr_mindex_range_count(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t* out_counts) {
-    int rc = range_check(m, q, out_counts, nq, min_score);
-    if (rc) return rc;
+// (arguments checked by the caller)
+static int32_t mindex_range_count(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, const RangeIds* f, int64_t* out_counts) {
+    int rc;
     std::shared_lock<std::shared_mutex> lk(m->mu);
     const std::vector<int> act = active_shards(m);
     std::fill(out_counts, out_counts + nq, (int64_t)0);
     if (act.empty()) return CMR_OK;
-    if (act.size() == 1) return cmr_index_range_count(m->shard[act[0]], q, nq, min_score, out_counts);
+    if (act.size() == 1) return shard_range_count(m->shard[act[0]], q, nq, min_score, f, out_counts);
     std::vector<int64_t> counts;
-    if ((rc = range_shard_counts(m, act, q, nq, min_score, counts))) return rc;
+    if ((rc = range_shard_counts(m, act, q, nq, min_score, f, counts))) return rc;
     for (size_t a = 0; a < act.size(); ++a)
         for (int i = 0; i < nq; ++i) out_counts[i] += counts[a * nq + i];
     return CMR_OK;
 }
 
-int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, cmr_range_result_t** out) {
-    if (out) *out = nullptr;
-    int rc = range_check(m, q, out, nq, min_score);
-    if (rc) return rc;
+int32_t cmr_mindex_range_count(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t* out_counts) {
+    const int rc = range_check(m, q, out_counts, nq, min_score);
+    return rc ? rc : mindex_range_count(m, q, nq, min_score, nullptr, out_counts);
+}
+
+int32_t cmr_mindex_range_count_ids(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
+                                   int64_t n_ids, int64_t* out_counts) {
+    const RangeIds f{mode, id_offsets, ids, n_ids};
+    const int rc = range_ids_check(m, q, out_counts, nq, min_score, f);
+    return rc ? rc : mindex_range_count(m, q, nq, min_score, &f, out_counts);
+}
+
+// (arguments checked by the caller, *out is NULL)
+static int32_t mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, const RangeIds* f, cmr_range_result_t** out) {
+    int rc;
     const long long limit = max_total > 0 ? max_total : CMR_RANGE_MAX_TOTAL;
     std::shared_lock<std::shared_mutex> lk(m->mu);
     const std::vector<int> act = active_shards(m);
@@ -902,11 +942,11 @@ int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, flo
         *out = res;
         return CMR_OK;
     }
-    if (A == 1) return cmr_index_range_search(m->shard[act[0]], q, nq, min_score, max_total, out);
+    if (A == 1) return shard_range_search(m->shard[act[0]], q, nq, min_score, max_total, f, out);
     // the limit is on the merged total: where the batch could exceed it, every shard counts before any shard compacts
     if ((double)nq * (double)m->total > (double)limit) {
         std::vector<int64_t> counts;
-        if ((rc = range_shard_counts(m, act, q, nq, min_score, counts))) return rc;
+        if ((rc = range_shard_counts(m, act, q, nq, min_score, f, counts))) return rc;
         long long total = 0;
         for (int64_t c : counts) total += c;
         if (total > limit)
@@ -915,7 +955,7 @@ int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, flo
     // every shard's search on its worker thread: it begins on all of them before it finishes on any
     std::vector<cmr_range_result_t*> part((size_t)A, nullptr);
     struct Free { std::vector<cmr_range_result_t*>& p; ~Free() { for (cmr_range_result_t* r : p) (void)cmr_range_result_destroy(r); } } free_parts{part};
-    rc = for_active(m, act, true, [&](int a, int s) { return cmr_index_range_search(m->shard[s], q, nq, min_score, limit, &part[a]); });
+    rc = for_active(m, act, true, [&](int a, int s) { return shard_range_search(m->shard[s], q, nq, min_score, limit, f, &part[a]); });
     if (rc) return rc;
     std::vector<const int64_t*> lims((size_t)A), ids((size_t)A);
     std::vector<const float*> sc((size_t)A);
@@ -930,6 +970,20 @@ int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, flo
     if (rc) { delete res; return rc; }
     *out = res;
     return CMR_OK;
+}
+
+int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, cmr_range_result_t** out) {
+    if (out) *out = nullptr;
+    const int rc = range_check(m, q, out, nq, min_score);
+    return rc ? rc : mindex_range_search(m, q, nq, min_score, max_total, nullptr, out);
+}
+
+int32_t cmr_mindex_range_search_ids(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, int32_t mode, const int64_t* id_offsets,
+                                    const int64_t* ids, int64_t n_ids, cmr_range_result_t** out) {
+    if (out) *out = nullptr;
+    const RangeIds f{mode, id_offsets, ids, n_ids};
+    const int rc = range_ids_check(m, q, out, nq, min_score, f);
+    return rc ? rc : mindex_range_search(m, q, nq, min_score, max_total, &f, out);
 }
 
 int32_t cmr_mindex_rescore(cmr_mindex_t* m, const float* q, int32_t nq, const int64_t* cand, int32_t n_cand, int32_t k, int64_t* out_ids,

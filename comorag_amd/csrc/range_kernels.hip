@@ -10,6 +10,9 @@
 //            from the block — never decoded from the key
 // The comparison is the threshold search's: the order-preserving code of the fp32 bits behind cmr_make_key's canonicalisation (v + 0.0f:
 // -0.0 and +0.0 are one value).  No floating-point operation beyond that.
+// Filtered range search (cmr_index_range_search_masked / _ids, _count_*): masked variants of count and compact — the same
+// bodies with MASKED set, where a hit also needs its bit in the query's allow words; offsets, sort and finish are shared.  The unmasked
+// kernels are the MASKED = false instantiations: no word is loaded, no branch is added.
 #include "../../include/comorag_hip.h"
 #include "cmr_kernels.h"
 
@@ -35,24 +38,45 @@ __device__ __forceinline__ unsigned range_flags(const float* __restrict__ row, s
     return f;
 }
 
+// filtered range search: the allow bits of the lane's four rows.  first % 4 == 0, so the four rows share one word of the
+// query's mask (one uint32 per 32-row panel): one load, the nibble at bit (first & 31).  first >= n loads nothing — first < n means
+// word first >> 5 < ceil(n / 32), the mask's length.
+__device__ __forceinline__ unsigned range_allow(const unsigned* __restrict__ words, size_t first, size_t n) {
+    return first < n ? (words[first >> 5] >> (unsigned)(first & 31)) & 0xFu : 0u;
+}
+
 // cnt[query][tile] = hits of the tile.  blockIdx.x = query * ntiles + tile
-__global__ __launch_bounds__(RANGE_T) void range_count_kernel(const float* __restrict__ scores, long long ld, size_t n, unsigned lo, unsigned ntiles,
-                                                              unsigned* __restrict__ cnt) {
+// MASKED: a hit also needs its allow bit.  words + (mq0 + query) * stride is the query's mask: stride 0 = one mask for every query; mq0 =
+// the index, in `words`, of the mask of the block's query 0 (a block starts anywhere in the call's batch: never derived from blockIdx)
+template <bool MASKED>
+__device__ __forceinline__ void range_count_body(const float* __restrict__ scores, long long ld, size_t n, unsigned lo, unsigned ntiles, unsigned* __restrict__ cnt,
+                                                 const unsigned* __restrict__ words, long long stride, unsigned mq0) {
     __shared__ unsigned wsum[RANGE_T / 64];
     const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned q = blockIdx.x / ntiles, tile = blockIdx.x % ntiles;
     const float* __restrict__ row = scores + (size_t)q * ld;
+    const unsigned* __restrict__ wq = MASKED ? words + (size_t)(mq0 + q) * (size_t)stride : nullptr;
     unsigned c = 0;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         unsigned code[4];
-        const unsigned f = range_flags(row, (size_t)tile * CMR_RANGE_TILE + h * RANGE_HALF + tid * 4, n, lo, code);
+        const size_t first = (size_t)tile * CMR_RANGE_TILE + h * RANGE_HALF + tid * 4;
+        unsigned f = range_flags(row, first, n, lo, code);
+        if constexpr (MASKED) f &= range_allow(wq, first, n);
 #pragma unroll
         for (int j = 0; j < 4; ++j) c += (unsigned)__popcll(__ballot((f >> j) & 1u));
     }
     if (lane == 0) wsum[wave] = c;
     __syncthreads();
     if (tid == 0) cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+__global__ __launch_bounds__(RANGE_T) void range_count_kernel(const float* __restrict__ scores, long long ld, size_t n, unsigned lo, unsigned ntiles,
+                                                              unsigned* __restrict__ cnt) {
+    range_count_body<false>(scores, ld, n, lo, ntiles, cnt, nullptr, 0, 0u);
+}
+__global__ __launch_bounds__(RANGE_T) void range_count_masked_kernel(const float* __restrict__ scores, long long ld, size_t n, unsigned lo, unsigned ntiles,
+                                                                     unsigned* __restrict__ cnt, const unsigned* __restrict__ words, long long stride, unsigned mq0) {
+    range_count_body<true>(scores, ld, n, lo, ntiles, cnt, words, stride, mq0);
 }
 
 // cnt[0, m) -> its exclusive prefix in place, cnt[m] = the total; counts[q] = hits of query q (m = nb * ntiles).  One workgroup.
@@ -87,18 +111,23 @@ __global__ __launch_bounds__(1024) void range_offsets_kernel(unsigned* __restric
 
 // the hits of queries [q_first, q_first + group queries) of the block, compacted: blockIdx.x = (query - q_first) * ntiles + tile.
 // cap = the group's hits (offs[(q_first + queries) * ntiles] - offs[q_first * ntiles]): no store at or beyond it.
-__global__ __launch_bounds__(RANGE_T) void range_compact_kernel(const float* __restrict__ scores, long long ld, size_t n, unsigned lo, unsigned ntiles,
-                                                                const unsigned* __restrict__ offs, unsigned q_first, unsigned cap,
-                                                                u64* __restrict__ key, unsigned* __restrict__ val) {
+// MASKED: the count kernel's words, stride and mq0 — query q of the block (q_first + the group's) reads the mask at index mq0 + q
+template <bool MASKED>
+__device__ __forceinline__ void range_compact_body(const float* __restrict__ scores, long long ld, size_t n, unsigned lo, unsigned ntiles,
+                                                   const unsigned* __restrict__ offs, unsigned q_first, unsigned cap, u64* __restrict__ key,
+                                                   unsigned* __restrict__ val, const unsigned* __restrict__ words, long long stride, unsigned mq0) {
     __shared__ unsigned wcnt[2][RANGE_T / 64];
     const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned qg = blockIdx.x / ntiles, tile = blockIdx.x % ntiles, q = q_first + qg;
     const float* __restrict__ row = scores + (size_t)q * ld;
+    const unsigned* __restrict__ wq = MASKED ? words + (size_t)(mq0 + q) * (size_t)stride : nullptr;
     const u64 lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     unsigned code[2][4], f[2], before[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        f[h] = range_flags(row, (size_t)tile * CMR_RANGE_TILE + h * RANGE_HALF + tid * 4, n, lo, code[h]);
+        const size_t first = (size_t)tile * CMR_RANGE_TILE + h * RANGE_HALF + tid * 4;
+        f[h] = range_flags(row, first, n, lo, code[h]);
+        if constexpr (MASKED) f[h] &= range_allow(wq, first, n);
         unsigned b = 0, tot = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -128,6 +157,16 @@ __global__ __launch_bounds__(RANGE_T) void range_compact_kernel(const float* __r
         for (int w = 0; w < RANGE_T / 64; ++w) pos += wcnt[h][w];
     }
 }
+__global__ __launch_bounds__(RANGE_T) void range_compact_kernel(const float* __restrict__ scores, long long ld, size_t n, unsigned lo, unsigned ntiles,
+                                                                const unsigned* __restrict__ offs, unsigned q_first, unsigned cap,
+                                                                u64* __restrict__ key, unsigned* __restrict__ val) {
+    range_compact_body<false>(scores, ld, n, lo, ntiles, offs, q_first, cap, key, val, nullptr, 0, 0u);
+}
+__global__ __launch_bounds__(RANGE_T) void range_compact_masked_kernel(const float* __restrict__ scores, long long ld, size_t n, unsigned lo, unsigned ntiles,
+                                                                       const unsigned* __restrict__ offs, unsigned q_first, unsigned cap, u64* __restrict__ key,
+                                                                       unsigned* __restrict__ val, const unsigned* __restrict__ words, long long stride, unsigned mq0) {
+    range_compact_body<true>(scores, ld, n, lo, ntiles, offs, q_first, cap, key, val, words, stride, mq0);
+}
 
 // sorted pair i of the group: its row (+ id_base) and the bits of its score, gathered from the block
 __global__ __launch_bounds__(RANGE_T) void range_finish_kernel(const u64* __restrict__ key, const unsigned* __restrict__ val, unsigned hits, const float* __restrict__ scores,
@@ -153,24 +192,35 @@ unsigned cmr_range_bound_code(float min_score) {
 
 size_t cmr_range_counter_bytes(long long n, int nb) { return ((size_t)nb * range_tiles(n) + 1) * sizeof(unsigned); }
 
-hipError_t cmr_launch_range_count(const float* scores, long long ld, long long n, int nb, unsigned lo, unsigned* cnt, long long* counts, hipStream_t s) {
+hipError_t cmr_launch_range_count(const float* scores, long long ld, long long n, int nb, unsigned lo, unsigned* cnt, long long* counts, hipStream_t s,
+                                  const CmrRangeMask* mask) {
     if (n <= 0 || nb <= 0) return hipSuccess;
     if (n >= (1ll << 32) || (ld & 3)) return hipErrorInvalidValue;
+    if (mask && (!mask->words || mask->stride < 0 || mask->q0 < 0)) return hipErrorInvalidValue;
     const unsigned ntiles = range_tiles(n);
     const unsigned long long m = (unsigned long long)nb * ntiles;
     if (m >= (1ull << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)m), dim3(RANGE_T), 0, s, scores, ld, (size_t)n, lo, ntiles, cnt);
+    if (mask)
+        hipLaunchKernelGGL(range_count_masked_kernel, dim3((unsigned)m), dim3(RANGE_T), 0, s, scores, ld, (size_t)n, lo, ntiles, cnt, mask->words, mask->stride,
+                           (unsigned)mask->q0);
+    else
+        hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)m), dim3(RANGE_T), 0, s, scores, ld, (size_t)n, lo, ntiles, cnt);
     hipLaunchKernelGGL(range_offsets_kernel, dim3(1), dim3(1024), 0, s, cnt, (unsigned)m, ntiles, (unsigned)nb, counts);
     return hipGetLastError();
 }
 
 hipError_t cmr_launch_range_compact(const float* scores, long long ld, long long n, unsigned lo, const unsigned* offs, int q_first, int nq_group, long long hits,
-                                    u64* key, unsigned* val, hipStream_t s) {
+                                    u64* key, unsigned* val, hipStream_t s, const CmrRangeMask* mask) {
     if (hits <= 0 || nq_group <= 0) return hipSuccess;
     if (n >= (1ll << 32) || hits >= (1ll << 32) || (ld & 3)) return hipErrorInvalidValue;
+    if (mask && (!mask->words || mask->stride < 0 || mask->q0 < 0)) return hipErrorInvalidValue;
     const unsigned ntiles = range_tiles(n);
-    hipLaunchKernelGGL(range_compact_kernel, dim3((unsigned)nq_group * ntiles), dim3(RANGE_T), 0, s, scores, ld, (size_t)n, lo, ntiles, offs, (unsigned)q_first,
-                       (unsigned)hits, key, val);
+    if (mask)
+        hipLaunchKernelGGL(range_compact_masked_kernel, dim3((unsigned)nq_group * ntiles), dim3(RANGE_T), 0, s, scores, ld, (size_t)n, lo, ntiles, offs,
+                           (unsigned)q_first, (unsigned)hits, key, val, mask->words, mask->stride, (unsigned)mask->q0);
+    else
+        hipLaunchKernelGGL(range_compact_kernel, dim3((unsigned)nq_group * ntiles), dim3(RANGE_T), 0, s, scores, ld, (size_t)n, lo, ntiles, offs, (unsigned)q_first,
+                           (unsigned)hits, key, val);
     return hipGetLastError();
 }
 

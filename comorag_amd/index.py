@@ -157,7 +157,8 @@ def renumber_after_removal(ids, removed) -> np.ndarray:
 
 # the calls whose host-array marshalling `DenseIndex` (cmr_index_*) and `MultiDeviceIndex` (cmr_mindex_*) share
 _HOST_CALLS = ("destroy", "size", "info", "append", "search", "search_exact", "search_min_score", "scores", "sorted_scores",
-               "rescore", "get_rows", "search_ids", "remove_ids", "update_rows", "range_count", "range_search")
+               "rescore", "get_rows", "search_ids", "remove_ids", "update_rows", "range_count", "range_search", "search_min_score_ids",
+               "range_count_ids", "range_search_ids")
 _bound = {}
 
 
@@ -323,6 +324,11 @@ class HostArrayIndex:
         nq = q.shape[0]
         res = C.c_void_p()
         L.check(self._c.range_search(self._h, _ptr(q), nq, float(min_score), int(max_total) if max_total is not None else 0, C.byref(res)))
+        return self._range_lists(res, nq)
+
+    @staticmethod
+    def _range_lists(res, nq: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """numpy copies of a cmr_range_result_t, which is destroyed"""
         try:
             n, lims_p, ids_p, sc_p = C.c_int32(0), C.c_void_p(), C.c_void_p(), C.c_void_p()
             L.check(L.lib().cmr_range_result_view(res, C.byref(n), C.byref(lims_p), C.byref(ids_p), C.byref(sc_p)))
@@ -343,6 +349,46 @@ class HostArrayIndex:
         q = self._queries(q)
         out = np.empty(q.shape[0], dtype=np.int64)
         L.check(self._c.range_count(self._h, _ptr(q), q.shape[0], float(min_score), _ptr(out)))
+        return out
+
+    # -- the score-bound searches among the rows id lists leave (cmr_index_*_ids / cmr_mindex_*_ids)
+    def _id_list_args(self, q, allow, exclude):
+        """→ (q [nq, dim], nq, (mode, offsets pointer | None, ids pointer | None, n_ids), the arrays behind the pointers)"""
+        offsets, lst = pack_id_lists(allow=allow, exclude=exclude)
+        q = self._queries(q)
+        nq = q.shape[0]
+        if offsets is not None and len(offsets) != nq + 1:
+            raise ValueError(f"{len(offsets) - 1} id lists for {nq} queries")
+        return q, nq, (L.CMR_IDS_ALLOW if allow is not None else L.CMR_IDS_EXCLUDE, _ptr(offsets) if offsets is not None else None,
+                       _ptr(lst) if len(lst) else None, len(lst)), (offsets, lst)
+
+    def search_min_score_filtered_ids(self, q, k: int, min_score: float, *, allow=None, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`search_min_score` among the rows the id lists leave (lists as `search_filtered_ids` takes them): row i of
+        `search_filtered_ids(q, k, ...)` with every entry whose score is below the bound replaced by -1 / -inf padding, bit for bit.
+        → (ids [nq,k], scores [nq,k]); k <= 128."""
+        q, nq, lists, _keep = self._id_list_args(q, allow, exclude)
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        L.check(self._c.search_min_score_ids(self._h, _ptr(q), nq, k, float(min_score), *lists, _ptr(ids), _ptr(sc)))
+        return ids, sc
+
+    def range_search_filtered_ids(self, q, min_score: float, *, allow=None, exclude=None, max_total: Optional[int] = None
+                                  ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`range_search` among the rows the id lists leave: list i is list i of `range_search` with the entries of disallowed rows
+        removed, bit for bit (order, ids, score words) — every row of a namespace at or above a similarity, or tri_retrieve's neighbours
+        down to a bound with the question's pool kept out.  Lists as `search_filtered_ids` takes them (ids as the searches return them;
+        `MultiDeviceIndex`: global ids; -1 padding is ignored).  -inf: the complete ranking of the allowed rows.  `max_total` is judged on
+        the filtered total.  A query that allows nothing gets an empty list.  → (lims [nq + 1], ids, scores)."""
+        q, nq, lists, _keep = self._id_list_args(q, allow, exclude)
+        res = C.c_void_p()
+        L.check(self._c.range_search_ids(self._h, _ptr(q), nq, float(min_score), int(max_total) if max_total is not None else 0, *lists, C.byref(res)))
+        return self._range_lists(res, nq)
+
+    def range_count_filtered_ids(self, q, min_score: float, *, allow=None, exclude=None) -> np.ndarray:
+        """`np.diff(lims)` of `range_search_filtered_ids` without the lists and without its limit: int64 [nq]."""
+        q, nq, lists, _keep = self._id_list_args(q, allow, exclude)
+        out = np.empty(nq, dtype=np.int64)
+        L.check(self._c.range_count_ids(self._h, _ptr(q), nq, float(min_score), *lists, _ptr(out)))
         return out
 
     # -- exact fp32 top-k (a 16-bit index created with keep_f32=True; an f32 index is exact already)
@@ -570,6 +616,54 @@ class DenseIndex(HostArrayIndex):
                                                 _ptr(mn) if with_minmax else None, _ptr(mx) if with_minmax else None))
         kk = min(k, _mask_popcount(mask, n))
         return ids[:, :kk], sc[:, :kk], mn, mx
+
+    # -- the score-bound searches among the rows allow bitmaps keep (cmr_index_search_min_score_masked, cmr_index_range_*_masked)
+    def _mask_words_args(self, q, masks, allow, exclude):
+        """→ (q [nq, dim], nq, masks uint32 [n_words] (shared) or [nq, n_words] (per query))"""
+        n = len(self)
+        q = self._queries(q)
+        nq = q.shape[0]
+        if masks is None:
+            masks = pack_row_mask(n, allow=allow, exclude=exclude)
+        elif allow is not None or exclude is not None:
+            raise ValueError("give masks or allow / exclude, not both")
+        masks = np.ascontiguousarray(masks, dtype=np.uint32)
+        nw = (n + 31) // 32
+        if masks.shape != (nw,) and masks.shape != (nq, nw):
+            raise ValueError(f"masks must be uint32 [{nw}] (shared) or [{nq}, {nw}] (one row of pack_row_mask words per query), got {masks.shape}")
+        return q, nq, masks
+
+    def search_min_score_filtered(self, q, k: int, min_score: float, masks=None, *, allow=None, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`search_min_score` among the allowed LOCAL rows: row i of `search_filtered` (shared `masks` [n_words], or `allow` / `exclude` as
+        `pack_row_mask` takes them) or `search_filtered_each` (`masks` [nq, n_words] as `pack_row_masks` lays them out) with every entry
+        whose score is below the bound replaced by -1 / -inf padding, bit for bit.  → (ids [nq,k], scores [nq,k]); k <= 128."""
+        q, nq, masks = self._mask_words_args(q, masks, allow, exclude)
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        L.check(L.lib().cmr_index_search_min_score_masked(self._h, _ptr(q), nq, k, float(min_score), _ptr(masks), masks.shape[-1],
+                                                          1 if masks.ndim == 1 else nq, _ptr(ids), _ptr(sc)))
+        return ids, sc
+
+    def range_search_filtered(self, q, min_score: float, masks=None, *, allow=None, exclude=None, max_total: Optional[int] = None
+                              ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`range_search` among the allowed LOCAL rows: list i is list i of `range_search` with the entries of disallowed rows removed, bit
+        for bit — every row of one namespace or level at or above a similarity; with -inf the complete ranking of the namespace.  `masks`:
+        uint32 [n_words] (one mask for every query) or [nq, n_words] (per query, `pack_row_masks`), or give `allow` / `exclude` as
+        `pack_row_mask` takes them (shared).  `max_total` is judged on the filtered total; a query that allows nothing gets an empty list.
+        → (lims [nq + 1], ids, scores) as `range_search`."""
+        q, nq, masks = self._mask_words_args(q, masks, allow, exclude)
+        res = C.c_void_p()
+        L.check(L.lib().cmr_index_range_search_masked(self._h, _ptr(q), nq, float(min_score), int(max_total) if max_total is not None else 0,
+                                                      _ptr(masks), masks.shape[-1], 1 if masks.ndim == 1 else nq, C.byref(res)))
+        return self._range_lists(res, nq)
+
+    def range_count_filtered(self, q, min_score: float, masks=None, *, allow=None, exclude=None) -> np.ndarray:
+        """`np.diff(lims)` of `range_search_filtered` without the lists and without its limit: int64 [nq]."""
+        q, nq, masks = self._mask_words_args(q, masks, allow, exclude)
+        out = np.empty(nq, dtype=np.int64)
+        L.check(L.lib().cmr_index_range_count_masked(self._h, _ptr(q), nq, float(min_score), _ptr(masks), masks.shape[-1],
+                                                     1 if masks.ndim == 1 else nq, _ptr(out)))
+        return out
 
     def search_filtered_dev(self, q_t, k: int, mask_t, out_ids=None, out_scores=None, out_min=None, out_max=None,
                             stream: Optional[int] = None):

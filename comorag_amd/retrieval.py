@@ -144,11 +144,17 @@ def get_similar_summaries(query: str, level_store, embedding_model, top_k: int =
     return [level_texts[i] for i in sorted_indices], sorted_scores.tolist()
 
 
-def neighbours_within(index, query_embeddings, min_score: float) -> List[Tuple[np.ndarray, np.ndarray]]:
+def neighbours_within(index, query_embeddings, min_score: float, *, allow_ids=None, exclude_ids=None) -> List[Tuple[np.ndarray, np.ndarray]]:
     """Every row of `index` (a `DenseIndex` or a `MultiDeviceIndex`) with raw score >= min_score, per query: a list of (ids int64, scores
     fp32), best first (ties: lower row id first) — the neighbours ComoRAG.add_synonymy_edges reads down to synonymy_edge_sim_threshold
-    (ComoRAG.py:670-712), however many there are.  One range search (cmr_index_range_search)."""
-    lims, ids, sc = index.range_search(_as_query(query_embeddings), min_score)
+    (ComoRAG.py:670-712), however many there are.  One range search (cmr_index_range_search).
+    `allow_ids` / `exclude_ids` (at most one; lists as `search_filtered_ids` takes them, ids as the searches return them): only the listed
+    rows / every row but the listed ones — one filtered range search (cmr_index_range_search_ids): the lists above without the entries of
+    the disallowed rows."""
+    if allow_ids is not None or exclude_ids is not None:
+        lims, ids, sc = index.range_search_filtered_ids(_as_query(query_embeddings), min_score, allow=allow_ids, exclude=exclude_ids)
+    else:
+        lims, ids, sc = index.range_search(_as_query(query_embeddings), min_score)
     return [(ids[lims[i]:lims[i + 1]], sc[lims[i]:lims[i + 1]]) for i in range(len(lims) - 1)]
 
 

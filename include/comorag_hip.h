@@ -189,8 +189,9 @@ int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_f32_dev, in
  * tile and loads that query's word of the panel; sampling passes read the same words, so each query's threshold is a bound among ITS
  * allowed rows.  last_route: CMR_ROUTE_CHAIN | CMR_ROUTE_FILTERED | CMR_ROUTE_FILTERED_EACH.
  * The host form uploads all nq blocks into scratch of its own call; the _dev form reads the caller's device words in place.
- * Not filtered, as before: the pipelined, exact, sorted, threshold and all-scores calls, PageRank; of cmr_mindex_* only
- * cmr_mindex_search_ids (below) filters.                                                                                           */
+ * Filtered besides the top-k calls: the threshold search, the range search and the range count ("filtered score-bound searches" below, host
+ * forms).  Not filtered: the pipelined, exact, sorted and all-scores calls, the _dev forms of the score-bound searches, PageRank; of
+ * cmr_mindex_* only the _ids calls filter.                                                                                            */
 int32_t cmr_index_search_masked_each(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k,
                                      const uint32_t* allow_words, int64_t n_words,
                                      int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
@@ -472,6 +473,55 @@ int32_t cmr_range_result_destroy(cmr_range_result_t* res);      /* NULL is a no-
 int32_t cmr_range_merge(int32_t n_shards, int32_t nq, const int64_t* const* lims, const int64_t* const* ids, const float* const* scores,
                         int64_t* out_lims, int64_t* out_ids, float* out_scores);
 
+/* ---- filtered score-bound searches ------------------------------------------
+ * The threshold search, the range search and the range count among the rows a filter keeps: every row of ONE namespace or level at or
+ * above a similarity (get_similar_summaries over the level stores, utils/embed_utils.py:152-158; a serving index with several
+ * namespaces), and tri_retrieve's searches that keep the question's memory pool out (ComoRAG.py:499-505, 515-522, 535-540) with the
+ * synonymy join's score bound (ComoRAG.add_synonymy_edges, ComoRAG.py:670-712).  Host forms only.
+ *   allow_words  exactly cmr_index_search_masked's bitmap: one uint32 per 32-row panel over the LOCAL rows, n_words == ceil(size / 32), bits
+ *                at or beyond size ignored.  n_masks == 1: [n_words], one mask for every query; n_masks == nq: [nq][n_words], query i's
+ *                words at allow_words + i * n_words.  Any other n_masks: CMR_ERR_INVALID.
+ *   mode, id_offsets, ids, n_ids   exactly cmr_index_search_ids's lists: ids as the searches return them (id base / block table applied;
+ *                cmr_mindex_*: global ids); negative ids, ids not held and duplicates are ignored; id_offsets == NULL: one shared list,
+ *                otherwise CSR with nq + 1 offsets.
+ * Range search / count: list i is list i of cmr_index_range_search on the same index with the entries of disallowed rows removed, bit for
+ *   bit — order, ids, fp32 score words; the comparison with the bound is that call's (a row that attains it is in, -0.0 and +0.0 one
+ *   value, NaN: CMR_ERR_INVALID); +inf: empty lists; -inf: every ALLOWED row, the complete ranking of a namespace.  out_counts[i] is the
+ *   length of list i.  max_total is judged on the FILTERED total: above it CMR_ERR_UNSUPPORTED with that total in the message, *out = NULL,
+ *   nothing compacted, sorted or allocated.  A query that allows nothing: an empty list, count 0, CMR_OK, its neighbours undisturbed.
+ * Threshold search: row i is row i of cmr_index_search_masked / _masked_each / _ids with the same k and filter, every entry whose score is
+ *   below the bound replaced by -1 / -inf padding, bit for bit.  k <= CMR_MAX_K (above: CMR_ERR_UNSUPPORTED); no min / max output, as
+ *   cmr_index_search_min_score.
+ * CMR_ERR_INVALID before any device call: a NULL handle, query or output; NULL words; n_words != ceil(size / 32); n_masks not 1 or nq; nq
+ * or k <= 0; a NaN bound; a mode other than 0 / 1; NULL ids with n_ids > 0, n_ids < 0; id_offsets[0] != 0, decreasing offsets,
+ * id_offsets[nq] != n_ids — every check but n_words before the handle is looked at.  Non-finite queries: as the unfiltered calls.
+ * How: the range pipeline of cmr_index_range_search with masked variants of its count and compaction kernels — a hit is a row whose code is
+ *   at or above the bound AND whose allow bit is set; a lane's four consecutive rows share one word of the query's mask, so it is one
+ *   word load per lane and never a word at or beyond n_words; ranks still come from the ballots; offsets, sort and gather are the
+ *   unfiltered call's.  The threshold search is the narrow masked chain of cmr_index_search_masked with the bound as every query's first
+ *   threshold (no sampling passes).  The words live in the call's own workspace; the id forms build them there with the launches of
+ *   cmr_index_row_masks_dev, never more than 64 queries' worth: per-query id lists run in blocks of at most 64 queries (which caps
+ *   "range_block_queries" there).  Results never depend on the blocks or groups.  Never combined, never the int8 pre-filter, the
+ *   single-launch paths or the finishing stage; nothing any other call returns changes.
+ * last_route: CMR_ROUTE_RANGE, or CMR_ROUTE_CHAIN with the threshold bit, plus CMR_ROUTE_FILTERED, plus CMR_ROUTE_FILTERED_EACH where every
+ *   query has words or a list of its own (n_masks > 1, id_offsets != NULL), plus CMR_ROUTE_FILTERED_IDS in the id forms.
+ * cmr_mindex_*_ids (further down): every non-empty shard gets the whole lists and keeps the ids it holds, the work begins on every shard
+ *   before it finishes on any, the host merges as the unfiltered calls do (cmr_range_merge / the top-k merge) — the result of one index
+ *   holding the same rows, bit for bit; max_total is judged on the sum over the shards before any shard compacts.                        */
+int32_t cmr_index_search_min_score_masked(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k, float min_score,
+                                          const uint32_t* allow_words, int64_t n_words, int32_t n_masks /* 1 | nq */, int64_t* out_ids,
+                                          float* out_scores);
+int32_t cmr_index_search_min_score_ids(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k, float min_score, int32_t mode,
+                                       const int64_t* id_offsets, const int64_t* ids, int64_t n_ids, int64_t* out_ids, float* out_scores);
+int32_t cmr_index_range_count_masked(cmr_index_t* idx, const float* q_f32, int32_t nq, float min_score, const uint32_t* allow_words,
+                                     int64_t n_words, int32_t n_masks /* 1 | nq */, int64_t* out_counts /*[nq]*/);
+int32_t cmr_index_range_count_ids(cmr_index_t* idx, const float* q_f32, int32_t nq, float min_score, int32_t mode, const int64_t* id_offsets,
+                                  const int64_t* ids, int64_t n_ids, int64_t* out_counts /*[nq]*/);
+int32_t cmr_index_range_search_masked(cmr_index_t* idx, const float* q_f32, int32_t nq, float min_score, int64_t max_total,
+                                      const uint32_t* allow_words, int64_t n_words, int32_t n_masks /* 1 | nq */, cmr_range_result_t** out);
+int32_t cmr_index_range_search_ids(cmr_index_t* idx, const float* q_f32, int32_t nq, float min_score, int64_t max_total, int32_t mode,
+                                   const int64_t* id_offsets, const int64_t* ids, int64_t n_ids, cmr_range_result_t** out);
+
 /* Exact fp32 re-score of candidate rows (BASELINE config 5 "cross-scores on top-100").  The
  * reference's rerank.py is an LLM filter with no numeric scoring (rerank.py:100-123); this is
  * the numeric stage the engine adds behind the same (indices, items, {'confidence'}) shape.
@@ -677,6 +727,16 @@ int32_t cmr_mindex_sorted_scores(cmr_mindex_t* m, const float* q_f32, int32_t nq
 int32_t cmr_mindex_range_count(cmr_mindex_t* m, const float* q_f32, int32_t nq, float min_score, int64_t* out_counts /*[nq]*/);
 int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q_f32, int32_t nq, float min_score, int64_t max_total,
                                 cmr_range_result_t** out);
+/* The filtered score-bound searches from GLOBAL row ids ("filtered score-bound searches" above has the semantics): the
+ * result of ONE cmr_index_t holding the same rows, bit for bit.                                                                        */
+int32_t cmr_mindex_search_min_score_ids(cmr_mindex_t* m, const float* q_f32, int32_t nq, int32_t k, float min_score, int32_t mode,
+                                        const int64_t* id_offsets, const int64_t* ids /* GLOBAL row ids */, int64_t n_ids, int64_t* out_ids,
+                                        float* out_scores);
+int32_t cmr_mindex_range_count_ids(cmr_mindex_t* m, const float* q_f32, int32_t nq, float min_score, int32_t mode, const int64_t* id_offsets,
+                                   const int64_t* ids /* GLOBAL row ids */, int64_t n_ids, int64_t* out_counts /*[nq]*/);
+int32_t cmr_mindex_range_search_ids(cmr_mindex_t* m, const float* q_f32, int32_t nq, float min_score, int64_t max_total, int32_t mode,
+                                    const int64_t* id_offsets, const int64_t* ids /* GLOBAL row ids */, int64_t n_ids,
+                                    cmr_range_result_t** out);
 int32_t cmr_mindex_rescore(cmr_mindex_t* m, const float* q_f32, int32_t nq, const int64_t* cand, int32_t n_cand, int32_t k,
                            int64_t* out_ids, float* out_scores);
 int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, float* out);
