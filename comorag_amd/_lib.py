@@ -27,6 +27,7 @@ CMR_PPR_RANK_TILE = 2048  # keys per workgroup of the ranked calls' radix sort
 CMR_RANGE_TILE = 2048     # rows per workgroup of the range search's count / compaction
 CMR_RANGE_MAX_TOTAL = 2**31 - 1   # cmr_index_range_search: hits per call unless max_total says otherwise
 CMR_ROUTE_RANGE = 11      # "last_route" & 0xF of a range search / count
+CMR_ROUTE_MMR = 1 << 15   # "last_route" bit of cmr_index_search_mmr*
 CMR_ENCODER_ROWS_MAX = 2048  # cmr_encoder_linear_rows*: 16 questions x 128 token rows
 DTYPES = {"f32": CMR_F32, "fp32": CMR_F32, "float32": CMR_F32, "bf16": CMR_BF16, "bfloat16": CMR_BF16,
           "f16": CMR_F16, "fp16": CMR_F16, "float16": CMR_F16}
@@ -99,6 +100,12 @@ SIGNATURES = {
     "cmr_index_search_exact_pipelined": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _P(_p)]),
     "cmr_index_round_stats": (_i32, [_p, _P(_f32), _P(_f32)]),
     "cmr_index_prefilter_stats": (_i32, [_p, _P(_f32), _P(_f32)]),
+    "cmr_mmr_select": (_i32, [_p, _p, _p, _i32, _i32, _i32, _f64, _p, _p]),
+    "cmr_index_pair_scores": (_i32, [_p, _p, _i32, _i32, _p]),
+    "cmr_index_mmr_select": (_i32, [_p, _p, _p, _i32, _i32, _i32, _f64, _p, _p]),
+    "cmr_index_mmr_select_dev": (_i32, [_p, _p, _p, _i32, _i32, _i32, _f64, _p, _p, _p]),
+    "cmr_index_search_mmr": (_i32, [_p, _p, _i32, _i32, _i32, _f64, _p, _p]),
+    "cmr_index_search_mmr_dev": (_i32, [_p, _p, _i32, _i32, _i32, _f64, _p, _p, _p]),
     "cmr_merge_topk": (_i32, [_p, _p, _i32, _i32, _i32, _p, _p]),
     "cmr_merge_topk_dev": (_i32, [_i32, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
     "cmr_graph_create": (_i32, [_i32, _i64, _i64, _p, _p, _p, _P(_p)]),
@@ -138,6 +145,9 @@ SIGNATURES = {
     "cmr_mindex_range_search_ids": (_i32, [_p, _p, _i32, _f32, _i64, _i32, _p, _p, _i64, _P(_p)]),
     "cmr_mindex_rescore": (_i32, [_p, _p, _i32, _p, _i32, _i32, _p, _p]),
     "cmr_mindex_get_rows": (_i32, [_p, _p, _i64, _p]),
+    "cmr_mindex_pair_scores": (_i32, [_p, _p, _i32, _i32, _p]),
+    "cmr_mindex_mmr_select": (_i32, [_p, _p, _p, _i32, _i32, _i32, _f64, _p, _p]),
+    "cmr_mindex_search_mmr": (_i32, [_p, _p, _i32, _i32, _i32, _f64, _p, _p]),
     "cmr_mindex_search_exact": (_i32, [_p, _p, _i32, _i32, _p, _p, _p]),
     "cmr_mindex_search_pipelined": (_i32, [_p, _p, _i32, _i32, _P(_p)]),
     "cmr_mindex_collect": (_i32, [_p, _p, _p, _p, _p, _p]),

@@ -8,7 +8,7 @@ Steps
     a variant whose ring registers are touched by compiler-generated code (after their first
     asm load) is marked unsafe
     and the library falls back to the compiler-counted ring for it → ring_audit.cpp
- 3. hipcc -c every other file of SOURCES (aux_kernels.hip, compact_kernels.hip, sort_kernels.hip, range_kernels.hip, prefilter_kernels.hip, api.hip, comm.hip, ppr.hip, encoder_kernels.hip, multi.hip) and
+ 3. hipcc -c every other file of SOURCES (aux_kernels.hip, compact_kernels.hip, sort_kernels.hip, range_kernels.hip, prefilter_kernels.hip, mmr_kernels.hip, api.hip, comm.hip, ppr.hip, encoder_kernels.hip, multi.hip) and
     ring_audit.cpp ; link → comorag_amd/lib/libcomorag_hip.so
 SOURCES and HEADERS also feed the build stamp: a file the library is built from and that is missing there would let a stale
 library pass for fresh.
@@ -39,8 +39,8 @@ if os.environ.get("CMR_BUILD_LIB"):          # experiment builds go to their own
 # completely — every register index is a constant only then; with the slow path inlined at two places of it, its
 # unrolled size exceeds LLVM's default limit for "#pragma unroll" (16 K) and hipcc silently keeps the loops.
 SCAN_FLAGS = ["-mllvm", "-pragma-unroll-threshold=1048576"]
-SOURCES = ["scan_kernels.hip", "aux_kernels.hip", "compact_kernels.hip", "sort_kernels.hip", "range_kernels.hip", "prefilter_kernels.hip", "api.hip", "comm.hip", "ppr.hip", "encoder_kernels.hip", "multi.hip"]
-HEADERS = ["cmr_device.h", "cmr_kernels.h", "cmr_internal.h", "combine.h", "cmr_select.h", "cmr_topk.h", "index_state.h", "search_plan.h", "prefilter_host.h", os.path.join("..", "..", "include", "comorag_hip.h")]
+SOURCES = ["scan_kernels.hip", "aux_kernels.hip", "compact_kernels.hip", "sort_kernels.hip", "range_kernels.hip", "prefilter_kernels.hip", "mmr_kernels.hip", "api.hip", "comm.hip", "ppr.hip", "encoder_kernels.hip", "multi.hip"]
+HEADERS = ["cmr_device.h", "cmr_kernels.h", "cmr_internal.h", "combine.h", "cmr_select.h", "cmr_topk.h", "index_state.h", "search_plan.h", "prefilter_host.h", "mmr_select.h", os.path.join("..", "..", "include", "comorag_hip.h")]
 
 _KERNEL_RE = re.compile(r"^_Z11scan_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEv5ScanP:")
 

@@ -87,6 +87,12 @@ int cmr_index_scores_to_device_batch(cmr_index_t* idx, const float* q_host, int 
 int cmr_index_scores_release(cmr_index_t* idx);
 long long cmr_index_row_count(cmr_index_t* idx);      // (no device call)
 
+// for multi.hip (cmr_mindex_pair_scores): the pair scores of candidate rows this shard may not hold.  rows [nq * T * 32, dim]
+// fp32 on the host, T = ceil(F / 32): query i's candidate rows at rows + i * T * 32 * dim, zero rows behind the F-th; they are packed as
+// queries and scored against the candidates of ids [nq, F] (global) that this shard holds: out[i][s][c] is finite where the shard holds
+// position c (and no earlier position repeats its id), -inf elsewhere, whatever position s is.
+int cmr_index_gram_rows(cmr_index_t* idx, const float* rows, const int64_t* ids, int nq, int F, float* out);
+
 // for ppr.hip: the combiner of an index (combine.h) — its width (0: off; *dim: floats of one query) and one submission
 // with the index's gather window
 int cmr_index_combine_width(cmr_index_t* idx, int* dim, int* dtype);

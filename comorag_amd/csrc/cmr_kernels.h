@@ -254,6 +254,18 @@ hipError_t cmr_launch_exact_certify(int dtype, const float* shadow, int dim, lon
                                     const float* q, int nq, const int64_t* cand_ids, const float* cand_sc, int kc, int k, const float* stats,
                                     void* part, int* arrive, int64_t* out_ids, float* out_scores, int* out_exact, hipStream_t s);
 
+// ---- diversified top-k (mmr_kernels.hip).  rows: candidate ids [nq, F] (global: id_base, or nb > 1: the block table) -> local
+// rows, -1 for a void position (negative, not held, or an earlier position of the query carries the same id).  gram: out [nq, F, F],
+// out[q][s][c] = the scan's score of (query = stored row of position s, corpus row of position c), -inf where either is void; F <= 128;
+// qfrag = nullptr: both operands gathered from the panels; else the query side comes from fragments [nq * ceil(F / 32)][ks][64] in
+// prep_queries' layout and only the corpus side can be void.  select: the greedy selection of mmr_select.h, out [nq, k] in pick order.
+hipError_t cmr_launch_mmr_rows(const int64_t* ids, int nq, int F, long long nrows, long long id_base, const long long* tab, int nb, long long* rows,
+                               hipStream_t s);
+hipError_t cmr_launch_mmr_gram(int dtype, const void* corpus, const void* qfrag, const long long* rows, int nq, int F, int dpad, float* out,
+                               hipStream_t s);
+hipError_t cmr_launch_mmr_select(const int64_t* ids, const float* rel, const long long* rows, const float* gram, int nq, int F, int k, float lam32,
+                                 int64_t* out_ids, float* out_scores, hipStream_t s);
+
 // ---- certified int8 pre-filter of the pipelined 16-bit scan (prefilter_kernels.hip)
 // companion of panels [panel0, panel0 + npanels): int8 blocks, (scale, quantisation error norm) per row, and the atomicMax of
 // (max ||x||, max error norm) into stats[2]; rows at or beyond nrows count as zero rows

@@ -77,7 +77,8 @@ struct Workspace {
     // synchronous search: queries in, (ids | scores | min | max | non-finite flag) out through ONE pinned host buffer and
     // one copy each way — five pageable D2H copies cost more than the search of a small corpus
     DevBuf d_pack;
-    DevBuf r_cnt, r_counts, r_hits;   // range search: (query, tile) counters / offsets, per-query counts, a group's [keys a | keys b | rows a | rows b | histograms]
+    DevBuf m_ids, m_sc, m_rows, m_gram;   // diversified top-k: a call's candidates [nq, F] (ids, scores), their local rows, their pair scores [nq, F, F]
+    DevBuf r_cnt, r_counts, r_hits;   // range search:(query, tile) counters / offsets, per-query counts, a group's [keys a | keys b | rows a | rows b | histograms]
     Q8Scratch q8;                // certified int8 pre-filter
     ExactScratch x;              // cmr_index_search_exact
     int* flag_ptr = nullptr;     // the non-finite-query flag the kernels set: flag.p, or the head of d_pack for the host API
@@ -114,6 +115,7 @@ struct Workspace {
         d_mask.release();
         d_lists.release();
         d_pack.release();
+        m_ids.release(); m_sc.release(); m_rows.release(); m_gram.release();
         r_cnt.release(); r_counts.release(); r_hits.release();
         q8.release();
         x.release();

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "cmr_internal.h"
+#include "mmr_select.h"
 
 namespace {
 
@@ -1043,10 +1044,8 @@ int32_t cmr_mindex_search_exact(cmr_mindex_t* m, const float* q, int32_t nq, int
     return CMR_OK;
 }
 
-int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, float* out) {
-    if (!m || (n > 0 && (!ids || !out))) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    if (n <= 0) return CMR_OK;
-    std::shared_lock<std::shared_mutex> lk(m->mu);
+// cmr_mindex_get_rows under the caller's shared lock
+static int get_rows_locked(cmr_mindex* m, const int64_t* ids, int64_t n, float* out) {
     std::vector<std::vector<int64_t>> want((size_t)m->S);
     std::vector<std::vector<int64_t>> pos((size_t)m->S);
     for (int64_t i = 0; i < n; ++i) {
@@ -1064,6 +1063,114 @@ int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, floa
         for (size_t j = 0; j < want[s].size(); ++j) memcpy(out + (size_t)pos[s][j] * m->dim, tmp.data() + j * (size_t)m->dim, (size_t)m->dim * 4);
     }
     return CMR_OK;
+}
+
+int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, float* out) {
+    if (!m || (n > 0 && (!ids || !out))) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    if (n <= 0) return CMR_OK;
+    std::shared_lock<std::shared_mutex> lk(m->mu);
+    return get_rows_locked(m, ids, n, out);
+}
+
+// ---- diversified top-k over the shards (include/comorag_hip.h: cmr_mindex_search_mmr).  Not a fast path: the candidates'
+// rows come to the host (cmr_mindex_get_rows), go to every shard as fp32 queries — packing a stored row reproduces its stored bits — and
+// are scored there against the candidates that shard holds, by the kernel and with the bits of one index; the host assembles G and runs
+// the selection of mmr_select.h.
+static int mmr_args_check(int nq, int F, int k, double lam) {
+    const int bad = cmr_mmr::check_args(nq, F, k, lam, CMR_MAX_K);
+    if (bad == 2) return cmr_fail(CMR_ERR_UNSUPPORTED, "fetch_k = %d above CMR_MAX_K = %d", F, CMR_MAX_K);
+    if (bad) return cmr_fail(CMR_ERR_INVALID, "need nq >= 1, 1 <= k <= fetch_k and lambda in [0, 1] (nq %d, k %d, fetch_k %d, lambda %g)", nq, k, F, lam);
+    return CMR_OK;
+}
+
+// void positions of ids [n_lists, F]: negative, held by no shard, or repeating an earlier position of the same list
+static std::vector<unsigned char> mmr_void_positions(const cmr_mindex* m, const int64_t* ids, int n_lists, int F) {
+    std::vector<unsigned char> v((size_t)n_lists * F);
+    for (int q = 0; q < n_lists; ++q) {
+        const int64_t* l = ids + (size_t)q * F;
+        for (int p = 0; p < F; ++p) {
+            bool dead = locate(m, l[p]).shard < 0;
+            for (int e = 0; e < p && !dead; ++e) dead = l[e] == l[p];
+            v[(size_t)q * F + p] = dead;
+        }
+    }
+    return v;
+}
+
+// pair scores over two or more active shards, under the caller's shared lock (arguments checked)
+static int pair_scores_locked(cmr_mindex* m, const std::vector<int>& act, const int64_t* ids, int nq, int F, float* out) {
+    const int T = (F + 31) / 32;
+    const size_t d = (size_t)m->dim, per_q = (size_t)T * 32 * d, FF = (size_t)F * F;
+    std::vector<float> flat((size_t)nq * F * d), rows((size_t)nq * per_q, 0.0f);
+    int rc = get_rows_locked(m, ids, (int64_t)nq * F, flat.data());      // (a row nobody holds: zeros; its position is void below)
+    if (rc) return rc;
+    for (int q = 0; q < nq; ++q) memcpy(rows.data() + (size_t)q * per_q, flat.data() + (size_t)q * F * d, (size_t)F * d * 4);
+    std::vector<float> part((size_t)nq * FF);
+    for (size_t i = 0; i < (size_t)nq * FF; ++i) out[i] = -INFINITY;
+    for (int s : act) {
+        rc = cmr_index_gram_rows(m->shard[s], rows.data(), ids, nq, F, part.data());
+        if (rc) return rc;
+        for (size_t i = 0; i < (size_t)nq * FF; ++i) if (part[i] > out[i]) out[i] = part[i];      // (a column is finite on the one shard that holds it)
+    }
+    const std::vector<unsigned char> dead = mmr_void_positions(m, ids, nq, F);
+    for (int q = 0; q < nq; ++q)
+        for (int p = 0; p < F; ++p)
+            if (dead[(size_t)q * F + p]) for (int c = 0; c < F; ++c) out[(size_t)q * FF + (size_t)p * F + c] = -INFINITY;
+    return CMR_OK;
+}
+
+int32_t cmr_mindex_pair_scores(cmr_mindex_t* m, const int64_t* ids, int32_t nq, int32_t F, float* out) {
+    if (!ids || !out) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    { const int rc_ = mmr_args_check(nq, F, 1, 0.0); if (rc_) return rc_; }
+    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
+    std::shared_lock<std::shared_mutex> lk(m->mu);
+    const std::vector<int> act = active_shards(m);
+    if (act.empty()) {
+        for (size_t i = 0; i < (size_t)nq * F * F; ++i) out[i] = -INFINITY;
+        return CMR_OK;
+    }
+    if (act.size() == 1) return cmr_index_pair_scores(m->shard[act[0]], ids, nq, F, out);
+    return pair_scores_locked(m, act, ids, nq, F, out);
+}
+
+int32_t cmr_mindex_mmr_select(cmr_mindex_t* m, const int64_t* cand_ids, const float* cand_scores, int32_t nq, int32_t F, int32_t k, double lam,
+                              int64_t* out_ids, float* out_scores) {
+    if (!cand_ids || !cand_scores || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    { const int rc_ = mmr_args_check(nq, F, k, lam); if (rc_) return rc_; }
+    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
+    if (cmr_mmr::any_nan(cand_scores, (size_t)nq * F)) return cmr_fail(CMR_ERR_INVALID, "NaN among the candidate scores");
+    std::shared_lock<std::shared_mutex> lk(m->mu);
+    const std::vector<int> act = active_shards(m);
+    if (act.empty()) {
+        for (size_t i = 0; i < (size_t)nq * k; ++i) { out_ids[i] = -1; out_scores[i] = -INFINITY; }
+        return CMR_OK;
+    }
+    if (act.size() == 1) return cmr_index_mmr_select(m->shard[act[0]], cand_ids, cand_scores, nq, F, k, lam, out_ids, out_scores);
+    std::vector<float> gram((size_t)nq * F * F);
+    const int rc = pair_scores_locked(m, act, cand_ids, nq, F, gram.data());
+    if (rc) return rc;
+    const std::vector<unsigned char> dead = mmr_void_positions(m, cand_ids, nq, F);
+    for (int q = 0; q < nq; ++q)
+        cmr_mmr::select_one(cand_scores + (size_t)q * F, gram.data() + (size_t)q * F * F, cand_ids + (size_t)q * F, F, k, (float)lam,
+                            dead.data() + (size_t)q * F, out_ids + (size_t)q * k, out_scores + (size_t)q * k);
+    return CMR_OK;
+}
+
+int32_t cmr_mindex_search_mmr(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int32_t fetch_k, double lam, int64_t* out_ids,
+                              float* out_scores) {
+    if (!q || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
+    { const int rc_ = mmr_args_check(nq, fetch_k, k, lam); if (rc_) return rc_; }
+    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
+    {   // one active shard: its own device path
+        std::shared_lock<std::shared_mutex> lk(m->mu);
+        const std::vector<int> act = active_shards(m);
+        if (act.size() == 1) return cmr_index_search_mmr(m->shard[act[0]], q, nq, k, fetch_k, lam, out_ids, out_scores);
+    }
+    std::vector<int64_t> ids((size_t)nq * fetch_k);
+    std::vector<float> sc((size_t)nq * fetch_k);
+    const int rc = cmr_mindex_search(m, q, nq, fetch_k, ids.data(), sc.data(), nullptr, nullptr);
+    if (rc) return rc;
+    return cmr_mindex_mmr_select(m, ids.data(), sc.data(), nq, fetch_k, k, lam, out_ids, out_scores);
 }
 
 // ---- throughput mode -------------------------------------------------------------------------------------------------------

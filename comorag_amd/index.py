@@ -158,7 +158,7 @@ def renumber_after_removal(ids, removed) -> np.ndarray:
 # the calls whose host-array marshalling `DenseIndex` (cmr_index_*) and `MultiDeviceIndex` (cmr_mindex_*) share
 _HOST_CALLS = ("destroy", "size", "info", "append", "search", "search_exact", "search_min_score", "scores", "sorted_scores",
                "rescore", "get_rows", "search_ids", "remove_ids", "update_rows", "range_count", "range_search", "search_min_score_ids",
-               "range_count_ids", "range_search_ids")
+               "range_count_ids", "range_search_ids", "pair_scores", "mmr_select", "search_mmr")
 _bound = {}
 
 
@@ -452,6 +452,66 @@ class HostArrayIndex:
             L.check(self._c.get_rows(self._h, _ptr(ids), len(ids), _ptr(out)))
         return out
 
+    # -- diversified top-k: maximal marginal relevance (cmr_index_search_mmr / cmr_mindex_search_mmr)
+    @staticmethod
+    def default_fetch_k(k: int) -> int:
+        return min(L.CMR_MAX_K, max(4 * int(k), 20))
+
+    def search_mmr(self, q, k: int, fetch_k: Optional[int] = None, lambda_mult: float = 0.5, *, allow=None, exclude=None
+                   ) -> Tuple[np.ndarray, np.ndarray]:
+        """MMR re-ranked top-k (LangChain's `max_marginal_relevance_search`): the `fetch_k` most relevant rows are fetched by the ordinary
+        search, then k of them are picked greedily, each maximising lambda_mult * relevance - (1 - lambda_mult) * (largest pair score with
+        a row picked before), in fp32 on the device (include/comorag_hip.h states the arithmetic; it is reproducible bit for bit).
+        → (ids [nq,k'], scores [nq,k']) in PICK order, k' = min(k, len(self)); scores are the raw relevance scores of the picked rows,
+        -1 / -inf behind the last pick.  `fetch_k` defaults to min(128, max(4 k, 20)) and is raised to k; 1 <= k <= fetch_k <= 128.
+        lambda_mult = 1 is exactly `search(q, k)`; on L2-normalised rows the pair scores are cosines, MMR's usual form.
+        One call and one host round trip.  With `allow` / `exclude` id lists (as `search_filtered_ids` takes them) it is TWO calls:
+        `search_filtered_ids(q, fetch_k, ...)` followed by `mmr_select`."""
+        q = self._queries(q)
+        nq, k = q.shape[0], int(k)
+        fetch_k = max(k, self.default_fetch_k(k) if fetch_k is None else int(fetch_k))
+        kk = min(k, len(self))
+        if allow is not None or exclude is not None:
+            cid, csc, _, _ = self.search_filtered_ids(q, fetch_k, allow=allow, exclude=exclude, with_minmax=False)
+            ids, sc = self.mmr_select(cid, csc, k, lambda_mult)
+            return ids[:, :kk], sc[:, :kk]
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        L.check(self._c.search_mmr(self._h, _ptr(q), nq, k, fetch_k, float(lambda_mult), _ptr(ids), _ptr(sc)))
+        return ids[:, :kk], sc[:, :kk]
+
+    def mmr_select(self, cand_ids, cand_scores, k: int, lambda_mult: float = 0.5) -> Tuple[np.ndarray, np.ndarray]:
+        """The MMR selection of `search_mmr` over candidates of ANY earlier search: `cand_ids` / `cand_scores` [nq, F] (or [F]) as a search
+        returned them — -1 / -inf padding, ids the index does not hold and repeated ids are skipped.  → (ids [nq,k], scores [nq,k]) in pick
+        order, -1 / -inf padded; k <= F <= 128."""
+        cand_ids = np.ascontiguousarray(cand_ids, dtype=np.int64)
+        cand_scores = _f32c(cand_scores)
+        if cand_ids.ndim == 1:
+            cand_ids, cand_scores = cand_ids[None, :], cand_scores.reshape(1, -1)
+        if cand_ids.ndim != 2 or cand_ids.shape != cand_scores.shape:
+            raise ValueError(f"cand_ids {cand_ids.shape} and cand_scores {cand_scores.shape} must be [nq, F] both")
+        nq, f = cand_ids.shape
+        k = int(k)
+        ids = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        L.check(self._c.mmr_select(self._h, _ptr(cand_ids), _ptr(cand_scores), nq, f, k, float(lambda_mult), _ptr(ids), _ptr(sc)))
+        return ids, sc
+
+    def pair_scores(self, ids) -> np.ndarray:
+        """Scores of stored rows against stored rows: ids [F] → [F, F], ids [nq, F] → [nq, F, F]; out[..., s, c] has the bits
+        `scores(get_rows([ids[s]]))[0, ids[c]]` returns.  Rows and columns of negative ids, ids the index does not hold and ids repeated
+        from an earlier position are -inf.  F <= 128."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        one = ids.ndim == 1
+        if one:
+            ids = ids[None, :]
+        if ids.ndim != 2:
+            raise ValueError(f"ids must be [F] or [nq, F], got {ids.shape}")
+        nq, f = ids.shape
+        out = np.empty((nq, f, f), dtype=np.float32)
+        L.check(self._c.pair_scores(self._h, _ptr(ids), nq, f, _ptr(out)))
+        return out[0] if one else out
+
 
 class DenseIndex(HostArrayIndex):
     _PREFIX = "cmr_index_"
@@ -587,6 +647,42 @@ class DenseIndex(HostArrayIndex):
             self._h, C.c_void_p(q_t.data_ptr()), nq, k, C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
             C.c_void_p(out_min.data_ptr()) if out_min is not None else None,
             C.c_void_p(out_max.data_ptr()) if out_max is not None else None, C.c_void_p(stream)))
+        return out_ids, out_scores
+
+    def search_mmr_dev(self, q_t, k: int, fetch_k: Optional[int] = None, lambda_mult: float = 0.5, out_ids=None, out_scores=None,
+                       stream: Optional[int] = None):
+        """`search_mmr` on torch CUDA tensors, enqueued on torch's current stream like `search_dev`: (ids [nq,k], scores [nq,k]), always k
+        columns, -1 / -inf padded."""
+        import torch
+        assert q_t.is_cuda and q_t.dtype == torch.float32 and q_t.is_contiguous() and q_t.shape[1] == self.dim
+        nq, k, dev = q_t.shape[0], int(k), q_t.device
+        fetch_k = max(k, self.default_fetch_k(k) if fetch_k is None else int(fetch_k))
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().cmr_index_search_mmr_dev(self._h, C.c_void_p(q_t.data_ptr()), nq, k, fetch_k, float(lambda_mult),
+                                                 C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()), C.c_void_p(stream)))
+        return out_ids, out_scores
+
+    def mmr_select_dev(self, cand_ids_t, cand_scores_t, k: int, lambda_mult: float = 0.5, out_ids=None, out_scores=None,
+                       stream: Optional[int] = None):
+        """`mmr_select` on torch CUDA tensors (int64 / float32 [nq, F], contiguous), enqueued on torch's current stream."""
+        import torch
+        assert cand_ids_t.is_cuda and cand_ids_t.dtype == torch.int64 and cand_ids_t.is_contiguous() and cand_ids_t.ndim == 2
+        assert cand_scores_t.is_cuda and cand_scores_t.dtype == torch.float32 and cand_scores_t.is_contiguous() and cand_scores_t.shape == cand_ids_t.shape
+        (nq, f), k, dev = cand_ids_t.shape, int(k), cand_ids_t.device
+        if out_ids is None:
+            out_ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        if out_scores is None:
+            out_scores = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(L.lib().cmr_index_mmr_select_dev(self._h, C.c_void_p(cand_ids_t.data_ptr()), C.c_void_p(cand_scores_t.data_ptr()), nq, f, k,
+                                                 float(lambda_mult), C.c_void_p(out_ids.data_ptr()), C.c_void_p(out_scores.data_ptr()),
+                                                 C.c_void_p(stream)))
         return out_ids, out_scores
 
     # -- filtered search (cmr_index_search_masked*): top-k among the rows an allow bitmap keeps

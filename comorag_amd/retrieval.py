@@ -105,6 +105,18 @@ def dense_passage_topk_filtered_ids(index, query_embeddings, k: int, exclude_ids
     return ids, np.where(ids < 0, -np.inf, norm).astype(np.float32)
 
 
+def dense_passage_topk_mmr(index, query_embeddings, k: int, fetch_k: Optional[int] = None, lambda_mult: float = 0.5, exclude_ids=None,
+                           allow_ids=None) -> Tuple[np.ndarray, np.ndarray]:
+    """`dense_passage_topk` with maximal-marginal-relevance re-ranking, on a `DenseIndex` or a `MultiDeviceIndex`: of the `fetch_k` most
+    relevant rows (default min(128, max(4 k, 20))), k are picked so that each trades relevance against its largest similarity to the rows
+    picked before — ComoRAG's chunks overlap, its summaries cover sliding windows and its fused notes paraphrase their passages, and
+    tri_retrieve drops exact hash matches only (ComoRAG.py:499-505, 515-522, 535-540).  `exclude_ids` / `allow_ids` as
+    `dense_passage_topk_filtered_ids` takes them (then the candidates come from the filtered search, in a second call).
+    ids [nq,k'], RAW scores [nq,k'] in pick order (not descending, not normalised: a pick's score is its relevance, and the ranking is
+    the order); lambda_mult = 1 is the plain top-k."""
+    return index.search_mmr(_as_query(query_embeddings), k, fetch_k, lambda_mult, allow=allow_ids, exclude=exclude_ids)
+
+
 def get_fact_scores(index: Optional[DenseIndex], query_embedding) -> np.ndarray:
     """ComoRAG.get_fact_scores (ComoRAG.py:937-948): full normalised vector over the fact matrix."""
     if index is None or len(index) == 0:

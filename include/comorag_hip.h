@@ -384,11 +384,13 @@ int32_t cmr_index_set_option(cmr_index_t* idx, const char* name, int64_t value);
  *   bit  11     the batch took more than one corpus pass: the bits above describe its first, later passes may be routed otherwise
  *   bit  12     filtered search (cmr_index_search_masked*): every scan of the pass is the masked variant
  *   bit  13     with bit 12: the per-query variant (cmr_index_search_masked_each*, or a combined batch of filtered calls)
- *   bit  14     with bit 12: the allow words were built on the device from row-id lists (cmr_index_search_ids*)                      */
+ *   bit  14     with bit 12: the allow words were built on the device from row-id lists (cmr_index_search_ids*)
+ *   bit  15     diversified top-k (cmr_index_search_mmr*): the bits below describe the candidate search in front of the selection   */
 #define CMR_ROUTE_MORE_PASSES (1 << 11)
 #define CMR_ROUTE_FILTERED (1 << 12)
 #define CMR_ROUTE_FILTERED_EACH (1 << 13)
 #define CMR_ROUTE_FILTERED_IDS (1 << 14)
+#define CMR_ROUTE_MMR (1 << 15)
 #define CMR_ROUTE_TINY 1          /* single launch, <= 1024 rows */
 #define CMR_ROUTE_SMALL 2         /* single launch, hierarchical selection */
 #define CMR_ROUTE_CHAIN 3         /* narrow kernel: pack / [sample] / scan / merge */
@@ -559,6 +561,44 @@ int32_t cmr_index_prefilter_stats(cmr_index_t* idx, float* max_row_norm, float* 
 
 /* Gather rows back to the host as fp32 (dequantised), out [n, dim]; ids as returned by search (with the id base). */
 int32_t cmr_index_get_rows(cmr_index_t* idx, const int64_t* ids, int64_t n, float* out);
+
+/* ---- diversified top-k: maximal marginal relevance ----------------------------------------------------
+ * ComoRAG's corpora are near-duplicates by construction (overlapping chunks, summaries of sliding windows, fused notes) and
+ * tri_retrieve removes exact hash matches only (ComoRAG.py:499-505, 515-522, 535-540).  These calls re-rank F candidates so that each
+ * pick trades relevance against similarity to the rows already picked, on the device, bit for bit reproducible.
+ *   Pair score  pair(a, b): the fp32 value cmr_index_scores returns for (query = stored row a as cmr_index_get_rows gives it, corpus
+ *     row b) — stored (rounded) rows on both sides, also with CMR_FLAG_KEEP_F32.
+ *   Selection, per query: positions 0 .. F-1 with ids, relevance rel (fp32) and G[s][c] = pair(id[s], id[c]).  A position is VOID when
+ *     its id is negative, the index does not hold it, or an earlier position carries the same id; void positions are never picked and
+ *     never penalise.  fp32 throughout, lam32 = (float)lam, oml = 1.0f - lam32.  Pick 1: the non-void position of largest rel.  Every later
+ *     pick: the non-void unpicked position of largest (lam32 * rel[c]) - (oml * pen[c]), pen[c] = max of G[s][c] over the picked s — both
+ *     products rounded to fp32, then one subtraction, no fused multiply-add.  IEEE comparisons (-0.0 == +0.0), ties to the lowest
+ *     position; it stops after k picks or when no position is left.  Output in pick order: ids as given, scores = the rel bits of the
+ *     picked positions, the rest -1 / -inf.  lam = 1 gives the first k non-void candidates in order — for cmr_index_search_mmr exactly
+ *     cmr_index_search(q, k); scores are raw inner products (cosines on L2-normalised rows, MMR's usual form).
+ *   Arguments, checked before the handle: NULL -> CMR_ERR_INVALID; nq >= 1, 1 <= k <= F (fetch_k), lam in [0, 1] and not NaN, else
+ *     CMR_ERR_INVALID; F > CMR_MAX_K -> CMR_ERR_UNSUPPORTED.  The host forms refuse NaN among the candidate scores (CMR_ERR_INVALID).
+ *   Never combined, pre-filtered or pipelined.
+ * cmr_mmr_select: the selection alone on host arrays (no device; void = negative or repeated id).  rel [nq, F], gram [nq, F, F],
+ *   ids [nq, F] -> out [nq, k].
+ * cmr_index_pair_scores: out [nq, F, F], out[q][s][c] = pair(ids[q][s], ids[q][c]), -inf in the rows and columns of void positions.
+ * cmr_index_mmr_select(_dev): the selection over candidates of ANY earlier search (padded results go straight in); _dev: device
+ *   buffers, enqueued on `stream`.
+ * cmr_index_search_mmr(_dev): the ordinary search for fetch_k on whichever route the plan picks, the pair scores and the selection on one
+ *   stream; only [nq, k] goes to the host, in one round trip.  last_route: the candidate search's route with CMR_ROUTE_MMR set.
+ * cmr_mindex_*: the same over global ids; every shard scores all candidate rows against the candidates it holds, the host assembles G
+ *   and selects (cmr_mmr_select).  Results equal one index holding the same rows, bit for bit.                                      */
+int32_t cmr_mmr_select(const float* rel, const float* gram, const int64_t* ids, int32_t nq, int32_t F, int32_t k, double lam,
+                       int64_t* out_ids, float* out_scores);
+int32_t cmr_index_pair_scores(cmr_index_t* idx, const int64_t* ids, int32_t nq, int32_t F, float* out);
+int32_t cmr_index_mmr_select(cmr_index_t* idx, const int64_t* cand_ids, const float* cand_scores, int32_t nq, int32_t F, int32_t k,
+                             double lam, int64_t* out_ids, float* out_scores);
+int32_t cmr_index_mmr_select_dev(cmr_index_t* idx, const int64_t* cand_ids_dev, const float* cand_scores_dev, int32_t nq, int32_t F,
+                                 int32_t k, double lam, int64_t* out_ids_dev, float* out_scores_dev, void* stream);
+int32_t cmr_index_search_mmr(cmr_index_t* idx, const float* q_f32, int32_t nq, int32_t k, int32_t fetch_k, double lam, int64_t* out_ids,
+                             float* out_scores);
+int32_t cmr_index_search_mmr_dev(cmr_index_t* idx, const float* q_f32_dev, int32_t nq, int32_t k, int32_t fetch_k, double lam,
+                                 int64_t* ids_dev, float* scores_dev, void* stream);
 
 /* ---- multi-shard merge ------------------------------------------------------------------
  * Final merge of per-shard candidates after the RCCL all-gather (no reference counterpart;
@@ -740,6 +780,12 @@ int32_t cmr_mindex_range_search_ids(cmr_mindex_t* m, const float* q_f32, int32_t
 int32_t cmr_mindex_rescore(cmr_mindex_t* m, const float* q_f32, int32_t nq, const int64_t* cand, int32_t n_cand, int32_t k,
                            int64_t* out_ids, float* out_scores);
 int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, float* out);
+/* Diversified top-k over the shards (see cmr_index_search_mmr): global ids; bit for bit what one index holding the same rows returns. */
+int32_t cmr_mindex_pair_scores(cmr_mindex_t* m, const int64_t* ids, int32_t nq, int32_t F, float* out);
+int32_t cmr_mindex_mmr_select(cmr_mindex_t* m, const int64_t* cand_ids, const float* cand_scores, int32_t nq, int32_t F, int32_t k,
+                              double lam, int64_t* out_ids, float* out_scores);
+int32_t cmr_mindex_search_mmr(cmr_mindex_t* m, const float* q_f32, int32_t nq, int32_t k, int32_t fetch_k, double lam, int64_t* out_ids,
+                              float* out_scores);
 /* Exact fp32 top-k over every shard (ComoRAG.py:958-966): each shard certifies its local top-k (cmr_index_search_exact: exact when
  * no row outside its candidates can beat its k-th by more than 2 E_q), the host merges the fp32 lists with the exported tie rule,
  * out_exact = AND over the shards.                                                                                             */
