@@ -11,7 +11,8 @@ Steps
  3. hipcc -c every other file of SOURCES (aux_kernels.hip, compact_kernels.hip, sort_kernels.hip, range_kernels.hip, prefilter_kernels.hip, mmr_kernels.hip, api.hip, comm.hip, ppr.hip, encoder_kernels.hip, multi.hip) and
     ring_audit.cpp ; link → comorag_amd/lib/libcomorag_hip.so
 SOURCES and HEADERS also feed the build stamp: a file the library is built from and that is missing there would let a stale
-library pass for fresh.
+library pass for fresh.  api.hip is one translation unit in several files: the headers it alone includes (search_plan.h,
+prefilter_host.h, row_filter.h, range_host.h, exact_host.h, mmr_host.h, mutate_host.h) are listed in HEADERS like any other.
 The .so is git-ignored but travels to the GPU box with the gpurun snapshot.
 """
 from __future__ import annotations
@@ -40,7 +41,7 @@ if os.environ.get("CMR_BUILD_LIB"):          # experiment builds go to their own
 # unrolled size exceeds LLVM's default limit for "#pragma unroll" (16 K) and hipcc silently keeps the loops.
 SCAN_FLAGS = ["-mllvm", "-pragma-unroll-threshold=1048576"]
 SOURCES = ["scan_kernels.hip", "aux_kernels.hip", "compact_kernels.hip", "sort_kernels.hip", "range_kernels.hip", "prefilter_kernels.hip", "mmr_kernels.hip", "api.hip", "comm.hip", "ppr.hip", "encoder_kernels.hip", "multi.hip"]
-HEADERS = ["cmr_device.h", "cmr_kernels.h", "cmr_internal.h", "combine.h", "cmr_select.h", "cmr_topk.h", "index_state.h", "search_plan.h", "prefilter_host.h", "mmr_select.h", os.path.join("..", "..", "include", "comorag_hip.h")]
+HEADERS = ["cmr_device.h", "cmr_kernels.h", "cmr_internal.h", "combine.h", "cmr_select.h", "cmr_topk.h", "index_state.h", "search_plan.h", "prefilter_host.h", "mmr_select.h", "row_filter.h", "range_host.h", "exact_host.h", "mmr_host.h", "mutate_host.h", os.path.join("..", "..", "include", "comorag_hip.h")]
 
 _KERNEL_RE = re.compile(r"^_Z11scan_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEv5ScanP:")
 

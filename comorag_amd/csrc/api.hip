@@ -1,5 +1,5 @@
 // C-ABI of libcomorag_hip.so (include/comorag_hip.h): index lifetime, append, search, scores,
-// re-score, shard merge, profiling.  Host-side C++: what a C entry point checks and how a planned pass is enqueued (the
+// re-score, shard merge, profiling; the filtered, range, exact, diversified and row-mutation calls are in the headers included at the end.  Host-side C++: what a C entry point checks and how a planned pass is enqueued (the
 // state lives in index_state.h, the route and shape decisions in search_plan.h); every numeric step is a HIP
 // kernel from scan_kernels.hip / aux_kernels.hip.  There is no CPU fallback in this library.
 #include <hip/hip_runtime.h>
@@ -453,33 +453,6 @@ int search_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, in
     const PassStreams st = PassStreams::one(ws->stream);
     for (PassSplit ps(idx, nq); ps.next();) {
         int rc = plan_and_enqueue_pass(idx, ws, st, ps, k, 0, q_dev, min_score, ids_dev, scores_dev, min_dev, max_dev);
-        if (rc) return rc;
-    }
-    return CMR_OK;
-}
-
-// Filtered search (cmr_index_search_masked*): the best k among the local rows whose bit is set in allow_dev (one word per
-// 32-row panel, on the device).  Narrow passes of the pack / [sample] / scan / merge chain on the masked scan variant, all on
-// ws->stream; one mask serves every query.  k <= CMR_MAX_K (checked by the caller).
-// mask_stride > 0 (cmr_index_search_masked_each*): allow_dev is [nq][mask_stride], query i's words at allow_dev + i * mask_stride;
-// the pass that starts at query q0 gets the pointer advanced by q0 blocks, its kernel indexes the pass's own queries from 0.
-// min_score (cmr_index_search_min_score_masked / _ids): the filtered threshold search — the bound is every query's initial
-// threshold as in search_enqueue, so no sampling passes; the same masked scans, the same merge.
-int search_masked_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, int k, const unsigned* allow_dev, int64_t* ids_dev,
-                          float* scores_dev, float* min_dev, float* max_dev, long long mask_stride = 0, const float* min_score = nullptr) {
-    const PassStreams st = PassStreams::one(ws->stream);
-    const int per_pass = idx->narrow_width(nq);
-    for (int q0 = 0; q0 < nq; q0 += per_pass) {
-        const int nqp = std::min(per_pass, nq - q0);
-        PassPlan plan;
-        PassRequest rq = st.request(nqp, k, Route::narrow, min_score != nullptr, 0);
-        rq.masked = true;
-        rq.masked_each = mask_stride > 0;
-        int rc = plan_pass(idx, rq, &plan);
-        if (rc) return rc;
-        if (q0 == 0) idx->last_route.store(route_code(plan, min_score != nullptr) | (nqp < nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
-        rc = enqueue_pass(idx, ws, st, plan, q_dev + (size_t)q0 * idx->dim, min_score, ids_dev + (size_t)q0 * k, scores_dev + (size_t)q0 * k,
-                          min_dev ? min_dev + q0 : nullptr, max_dev ? max_dev + q0 : nullptr, allow_dev + (size_t)q0 * (size_t)mask_stride, mask_stride);
         if (rc) return rc;
     }
     return CMR_OK;
@@ -979,49 +952,12 @@ int32_t cmr_index_search_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, i
     return search_enqueue(idx, call.ws, q_dev, nq, k, ids_dev, scores_dev, min_dev, max_dev);
 }
 
-// ---- filtered search (include/comorag_hip.h: cmr_index_search_masked*, cmr_index_search_masked_each*).  Never
-// pre-filtered; the _dev forms go straight to search_masked_enqueue, the host forms through the combiner where "combine_filtered" is set
-// (further down, beside the other combined calls).
-static int words_check(const cmr_index* idx, int64_t n_words) {      // a mask is one word per 32-row panel (under the index lock)
-    if (n_words != panels_of(idx->n)) return fail(CMR_ERR_INVALID, "n_words %lld != ceil(%lld rows / 32) = %lld", (long long)n_words, idx->n, panels_of(idx->n));
-    return CMR_OK;
-}
-static int masked_check(const cmr_index* idx, int nq, int k, int64_t n_words) {      // (under the index lock; no device call)
-    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
-    if (k <= 0) return fail(CMR_ERR_INVALID, "k must be > 0");
-    if (int rc = words_check(idx, n_words)) return rc;
-    if (k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "filtered search supports k <= %d", CMR_MAX_K);
-    return CMR_OK;
-}
-
-// each = false: allow_dev is [n_words], one mask for every query; each = true: [nq][n_words]
-static int32_t masked_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words, bool each,
-                          int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
-    if (!idx || !q_dev || !allow_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
-    DevCall call(idx);
-    int rc = masked_check(idx, nq, k, n_words);
-    if (rc) return rc;
-    rc = call.open(stream);
-    if (rc) return rc;
-    return search_masked_enqueue(idx, call.ws, q_dev, nq, k, allow_dev, ids_dev, scores_dev, min_dev, max_dev, each ? (long long)n_words : 0);
-}
-
-int32_t cmr_index_search_masked_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words,
-                                    int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
-    return masked_dev(idx, q_dev, nq, k, allow_dev, n_words, false, ids_dev, scores_dev, min_dev, max_dev, stream);
-}
-
-int32_t cmr_index_search_masked_each_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, const uint32_t* allow_dev, int64_t n_words,
-                                         int64_t* ids_dev, float* scores_dev, float* min_dev, float* max_dev, void* stream) {
-    return masked_dev(idx, q_dev, nq, k, allow_dev, n_words, true, ids_dev, scores_dev, min_dev, max_dev, stream);
-}
-
 int32_t cmr_index_search_min_score_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, float min_score, int64_t* ids_dev,
                                        float* scores_dev, void* stream) {
     if (!idx || !q_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
     if (k <= 0 || k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "threshold search supports k in [1, %d]", CMR_MAX_K);
-    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (int rc_ = cmr_min_score_check(min_score)) return rc_;
     DevCall call(idx);
     int rc = call.open(stream);
     if (rc) return rc;
@@ -1047,7 +983,7 @@ int32_t cmr_index_search_min_score_pipelined(cmr_index_t* idx, const float* q_de
     if (!idx || !q_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
     if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
     if (k <= 0 || k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "threshold search supports k in [1, %d]", CMR_MAX_K);
-    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (int rc_ = cmr_min_score_check(min_score)) return rc_;
     std::shared_lock<std::shared_mutex> lk(idx->mu);
     int rc = cmr_set_device(idx->device);
     if (rc) return rc;
@@ -1384,374 +1320,6 @@ void cmr_index_search_abandon(CmrPending* P) {
     pending_release(P);
 }
 
-// ---- filtered search from row-id lists (include/comorag_hip.h: cmr_index_row_masks_dev, cmr_index_search_ids*).  The
-// caller hands over row ids in the domain the searches return; the device builds the allow words next to the corpus (aux_kernels.hip:
-// row_mask_fill, row_mask_apply_ids) and the masked scans of 4.15 / 4.15b run on them unchanged.  Never combined.
-
-// every check of the id-list calls that needs neither the index nor a device; off_host: CSR offsets the host can read (nullptr: a shared
-// list, or device offsets, which the kernel clamps instead)
-int cmr_ids_args_check(int mode, int nq, int k, const int64_t* off_host, const int64_t* ids, int64_t n_ids) {
-    if (mode != CMR_IDS_EXCLUDE && mode != CMR_IDS_ALLOW) return fail(CMR_ERR_INVALID, "mode %d is neither CMR_IDS_EXCLUDE nor CMR_IDS_ALLOW", mode);
-    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
-    if (k <= 0) return fail(CMR_ERR_INVALID, "k must be > 0");
-    if (n_ids < 0) return fail(CMR_ERR_INVALID, "n_ids %lld < 0", (long long)n_ids);
-    if (n_ids > 0 && !ids) return fail(CMR_ERR_INVALID, "NULL ids with n_ids = %lld", (long long)n_ids);
-    if (off_host) {
-        if (off_host[0] != 0) return fail(CMR_ERR_INVALID, "id_offsets[0] = %lld, not 0", (long long)off_host[0]);
-        for (int i = 0; i < nq; ++i)
-            if (off_host[i + 1] < off_host[i]) return fail(CMR_ERR_INVALID, "id_offsets decrease at query %d (%lld after %lld)", i, (long long)off_host[i + 1], (long long)off_host[i]);
-        if (off_host[nq] != n_ids) return fail(CMR_ERR_INVALID, "id_offsets[nq] = %lld, not n_ids = %lld", (long long)off_host[nq], (long long)n_ids);
-    }
-    if (k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "filtered search supports k <= %d", CMR_MAX_K);
-    return CMR_OK;
-}
-
-namespace {
-
-constexpr int kIdsGroup = 64;      // queries whose words are built and scanned together: the scratch never holds more than this many masks
-
-// words [nm][npanels] (nm = nq with offsets, 1 without) from the lists, on s
-int row_masks_enqueue(cmr_index* idx, int mode, int nq, const int64_t* off_dev, const int64_t* ids_dev, int64_t n_ids, unsigned* words, hipStream_t s) {
-    const int nm = off_dev ? nq : 1, nb = (int)idx->blk_local.size(), exclude = mode == CMR_IDS_EXCLUDE;
-    HIP_TRY(cmr_launch_row_mask_fill(words, nm, idx->npanels(), idx->n, exclude, s));
-    HIP_TRY(cmr_launch_row_mask_apply_ids(words, idx->npanels(), idx->n, exclude, (const long long*)off_dev, nm, (const long long*)ids_dev, n_ids,
-                                          kernel_id_base(idx), nb > 1 ? idx->d_blk : nullptr, nb, s));
-    return CMR_OK;
-}
-
-// Build and scan on ws->stream.  A shared list: one mask in ws->d_mask, every query on the shared-mask scan.  Per-query lists: groups of
-// kIdsGroup queries, each group's words built into the same scratch behind the previous group's scan (stream order) and scanned by the
-// per-query variant; a query's row does not depend on the group it falls into.
-int search_ids_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, int k, int mode, const int64_t* off_dev, const int64_t* ids_dev,
-                       int64_t n_ids, int64_t* ids_out, float* scores_out, float* min_out, float* max_out, const float* min_score = nullptr) {
-    const long long nw = idx->npanels();
-    const int group = off_dev ? kIdsGroup : nq;
-    HIP_TRY(ws->d_mask.ensure(std::max<size_t>((size_t)(off_dev ? std::min(nq, kIdsGroup) : 1) * (size_t)nw * 4, 4)));
-    unsigned* const words = (unsigned*)ws->d_mask.p;
-    long long route = 0;
-    for (int q0 = 0; q0 < nq; q0 += group) {
-        const int nqg = std::min(group, nq - q0);
-        int rc = row_masks_enqueue(idx, mode, nqg, off_dev ? off_dev + q0 : nullptr, ids_dev, n_ids, words, ws->stream);
-        if (rc) return rc;
-        rc = search_masked_enqueue(idx, ws, q_dev + (size_t)q0 * idx->dim, nqg, k, words, ids_out + (size_t)q0 * k, scores_out + (size_t)q0 * k,
-                                   min_out ? min_out + q0 : nullptr, max_out ? max_out + q0 : nullptr, off_dev ? nw : 0, min_score);
-        if (rc) return rc;
-        if (q0 == 0) route = idx->last_route.load(std::memory_order_relaxed);
-    }
-    idx->last_route.store(route | CMR_ROUTE_FILTERED_IDS | (group < nq ? CMR_ROUTE_MORE_PASSES : 0), std::memory_order_relaxed);
-    return CMR_OK;
-}
-
-}  // namespace
-
-// cmr_index_search_ids in two halves, as cmr_index_search_begin: arguments checked by the caller (cmr_ids_args_check); finished or
-// abandoned through cmr_index_search_finish / _abandon.  The packed round trip (packed_begin) with two inputs: the queries, and
-// [offsets (nq + 1) | ids] as one block into d_lists.
-int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, int mode, const int64_t* off, const int64_t* ids, int64_t n_ids,
-                               bool take_lock, CmrPending** out, const float* min_score) {
-    if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
-    *out = nullptr;
-    const size_t off_bytes = off ? ((size_t)nq + 1) * 8 : 0;
-    const PackedInput in[] = {{&Workspace::d_q, q, (size_t)nq * idx->dim * 4}, {&Workspace::d_lists, off, off_bytes, ids, (size_t)n_ids * 8}};
-    return packed_begin(idx, nq, k, take_lock, in, [&](Workspace* ws, int64_t* ids_out, float* sc, float* mn, float* mx) {
-        return search_ids_enqueue(idx, ws, (const float*)ws->d_q.p, nq, k, mode, off ? (const int64_t*)ws->d_lists.p : nullptr,
-                                  (const int64_t*)((char*)ws->d_lists.p + off_bytes), n_ids, ids_out, sc, mn, mx, min_score);
-    }, out);
-}
-
-extern "C" {
-
-int32_t cmr_index_row_masks_dev(cmr_index_t* idx, int32_t mode, int32_t nq, const int64_t* id_offsets_dev, const int64_t* ids_dev, int64_t n_ids,
-                                uint32_t* words_dev, int64_t n_words, void* stream) {
-    if (!words_dev) return fail(CMR_ERR_INVALID, "NULL argument");
-    int rc = cmr_ids_args_check(mode, nq, 1, nullptr, ids_dev, n_ids);
-    if (rc) return rc;
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    DevCall call(idx);
-    rc = words_check(idx, n_words);
-    if (rc) return rc;
-    rc = call.open();      // (no workspace: the words are the caller's)
-    if (rc) return rc;
-    return row_masks_enqueue(idx, mode, nq, id_offsets_dev, ids_dev, n_ids, words_dev, (hipStream_t)stream);
-}
-
-int32_t cmr_index_search_ids_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets_dev,
-                                 const int64_t* ids_dev, int64_t n_ids, int64_t* ids_out_dev, float* scores_out_dev, float* min_dev, float* max_dev,
-                                 void* stream) {
-    if (!q_dev || !ids_out_dev || !scores_out_dev) return fail(CMR_ERR_INVALID, "NULL argument");
-    int rc = cmr_ids_args_check(mode, nq, k, nullptr, ids_dev, n_ids);
-    if (rc) return rc;
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    DevCall call(idx);
-    rc = call.open(stream);
-    if (rc) return rc;
-    return search_ids_enqueue(idx, call.ws, q_dev, nq, k, mode, id_offsets_dev, ids_dev, n_ids, ids_out_dev, scores_out_dev, min_dev, max_dev);
-}
-
-int32_t cmr_index_search_ids(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
-                             int64_t n_ids, int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
-    if (!q || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    int rc = cmr_ids_args_check(mode, nq, k, id_offsets, ids, n_ids);
-    if (rc) return rc;
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    CmrPending* p = nullptr;
-    rc = cmr_index_search_ids_begin(idx, q, nq, k, mode, id_offsets, ids, n_ids, true, &p);
-    if (rc) return rc;
-    return cmr_index_search_finish(p, out_ids, out_scores, out_min, out_max);
-}
-
-}  // extern "C"
-
-// roll a shard back to n_rows (multi.hip: an append that failed on a later shard).  Slots beyond n_rows keep stale data:
-// every kernel masks by row index, and the next append rewrites them.
-int cmr_index_truncate(cmr_index_t* idx, long long n_rows) {
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    std::unique_lock<std::shared_mutex> lk(idx->mu);
-    if (n_rows < 0 || n_rows > idx->n) return fail(CMR_ERR_INVALID, "truncate to %lld rows of %lld", n_rows, idx->n);
-    idx->n = n_rows;
-    idx->q8c.rows = std::min(idx->q8c.rows, n_rows);      // (the next append rewrites the slots behind: their int8 companion is stale then)
-    return CMR_OK;
-}
-
-// ---- row removal by stable in-place compaction (include/comorag_hip.h: cmr_index_remove_ids; compact_kernels.hip).
-// The exclusive lock is held by the caller.  Everything that can fail for want of memory happens before the first row moves.
-static int remove_ids_locked(cmr_index* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
-    idx->rm_chunks_last = 0;
-    if (n_ids == 0 || idx->n == 0) return CMR_OK;
-    int rc = cmr_set_device(idx->device);
-    if (rc) return rc;
-    // searches hold the shared lock only while they enqueue (_dev, pipelined) or until they finish (host API): whatever this process
-    // has in flight on the device — the pipeline's streams, the workspaces', callers' streams — reads the rows where they are now
-    HIP_TRY(hipDeviceSynchronize());
-    const long long n = idx->n, nw = idx->npanels();
-    hipStream_t s = nullptr;
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t o_words = 16, o_kb = o_words + up16((size_t)nw * 4), o_ids = o_kb + up16(((size_t)nw + 1) * 4);
-    HIP_TRY(idx->rm_buf.ensure(o_ids + (size_t)n_ids * 8));
-    char* const b = (char*)idx->rm_buf.p;
-    long long* const info = (long long*)b;
-    unsigned* const words = (unsigned*)(b + o_words);
-    unsigned* const kept_before = (unsigned*)(b + o_kb);
-    HIP_TRY(hipMemcpy(b + o_ids, ids, (size_t)n_ids * 8, hipMemcpyHostToDevice));
-    // the keep words by the builder of the id-list searches: its ignoring rules (negative ids, ids this index does not hold, duplicates), its translation
-    rc = row_masks_enqueue(idx, CMR_IDS_EXCLUDE, 1, nullptr, (const int64_t*)(b + o_ids), n_ids, words, s);
-    if (rc) return rc;
-    HIP_TRY(cmr_launch_keep_prefix(words, nw, n, kept_before, info, s));
-    long long h[2] = {n, n};
-    HIP_TRY(hipMemcpy(h, info, sizeof(h), hipMemcpyDeviceToHost));
-    const long long kept = h[0], first = h[1];
-    if (kept < 0 || kept > n || first < 0 || first > n) return fail(CMR_ERR_HIP, "row removal: prefix sum returned %lld kept rows, first removed row %lld of %lld", kept, first, n);
-    if (kept == n) return CMR_OK;
-    if (first < kept) {      // (first == kept: the removed rows are the tail — a truncate)
-        const long long p0 = first / CMR_PANEL_ROWS, affected = nw - p0;
-        const size_t pb = idx->panel_bytes();
-        long long sp = idx->rm_stage_panels ? idx->rm_stage_panels : std::max<long long>(2, (long long)((64ull << 20) / pb));
-        sp = std::max<long long>(2, std::min(sp, affected + 1));
-        const size_t stage_bytes = (size_t)sp * pb;
-        HIP_TRY(idx->stage.ensure(stage_bytes));
-        // from here on rows move: whatever happens, the int8 companion is no longer trusted behind the first removed row
-        idx->q8c.rows = std::min(idx->q8c.rows, first);
-        const int ks = idx->ks();
-        const long long c_panels = sp - 1;      // the destination rows of c_panels source panels may straddle one panel more
-        for (long long p = p0; p < nw; p += c_panels) {
-            HIP_TRY(cmr_launch_compact_chunk(idx->corpus, ks, words, kept_before, p, std::min(nw, p + c_panels), idx->stage.p, sp, s));
-            ++idx->rm_chunks_last;
-        }
-        if (idx->shadow) {      // the same buffer, at row granularity: sp * panel bytes >= 2 * 32 * dpad * 2 bytes hold at least one panel's 32 fp32 rows
-            const long long stage_rows = (long long)(stage_bytes / ((size_t)idx->dim * 4)), s_panels = stage_rows / CMR_PANEL_ROWS;
-            for (long long p = p0; p < nw; p += s_panels)
-                HIP_TRY(cmr_launch_compact_shadow_chunk(idx->shadow, idx->dim, words, kept_before, p, std::min(nw, p + s_panels), idx->stage.p, stage_rows, s));
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    idx->n = kept;
-    idx->q8c.rows = std::min(idx->q8c.rows, first);      // the int8 companion is not compacted: the next pre-filtered call quantises again from the first removed row's panel
-    if (n_removed) *n_removed = n - kept;
-    return CMR_OK;
-}
-
-// cmr_index_remove_ids without the block-table restriction, for an owner that replaces the table itself right after (multi.hip:
-// the ids are translated through the table the shard has NOW; the shard's table is stale when this returns with *n_removed > 0)
-int cmr_index_compact_ids(cmr_index_t* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
-    if (n_removed) *n_removed = 0;
-    if (!idx || (n_ids > 0 && !ids) || n_ids < 0) return fail(CMR_ERR_INVALID, "bad argument");
-    std::unique_lock<std::shared_mutex> lk(idx->mu);
-    return remove_ids_locked(idx, ids, n_ids, n_removed);
-}
-
-extern "C" int32_t cmr_index_remove_ids(cmr_index_t* idx, const int64_t* ids, int64_t n_ids, int64_t* n_removed) {
-    if (n_removed) *n_removed = 0;
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    if (n_ids < 0) return fail(CMR_ERR_INVALID, "n_ids %lld < 0", (long long)n_ids);
-    if (n_ids > 0 && !ids) return fail(CMR_ERR_INVALID, "NULL ids with n_ids = %lld", (long long)n_ids);
-    std::unique_lock<std::shared_mutex> lk(idx->mu);
-    if (!idx->single_block())
-        return fail(CMR_ERR_UNSUPPORTED, "row removal on an index with a block table of %d blocks (cmr_index_set_id_blocks): the owner of the table removes (cmr_mindex_remove_ids)",
-                    (int)idx->blk_local.size());
-    return remove_ids_locked(idx, ids, n_ids, n_removed);
-}
-
-// ---- in-place row update (include/comorag_hip.h: cmr_index_update_rows; update_rows_kernel in aux_kernels.hip).
-// The exclusive lock is held by the caller.  Entry i of the plan replaces local row dst[i] (strictly ascending) by source row src[i] of
-// `rows` [n_rows, dim] — host memory, or device memory (on_device: read in place, one chunk).  phases: CMR_UPD_CHECK runs the check
-// launch over every winning row and reports the flag, CMR_UPD_WRITE scatters and folds the maxima; both at once is the one-index call,
-// which reads the flag once at the end when everything fits one chunk (the scatter and the maxima return on a raised flag by
-// themselves) and runs all checks before the first store otherwise.
-static int update_planned_locked(cmr_index* idx, const int64_t* dst, const int64_t* src, long long m, const float* rows, long long n_rows,
-                                 bool on_device, hipStream_t s, int phases) {
-    if (phases & CMR_UPD_WRITE) idx->upd_chunks_last = 0;
-    if (m <= 0) return CMR_OK;
-    for (long long i = 0; i < m; ++i)      // the plan is the only thing between the launches and memory that is not theirs
-        if (dst[i] < 0 || dst[i] >= idx->n || (i && dst[i] <= dst[i - 1]) || src[i] < 0 || src[i] >= n_rows)
-            return fail(CMR_ERR_INVALID, "row update: plan entry %lld (row %lld of %lld <- source row %lld of %lld) out of range or out of order", i,
-                        (long long)dst[i], idx->n, (long long)src[i], n_rows);
-    int rc = cmr_set_device(idx->device);
-    if (rc) return rc;
-    // searches hold the shared lock only while they enqueue (_dev, pipelined): whatever is in flight on the device reads the rows as they are now
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t row_bytes = (size_t)idx->dim * 4;
-    const bool both = phases == (CMR_UPD_CHECK | CMR_UPD_WRITE);
-    // chunks: the source rows go through the staging buffer upd_stage_rows (default: 256 MiB worth) at a time; a chunk's entries are the
-    // plan's entries whose source row lies in it, in the plan's order (ascending rows still), and only the span they use is uploaded
-    const long long chunk_rows = on_device ? std::max<long long>(1, n_rows) : idx->upd_stage_rows ? idx->upd_stage_rows : std::max<long long>(1, (256ll << 20) / (long long)row_bytes);
-    const long long n_chunks = (n_rows + chunk_rows - 1) / chunk_rows;
-    std::vector<long long> at((size_t)n_chunks + 1, 0), lo((size_t)n_chunks, n_rows), hi((size_t)n_chunks, -1);
-    for (long long i = 0; i < m; ++i) {
-        const size_t c = (size_t)(src[i] / chunk_rows);
-        ++at[c + 1]; lo[c] = std::min<long long>(lo[c], src[i]); hi[c] = std::max<long long>(hi[c], src[i]);
-    }
-    if (on_device) lo[0] = 0;
-    for (long long c = 0; c < n_chunks; ++c) at[(size_t)c + 1] += at[(size_t)c];
-    std::vector<long long> plan((size_t)2 * m);      // [dst[m] | src[m], relative to the chunk's first uploaded row], chunk by chunk
-    {
-        std::vector<long long> fill(at.begin(), at.end() - 1);
-        for (long long i = 0; i < m; ++i) {
-            const size_t c = (size_t)(src[i] / chunk_rows);
-            const long long o = fill[c]++;
-            plan[(size_t)o] = dst[i]; plan[(size_t)(m + o)] = src[i] - lo[c];
-        }
-    }
-    long long used = 0;
-    for (long long c = 0; c < n_chunks; ++c) used += at[(size_t)c + 1] > at[(size_t)c];
-    const bool mapped = !on_device && used == 1 && idx->zero_copy && !idx->upd_stage_rows && (size_t)n_rows * row_bytes <= kMappedAppendMax && (size_t)m * 16 <= kMappedPlanMax;
-    const long long* d_dst = nullptr; const long long* d_src = nullptr;
-    int* flag = nullptr;
-    char* h = nullptr;
-    if (mapped) {      // rows, plan and flag in the append's pinned, device-mapped buffer: no copy in front of the launches, no flag copy behind
-        { int rc_ = ensure_h_pin(idx); if (rc_) return rc_; }
-        h = (char*)idx->h_pin;
-        char* d = (char*)idx->h_pin_dev;
-        memset(h, 0, 8);
-        memcpy(h + 256 + kMappedAppendMax, plan.data(), (size_t)m * 16);
-        flag = (int*)d;
-        d_dst = (const long long*)(d + 256 + kMappedAppendMax); d_src = d_dst + m;
-    } else {
-        HIP_TRY(idx->rm_buf.ensure((size_t)m * 16));
-        HIP_TRY(hipMemcpy(idx->rm_buf.p, plan.data(), (size_t)m * 16, hipMemcpyHostToDevice));
-        flag = idx->d_flag;
-        HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), s));
-        d_dst = (const long long*)idx->rm_buf.p; d_src = d_dst + m;
-        if (!on_device) {
-            long long span = 0;
-            for (long long c = 0; c < n_chunks; ++c) span = std::max(span, hi[(size_t)c] - lo[(size_t)c] + 1);
-            hipError_t e = idx->stage.ensure((size_t)span * row_bytes);
-            if (e != hipSuccess) return fail(CMR_ERR_OOM, "row update staging: %s", hipGetErrorString(e));
-        }
-    }
-    // the chunk's source rows where the launches read them
-    auto stage_chunk = [&](long long c, const float** out) -> int {
-        if (on_device) { *out = rows; return CMR_OK; }
-        const size_t bytes = (size_t)(hi[(size_t)c] - lo[(size_t)c] + 1) * row_bytes;
-        const float* from = rows + (size_t)lo[(size_t)c] * idx->dim;
-        if (mapped) { memcpy(h + 256, from, bytes); *out = (const float*)((char*)idx->h_pin_dev + 256); return CMR_OK; }
-        HIP_TRY(hipMemcpyAsync(idx->stage.p, from, bytes, hipMemcpyHostToDevice, s));
-        *out = (const float*)idx->stage.p;
-        return CMR_OK;
-    };
-    auto read_flag = [&](int* out) -> int {
-        if (mapped) { HIP_TRY(hipStreamSynchronize(s)); memcpy(out, h, sizeof(int)); return CMR_OK; }
-        HIP_TRY(hipMemcpyAsync(out, flag, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return CMR_OK;
-    };
-    auto write_chunk = [&](long long c, const float* r) -> int {
-        const long long o = at[(size_t)c], mc = at[(size_t)c + 1] - o;
-        HIP_TRY(cmr_launch_update_rows(idx->dtype, false, r, d_dst + o, d_src + o, mc, idx->dim, idx->dpad, idx->corpus, idx->shadow, flag, s));
-        HIP_TRY(cmr_launch_round_stats(idx->dtype, r, mc, idx->dim, flag, idx->d_stats, s, d_src + o));
-        ++idx->upd_chunks_last;
-        return CMR_OK;
-    };
-    const char* const nonfinite = "updated rows contain NaN/Inf or a value that rounds to Inf in the index dtype (index unchanged)";
-    int flagged = 0;
-    const bool one_pass = both && used == 1;
-    if (phases & CMR_UPD_CHECK) {
-        for (long long c = 0; c < n_chunks; ++c) {
-            const long long o = at[(size_t)c], mc = at[(size_t)c + 1] - o;
-            if (!mc) continue;
-            const float* r = nullptr;
-            if ((rc = stage_chunk(c, &r))) return rc;
-            HIP_TRY(cmr_launch_update_rows(idx->dtype, true, r, d_dst + o, d_src + o, mc, idx->dim, idx->dpad, nullptr, nullptr, flag, s));
-            if (one_pass) {      // the same upload feeds the stores: they return on the flag the check launch in front of them raised
-                idx->q8c.rows = std::min<long long>(idx->q8c.rows, dst[0]);
-                if ((rc = write_chunk(c, r))) return rc;
-            }
-        }
-        if ((rc = read_flag(&flagged))) return rc;
-        if (flagged) { idx->upd_chunks_last = 0; return fail(CMR_ERR_NONFINITE, "%s", nonfinite); }
-        if (one_pass) return CMR_OK;
-    }
-    if (phases & CMR_UPD_WRITE) {
-        // from the first store on the int8 companion is stale behind the first updated row: the next pre-filtered call quantises again from its panel
-        idx->q8c.rows = std::min<long long>(idx->q8c.rows, dst[0]);
-        for (long long c = 0; c < n_chunks; ++c) {
-            if (at[(size_t)c + 1] == at[(size_t)c]) continue;
-            const float* r = nullptr;
-            if ((rc = stage_chunk(c, &r))) return rc;
-            if ((rc = write_chunk(c, r))) return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return CMR_OK;
-}
-
-// one shard's share of cmr_mindex_update_rows (multi.hip plans and owns the block tables): local rows, ascending, and the source rows they take
-int cmr_index_update_planned(cmr_index_t* idx, const int64_t* local_rows, const int64_t* src, int64_t m, const float* rows, int64_t n_rows, int phases) {
-    if (!idx || m < 0 || (m > 0 && (!local_rows || !src || !rows))) return fail(CMR_ERR_INVALID, "bad argument");
-    std::unique_lock<std::shared_mutex> lk(idx->mu);
-    return update_planned_locked(idx, local_rows, src, m, rows, n_rows, false, nullptr, phases);
-}
-
-static int32_t update_rows_entry(cmr_index_t* idx, const int64_t* ids, const float* rows, int64_t n, bool on_device, void* stream, int64_t* n_updated) {
-    if (n_updated) *n_updated = 0;
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    if (n < 0) return fail(CMR_ERR_INVALID, "n %lld < 0", (long long)n);
-    if (n > 0 && (!ids || !rows)) return fail(CMR_ERR_INVALID, "NULL ids or rows with n = %lld", (long long)n);
-    std::unique_lock<std::shared_mutex> lk(idx->mu);
-    idx->upd_chunks_last = 0;
-    if (n == 0 || idx->n == 0) return CMR_OK;
-    // the one id parser (cmr_mindex_plan_update): this index is its one-shard case, id base or block table as shard 0's table
-    const int64_t rows_of = idx->n, zero = 0, base = idx->id_base;
-    const int32_t nb = idx->single_block() ? 1 : (int32_t)idx->blk_local.size();
-    const int64_t* bl = idx->single_block() ? &zero : (const int64_t*)idx->blk_local.data();
-    const int64_t* bg = idx->single_block() ? &base : (const int64_t*)idx->blk_global.data();
-    std::vector<int32_t> shard((size_t)n);
-    std::vector<int64_t> local((size_t)n), src((size_t)n);
-    int64_t count = 0, m = 0;
-    int rc = cmr_mindex_plan_update(1, &rows_of, &nb, bl, bg, ids, n, shard.data(), local.data(), src.data(), &count, &m);
-    if (rc) return rc;
-    rc = update_planned_locked(idx, local.data(), src.data(), m, rows, n, on_device, (hipStream_t)stream, CMR_UPD_CHECK | CMR_UPD_WRITE);
-    if (!rc && n_updated) *n_updated = m;
-    return rc;
-}
-
-extern "C" int32_t cmr_index_update_rows(cmr_index_t* idx, const int64_t* ids, const float* rows_f32, int64_t n, int64_t* n_updated) {
-    return update_rows_entry(idx, ids, rows_f32, n, false, nullptr, n_updated);
-}
-
-extern "C" int32_t cmr_index_update_rows_dev(cmr_index_t* idx, const int64_t* ids_host, const float* rows_f32_dev, int64_t n, void* stream, int64_t* n_updated) {
-    return update_rows_entry(idx, ids_host, rows_f32_dev, n, true, stream, n_updated);
-}
-
 extern "C" {
 
 static int32_t host_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores,
@@ -1833,147 +1401,10 @@ int32_t cmr_index_search(cmr_index_t* idx, const float* q, int32_t nq, int32_t k
     return combine_result(r);
 }
 
-// ---- filtered host calls.  With "combine" >= 2 AND "combine_filtered" = 1, concurrent cmr_index_search_masked /
-// cmr_index_search_masked_each calls of one k and one word count share ONE per-query-mask search: the leader lays the participants'
-// queries and masks out as one [total][n_words] block (a shared-mask participant's words once per query of its own) and scatters the
-// rows, which hold the bits of each caller's solo call (4.15b's contract).  A batch of one is the caller's own call, unchanged.
-// each = false: `allow` is [n_words], one mask for every query; each = true: [nq][n_words]
-// min_score: the filtered threshold search (cmr_index_search_min_score_masked), which never queues
-struct CombinedMasked : CombinedSearch { const uint32_t* allow; int64_t n_words; bool each; const float* min_score = nullptr; };
-static const CombinedMasked* masked_args(const cmr_combine::Request* r) { return static_cast<const CombinedMasked*>(search_args(r)); }
-
-// The synchronous filtered search behind cmr_index_search_masked and cmr_index_search_masked_each: the packed round trip (packed_begin)
-// with the queries and the allow words as inputs.  The caller holds the index's shared lock and has checked the arguments under it
-// (masked_check), so the pending call takes none.
-static int masked_call(cmr_index* idx, const CombinedMasked& a) {
-    const PackedInput in[] = {{&Workspace::d_q, a.q, (size_t)a.nq * idx->dim * 4},
-                              {&Workspace::d_mask, a.allow, (size_t)a.n_words * 4 * (a.each ? (size_t)a.nq : 1)}};
-    CmrPending* p = nullptr;
-    const int rc = packed_begin(idx, a.nq, a.k, false, in, [&](Workspace* ws, int64_t* ids, float* sc, float* mn, float* mx) {
-        return search_masked_enqueue(idx, ws, (const float*)ws->d_q.p, a.nq, a.k, (const unsigned*)ws->d_mask.p, ids, sc, mn, mx, a.each ? (long long)a.n_words : 0,
-                                     a.min_score);
-    }, &p);
-    return rc ? rc : cmr_index_search_finish(p, a.ids, a.scores, a.mn, a.mx);
-}
-
-static int masked_single(cmr_index* idx, const CombinedMasked& a) {
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    const int rc = masked_check(idx, a.nq, a.k, a.n_words);
-    return rc ? rc : masked_call(idx, a);
-}
-
-// one lock for the batch; every participant's word count is judged under it (an append may have come in since it queued) and a
-// participant that fails is answered alone
-static void combined_masked_run(void* ctx, cmr_combine::Request** reqs, int n) {
-    cmr_index* const idx = (cmr_index*)ctx;
-    if (n == 1) { combine_answer(reqs[0], masked_single(idx, *masked_args(reqs[0]))); return; }
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    cmr_combine::Request* live[cmr_combine::kMaxWidth];
-    int nl = 0;
-    for (int i = 0; i < n; ++i) {
-        const CombinedMasked* a = masked_args(reqs[i]);
-        const int rc = masked_check(idx, a->nq, a->k, a->n_words);
-        if (rc) { combine_answer(reqs[i], rc); continue; }
-        live[nl++] = reqs[i];
-    }
-    if (nl == 0) return;
-    if (nl == 1) { combine_answer(live[0], masked_call(idx, *masked_args(live[0]))); return; }
-    const CombinedTopk b(live, nl, (size_t)idx->dim);
-    const size_t nw = (size_t)masked_args(live[0])->n_words;      // (k and the word count are part of the batch's key)
-    std::vector<uint32_t> words((size_t)b.all.nq * nw);
-    for (int i = 0, at = 0; i < nl; at += live[i++]->nq) {
-        const CombinedMasked* a = masked_args(live[i]);
-        for (int qi = 0; qi < a->nq; ++qi) memcpy(words.data() + (size_t)(at + qi) * nw, a->allow + (a->each ? (size_t)qi * nw : 0), nw * 4);
-    }
-    b.answer(live, nl, masked_call(idx, CombinedMasked{b.all, words.data(), (int64_t)nw, true}));
-}
-
-static int32_t host_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words, bool each,
-                           int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
-    if (!idx || !q || !allow || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    const CombinedMasked a{{q, nq, k, out_ids, out_scores, out_min, out_max}, allow, n_words, each};
-    const int W = idx->combine_filtered.load(std::memory_order_relaxed) ? idx->combine.load(std::memory_order_relaxed) : 0;
-    // joins a batch: as cmr_index_search — fewer queries than the batch holds, arguments that pass the checks which need no lock, finite queries
-    // (the batch carries one non-finite flag); everything else takes the single call and gets its result or its error there
-    if (!W || nq <= 0 || nq >= W || k <= 0 || k > CMR_MAX_K || n_words <= 0 || !cmr_combine::all_finite(q, (size_t)nq * idx->dim, idx->dtype))
-        return masked_single(idx, a);
-    {   // a word count the index refuses gets its error here, alone (the lock is let go before the call queues: a queued caller holds none)
-        std::shared_lock<std::shared_mutex> lk(idx->mu);
-        const int rc = masked_check(idx, nq, k, n_words);
-        if (rc) return rc;
-    }
-    cmr_combine::Request r;
-    r.args = (void*)static_cast<const CombinedSearch*>(&a); r.nq = nq;      // (what search_args / masked_args read)
-    cmr_combine::Key key;
-    key.w[0] = 5; key.w[1] = (uint64_t)k; key.w[2] = (uint64_t)n_words;      // (one kind for both forms: they share batches; never with kind 1, the unfiltered search)
-    idx->combiner.submit(key, &r, W, idx->combine_wait_us.load(std::memory_order_relaxed), combined_masked_run, idx);
-    return combine_result(r);
-}
-
-int32_t cmr_index_search_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words,
-                                int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
-    return host_masked(idx, q, nq, k, allow, n_words, false, out_ids, out_scores, out_min, out_max);
-}
-
-int32_t cmr_index_search_masked_each(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_words,
-                                     int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
-    return host_masked(idx, q, nq, k, allow, n_words, true, out_ids, out_scores, out_min, out_max);
-}
-
 int32_t cmr_index_search_min_score(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, float min_score, int64_t* out_ids,
                                    float* out_scores) {
-    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (int rc_ = cmr_min_score_check(min_score)) return rc_;
     return host_search(idx, q, nq, k, out_ids, out_scores, nullptr, nullptr, &min_score);
-}
-
-// ---- filtered threshold search: the masked / id-list searches above with the bound as every query's initial threshold.
-// Never combined: the words form is masked_single whatever "combine_filtered" says.
-// every check of the words forms that needs neither the index nor a device (n_words against the index: words_check, under its lock)
-static int mask_words_args_check(const void* allow, int nq, int64_t n_words, int n_masks) {
-    if (!allow) return fail(CMR_ERR_INVALID, "NULL allow words");
-    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
-    if (n_words < 0) return fail(CMR_ERR_INVALID, "n_words %lld < 0", (long long)n_words);
-    if (n_masks != 1 && n_masks != nq) return fail(CMR_ERR_INVALID, "n_masks %d is neither 1 nor nq = %d", n_masks, nq);
-    return CMR_OK;
-}
-
-static void threshold_padding(int nq, int k, int64_t* out_ids, float* out_scores) {
-    std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
-    std::fill(out_scores, out_scores + (size_t)nq * k, -INFINITY);
-}
-
-int32_t cmr_index_search_min_score_masked(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, float min_score, const uint32_t* allow, int64_t n_words,
-                                          int32_t n_masks, int64_t* out_ids, float* out_scores) {
-    if (!q || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    int rc = mask_words_args_check(allow, nq, n_words, n_masks);
-    if (rc) return rc;
-    if (k <= 0) return fail(CMR_ERR_INVALID, "k must be > 0");
-    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
-    if (k > CMR_MAX_K) return fail(CMR_ERR_UNSUPPORTED, "filtered threshold search supports k <= %d", CMR_MAX_K);
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    CombinedMasked a{{q, nq, k, out_ids, out_scores, nullptr, nullptr}, allow, n_words, n_masks > 1};
-    a.min_score = &min_score;
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    if ((rc = masked_check(idx, nq, k, n_words))) return rc;
-    if (idx->n == 0) { threshold_padding(nq, k, out_ids, out_scores); return CMR_OK; }      // no row: no device call
-    return masked_call(idx, a);
-}
-
-int32_t cmr_index_search_min_score_ids(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, float min_score, int32_t mode, const int64_t* id_offsets,
-                                       const int64_t* ids, int64_t n_ids, int64_t* out_ids, float* out_scores) {
-    if (!q || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    int rc = cmr_ids_args_check(mode, nq, k, id_offsets, ids, n_ids);
-    if (rc) return rc;
-    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    {
-        std::shared_lock<std::shared_mutex> lk(idx->mu);
-        if (idx->n == 0) { threshold_padding(nq, k, out_ids, out_scores); return CMR_OK; }      // no row: no device call
-    }
-    CmrPending* p = nullptr;
-    rc = cmr_index_search_ids_begin(idx, q, nq, k, mode, id_offsets, ids, n_ids, true, &p, &min_score);
-    if (rc) return rc;
-    return cmr_index_search_finish(p, out_ids, out_scores, nullptr, nullptr);
 }
 
 int32_t cmr_index_scores_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, float* out_dev, int64_t ld, void* stream) {
@@ -2163,350 +1594,6 @@ int32_t cmr_index_sorted_scores(cmr_index_t* idx, const float* q, int32_t nq, in
     return check_query_flag(ws);
 }
 
-// ---- range search: every row at or above a score bound, per query.  Per block of queries: scores_enqueue, count + offsets
-// (range_kernels.hip), ONE small round trip for the per-query counts, then per group of consecutive queries compaction, the stable sort of
-// (query | complemented score code, row) pairs and the gather of ids and score bits — all on the workspace's one stream.
-static int range_block_queries(const cmr_index* idx, int nq, long long ld) {
-    long long b = std::max<long long>(1, std::min<long long>(nq, (1ll << 31) / std::max<long long>(ld * 4, 1)));      // <= 2 GiB of scores
-    if (idx->range_block_queries > 0) b = std::min<long long>(b, idx->range_block_queries);
-    return (int)b;
-}
-static int range_args_check(const void* idx, const void* q, const void* out, int nq, float min_score) {
-    if (!idx || !q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
-    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
-    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
-    return CMR_OK;
-}
-static int range_rows_check(const cmr_index* idx) {
-    return idx->n < (1ll << 32) ? CMR_OK : fail(CMR_ERR_UNSUPPORTED, "range search needs fewer than 2^32 rows, the index holds %lld", idx->n);
-}
-// Filtered range search / count: the filter as the caller gave it (host pointers) ...
-struct RangeFilter {
-    const uint32_t* words = nullptr; int64_t n_words = 0; int n_masks = 0;                                            // the words forms: [n_masks][n_words]
-    bool by_ids = false; int mode = 0; const int64_t* off = nullptr; const int64_t* ids = nullptr; int64_t n_ids = 0;   // the id forms
-};
-// ... and in the call's workspace: the allow words the masked count / compaction kernels read (ws->d_mask).  Words forms and a shared id
-// list: every mask of the call, laid down once.  Per-query id lists (off_dev): the words of ONE block of at most kIdsGroup queries, built in
-// front of the block's count from the lists in ws->d_lists — the scratch never holds more than that many masks.
-struct RangeMasks {
-    unsigned* words = nullptr; long long stride = 0, route = 0;
-    int mode = 0; const int64_t* off_dev = nullptr; const int64_t* ids_dev = nullptr; int64_t n_ids = 0;
-    // the kernels' view for the block whose first query is query q0 of the call
-    CmrRangeMask kernel(int q0) const { return CmrRangeMask{words, stride, off_dev ? 0 : (long long)q0}; }
-};
-// (under the index lock, n > 0, n_words checked by the caller) uploads on ws->stream
-static int range_masks_open(cmr_index* idx, Workspace* ws, const RangeFilter& f, int nq, RangeMasks* mk) {
-    hipStream_t const s = ws->stream;
-    const size_t nw = (size_t)idx->npanels();
-    if (!f.by_ids) {
-        const size_t bytes = (size_t)f.n_masks * nw * 4;
-        HIP_TRY(ws->d_mask.ensure(std::max<size_t>(bytes, 4)));
-        HIP_TRY(hipMemcpyAsync(ws->d_mask.p, f.words, bytes, hipMemcpyHostToDevice, s));
-        mk->words = (unsigned*)ws->d_mask.p;
-        mk->stride = f.n_masks > 1 ? (long long)nw : 0;
-        mk->route = CMR_ROUTE_FILTERED | (f.n_masks > 1 ? CMR_ROUTE_FILTERED_EACH : 0);
-        return CMR_OK;
-    }
-    const size_t off_bytes = f.off ? ((size_t)nq + 1) * 8 : 0, ids_bytes = (size_t)f.n_ids * 8;
-    HIP_TRY(ws->d_lists.ensure(std::max<size_t>(off_bytes + ids_bytes, 8)));
-    if (off_bytes) HIP_TRY(hipMemcpyAsync(ws->d_lists.p, f.off, off_bytes, hipMemcpyHostToDevice, s));
-    if (ids_bytes) HIP_TRY(hipMemcpyAsync((char*)ws->d_lists.p + off_bytes, f.ids, ids_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(ws->d_mask.ensure(std::max<size_t>((size_t)(f.off ? std::min(nq, kIdsGroup) : 1) * nw * 4, 4)));
-    mk->words = (unsigned*)ws->d_mask.p;
-    mk->mode = f.mode; mk->ids_dev = (const int64_t*)((char*)ws->d_lists.p + off_bytes); mk->n_ids = f.n_ids;
-    mk->route = CMR_ROUTE_FILTERED | CMR_ROUTE_FILTERED_IDS | (f.off ? CMR_ROUTE_FILTERED_EACH : 0);
-    if (f.off) { mk->off_dev = (const int64_t*)ws->d_lists.p; mk->stride = (long long)nw; return CMR_OK; }
-    return row_masks_enqueue(idx, f.mode, 1, nullptr, mk->ids_dev, f.n_ids, mk->words, s);
-}
-// scores of nb queries into ws->d_out [nb][ld], the (query, tile) offsets into ws->r_cnt, the per-query counts to counts_dev [nb]
-// mk: only the allowed rows count; the block's first query is query q0 of the call
-static int range_count_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nb, long long ld, unsigned lo, long long* counts_dev,
-                               const RangeMasks* mk = nullptr, int q0 = 0) {
-    HIP_TRY(ws->d_out.ensure((size_t)nb * ld * 4));
-    HIP_TRY(ws->r_cnt.ensure(cmr_range_counter_bytes(idx->n, nb)));
-    int rc = scores_enqueue(idx, ws, q_dev, nb, (float*)ws->d_out.p, ld);
-    if (rc) return rc;
-    idx->last_route.store(route_code(CMR_ROUTE_RANGE) | (mk ? mk->route : 0), std::memory_order_relaxed);
-    if (mk && mk->off_dev && (rc = row_masks_enqueue(idx, mk->mode, nb, mk->off_dev + q0, mk->ids_dev, mk->n_ids, mk->words, ws->stream))) return rc;
-    const CmrRangeMask km = mk ? mk->kernel(q0) : CmrRangeMask{};
-    HIP_TRY(cmr_launch_range_count((const float*)ws->d_out.p, ld, idx->n, nb, lo, (unsigned*)ws->r_cnt.p, counts_dev, ws->stream, mk ? &km : nullptr));
-    return CMR_OK;
-}
-// the counts of a block on the host (the block's round trip), with the non-finite flag of its queries
-static int range_counts_to_host(Workspace* ws, int nb, int64_t* counts) {
-    int flagged = 0;
-    HIP_TRY(hipMemcpyAsync(counts, ws->r_counts.p, (size_t)nb * 8, hipMemcpyDeviceToHost, ws->stream));
-    HIP_TRY(hipMemcpyAsync(&flagged, ws->flag_ptr, sizeof(int), hipMemcpyDeviceToHost, ws->stream));
-    HIP_TRY(hipStreamSynchronize(ws->stream));
-    if (flagged) {
-        HIP_TRY(hipMemsetAsync(ws->flag_ptr, 0, sizeof(int), ws->stream));
-        return fail(CMR_ERR_NONFINITE, "query contains NaN/Inf or a value that rounds to Inf in the index dtype");
-    }
-    return CMR_OK;
-}
-// queries [g0, g1) of the block whose scores and offsets the workspace holds -> their `hits` sorted entries at out_ids / out_scores (host)
-static int range_group(cmr_index* idx, Workspace* ws, long long ld, unsigned lo, int g0, int g1, long long hits, int64_t* out_ids, float* out_scores,
-                       const CmrRangeMask* km = nullptr) {
-    if (hits == 0) return CMR_OK;
-    hipStream_t const s = ws->stream;
-    const size_t h = (size_t)hits;
-    HIP_TRY(ws->r_hits.ensure(h * 24 + cmr_sort_keys64_hist_bytes(hits)));
-    u64 *ka = (u64*)ws->r_hits.p, *kb = ka + h;
-    unsigned *va = (unsigned*)(kb + h), *vb = va + h, *hist = vb + h;
-    HIP_TRY(cmr_launch_range_compact((const float*)ws->d_out.p, ld, idx->n, lo, (const unsigned*)ws->r_cnt.p, g0, g1 - g0, hits, ka, va, s, km));
-    // the four score digits first, then the query digits that can differ inside the group: equal scores keep ascending rows
-    unsigned digits = 0x0Fu;
-    for (unsigned span = (unsigned)(g1 - g0 - 1), p = 4; span; span >>= 8, ++p) digits |= 1u << p;
-    u64* ks = nullptr;
-    unsigned* vs = nullptr;
-    HIP_TRY(cmr_launch_sort_keys64(ka, kb, va, vb, hist, hits, digits, &ks, &vs, s));
-    // ids over the dead key buffer, scores over the dead row buffer
-    int64_t* ids_dev = (int64_t*)(ks == ka ? kb : ka);
-    float* sc_dev = (float*)(vs == va ? vb : va);
-    HIP_TRY(cmr_launch_range_finish(ks, vs, hits, (const float*)ws->d_out.p, ld, g0, kernel_id_base(idx), ids_dev, sc_dev, s));
-    int rc = remap_ids_enqueue(idx, ids_dev, hits, s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_ids, ids_dev, h * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_scores, sc_dev, h * 4, hipMemcpyDeviceToHost, s));
-    return CMR_OK;
-}
-
-int32_t cmr_index_range_count_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, float min_score, int64_t* out_counts_dev, void* stream) {
-    int rc = range_args_check(idx, q_dev, out_counts_dev, nq, min_score);
-    if (rc) return rc;
-    DevCall call(idx);
-    if ((rc = range_rows_check(idx))) return rc;
-    if ((rc = call.open(stream))) return rc;
-    if (idx->n == 0) { HIP_TRY(hipMemsetAsync(out_counts_dev, 0, (size_t)nq * 8, call.ws->stream)); return CMR_OK; }
-    const long long ld = (idx->n + 3) / 4 * 4;
-    const int blockq = range_block_queries(idx, nq, ld);
-    const unsigned lo = cmr_range_bound_code(min_score);
-    for (int q0 = 0; q0 < nq; q0 += blockq)
-        if ((rc = range_count_enqueue(idx, call.ws, q_dev + (size_t)q0 * idx->dim, std::min(blockq, nq - q0), ld, lo, (long long*)out_counts_dev + q0))) return rc;
-    return CMR_OK;
-}
-
-// the arguments are checked; f: the filtered forms (nullptr: every row)
-static int range_count_host(cmr_index* idx, const float* q, int nq, float min_score, int64_t* out_counts, const RangeFilter* f) {
-    int rc;
-    SyncCall call(idx);
-    if ((rc = range_rows_check(idx))) return rc;
-    if (f && !f->by_ids && (rc = words_check(idx, f->n_words))) return rc;
-    if (idx->n == 0) { std::fill(out_counts, out_counts + nq, (int64_t)0); return CMR_OK; }
-    if ((rc = call.open())) return rc;
-    Workspace* const ws = call.ws;
-    const long long ld = (idx->n + 3) / 4 * 4;
-    const int blockq = f && f->by_ids && f->off ? std::min(range_block_queries(idx, nq, ld), kIdsGroup) : range_block_queries(idx, nq, ld);
-    const unsigned lo = cmr_range_bound_code(min_score);
-    HIP_TRY(ws->d_q.ensure((size_t)nq * idx->dim * 4));
-    HIP_TRY(ws->r_counts.ensure((size_t)nq * 8));
-    HIP_TRY(hipMemcpyAsync(ws->d_q.p, q, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, call.s));
-    RangeMasks mk;
-    if (f) rc = range_masks_open(idx, ws, *f, nq, &mk);
-    for (int q0 = 0; q0 < nq && !rc; q0 += blockq)
-        rc = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, std::min(blockq, nq - q0), ld, lo, (long long*)ws->r_counts.p + q0,
-                                 f ? &mk : nullptr, q0);
-    if (rc) { (void)hipStreamSynchronize(call.s); return rc; }
-    return range_counts_to_host(ws, nq, out_counts);
-}
-
-int32_t cmr_index_range_count(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t* out_counts) {
-    const int rc = range_args_check(idx, q, out_counts, nq, min_score);
-    return rc ? rc : range_count_host(idx, q, nq, min_score, out_counts, nullptr);
-}
-
-// the arguments are checked, *out is NULL; f: the filtered forms (nullptr: every row)
-static int range_search_host(cmr_index* idx, const float* q, int nq, float min_score, int64_t max_total, cmr_range_result_t** out, const RangeFilter* f) {
-    int rc;
-    const long long limit = max_total > 0 ? max_total : CMR_RANGE_MAX_TOTAL;
-    SyncCall call(idx);
-    if ((rc = range_rows_check(idx))) return rc;
-    if (f && !f->by_ids && (rc = words_check(idx, f->n_words))) return rc;
-    std::unique_ptr<cmr_range_result> res(new cmr_range_result());
-    res->nq = nq;
-    res->lims = new int64_t[(size_t)nq + 1]();
-    if (idx->n == 0) { *out = res.release(); return CMR_OK; }
-    if ((rc = call.open())) return rc;
-    Workspace* const ws = call.ws;
-    hipStream_t const s = call.s;
-    const long long ld = (idx->n + 3) / 4 * 4;
-    // (per-query id lists: a block is at most one group of masks)
-    const int blockq = f && f->by_ids && f->off ? std::min(range_block_queries(idx, nq, ld), kIdsGroup) : range_block_queries(idx, nq, ld);
-    const int nblocks = (nq + blockq - 1) / blockq;
-    const unsigned lo = cmr_range_bound_code(min_score);
-    const long long cap_hits = idx->range_scratch_hits > 0 ? idx->range_scratch_hits : (1ll << 30) / 24;
-    HIP_TRY(ws->d_q.ensure((size_t)nq * idx->dim * 4));
-    HIP_TRY(ws->r_counts.ensure((size_t)blockq * 8));
-    HIP_TRY(hipMemcpyAsync(ws->d_q.p, q, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, s));
-    std::vector<int64_t> counts((size_t)nq);
-    long long groups = 0;
-    RangeMasks mk;
-    const RangeMasks* const mkp = f ? &mk : nullptr;
-    if (f && (rc = range_masks_open(idx, ws, *f, nq, &mk))) { (void)hipStreamSynchronize(s); return rc; }
-    auto count_block = [&](int q0, int nb) -> int {
-        int rc_ = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, nb, ld, lo, (long long*)ws->r_counts.p, mkp, q0);
-        if (!rc_) rc_ = range_counts_to_host(ws, nb, counts.data() + q0);
-        return rc_;
-    };
-    // the size of the result is known once every block is counted, and the limit is judged before anything is allocated, compacted or
-    // sorted: a batch of one block counts once; a batch of several counts them all first and scans each block again for its lists
-    auto body = [&]() -> int {
-        for (int q0 = 0; q0 < nq; q0 += blockq) { int rc_ = count_block(q0, std::min(blockq, nq - q0)); if (rc_) return rc_; }
-        long long total = 0;
-        for (int i = 0; i < nq; ++i) { total += counts[i]; res->lims[i + 1] = total; }
-        if (total > limit)
-            return fail(CMR_ERR_UNSUPPORTED, "range search: the batch has %lld hits, above the limit of %lld (cmr_index_range_count sizes a request)", total, limit);
-        res->ids = new int64_t[(size_t)std::max<long long>(total, 1)];
-        res->scores = new float[(size_t)std::max<long long>(total, 1)];
-        for (int q0 = 0; q0 < nq; q0 += blockq) {
-            const int nb = std::min(blockq, nq - q0);
-            if (res->lims[q0 + nb] == res->lims[q0]) continue;          // no hit in the block
-            if (nblocks > 1) {      // the workspace holds the last block's scores (and words): this block's again (same launches, same bits)
-                int rc_ = range_count_enqueue(idx, ws, (const float*)ws->d_q.p + (size_t)q0 * idx->dim, nb, ld, lo, (long long*)ws->r_counts.p, mkp, q0);
-                if (rc_) return rc_;
-            }
-            const CmrRangeMask km = mkp ? mk.kernel(q0) : CmrRangeMask{};
-            for (int g0 = 0; g0 < nb;) {      // groups of consecutive queries of at most cap_hits hits; a query is never split
-                int g1 = g0 + 1;
-                long long hits = counts[q0 + g0];
-                while (g1 < nb && hits + counts[q0 + g1] <= cap_hits) hits += counts[q0 + g1++];
-                if (hits) {
-                    ++groups;
-                    int rc_ = range_group(idx, ws, ld, lo, g0, g1, hits, res->ids + res->lims[q0 + g0], res->scores + res->lims[q0 + g0], mkp ? &km : nullptr);
-                    if (rc_) return rc_;
-                }
-                g0 = g1;
-            }
-        }
-        return CMR_OK;
-    };
-    rc = body();
-    const hipError_t e = hipStreamSynchronize(s);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(CMR_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
-    idx->range_blocks_last.store(nblocks, std::memory_order_relaxed);
-    idx->range_groups_last.store(groups, std::memory_order_relaxed);
-    *out = res.release();
-    return CMR_OK;
-}
-
-int32_t cmr_index_range_search(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t max_total, cmr_range_result_t** out) {
-    if (out) *out = nullptr;
-    const int rc = range_args_check(idx, q, out, nq, min_score);
-    return rc ? rc : range_search_host(idx, q, nq, min_score, max_total, out, nullptr);
-}
-
-// ---- filtered range search / count: the calls above among the rows an allow bitmap or id lists keep.  Every check that
-// needs no index comes first, the handle last (as cmr_index_search_ids).
-static int range_words_check(const void* idx, const void* q, const void* out, int nq, float min_score, const uint32_t* allow, int64_t n_words, int n_masks,
-                             RangeFilter* f) {
-    if (!q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
-    int rc = mask_words_args_check(allow, nq, n_words, n_masks);
-    if (rc) return rc;
-    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    f->words = allow; f->n_words = n_words; f->n_masks = n_masks;
-    return CMR_OK;
-}
-static int range_ids_check(const void* idx, const void* q, const void* out, int nq, float min_score, int mode, const int64_t* off, const int64_t* ids, int64_t n_ids) {
-    if (!q || !out) return fail(CMR_ERR_INVALID, "NULL argument");
-    int rc = cmr_ids_args_check(mode, nq, 1, off, ids, n_ids);
-    if (rc) return rc;
-    if (!(min_score == min_score)) return fail(CMR_ERR_INVALID, "min_score is NaN");
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    return CMR_OK;
-}
-static RangeFilter range_ids_filter(int mode, const int64_t* off, const int64_t* ids, int64_t n_ids) {
-    RangeFilter f;
-    f.by_ids = true; f.mode = mode; f.off = off; f.ids = ids; f.n_ids = n_ids;
-    return f;
-}
-
-int32_t cmr_index_range_count_masked(cmr_index_t* idx, const float* q, int32_t nq, float min_score, const uint32_t* allow, int64_t n_words, int32_t n_masks,
-                                     int64_t* out_counts) {
-    RangeFilter f;
-    const int rc = range_words_check(idx, q, out_counts, nq, min_score, allow, n_words, n_masks, &f);
-    return rc ? rc : range_count_host(idx, q, nq, min_score, out_counts, &f);
-}
-
-int32_t cmr_index_range_count_ids(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
-                                  int64_t n_ids, int64_t* out_counts) {
-    const int rc = range_ids_check(idx, q, out_counts, nq, min_score, mode, id_offsets, ids, n_ids);
-    if (rc) return rc;
-    const RangeFilter f = range_ids_filter(mode, id_offsets, ids, n_ids);
-    return range_count_host(idx, q, nq, min_score, out_counts, &f);
-}
-
-int32_t cmr_index_range_search_masked(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t max_total, const uint32_t* allow, int64_t n_words,
-                                      int32_t n_masks, cmr_range_result_t** out) {
-    if (out) *out = nullptr;
-    RangeFilter f;
-    const int rc = range_words_check(idx, q, out, nq, min_score, allow, n_words, n_masks, &f);
-    return rc ? rc : range_search_host(idx, q, nq, min_score, max_total, out, &f);
-}
-
-int32_t cmr_index_range_search_ids(cmr_index_t* idx, const float* q, int32_t nq, float min_score, int64_t max_total, int32_t mode, const int64_t* id_offsets,
-                                   const int64_t* ids, int64_t n_ids, cmr_range_result_t** out) {
-    if (out) *out = nullptr;
-    const int rc = range_ids_check(idx, q, out, nq, min_score, mode, id_offsets, ids, n_ids);
-    if (rc) return rc;
-    const RangeFilter f = range_ids_filter(mode, id_offsets, ids, n_ids);
-    return range_search_host(idx, q, nq, min_score, max_total, out, &f);
-}
-
-int32_t cmr_range_result_view(const cmr_range_result_t* res, int32_t* nq, const int64_t** lims, const int64_t** ids, const float** scores) {
-    if (!res) return fail(CMR_ERR_INVALID, "NULL result");
-    if (nq) *nq = res->nq;
-    if (lims) *lims = res->lims;
-    if (ids) *ids = res->ids;
-    if (scores) *scores = res->scores;
-    return CMR_OK;
-}
-
-int32_t cmr_range_result_destroy(cmr_range_result_t* res) {
-    delete res;
-    return CMR_OK;
-}
-
-// per query an S-way merge of lists that are each in the exported order (score descending through the canonical comparison, then id
-// ascending); the scores keep their bits
-int32_t cmr_range_merge(int32_t n_shards, int32_t nq, const int64_t* const* lims, const int64_t* const* ids, const float* const* scores, int64_t* out_lims,
-                        int64_t* out_ids, float* out_scores) {
-    if (n_shards <= 0 || nq <= 0) return fail(CMR_ERR_INVALID, "n_shards and nq must be > 0");
-    if (!lims || !ids || !scores || !out_lims) return fail(CMR_ERR_INVALID, "NULL argument");
-    long long total = 0;
-    for (int a = 0; a < n_shards; ++a) {
-        if (!lims[a]) return fail(CMR_ERR_INVALID, "NULL lims of shard %d", a);
-        if (lims[a][nq] > 0 && (!ids[a] || !scores[a])) return fail(CMR_ERR_INVALID, "NULL lists of shard %d", a);
-        total += lims[a][nq];
-    }
-    if (total > 0 && (!out_ids || !out_scores)) return fail(CMR_ERR_INVALID, "NULL output");
-    std::vector<int64_t> head((size_t)n_shards);
-    int64_t at = 0;
-    out_lims[0] = 0;
-    for (int qi = 0; qi < nq; ++qi) {
-        for (int a = 0; a < n_shards; ++a) head[a] = lims[a][qi];
-        for (;;) {
-            int best = -1;
-            float bs = 0.0f;
-            int64_t bi = 0;
-            for (int a = 0; a < n_shards; ++a) {
-                if (head[a] >= lims[a][qi + 1]) continue;
-                const float sc = scores[a][head[a]] + 0.0f;
-                const int64_t id = ids[a][head[a]];
-                if (best < 0 || sc > bs || (sc == bs && id < bi)) { best = a; bs = sc; bi = id; }
-            }
-            if (best < 0) break;
-            out_ids[at] = bi;
-            out_scores[at] = scores[best][head[best]];
-            ++at;
-            ++head[best];
-        }
-        out_lims[qi + 1] = at;
-    }
-    return CMR_OK;
-}
-
 int32_t cmr_index_rescore(cmr_index_t* idx, const float* q, int32_t nq, const int64_t* cand, int32_t n_cand, int32_t k,
                           int64_t* out_ids, float* out_scores) {
     if (!idx || !q || !cand || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
@@ -2564,131 +1651,6 @@ int32_t cmr_index_rescore(cmr_index_t* idx, const float* q, int32_t nq, const in
     HIP_TRY(hipMemcpyAsync(out_ids, ws->d_ids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out_scores, ws->d_scores.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    return CMR_OK;
-}
-
-// ---- exact fp32 top-k of a 16-bit index (include/comorag_hip.h: cmr_index_search_exact)
-namespace {
-
-int exact_scratch(ExactScratch* X, int nq, int kc, int k, bool outs, hipStream_t s) {
-    HIP_TRY(X->ids.ensure((size_t)nq * kc * 8));
-    HIP_TRY(X->sc.ensure((size_t)nq * kc * 4));
-    HIP_TRY(X->part.ensure(cmr_exact_part_bytes(nq, kc)));
-    if ((size_t)nq * sizeof(int) > X->arrive.cap || !X->arrive.p) {      // arrival counters: zeroed once, re-armed by the kernel
-        HIP_TRY(X->arrive.ensure((size_t)nq * sizeof(int)));
-        HIP_TRY(hipMemsetAsync(X->arrive.p, 0, X->arrive.cap, s));
-    }
-    if (outs) {
-        HIP_TRY(X->oids.ensure((size_t)nq * k * 8));
-        HIP_TRY(X->osc.ensure((size_t)nq * k * 4));
-        HIP_TRY(X->oex.ensure((size_t)nq * 4));
-    }
-    return CMR_OK;
-}
-
-// re-score + certify the stage-1 lists in X (global ids, as every search returns them) on `s`; output ids translated like any search's
-int exact_certify_enqueue(cmr_index* idx, ExactScratch* X, const float* q_dev, int nq, int kc, int k, int64_t* ids_dev, float* scores_dev,
-                          int* exact_dev, hipStream_t s) {
-    const int nb = (int)idx->blk_local.size();
-    HIP_TRY(cmr_launch_exact_certify(idx->dtype, idx->shadow, idx->dim, idx->n, kernel_id_base(idx), nb > 1 ? idx->d_blk : nullptr, nb, q_dev, nq,
-                                     (const int64_t*)X->ids.p, (const float*)X->sc.p, kc, k, idx->d_stats, X->part.p, (int*)X->arrive.p,
-                                     ids_dev, scores_dev, exact_dev, s));
-    return remap_ids_enqueue(idx, ids_dev, (long long)nq * k, s);
-}
-
-int exact_check(const cmr_index* idx, int k) {
-    if (k <= 0 || k > 64) return fail(CMR_ERR_UNSUPPORTED, "exact search supports k in [1, 64], got %d", k);
-    if (idx->dtype == CMR_F32) return CMR_OK;
-    if (!(idx->flags & CMR_FLAG_KEEP_F32)) return fail(CMR_ERR_UNSUPPORTED, "exact search of a 16-bit index needs CMR_FLAG_KEEP_F32 (the fp32 shadow)");
-    if (idx->exact_cand <= k) return fail(CMR_ERR_UNSUPPORTED, "exact_cand %d must be > k %d", idx->exact_cand, k);
-    return CMR_OK;
-}
-
-}  // namespace
-
-int32_t cmr_index_search_exact(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores, int32_t* out_exact) {
-    if (!idx || !q || !out_ids || !out_scores || !out_exact) return fail(CMR_ERR_INVALID, "NULL argument");
-    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
-    { int rc_ = exact_check(idx, k); if (rc_) return rc_; }
-    if (idx->dtype == CMR_F32) {      // an fp32 index ranks with fp32 arithmetic already: the plain search is the exact one
-        const int rc = host_search(idx, q, nq, k, out_ids, out_scores, nullptr, nullptr, nullptr);
-        if (rc) return rc;
-        for (int i = 0; i < nq; ++i) out_exact[i] = 1;
-        return CMR_OK;
-    }
-    SyncCall call(idx);
-    int rc = call.open();
-    if (rc) return rc;
-    Workspace* const ws = call.ws;
-    hipStream_t const s = call.s;
-    ExactScratch* X = &ws->x;
-    // one stage: top-kc of the 16-bit scan, re-score + certify, results to the host
-    auto stage = [&](const float* qh, int n_q, int kc, int64_t* oi, float* os, int32_t* oe) -> int {
-        HIP_TRY(ws->d_q.ensure((size_t)n_q * idx->dim * 4));
-        HIP_TRY(hipMemcpyAsync(ws->d_q.p, qh, (size_t)n_q * idx->dim * 4, hipMemcpyHostToDevice, s));
-        int rc_ = exact_scratch(X, n_q, kc, k, true, s);
-        if (!rc_) rc_ = arm_flag(ws, s);
-        if (!rc_) rc_ = search_enqueue(idx, ws, (const float*)ws->d_q.p, n_q, kc, (int64_t*)X->ids.p, (float*)X->sc.p, nullptr, nullptr);
-        if (!rc_) rc_ = exact_certify_enqueue(idx, X, (const float*)ws->d_q.p, n_q, kc, k, (int64_t*)X->oids.p, (float*)X->osc.p, (int*)X->oex.p, s);
-        if (rc_) { (void)hipStreamSynchronize(s); return rc_; }
-        HIP_TRY(hipMemcpyAsync(oi, X->oids.p, (size_t)n_q * k * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(os, X->osc.p, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(oe, X->oex.p, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
-        return check_query_flag(ws);     // (synchronises)
-    };
-    rc = stage(q, nq, idx->exact_cand, out_ids, out_scores, out_exact);
-    if (rc) return rc;
-    // stage 2: the queries stage 1 could not certify, again from the two-pass search's CMR_MAX_K_2PASS candidates
-    std::vector<int> u;
-    for (int i = 0; i < nq; ++i) if (!out_exact[i]) u.push_back(i);
-    if (u.empty() || idx->n <= idx->exact_cand) return CMR_OK;
-    const int nu = (int)u.size(), kc2 = (int)std::min<long long>(CMR_MAX_K_2PASS, idx->n), d = idx->dim;
-    std::vector<float> q2((size_t)nu * d);
-    std::vector<int64_t> i2((size_t)nu * k);
-    std::vector<float> s2((size_t)nu * k);
-    std::vector<int32_t> e2((size_t)nu);
-    for (int j = 0; j < nu; ++j) memcpy(&q2[(size_t)j * d], q + (size_t)u[j] * d, (size_t)d * 4);
-    rc = stage(q2.data(), nu, kc2, i2.data(), s2.data(), e2.data());
-    if (rc) return rc;
-    for (int j = 0; j < nu; ++j) {
-        memcpy(out_ids + (size_t)u[j] * k, &i2[(size_t)j * k], (size_t)k * 8);
-        memcpy(out_scores + (size_t)u[j] * k, &s2[(size_t)j * k], (size_t)k * 4);
-        out_exact[u[j]] = e2[j];
-    }
-    return CMR_OK;
-}
-
-int32_t cmr_index_search_exact_pipelined(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, int64_t* ids_dev, float* scores_dev,
-                                         int32_t* exact_dev, void* wait_event, void** done_event) {
-    if (!idx || !q_dev || !ids_dev || !scores_dev || !exact_dev) return fail(CMR_ERR_INVALID, "NULL argument");
-    if (nq <= 0) return fail(CMR_ERR_INVALID, "nq must be > 0");
-    { int rc_ = exact_check(idx, k); if (rc_) return rc_; }
-    std::shared_lock<std::shared_mutex> lk(idx->mu);
-    int rc = cmr_set_device(idx->device);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> pl(idx->pipe_mu);
-    rc = ensure_pipe(idx);
-    if (rc) return rc;
-    hipStream_t const sq = idx->pipe.st[Pipe::sq];
-    hipEvent_t done = nullptr;
-    if (idx->dtype == CMR_F32) {
-        rc = search_pipelined_enqueue_locked(idx, q_dev, nq, k, ids_dev, scores_dev, nullptr, nullptr, (hipEvent_t)wait_event, &done, nullptr);
-        if (rc) return rc;
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)exact_dev, 1, (size_t)nq, sq));
-    } else {
-        // stage-1 candidates in per-slot scratch: their writers (the merges) and their reader (the re-score) are all on the post stream,
-        // which orders each slot's next use behind this one
-        const int kc = idx->exact_cand;
-        ExactScratch* X = &idx->x_slot[idx->x_next++ % CMR_PIPE_SLOTS];
-        rc = exact_scratch(X, nq, kc, k, false, sq);
-        if (rc) return rc;
-        rc = search_pipelined_enqueue_locked(idx, q_dev, nq, kc, (int64_t*)X->ids.p, (float*)X->sc.p, nullptr, nullptr, (hipEvent_t)wait_event, &done, nullptr);
-        if (rc) return rc;
-        rc = exact_certify_enqueue(idx, X, q_dev, nq, kc, k, ids_dev, scores_dev, exact_dev, sq);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipEventRecord(done, sq));      // (the last slot's main_done, re-recorded behind the re-score)
-    if (done_event) *done_event = (void*)done;
     return CMR_OK;
 }
 
@@ -2818,154 +1780,12 @@ int32_t cmr_profile_collect(cmr_index_t* idx, int64_t* n_launches, double* total
     return CMR_OK;
 }
 
-
-// ---- diversified top-k: maximal marginal relevance (include/comorag_hip.h: cmr_index_search_mmr, cmr_index_mmr_select,
-// cmr_index_pair_scores).  Candidates [nq, F] of ANY search (global ids, -1 / -inf padded) -> their local rows (void
-// positions -1) -> their pair scores with the scan's bits -> the greedy selection, all on the call's stream; only [nq, k] comes back.
-// Never combined, pre-filtered or pipelined.
-static int mmr_args_check(int nq, int F, int k, double lam) {
-    const int bad = cmr_mmr::check_args(nq, F, k, lam, CMR_MAX_K);
-    if (bad == 2) return fail(CMR_ERR_UNSUPPORTED, "fetch_k = %d above CMR_MAX_K = %d", F, CMR_MAX_K);
-    if (bad) return fail(CMR_ERR_INVALID, "need nq >= 1, 1 <= k <= fetch_k and lambda in [0, 1] (nq %d, k %d, fetch_k %d, lambda %g)", nq, k, F, lam);
-    return CMR_OK;
-}
-
-// local rows and pair scores of the candidates ids_dev [nq, F] into ws->m_rows / ws->m_gram; qfrag: see cmr_launch_mmr_gram
-static int mmr_gram_enqueue(cmr_index* idx, Workspace* ws, const int64_t* ids_dev, int nq, int F, const void* qfrag) {
-    hipStream_t const s = ws->stream;
-    const int nb = (int)idx->blk_local.size();
-    HIP_TRY(ws->m_rows.ensure((size_t)nq * F * 8));
-    HIP_TRY(ws->m_gram.ensure((size_t)nq * F * F * 4));
-    HIP_TRY(cmr_launch_mmr_rows(ids_dev, nq, F, idx->n, kernel_id_base(idx), nb > 1 ? idx->d_blk : nullptr, nb, (long long*)ws->m_rows.p, s));
-    HIP_TRY(cmr_launch_mmr_gram(idx->dtype, idx->corpus, qfrag, (const long long*)ws->m_rows.p, nq, F, idx->dpad, (float*)ws->m_gram.p, s));
-    return CMR_OK;
-}
-
-static int mmr_select_enqueue(cmr_index* idx, Workspace* ws, const int64_t* ids_dev, const float* sc_dev, int nq, int F, int k, float lam32,
-                              int64_t* out_ids_dev, float* out_scores_dev) {
-    const int rc = mmr_gram_enqueue(idx, ws, ids_dev, nq, F, nullptr);
-    if (rc) return rc;
-    HIP_TRY(cmr_launch_mmr_select(ids_dev, sc_dev, (const long long*)ws->m_rows.p, (const float*)ws->m_gram.p, nq, F, k, lam32, out_ids_dev,
-                                  out_scores_dev, ws->stream));
-    return CMR_OK;
-}
-
-// the ordinary search for F candidates (whichever route the plan picks) into ws->m_ids / ws->m_sc, then the selection
-static int search_mmr_enqueue(cmr_index* idx, Workspace* ws, const float* q_dev, int nq, int k, int F, float lam32, int64_t* out_ids_dev,
-                              float* out_scores_dev) {
-    HIP_TRY(ws->m_ids.ensure((size_t)nq * F * 8));
-    HIP_TRY(ws->m_sc.ensure((size_t)nq * F * 4));
-    if (idx->n > 0) {
-        const int rc = search_enqueue(idx, ws, q_dev, nq, F, (int64_t*)ws->m_ids.p, (float*)ws->m_sc.p, nullptr, nullptr);
-        if (rc) return rc;
-        idx->last_route.fetch_or(CMR_ROUTE_MMR, std::memory_order_relaxed);
-    } else {      // no rows: every candidate is padding (id -1; its score is never read)
-        HIP_TRY(hipMemsetAsync(ws->m_ids.p, 0xFF, (size_t)nq * F * 8, ws->stream));
-        HIP_TRY(hipMemsetAsync(ws->m_sc.p, 0, (size_t)nq * F * 4, ws->stream));
-        idx->last_route.store(CMR_ROUTE_MMR, std::memory_order_relaxed);
-    }
-    return mmr_select_enqueue(idx, ws, (const int64_t*)ws->m_ids.p, (const float*)ws->m_sc.p, nq, F, k, lam32, out_ids_dev, out_scores_dev);
-}
-
-int32_t cmr_mmr_select(const float* rel, const float* gram, const int64_t* ids, int32_t nq, int32_t F, int32_t k, double lam, int64_t* out_ids,
-                       float* out_scores) {
-    if (!rel || !gram || !ids || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    { int rc_ = mmr_args_check(nq, F, k, lam); if (rc_) return rc_; }
-    if (cmr_mmr::any_nan(rel, (size_t)nq * F)) return fail(CMR_ERR_INVALID, "NaN among the relevance scores");
-    cmr_mmr::select(rel, gram, ids, nq, F, k, (float)lam, out_ids, out_scores);
-    return CMR_OK;
-}
-
-int32_t cmr_index_pair_scores(cmr_index_t* idx, const int64_t* ids, int32_t nq, int32_t F, float* out) {
-    if (!ids || !out) return fail(CMR_ERR_INVALID, "NULL argument");
-    { int rc_ = mmr_args_check(nq, F, 1, 0.0); if (rc_) return rc_; }
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    SyncCall call(idx);
-    int rc = call.open();
-    if (rc) return rc;
-    Workspace* const ws = call.ws;
-    hipStream_t const s = call.s;
-    HIP_TRY(ws->m_ids.ensure((size_t)nq * F * 8));
-    HIP_TRY(hipMemcpyAsync(ws->m_ids.p, ids, (size_t)nq * F * 8, hipMemcpyHostToDevice, s));
-    rc = mmr_gram_enqueue(idx, ws, (const int64_t*)ws->m_ids.p, nq, F, nullptr);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    HIP_TRY(hipMemcpyAsync(out, ws->m_gram.p, (size_t)nq * F * F * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return CMR_OK;
-}
-
-int32_t cmr_index_mmr_select_dev(cmr_index_t* idx, const int64_t* cand_ids_dev, const float* cand_scores_dev, int32_t nq, int32_t F, int32_t k,
-                                 double lam, int64_t* out_ids_dev, float* out_scores_dev, void* stream) {
-    if (!cand_ids_dev || !cand_scores_dev || !out_ids_dev || !out_scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
-    { int rc_ = mmr_args_check(nq, F, k, lam); if (rc_) return rc_; }
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    DevCall call(idx);
-    const int rc = call.open(stream);
-    if (rc) return rc;
-    return mmr_select_enqueue(idx, call.ws, cand_ids_dev, cand_scores_dev, nq, F, k, (float)lam, out_ids_dev, out_scores_dev);
-}
-
-int32_t cmr_index_mmr_select(cmr_index_t* idx, const int64_t* cand_ids, const float* cand_scores, int32_t nq, int32_t F, int32_t k, double lam,
-                             int64_t* out_ids, float* out_scores) {
-    if (!cand_ids || !cand_scores || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    { int rc_ = mmr_args_check(nq, F, k, lam); if (rc_) return rc_; }
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    if (cmr_mmr::any_nan(cand_scores, (size_t)nq * F)) return fail(CMR_ERR_INVALID, "NaN among the candidate scores");
-    const PackedInput in[] = {{&Workspace::m_ids, cand_ids, (size_t)nq * F * 8}, {&Workspace::m_sc, cand_scores, (size_t)nq * F * 4}};
-    CmrPending* p = nullptr;
-    const int rc = packed_begin(idx, nq, k, true, in, [&](Workspace* w, int64_t* ids, float* sc, float*, float*) {
-        return mmr_select_enqueue(idx, w, (const int64_t*)w->m_ids.p, (const float*)w->m_sc.p, nq, F, k, (float)lam, ids, sc);
-    }, &p);
-    if (rc) return rc;
-    return cmr_index_search_finish(p, out_ids, out_scores, nullptr, nullptr);
-}
-
-int32_t cmr_index_search_mmr_dev(cmr_index_t* idx, const float* q_dev, int32_t nq, int32_t k, int32_t fetch_k, double lam, int64_t* ids_dev,
-                                 float* scores_dev, void* stream) {
-    if (!q_dev || !ids_dev || !scores_dev) return fail(CMR_ERR_INVALID, "NULL argument");
-    { int rc_ = mmr_args_check(nq, fetch_k, k, lam); if (rc_) return rc_; }
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    DevCall call(idx);
-    const int rc = call.open(stream);
-    if (rc) return rc;
-    return search_mmr_enqueue(idx, call.ws, q_dev, nq, k, fetch_k, (float)lam, ids_dev, scores_dev);
-}
-
-// one packed round trip: the queries up, [nq, k] ids and scores and the non-finite flag down
-int32_t cmr_index_search_mmr(cmr_index_t* idx, const float* q, int32_t nq, int32_t k, int32_t fetch_k, double lam, int64_t* out_ids,
-                             float* out_scores) {
-    if (!q || !out_ids || !out_scores) return fail(CMR_ERR_INVALID, "NULL argument");
-    { int rc_ = mmr_args_check(nq, fetch_k, k, lam); if (rc_) return rc_; }
-    if (!idx) return fail(CMR_ERR_INVALID, "NULL index");
-    const PackedInput in[] = {{&Workspace::d_q, q, (size_t)nq * idx->dim * 4}};
-    CmrPending* p = nullptr;
-    const int rc = packed_begin(idx, nq, k, true, in, [&](Workspace* w, int64_t* ids, float* sc, float*, float*) {
-        return search_mmr_enqueue(idx, w, (const float*)w->d_q.p, nq, k, fetch_k, (float)lam, ids, sc);
-    }, &p);
-    if (rc) return rc;
-    return cmr_index_search_finish(p, out_ids, out_scores, nullptr, nullptr);
-}
-
 }  // extern "C"
 
-int cmr_index_gram_rows(cmr_index_t* idx, const float* rows, const int64_t* ids, int nq, int F, float* out) {
-    SyncCall call(idx);
-    int rc = call.open();
-    if (rc) return rc;
-    Workspace* const ws = call.ws;
-    hipStream_t const s = call.s;
-    const int T = (F + 31) / 32;
-    const size_t row_bytes = (size_t)nq * T * 32 * idx->dim * 4;
-    HIP_TRY(ws->d_q.ensure(row_bytes));
-    HIP_TRY(ws->m_ids.ensure((size_t)nq * F * 8));
-    HIP_TRY(ws->qfrag.ensure((size_t)nq * T * idx->ks() * 1024));
-    rc = arm_flag(ws, s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ws->d_q.p, rows, row_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ws->m_ids.p, ids, (size_t)nq * F * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(cmr_launch_prep_queries(idx->dtype, (const float*)ws->d_q.p, nq * T * 32, idx->dim, idx->dpad, nq * T, ws->qfrag.p, ws->flag_ptr, s));
-    rc = mmr_gram_enqueue(idx, ws, (const int64_t*)ws->m_ids.p, nq, F, ws->qfrag.p);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    HIP_TRY(hipMemcpyAsync(out, ws->m_gram.p, (size_t)nq * F * F * 4, hipMemcpyDeviceToHost, s));
-    return check_query_flag(ws);      // (synchronises; stored rows are finite, so the flag stays clear)
-}
+// ---- the call families that share nothing but the index and what is above: a header each, included by this file only
+#include "row_filter.h"      // the row filter; filtered top-k and threshold search
+#include "range_host.h"      // range search and count, filtered or not
+#include "exact_host.h"      // exact fp32 search
+#include "mmr_host.h"        // diversified top-k
+#include "mutate_host.h"     // remove, update, truncate
+

@@ -1,5 +1,5 @@
-// Library-internal entry points and helpers shared by the host sources (api.hip, comm.hip, multi.hip, ppr.hip and the entry points
-// at the end of aux_kernels.hip / encoder_kernels.hip).  NOT part of the C-ABI (include/comorag_hip.h).
+// Library-internal entry points and helpers shared by the host sources (api.hip and the headers it alone includes, comm.hip, multi.hip,
+// ppr.hip and the entry points at the end of aux_kernels.hip / encoder_kernels.hip).  NOT part of the C-ABI (include/comorag_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,14 +53,38 @@ struct CmrPending;
 int cmr_index_search_begin(cmr_index_t* idx, const float* q, int nq, int k, const float* min_score, bool take_lock, CmrPending** out);
 int cmr_index_search_finish(CmrPending* p, int64_t* out_ids, float* out_scores, float* out_min, float* out_max);
 void cmr_index_search_abandon(CmrPending* p);
-// cmr_index_search_ids the same way: cmr_ids_args_check is every argument check that needs neither an index nor a device
-// (off_host: CSR offsets readable here, or NULL); `begin` takes checked arguments, the pending search ends in cmr_index_search_finish / _abandon.
-// min_score (read during `begin` only): the filtered threshold search, entries below the bound come back as padding
+// The row filter of a filtered call as the caller gave it — host pointers, or device pointers for the
+// _dev calls; none: every row.  The words forms: [n_masks][n_words] allow words, one word per 32-row panel.  The id forms: row ids in the
+// domain the searches return, `mode` CMR_IDS_ALLOW or CMR_IDS_EXCLUDE, one list for every query (off NULL) or CSR per query.  each: one
+// mask or list per query (a batch of one query included: the per-query scan variant and its route bits).  Everything that reads a filter
+// (row_filter.h, range_host.h, multi.hip) reads this struct.
+struct RowFilter {
+    enum Kind { none, words_form, ids_form } kind = none;
+    bool each = false;
+    const uint32_t* words = nullptr; int64_t n_words = 0; int n_masks = 0;
+    int mode = 0; const int64_t* off = nullptr; const int64_t* ids = nullptr; int64_t n_ids = 0;
+    static RowFilter of_words(const uint32_t* words, int64_t n_words, int n_masks, bool each) { return {words_form, each, words, n_words, n_masks}; }
+    static RowFilter of_ids(int mode, const int64_t* off, const int64_t* ids, int64_t n_ids) { return {ids_form, off != nullptr, nullptr, 0, 0, mode, off, ids, n_ids}; }
+};
+// every check of a filtered call that needs neither an index nor a device (row_filter.h, range_host.h, mmr_host.h), one of each: the bound, the
+// words ladder, the id-list ladder (off_host: CSR offsets readable here, or NULL), the ladder of a host filter's form, the arguments of
+// a range search or count (f none: the unfiltered call's), the arguments of the diversified top-k
+int cmr_min_score_check(float min_score);
+int cmr_words_args_check(const void* allow, int nq, int64_t n_words, int n_masks);
 int cmr_ids_args_check(int mode, int nq, int k, const int64_t* off_host, const int64_t* ids, int64_t n_ids);
-int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, int mode, const int64_t* id_offsets, const int64_t* ids, int64_t n_ids,
-                               bool take_lock, CmrPending** out, const float* min_score = nullptr);
+int cmr_filter_args_check(const RowFilter& f, int nq, int k);
+int cmr_range_args_check(const void* idx, const void* q, const void* out, int nq, float min_score, const RowFilter& f);
+int cmr_mmr_args_check(int nq, int F, int k, double lam);
+// the filtered top-k the same way as cmr_index_search_begin: `begin` takes checked arguments, the pending search ends in
+// cmr_index_search_finish / _abandon.  min_score (read during `begin` only): the filtered threshold search, entries below the
+// bound come back as padding
+int cmr_index_search_ids_begin(cmr_index_t* idx, const float* q, int nq, int k, const RowFilter& f, bool take_lock, CmrPending** out,
+                               const float* min_score = nullptr);
+// range search and count of one index behind their argument checks (range_host.h; *out is NULL), for the shards of multi.hip
+int cmr_index_range_count_host(cmr_index_t* idx, const float* q, int nq, float min_score, int64_t* out_counts, const RowFilter& f);
+int cmr_index_range_search_host(cmr_index_t* idx, const float* q, int nq, float min_score, int64_t max_total, cmr_range_result_t** out, const RowFilter& f);
 
-// the result of a range search (cmr_range_result_t): CSR lists in host arrays the library owns.  api.hip and multi.hip fill it.
+// the result of a range search (cmr_range_result_t): CSR lists in host arrays the library owns.  range_host.h and multi.hip fill it.
 struct cmr_range_result {
     int nq = 0;
     int64_t* lims = nullptr;      // [nq + 1]

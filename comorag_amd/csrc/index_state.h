@@ -1,6 +1,7 @@
 // State of one index (cmr_index_t) and of the calls in flight on it: device buffers, per-stream workspaces, the pipeline's
 // streams and slots, the quantities every route decision derives from the index shape, and the guards of the synchronous entry
-// points.  Included by api.hip only (one translation unit owns the index).
+// points.  Included by api.hip only (one translation unit owns the index); the headers that hold its call families (search_plan.h,
+// prefilter_host.h, row_filter.h, range_host.h, exact_host.h, mmr_host.h, mutate_host.h) are parts of that unit.
 #pragma once
 #include <hip/hip_runtime.h>
 

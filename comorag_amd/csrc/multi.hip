@@ -759,26 +759,26 @@ static int32_t mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_
 
 // Filtered search from GLOBAL row ids: every non-empty shard gets the whole list and keeps the ids it holds — the kernel's
 // "not held, so skipped" rule does the routing, there is no host-side split — and answers in global ids through its block table.
-int32_t cmr_mindex_search_ids(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
-                              int64_t n_ids, int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+// min_score: with a score bound — every shard pads below the bound, the merge of padded sorted lists is the padded merge
+static int32_t mindex_search_ids(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, const float* min_score, const RowFilter& f, int64_t* out_ids,
+                                 float* out_scores, float* out_min, float* out_max) {
     if (!q || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    const int rc = cmr_ids_args_check(mode, nq, k, id_offsets, ids, n_ids);
+    int rc = cmr_filter_args_check(f, nq, k);
     if (rc) return rc;
+    if (min_score && (rc = cmr_min_score_check(*min_score))) return rc;
     if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
-    return mindex_gather(m, nq, k, [&](int s, CmrPending** p) { return cmr_index_search_ids_begin(m->shard[s], q, nq, k, mode, id_offsets, ids, n_ids, false, p); },
+    return mindex_gather(m, nq, k, [&](int s, CmrPending** p) { return cmr_index_search_ids_begin(m->shard[s], q, nq, k, f, false, p, min_score); },
                          out_ids, out_scores, out_min, out_max);
 }
 
-// ... and with a score bound: every shard pads below the bound, the merge of padded sorted lists is the padded merge
+int32_t cmr_mindex_search_ids(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
+                              int64_t n_ids, int64_t* out_ids, float* out_scores, float* out_min, float* out_max) {
+    return mindex_search_ids(m, q, nq, k, nullptr, RowFilter::of_ids(mode, id_offsets, ids, n_ids), out_ids, out_scores, out_min, out_max);
+}
+
 int32_t cmr_mindex_search_min_score_ids(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, float min_score, int32_t mode, const int64_t* id_offsets,
                                         const int64_t* ids, int64_t n_ids, int64_t* out_ids, float* out_scores) {
-    if (!q || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    const int rc = cmr_ids_args_check(mode, nq, k, id_offsets, ids, n_ids);
-    if (rc) return rc;
-    if (!(min_score == min_score)) return cmr_fail(CMR_ERR_INVALID, "min_score is NaN");
-    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
-    return mindex_gather(m, nq, k, [&](int s, CmrPending** p) { return cmr_index_search_ids_begin(m->shard[s], q, nq, k, mode, id_offsets, ids, n_ids, false, p, &min_score); },
-                         out_ids, out_scores, nullptr, nullptr);
+    return mindex_search_ids(m, q, nq, k, &min_score, RowFilter::of_ids(mode, id_offsets, ids, n_ids), out_ids, out_scores, nullptr, nullptr);
 }
 
 int32_t cmr_mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores, float* out_min,
@@ -787,7 +787,7 @@ int32_t cmr_mindex_search(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k
 }
 
 int32_t cmr_mindex_search_min_score(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, float min_score, int64_t* out_ids, float* out_scores) {
-    if (!(min_score == min_score)) return cmr_fail(CMR_ERR_INVALID, "min_score is NaN");
+    if (const int rc = cmr_min_score_check(min_score)) return rc;
     if (k > CMR_MAX_K) return cmr_fail(CMR_ERR_UNSUPPORTED, "threshold search supports k in [1, %d]", CMR_MAX_K);
     return mindex_search(m, q, nq, k, &min_score, out_ids, out_scores, nullptr, nullptr);
 }
@@ -873,43 +873,22 @@ int32_t cmr_mindex_sorted_scores(cmr_mindex_t* m, const float* q, int32_t nq, in
 
 // Range search over the shards.  A shard answers in global ids, each list in the exported order (local row order is global id
 // order inside a shard), so the host's per-query merge gives what one index holding all rows gives.
-static int range_check(const void* m, const void* q, const void* out, int nq, float min_score) {
-    if (!m || !q || !out) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    if (nq <= 0) return cmr_fail(CMR_ERR_INVALID, "nq must be > 0");
-    if (!(min_score == min_score)) return cmr_fail(CMR_ERR_INVALID, "min_score is NaN");
-    return CMR_OK;
-}
+// the filtered forms (f none: every row) carry GLOBAL ids — every shard gets the whole lists and keeps the ids it holds.
+// A shard runs the one-index call behind its argument checks, which ran here.
 // counts [A][nq] of the active shards, all shards at once
-// the id lists of the filtered forms (nullptr: every row): GLOBAL ids — every shard gets the whole lists and keeps the ids it holds
-struct RangeIds { int mode; const int64_t* off; const int64_t* ids; int64_t n_ids; };
-static int range_ids_check(const void* m, const void* q, const void* out, int nq, float min_score, const RangeIds& f) {
-    if (!q || !out) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    const int rc = cmr_ids_args_check(f.mode, nq, 1, f.off, f.ids, f.n_ids);
-    if (rc) return rc;
-    if (!(min_score == min_score)) return cmr_fail(CMR_ERR_INVALID, "min_score is NaN");
-    if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
-    return CMR_OK;
-}
-static int shard_range_count(cmr_index_t* idx, const float* q, int nq, float min_score, const RangeIds* f, int64_t* counts) {
-    return f ? cmr_index_range_count_ids(idx, q, nq, min_score, f->mode, f->off, f->ids, f->n_ids, counts) : cmr_index_range_count(idx, q, nq, min_score, counts);
-}
-static int shard_range_search(cmr_index_t* idx, const float* q, int nq, float min_score, int64_t max_total, const RangeIds* f, cmr_range_result_t** out) {
-    return f ? cmr_index_range_search_ids(idx, q, nq, min_score, max_total, f->mode, f->off, f->ids, f->n_ids, out)
-             : cmr_index_range_search(idx, q, nq, min_score, max_total, out);
-}
-static int range_shard_counts(cmr_mindex* m, const std::vector<int>& act, const float* q, int nq, float min_score, const RangeIds* f, std::vector<int64_t>& counts) {
+static int range_shard_counts(cmr_mindex* m, const std::vector<int>& act, const float* q, int nq, float min_score, const RowFilter& f, std::vector<int64_t>& counts) {
     counts.assign(act.size() * (size_t)nq, 0);
-    return for_active(m, act, true, [&](int a, int s) { return shard_range_count(m->shard[s], q, nq, min_score, f, counts.data() + (size_t)a * nq); });
+    return for_active(m, act, true, [&](int a, int s) { return cmr_index_range_count_host(m->shard[s], q, nq, min_score, counts.data() + (size_t)a * nq, f); });
 }
 
 // (arguments checked by the caller)
-static int32_t mindex_range_count(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, const RangeIds* f, int64_t* out_counts) {
+static int32_t mindex_range_count(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, const RowFilter& f, int64_t* out_counts) {
     int rc;
     std::shared_lock<std::shared_mutex> lk(m->mu);
     const std::vector<int> act = active_shards(m);
     std::fill(out_counts, out_counts + nq, (int64_t)0);
     if (act.empty()) return CMR_OK;
-    if (act.size() == 1) return shard_range_count(m->shard[act[0]], q, nq, min_score, f, out_counts);
+    if (act.size() == 1) return cmr_index_range_count_host(m->shard[act[0]], q, nq, min_score, out_counts, f);
     std::vector<int64_t> counts;
     if ((rc = range_shard_counts(m, act, q, nq, min_score, f, counts))) return rc;
     for (size_t a = 0; a < act.size(); ++a)
@@ -917,20 +896,22 @@ static int32_t mindex_range_count(cmr_mindex_t* m, const float* q, int32_t nq, f
     return CMR_OK;
 }
 
+static int32_t mindex_range_count_entry(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, const RowFilter& f, int64_t* out_counts) {
+    const int rc = cmr_range_args_check(m, q, out_counts, nq, min_score, f);
+    return rc ? rc : mindex_range_count(m, q, nq, min_score, f, out_counts);
+}
+
 int32_t cmr_mindex_range_count(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t* out_counts) {
-    const int rc = range_check(m, q, out_counts, nq, min_score);
-    return rc ? rc : mindex_range_count(m, q, nq, min_score, nullptr, out_counts);
+    return mindex_range_count_entry(m, q, nq, min_score, RowFilter{}, out_counts);
 }
 
 int32_t cmr_mindex_range_count_ids(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int32_t mode, const int64_t* id_offsets, const int64_t* ids,
                                    int64_t n_ids, int64_t* out_counts) {
-    const RangeIds f{mode, id_offsets, ids, n_ids};
-    const int rc = range_ids_check(m, q, out_counts, nq, min_score, f);
-    return rc ? rc : mindex_range_count(m, q, nq, min_score, &f, out_counts);
+    return mindex_range_count_entry(m, q, nq, min_score, RowFilter::of_ids(mode, id_offsets, ids, n_ids), out_counts);
 }
 
 // (arguments checked by the caller, *out is NULL)
-static int32_t mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, const RangeIds* f, cmr_range_result_t** out) {
+static int32_t mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, const RowFilter& f, cmr_range_result_t** out) {
     int rc;
     const long long limit = max_total > 0 ? max_total : CMR_RANGE_MAX_TOTAL;
     std::shared_lock<std::shared_mutex> lk(m->mu);
@@ -943,7 +924,7 @@ static int32_t mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, 
         *out = res;
         return CMR_OK;
     }
-    if (A == 1) return shard_range_search(m->shard[act[0]], q, nq, min_score, max_total, f, out);
+    if (A == 1) return cmr_index_range_search_host(m->shard[act[0]], q, nq, min_score, max_total, out, f);
     // the limit is on the merged total: where the batch could exceed it, every shard counts before any shard compacts
     if ((double)nq * (double)m->total > (double)limit) {
         std::vector<int64_t> counts;
@@ -956,7 +937,7 @@ static int32_t mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, 
     // every shard's search on its worker thread: it begins on all of them before it finishes on any
     std::vector<cmr_range_result_t*> part((size_t)A, nullptr);
     struct Free { std::vector<cmr_range_result_t*>& p; ~Free() { for (cmr_range_result_t* r : p) (void)cmr_range_result_destroy(r); } } free_parts{part};
-    rc = for_active(m, act, true, [&](int a, int s) { return shard_range_search(m->shard[s], q, nq, min_score, limit, f, &part[a]); });
+    rc = for_active(m, act, true, [&](int a, int s) { return cmr_index_range_search_host(m->shard[s], q, nq, min_score, limit, &part[a], f); });
     if (rc) return rc;
     std::vector<const int64_t*> lims((size_t)A), ids((size_t)A);
     std::vector<const float*> sc((size_t)A);
@@ -973,18 +954,19 @@ static int32_t mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, 
     return CMR_OK;
 }
 
-int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, cmr_range_result_t** out) {
+static int32_t mindex_range_search_entry(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, const RowFilter& f, cmr_range_result_t** out) {
     if (out) *out = nullptr;
-    const int rc = range_check(m, q, out, nq, min_score);
-    return rc ? rc : mindex_range_search(m, q, nq, min_score, max_total, nullptr, out);
+    const int rc = cmr_range_args_check(m, q, out, nq, min_score, f);
+    return rc ? rc : mindex_range_search(m, q, nq, min_score, max_total, f, out);
+}
+
+int32_t cmr_mindex_range_search(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, cmr_range_result_t** out) {
+    return mindex_range_search_entry(m, q, nq, min_score, max_total, RowFilter{}, out);
 }
 
 int32_t cmr_mindex_range_search_ids(cmr_mindex_t* m, const float* q, int32_t nq, float min_score, int64_t max_total, int32_t mode, const int64_t* id_offsets,
                                     const int64_t* ids, int64_t n_ids, cmr_range_result_t** out) {
-    if (out) *out = nullptr;
-    const RangeIds f{mode, id_offsets, ids, n_ids};
-    const int rc = range_ids_check(m, q, out, nq, min_score, f);
-    return rc ? rc : mindex_range_search(m, q, nq, min_score, max_total, &f, out);
+    return mindex_range_search_entry(m, q, nq, min_score, max_total, RowFilter::of_ids(mode, id_offsets, ids, n_ids), out);
 }
 
 int32_t cmr_mindex_rescore(cmr_mindex_t* m, const float* q, int32_t nq, const int64_t* cand, int32_t n_cand, int32_t k, int64_t* out_ids,
@@ -1076,13 +1058,6 @@ int32_t cmr_mindex_get_rows(cmr_mindex_t* m, const int64_t* ids, int64_t n, floa
 // rows come to the host (cmr_mindex_get_rows), go to every shard as fp32 queries — packing a stored row reproduces its stored bits — and
 // are scored there against the candidates that shard holds, by the kernel and with the bits of one index; the host assembles G and runs
 // the selection of mmr_select.h.
-static int mmr_args_check(int nq, int F, int k, double lam) {
-    const int bad = cmr_mmr::check_args(nq, F, k, lam, CMR_MAX_K);
-    if (bad == 2) return cmr_fail(CMR_ERR_UNSUPPORTED, "fetch_k = %d above CMR_MAX_K = %d", F, CMR_MAX_K);
-    if (bad) return cmr_fail(CMR_ERR_INVALID, "need nq >= 1, 1 <= k <= fetch_k and lambda in [0, 1] (nq %d, k %d, fetch_k %d, lambda %g)", nq, k, F, lam);
-    return CMR_OK;
-}
-
 // void positions of ids [n_lists, F]: negative, held by no shard, or repeating an earlier position of the same list
 static std::vector<unsigned char> mmr_void_positions(const cmr_mindex* m, const int64_t* ids, int n_lists, int F) {
     std::vector<unsigned char> v((size_t)n_lists * F);
@@ -1121,7 +1096,7 @@ static int pair_scores_locked(cmr_mindex* m, const std::vector<int>& act, const 
 
 int32_t cmr_mindex_pair_scores(cmr_mindex_t* m, const int64_t* ids, int32_t nq, int32_t F, float* out) {
     if (!ids || !out) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    { const int rc_ = mmr_args_check(nq, F, 1, 0.0); if (rc_) return rc_; }
+    { const int rc_ = cmr_mmr_args_check(nq, F, 1, 0.0); if (rc_) return rc_; }
     if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
     std::shared_lock<std::shared_mutex> lk(m->mu);
     const std::vector<int> act = active_shards(m);
@@ -1136,7 +1111,7 @@ int32_t cmr_mindex_pair_scores(cmr_mindex_t* m, const int64_t* ids, int32_t nq, 
 int32_t cmr_mindex_mmr_select(cmr_mindex_t* m, const int64_t* cand_ids, const float* cand_scores, int32_t nq, int32_t F, int32_t k, double lam,
                               int64_t* out_ids, float* out_scores) {
     if (!cand_ids || !cand_scores || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    { const int rc_ = mmr_args_check(nq, F, k, lam); if (rc_) return rc_; }
+    { const int rc_ = cmr_mmr_args_check(nq, F, k, lam); if (rc_) return rc_; }
     if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
     if (cmr_mmr::any_nan(cand_scores, (size_t)nq * F)) return cmr_fail(CMR_ERR_INVALID, "NaN among the candidate scores");
     std::shared_lock<std::shared_mutex> lk(m->mu);
@@ -1159,7 +1134,7 @@ int32_t cmr_mindex_mmr_select(cmr_mindex_t* m, const int64_t* cand_ids, const fl
 int32_t cmr_mindex_search_mmr(cmr_mindex_t* m, const float* q, int32_t nq, int32_t k, int32_t fetch_k, double lam, int64_t* out_ids,
                               float* out_scores) {
     if (!q || !out_ids || !out_scores) return cmr_fail(CMR_ERR_INVALID, "NULL argument");
-    { const int rc_ = mmr_args_check(nq, fetch_k, k, lam); if (rc_) return rc_; }
+    { const int rc_ = cmr_mmr_args_check(nq, fetch_k, k, lam); if (rc_) return rc_; }
     if (!m) return cmr_fail(CMR_ERR_INVALID, "NULL index");
     {   // one active shard: its own device path
         std::shared_lock<std::shared_mutex> lk(m->mu);
